@@ -7,7 +7,12 @@ kernel per env range that moves agents, resolves conflicts, fires beams, respawn
 uint8 observations [E,N,15,15,3], rewards and dones.  Inputs (all env state) are resident in
 HBM when the timed region starts; `horizon` auto-resets are inside the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--game harvest|cleanup] [--envs E]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--game harvest|cleanup] [--envs E] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline; every optional leg below runs only with `--full`.
+`--dump-outputs DIR` writes what the timed call computed in its last step (rank 0's shard) as DIR/<name>.npy: the
+arrays are float32, 64 MB at most (a fixed, seeded sample of envs beyond that), the inputs are seeded, so two builds
+can be compared output for output.
 
 N > 1: one rank per GPU under torch.distributed.run (RCCL).  When the process is not already a rank of such a
 job (WORLD_SIZE unset) it starts the N ranks itself -- as a CHILD process, before this process has touched
@@ -16,7 +21,7 @@ collective (weak scaling: --envs is per GPU).  `--dry-run` is the launcher and s
 engine): what the CPU tests run.
 
 Prints ONE JSON line (rank 0).  THE HEADLINE COMES FIRST AND CANNOT BE LOST: `value`, `ms_per_step`, `roofline` are
-computed as soon as the K timed steps are done; everything after that -- the call-overhead leg, the fused leg, the
+computed as soon as the K timed steps are done; everything after that (`--full` only) -- the call-overhead leg, the fused leg, the
 policy-step legs, the other configurations, the CPU baseline, the optional gather legs -- is an OPTIONAL LEG that
 runs inside its own guard: whatever it raises (an exception, SystemExit, an out-of-memory error) lands as
 {"error": "..."} in that leg's slot of the line, and the line is printed with exit status 0 all the same.  Legs that
@@ -131,6 +136,30 @@ def spawn_ranks(n, argv):
         # must not make the caller throw the line away
         print("bench.py: the %d-rank job ended with status %d AFTER rank 0 had printed its line" % (n, rc), file=sys.stderr)
     return 0
+
+
+DUMP_BYTES = 64 << 20                               # --dump-outputs: at most this much in all
+
+
+def dump_outputs(directory, arrays, seed=0):
+    """--dump-outputs: the named device arrays (leading dimension: envs) as <directory>/<name>.npy, float32.  Past DUMP_BYTES in
+    all, the same fixed, seeded sample of envs from every array instead, their indices in env_index.npy."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    E = int(next(iter(arrays.values())).shape[0])
+    per_env = sum(4 * (t.numel() // E) for t in arrays.values())
+    rows = None
+    if per_env * E > DUMP_BYTES:
+        keep = (DUMP_BYTES - 4096) // (per_env + 8)      # (room for the .npy headers and env_index.npy)
+        rows = np.sort(np.random.default_rng(seed).choice(E, size=keep, replace=False))
+        np.save(os.path.join(directory, "env_index.npy"), rows.astype(np.float64))
+    for name, t in arrays.items():
+        if rows is not None:
+            t = t[torch.from_numpy(rows).to(t.device)]
+        np.save(os.path.join(directory, name + ".npy"), t.cpu().numpy().astype(np.float32))
+    print("bench.py: outputs of the last timed step written to %s (%s)" % (directory, "all %d envs" % E if rows is None else
+          "a sample of %d of %d envs" % (len(rows), E)), file=sys.stderr)
 
 
 GAMES = {"harvest": (0, "HARVEST_MAP", 5), "cleanup": (1, "CLEANUP_MAP", 5),
@@ -337,9 +366,15 @@ def main():
     ap.add_argument("--dry-run", action="store_true", help="launcher + sharding only: gloo ranks, no GPU, no engine")
     ap.add_argument("--dry-run-legs", action="store_true", help="--dry-run: also run the legs that need no GPU (a short cpu_baseline) "
                     "through the same guards as the real run")
+    ap.add_argument("--full", action="store_true", help="also run every optional leg (call overhead, fused and automatic forms, "
+                    "policy step, the other configurations, the CPU baseline, --gather-leg); without it only the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the obs / rew / done of the timed call's last step "
+                    "(rank 0's shard) as DIR/<name>.npy, float32, at most 64 MB (a fixed, seeded sample of envs beyond that)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if not args.full:                              # a plain run: the headline and nothing else
+        args.no_extras = True
     if args.no_extras:
         args.no_cpu_baseline = args.no_configs = True
 
@@ -626,6 +661,15 @@ def main():
         run_leg(res, "_traffic", traffic)
         if "_traffic" in res:                      # (only ever an error slot)
             res["roofline"]["traffic_error"] = res.pop("_traffic")["error"]
+        if args.dump_outputs:                      # (before any optional leg writes into the same buffers)
+            k_last = args.warmup + args.steps - 1
+            if do_gather:                          # the ring of the last chunk (run_steps), the step's slot in it
+                bufs, slot = G["rings"][((args.warmup + (args.steps - 1) // GR * GR) // GR) % 2], k_last % GR
+            elif use_rollout:
+                bufs, slot = ring, k_last % ring[0].shape[0]
+            else:
+                bufs, slot = tuple(t.unsqueeze(0) for t in out), 0
+            dump_outputs(args.dump_outputs, {"obs": bufs[0][slot], "rew": bufs[1][slot], "done": bufs[2][slot]})
     holder = res if res is not None else {}        # (every rank runs the legs; only rank 0's slots are printed)
 
     try:

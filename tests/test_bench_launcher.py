@@ -9,7 +9,7 @@ import sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(args, env_extra=None, drop=("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")):
+def _run(args, env_extra=None, drop=("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR", "GPU_MAX_HW_QUEUES")):
     env = {k: v for k, v in os.environ.items() if k not in drop}
     env.update(env_extra or {})
     return subprocess.run([sys.executable, os.path.join(REPO, "bench.py")] + args, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
@@ -76,11 +76,42 @@ def test_a_failing_optional_leg_does_not_cost_the_headline():
     assert p.returncode == 0 and "error" in res["cpu_baseline"] and "error" in res["configs"] and res["n_gpus"] == 1
 
 
-def test_run_leg_catches_system_exit_and_memory_error():
+def _bench_module():
     import importlib.util
     spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(REPO, "bench.py"))
     bench = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(bench)
+    return bench
+
+
+def test_dump_outputs_is_float32_and_a_fixed_sample_past_the_limit(tmp_path):
+    """--dump-outputs: every array as <name>.npy in float32, whole while it fits; past the limit the same seeded rows of every
+    array (their indices in env_index.npy), within the limit, the same rows on every run."""
+    import numpy as np
+    import torch
+    bench = _bench_module()
+    obs = torch.arange(100 * 3 * 6, dtype=torch.int32).reshape(100, 3, 6).to(torch.uint8)
+    rew = torch.arange(100 * 3, dtype=torch.int32).reshape(100, 3) - 7
+    bench.dump_outputs(str(tmp_path / "whole"), {"obs": obs, "rew": rew})
+    assert sorted(p.name for p in (tmp_path / "whole").iterdir()) == ["obs.npy", "rew.npy"]
+    a = np.load(str(tmp_path / "whole" / "obs.npy"))
+    assert a.dtype == np.float32 and np.array_equal(a, obs.numpy().astype(np.float32))
+    bench.DUMP_BYTES = 4096 + 40 * (4 * 3 * 6 + 4 * 3 + 8)          # room for 40 of the 100 envs
+    rows = []
+    for run in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / run), {"obs": obs, "rew": rew})
+        idx = np.load(str(tmp_path / run / "env_index.npy"))
+        assert idx.dtype == np.float64 and len(idx) == 40 and len(set(idx.tolist())) == 40
+        got_obs, got_rew = np.load(str(tmp_path / run / "obs.npy")), np.load(str(tmp_path / run / "rew.npy"))
+        assert got_obs.dtype == got_rew.dtype == np.float32
+        assert np.array_equal(got_obs, obs.numpy()[idx.astype(int)]) and np.array_equal(got_rew, rew.numpy()[idx.astype(int)])
+        assert sum(p.stat().st_size for p in (tmp_path / run).iterdir()) <= bench.DUMP_BYTES
+        rows.append(idx)
+    assert np.array_equal(rows[0], rows[1])
+
+
+def test_run_leg_catches_system_exit_and_memory_error():
+    bench = _bench_module()
     res = {"value": 1.0}
 
     def boom(exc):

@@ -108,7 +108,7 @@ def test_bench_with_two_ranks_rehearsed_on_one_gpu():
         env.pop(k, None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
-                        "--no-configs", "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=420)
+                        "--full", "--no-configs", "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=420)
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-3000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, lines
@@ -137,7 +137,7 @@ def test_bench_line_survives_failing_legs():
     env = dict(os.environ, SSD_BENCH_FAIL_LEG="fused_rollout,policy_step,configs,cpu_baseline")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5"], env=env,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--full"], env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=420)
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-3000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
@@ -147,6 +147,34 @@ def test_bench_line_survives_failing_legs():
     for leg in ("fused_rollout", "policy_step", "configs", "cpu_baseline"):
         assert "injected failure" in res[leg]["error"], (leg, res[leg])
     assert "call_overhead_us" in res and "us_per_call" in res["busy_stream_call"]       # the legs that were not told to fail ran
+
+
+def test_plain_bench_run_is_the_headline_and_dumps_its_last_step(tmp_path):
+    """bench.py without --full: the headline and no optional leg; --dump-outputs writes what the timed call computed in its last
+    step, float32 -- here (64 envs, W = 5, K = 7: step 11) equal to the oracle's step 11 of the same seeded envs."""
+    import json
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR", "SSD_BENCH_FAIL_LEG"):
+        env.pop(k, None)
+    d = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--envs", "64", "--steps", "7", "--warmup", "5",
+                        "--dump-outputs", str(d)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert r.returncode == 0, r.stderr.decode(errors="replace")[-3000:]
+    lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, lines
+    res = json.loads(lines[0])
+    assert res["steps"] == 7 and res["warmup"] == 5 and res["ms_per_step"] > 0 and res["value"] > 0
+    for leg in ("call_overhead_us", "warm_process_call", "busy_stream_call", "output_ring_32", "fused_rollout", "rollout_auto",
+                "policy_step", "configs", "cpu_baseline"):
+        assert leg not in res, leg
+    ora = pyoracle.Oracle(K.GAME_HARVEST, K.HARVEST_MAP, 64, 5, G.default_lut(), seed=0)
+    ora.reset()
+    for k in range(12):
+        _, o_obs, o_rew, _ = ora.step_random(want_obs=(k == 11))
+    got = {name: np.load(str(d / (name + ".npy"))) for name in ("obs", "rew", "done")}
+    assert all(a.dtype == np.float32 for a in got.values()) and sorted(p.name for p in d.iterdir()) == ["done.npy", "obs.npy", "rew.npy"]
+    assert np.array_equal(got["obs"], o_obs.astype(np.float32)) and np.array_equal(got["rew"], o_rew.astype(np.float32))
+    assert got["done"].shape == (64, 5) and not got["done"].any()
 
 
 _LOAD_SCRIPT = r'''
