@@ -2,6 +2,7 @@
 
     from sequential_social_dilemma_games_amd import HarvestEnv, CleanupEnv     # dict API (RLlib MultiAgentEnv)
     from sequential_social_dilemma_games_amd import VecEngine                  # batched tensor API
+    from sequential_social_dilemma_games_amd import WatershedSeqEnv, WatershedSeqCommEnv, WatershedVecEngine
 
 Everything that steps an env goes through libssd_hip.so (include/ssd.h); importing this package does
 not load it, constructing an env does -- and fails loudly if it is missing.
@@ -19,6 +20,9 @@ def __getattr__(name):
     if name in ("CleanupEnv", "CleanupAgent"):
         from . import cleanup
         return getattr(cleanup, name)
+    if name in ("WatershedSeqEnv", "WatershedSeqCommEnv", "WatershedVecEngine"):
+        from . import watershed
+        return getattr(watershed, name)
     if name == "MapEnv":
         from .map_env import MapEnv
         return MapEnv

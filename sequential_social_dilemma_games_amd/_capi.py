@@ -15,13 +15,19 @@ SSD_OK, SSD_E_INVALID, SSD_E_DEVICE, SSD_E_NOMEM, SSD_E_STATE = 0, -1, -2, -3, -
 SSD_HOST_PTRS, SSD_NO_ROTATE, SSD_OBS_F32, SSD_ROLLOUT_FUSED, SSD_AUTO_RESET, SSD_ROLLOUT_AUTO = 1, 2, 4, 8, 16, 128
 SSD_PATH_AQL, SSD_PATH_COHERENT, SSD_PATH_SPLIT, SSD_PATH_FUSED, SSD_PATH_SYNC, SSD_PATH_QUEUE_DROPPED, SSD_PATH_FORKED = 1, 2, 4, 8, 16, 32, 64
 SSD_ST_BAD_ACTION, SSD_ST_NO_SPAWN, SSD_ST_MOVE_LOOKUP, SSD_ST_WAIT_TIMEOUT = 1, 2, 4, 8
-ABI_VERSION = 3
+ABI_VERSION = 4
+SSD_WS_SEQ, SSD_WS_SEQ_COMM = 0, 1
+SSD_WS_DONE_AGENT, SSD_WS_DONE_ALL, SSD_WS_END, SSD_WS_REW_INT, SSD_WS_REW_F64 = 1, 2, 4, 8, 16
+SSD_ST_NOT_RESET = 16
+SSD_WS_OBS_WIDTH = 12
 
 # every symbol include/ssd.h declares
 SYMBOLS = ("ssd_create", "ssd_destroy", "ssd_reset", "ssd_step", "ssd_step_random", "ssd_rollout_random", "ssd_rollout_actions", "ssd_rollout_path", "ssd_set_rollout_chains",
            "ssd_profiler_attached", "ssd_observe",
            "ssd_get_state", "ssd_set_state", "ssd_get_waste_count", "ssd_render_full", "ssd_render_frames", "ssd_agent_action_obs", "ssd_set_horizon", "ssd_potential_waste_area",
-           "ssd_device_status", "ssd_synchronize", "ssd_last_error", "ssd_abi_version")
+           "ssd_device_status", "ssd_synchronize", "ssd_last_error", "ssd_abi_version",
+           "ssd_ws_create", "ssd_ws_destroy", "ssd_ws_reset", "ssd_ws_step", "ssd_ws_rollout_actions", "ssd_ws_info", "ssd_ws_get_state",
+           "ssd_ws_set_state", "ssd_ws_device_status", "ssd_ws_last_error")
 
 
 class SsdConfig(C.Structure):
@@ -31,6 +37,17 @@ class SsdConfig(C.Structure):
                 ("env_index_base", C.c_uint32), ("device_id", C.c_int32), ("keep_beams", C.c_int32),
                 ("color_lut", C.c_void_p), ("harvest_thresholds", C.c_void_p),
                 ("cleanup_apple_thresholds", C.c_void_p), ("cleanup_waste_thresholds", C.c_void_p)]
+
+
+class WsConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("variant", C.c_int32), ("num_envs", C.c_int32), ("local_obs", C.c_int32),
+                ("local_rew", C.c_int32), ("device_id", C.c_int32), ("seed", C.c_uint64), ("env_index_base", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class WsState(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in ("season", "phase", "wrapped", "viol", "round", "episode", "hist", "f_rew", "pen",
+                                                 "current_sums", "running_rew", "prev_actions")]
 
 
 class SsdError(RuntimeError):
@@ -100,12 +117,29 @@ def lib():
         L.ssd_last_error.argtypes = [vp]
         L.ssd_last_error.restype = C.c_char_p
         L.ssd_abi_version.argtypes = []
+        L.ssd_ws_create.argtypes = [C.POINTER(WsConfig), C.POINTER(vp)]
+        L.ssd_ws_destroy.argtypes = [vp]
+        L.ssd_ws_reset.argtypes = [vp, vp, vp, vp, vp]
+        L.ssd_ws_step.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp]
+        L.ssd_ws_rollout_actions.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, u32, vp]
+        L.ssd_ws_info.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        L.ssd_ws_get_state.argtypes = [vp, C.POINTER(WsState)]
+        L.ssd_ws_set_state.argtypes = [vp, C.POINTER(WsState)]
+        L.ssd_ws_device_status.argtypes = [vp, C.POINTER(u32), C.c_int]
+        L.ssd_ws_last_error.argtypes = [vp]
+        L.ssd_ws_last_error.restype = C.c_char_p
         for name in SYMBOLS:
             getattr(L, name)
         if L.ssd_abi_version() != ABI_VERSION:
             raise SsdError("libssd_hip.so ABI %d != expected %d: rebuild" % (L.ssd_abi_version(), ABI_VERSION))
         _lib = L
     return _lib
+
+
+def ws_check(rc, handle=None):
+    if rc != SSD_OK:
+        msg = lib().ssd_ws_last_error(handle)
+        raise SsdError("libssd_hip Watershed call failed (%d): %s" % (rc, msg.decode() if msg else "?"))
 
 
 def check(rc, handle=None):

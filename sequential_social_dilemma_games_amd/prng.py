@@ -22,6 +22,8 @@ Streams (the `index` word is given in brackets):
     WASTE_COIN  [cell]                (replaces cleanup.py:150)
     WASTE_ORDER [cell]                (replaces cleanup.py:145)
     ACTION      [agent]               random-action rollouts (rollout.py:65)
+    SEASON      [0]                   Watershed reset, t = 0: the season, randint(draw, 108)
+                                      (replaces watershedOrderedComm.py:69; once per (env, episode))
 `cell` is `row * W + col`; `t` is 0 for reset and k for the k-th step after it.
 """
 
@@ -37,6 +39,7 @@ S_APPLE = 4
 S_WASTE_COIN = 5
 S_WASTE_ORDER = 6
 S_ACTION = 7
+S_SEASON = 8
 
 
 def mix32(x):
