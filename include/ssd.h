@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SSD_ABI_VERSION 4   /* 4: the Watershed games (ssd_ws_*).  3: SSD_ROLLOUT_AUTO; SSD_STEP_CHAINS removed.  2: ssd_rollout_actions, ssd_profiler_attached; SSD_ROLLOUT_PIPELINED removed */
+#define SSD_ABI_VERSION 5   /* 5: episode statistics (ssd_stats_*).  4: the Watershed games (ssd_ws_*).  3: SSD_ROLLOUT_AUTO; SSD_STEP_CHAINS removed.  2: ssd_rollout_actions, ssd_profiler_attached; SSD_ROLLOUT_PIPELINED removed */
 
 enum {
     SSD_OK = 0,
@@ -358,6 +358,60 @@ int ssd_ws_get_state(ssd_ws_env *env, const ssd_ws_state *st);
 int ssd_ws_set_state(ssd_ws_env *env, const ssd_ws_state *st);
 int ssd_ws_device_status(ssd_ws_env *env, uint32_t *status, int clear);   /* synchronises the handle's device */
 const char *ssd_ws_last_error(const ssd_ws_env *env);                   /* NULL env: error of the last failed ssd_ws_create */
+
+
+/* ======================================================================================================================
+ * EPISODE STATISTICS -- per-episode returns and the social-outcome metrics of Perolat et al. 2017 (efficiency, equality,
+ * sustainability, peace), folded on the device from the step outputs (csrc/ssd_stats.hip).  An
+ * ssd_stats object is independent of any ssd_env: it reads the rew (and done) rings the stepping calls wrote.
+ *
+ * A step's reward is r = a - f - 50h (agent.py:166-183, :205-222): a apple eaten, f FIRE cost, h beams that hit the agent.
+ * Since |a - f| <= 1 < 25, h = floor((1 - r) / 50) and r > 0 iff (a,f,h) = (1,0,0); nothing but rew is needed.
+ * Per episode of T >= 1 steps (t = 1..T) and agent i: R_i = sum r, pos_i = #{r > 0}, tsum_i = sum of t over those steps,
+ * tagged_i = #{h > 0}, hits_i = sum h; C = sum_i R_i.  In float64, no contraction:
+ *   efficiency      U  = (double)C / T
+ *   equality        Eq = 1 - (double)G / (double)(2 N C),  G = sum_i sum_j |R_i - R_j| (int64); C = 0 gives -inf / NaN, and
+ *                   the value means something only when every R_i >= 0
+ *   sustainability  S  = mean over agents with pos_i > 0 of (double)tsum_i / pos_i, summed in agent order; NaN if none
+ *   peace           P  = (double)(N T - sum_i tagged_i) / T
+ * Every env starts at t = 0.  The step at fold index k ends env e's episode when done != NULL and done[slot,e,0] != 0
+ * (the adapter's contract: done envs are reset before their next step), or when reset_every > 0 and
+ * (step0 + k + 1) % reset_every == 0 (the rollout calls' full resets).  When reset_every > 0 and step0 % reset_every == 0
+ * the rollout resets every env before its first step: an open episode (t > 0) is discarded and counted as truncated.
+ *
+ * Accumulated per env until the next drain: episodes, truncated, sum of lengths, sum of C, per agent the sums of R_i,
+ * hits_i and tagged_i; per metric the float64 sum of its finite values in chronological order and their count; and the
+ * record of the last episode that ended (length, R_i, the four metrics).  The results do not depend on how the steps are
+ * split into folds nor on the fold's chunk length.
+ * ====================================================================================================================== */
+enum { SSD_STATS_KEEP = 1u << 0 };  /* ssd_stats_drain: copy out without clearing */
+
+typedef struct ssd_stats ssd_stats;
+
+/* num_envs 1..2^26, num_agents 1..64 (else SSD_E_INVALID); SSD_E_DEVICE without a usable HIP device. */
+int ssd_stats_create(int32_t num_envs, int32_t num_agents, int32_t device_id, ssd_stats **out);
+int ssd_stats_destroy(ssd_stats *st);
+/* Fold n_steps steps: step k < n_steps reads slot (step0 + k) % ring of rew i32 [ring,E,N] and done u8 [ring,E,N] (device
+ * pointers; done may be NULL).  n_steps <= ring, else SSD_E_INVALID.  flags: 0.  Two launches on `stream`; the object keeps
+ * a scratch buffer of about n_steps * E * N bytes, grown (with a device synchronisation) when a fold needs more. */
+int ssd_stats_fold(ssd_stats *st, const int32_t *rew, const uint8_t *done, int32_t ring, int32_t step0, int32_t n_steps,
+                   int32_t reset_every, uint32_t flags, void *stream);
+/* Steps per time chunk of the fold (0 = automatic, 64).  Changes speed only, never a result. */
+int ssd_stats_set_chunk(ssd_stats *st, int32_t steps);
+/* Discard the open episode of every env with env_mask[e] != 0 (u8 [E] device, NULL = all) that has t > 0; it counts as
+ * truncated. */
+int ssd_stats_discard(ssd_stats *st, const uint8_t *env_mask, void *stream);
+/* Copy the accumulators out (device pointers, any may be NULL) and clear them (unless SSD_STATS_KEEP):
+ *   counts        i64 [E,4]    episodes, truncated, sum of lengths, sum of collective returns C
+ *   agent_sums    i64 [E,3,N]  sums of R_i, hits_i, tagged_i
+ *   metric_sums   f64 [E,4]    U, Eq, S, P: sums of the finite values, chronological
+ *   metric_counts i64 [E,4]    how many values each sum holds
+ *   last_len      i64 [E]      length of the last episode that ended (0: none since the last drain)
+ *   last_ret      i64 [E,N]    its R_i
+ *   last_metrics  f64 [E,4]    its U, Eq, S, P (non-finite values included) */
+int ssd_stats_drain(ssd_stats *st, int64_t *counts, int64_t *agent_sums, double *metric_sums, int64_t *metric_counts,
+                    int64_t *last_len, int64_t *last_ret, double *last_metrics, uint32_t flags, void *stream);
+const char *ssd_stats_last_error(const ssd_stats *st);  /* NULL st: error of the last failed ssd_stats_create */
 
 #ifdef __cplusplus
 }

@@ -3,6 +3,7 @@
     from sequential_social_dilemma_games_amd import HarvestEnv, CleanupEnv     # dict API (RLlib MultiAgentEnv)
     from sequential_social_dilemma_games_amd import VecEngine                  # batched tensor API
     from sequential_social_dilemma_games_amd import WatershedSeqEnv, WatershedSeqCommEnv, WatershedVecEngine
+    from sequential_social_dilemma_games_amd import EpisodeStats                # per-episode returns and social metrics
 
 Everything that steps an env goes through libssd_hip.so (include/ssd.h); importing this package does
 not load it, constructing an env does -- and fails loudly if it is missing.
@@ -23,6 +24,9 @@ def __getattr__(name):
     if name in ("WatershedSeqEnv", "WatershedSeqCommEnv", "WatershedVecEngine"):
         from . import watershed
         return getattr(watershed, name)
+    if name == "EpisodeStats":
+        from .episode_stats import EpisodeStats
+        return EpisodeStats
     if name == "MapEnv":
         from .map_env import MapEnv
         return MapEnv

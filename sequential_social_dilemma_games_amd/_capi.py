@@ -15,11 +15,12 @@ SSD_OK, SSD_E_INVALID, SSD_E_DEVICE, SSD_E_NOMEM, SSD_E_STATE = 0, -1, -2, -3, -
 SSD_HOST_PTRS, SSD_NO_ROTATE, SSD_OBS_F32, SSD_ROLLOUT_FUSED, SSD_AUTO_RESET, SSD_ROLLOUT_AUTO = 1, 2, 4, 8, 16, 128
 SSD_PATH_AQL, SSD_PATH_COHERENT, SSD_PATH_SPLIT, SSD_PATH_FUSED, SSD_PATH_SYNC, SSD_PATH_QUEUE_DROPPED, SSD_PATH_FORKED = 1, 2, 4, 8, 16, 32, 64
 SSD_ST_BAD_ACTION, SSD_ST_NO_SPAWN, SSD_ST_MOVE_LOOKUP, SSD_ST_WAIT_TIMEOUT = 1, 2, 4, 8
-ABI_VERSION = 4
+ABI_VERSION = 5
 SSD_WS_SEQ, SSD_WS_SEQ_COMM = 0, 1
 SSD_WS_DONE_AGENT, SSD_WS_DONE_ALL, SSD_WS_END, SSD_WS_REW_INT, SSD_WS_REW_F64 = 1, 2, 4, 8, 16
 SSD_ST_NOT_RESET = 16
 SSD_WS_OBS_WIDTH = 12
+SSD_STATS_KEEP = 1
 
 # every symbol include/ssd.h declares
 SYMBOLS = ("ssd_create", "ssd_destroy", "ssd_reset", "ssd_step", "ssd_step_random", "ssd_rollout_random", "ssd_rollout_actions", "ssd_rollout_path", "ssd_set_rollout_chains",
@@ -27,7 +28,9 @@ SYMBOLS = ("ssd_create", "ssd_destroy", "ssd_reset", "ssd_step", "ssd_step_rando
            "ssd_get_state", "ssd_set_state", "ssd_get_waste_count", "ssd_render_full", "ssd_render_frames", "ssd_agent_action_obs", "ssd_set_horizon", "ssd_potential_waste_area",
            "ssd_device_status", "ssd_synchronize", "ssd_last_error", "ssd_abi_version",
            "ssd_ws_create", "ssd_ws_destroy", "ssd_ws_reset", "ssd_ws_step", "ssd_ws_rollout_actions", "ssd_ws_info", "ssd_ws_get_state",
-           "ssd_ws_set_state", "ssd_ws_device_status", "ssd_ws_last_error")
+           "ssd_ws_set_state", "ssd_ws_device_status", "ssd_ws_last_error",
+           "ssd_stats_create", "ssd_stats_destroy", "ssd_stats_fold", "ssd_stats_set_chunk", "ssd_stats_discard", "ssd_stats_drain",
+           "ssd_stats_last_error")
 
 
 class SsdConfig(C.Structure):
@@ -128,6 +131,14 @@ def lib():
         L.ssd_ws_device_status.argtypes = [vp, C.POINTER(u32), C.c_int]
         L.ssd_ws_last_error.argtypes = [vp]
         L.ssd_ws_last_error.restype = C.c_char_p
+        L.ssd_stats_create.argtypes = [i32, i32, i32, C.POINTER(vp)]
+        L.ssd_stats_destroy.argtypes = [vp]
+        L.ssd_stats_fold.argtypes = [vp, vp, vp, i32, i32, i32, i32, u32, vp]
+        L.ssd_stats_set_chunk.argtypes = [vp, i32]
+        L.ssd_stats_discard.argtypes = [vp, vp, vp]
+        L.ssd_stats_drain.argtypes = [vp] + [vp] * 7 + [u32, vp]
+        L.ssd_stats_last_error.argtypes = [vp]
+        L.ssd_stats_last_error.restype = C.c_char_p
         for name in SYMBOLS:
             getattr(L, name)
         if L.ssd_abi_version() != ABI_VERSION:
@@ -140,6 +151,12 @@ def ws_check(rc, handle=None):
     if rc != SSD_OK:
         msg = lib().ssd_ws_last_error(handle)
         raise SsdError("libssd_hip Watershed call failed (%d): %s" % (rc, msg.decode() if msg else "?"))
+
+
+def stats_check(rc, handle=None):
+    if rc != SSD_OK:
+        msg = lib().ssd_stats_last_error(handle)
+        raise SsdError("libssd_hip episode-statistics call failed (%d): %s" % (rc, msg.decode() if msg else "?"))
 
 
 def check(rc, handle=None):

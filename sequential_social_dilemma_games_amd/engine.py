@@ -55,6 +55,7 @@ class VecEngine(object):
         _capi.check(L.ssd_create(C.byref(c), C.byref(self._h)))
         self._L = L
         self._out_cache = (None, None)               # (outputs tuple, its pointers) of the last step_random call
+        self._ring_out_cache = {}                    # id(outputs tuple) -> (tuple, pointers): register_outputs()
         # Steps since the last reset of ALL envs, or None once envs may be at different points of their episodes (a masked
         # reset, set_state(t=...)): lets SSDVectorEnv know, without asking the device, on which step everybody reaches the
         # horizon.
@@ -144,14 +145,30 @@ class VecEngine(object):
             po, pr, pd, fl = self._out_cache[1]
         else:
             obs, rew, done = out if out is not None else self.alloc_outputs()
-            po, pr, pd, fl = self._dp(obs), self._dp(rew), self._dp(done), self._obs_flags(obs)
-            self._out_cache = (out, (po, pr, pd, fl))
+            po, pr, pd, fl = self._out_pointers(out, obs, rew, done)
         rc = self._L.ssd_step(self._h, C.c_void_p(actions.data_ptr()), self._dp(order), po, pr, pd,
                               fl | (_capi.SSD_AUTO_RESET if auto_reset else 0), self._stream())
         if rc:
             _capi.check(rc, self._h)
         self._count_after_step(auto_reset)
         return obs, rew, done
+
+    def _out_pointers(self, out, obs, rew, done):
+        hit = self._ring_out_cache.get(id(out)) if out is not None else None
+        if hit is not None and hit[0] is out:
+            ptrs = hit[1]
+        else:
+            ptrs = (self._dp(obs), self._dp(rew), self._dp(done), self._obs_flags(obs))
+        self._out_cache = (out, ptrs)
+        return ptrs
+
+    def register_outputs(self, outs):
+        """Output tuples (obs, rew, done) that step() / step_random() will be handed in turn -- the slots of an output ring
+        (SSDVectorEnv(track_episodes=True)): their pointers are worked out once, here.  Replaces the previous registration."""
+        self._ring_out_cache = {}
+        for out in outs:
+            obs, rew, done = out
+            self._ring_out_cache[id(out)] = (out, (self._dp(obs), self._dp(rew), self._dp(done), self._obs_flags(obs)))
 
     def _count_after_step(self, auto_reset):
         self._count_steps(1)
@@ -166,8 +183,7 @@ class VecEngine(object):
             po, pr, pd, fl = self._out_cache[1]
         else:
             obs, rew, done = out if out is not None else self.alloc_outputs()
-            po, pr, pd, fl = self._dp(obs), self._dp(rew), self._dp(done), self._obs_flags(obs)
-            self._out_cache = (out, (po, pr, pd, fl))
+            po, pr, pd, fl = self._out_pointers(out, obs, rew, done)
         na = self.num_actions if num_actions is None else int(num_actions)
         rc = self._L.ssd_step_random(self._h, na, self._dp(actions_out), po, pr, pd,
                                      fl | (_capi.SSD_AUTO_RESET if auto_reset else 0), self._stream())
@@ -217,14 +233,30 @@ class VecEngine(object):
         else:
             self._count_steps(n_steps)
 
-    def rollout_random(self, n_steps, obs, rew=None, done=None, reset_every=0, step0=0, num_actions=None, fused=False):
+    def _check_stats(self, stats, rew, n_steps):
+        """A rollout with `stats` (an EpisodeStats of this batch) needs its rew ring, long enough to hold every step of the call."""
+        if stats is None:
+            return
+        if rew is None:
+            raise ValueError("stats need the call's rewards: pass rew")
+        if stats.E != self.E or stats.N != self.N or stats.device != self.device:
+            raise ValueError("stats were made for %d envs x %d agents on device %d, the engine has %d x %d on device %d"
+                             % (stats.E, stats.N, stats.device, self.E, self.N, self.device))
+        if int(rew.shape[0]) < int(n_steps):
+            raise ValueError("stats need every step's rewards: the rew ring (%d) is shorter than n_steps (%d)"
+                             % (int(rew.shape[0]), int(n_steps)))
+
+    def rollout_random(self, n_steps, obs, rew=None, done=None, reset_every=0, step0=0, num_actions=None, fused=False, stats=None):
         """rollout.py:58-70 as ONE library call: `n_steps` random-action steps (plus a full reset whenever
         (step0 + k) % reset_every == 0) enqueued back to back.  obs / rew / done are device tensors with a leading ring
         dimension R: step k writes slot (step0 + k) % R  (obs u8 or f32 [R,E,N,V,V,3], rew i32 [R,E,N], done u8 [R,E,N]).
         Same launches as n_steps calls of step_random(); the host just stops being the bottleneck.
         fused=True: ONE kernel launch for the whole call (SSD_ROLLOUT_FUSED) -- every env stays in LDS / registers across
         its steps; same results, uint8 observations only.  fused="auto": the library picks (SSD_ROLLOUT_AUTO: the fused kernel
-        for uint8 observations and two steps or more, the chains otherwise; rollout_path() says which form ran)."""
+        for uint8 observations and two steps or more, the chains otherwise; rollout_path() says which form ran).
+        stats: an EpisodeStats of this batch, folded after the call from its rew ring (episodes end at the full resets of
+        reset_every only; rew is required and its ring must hold n_steps steps)."""
+        self._check_stats(stats, rew, n_steps)
         po, pr, pd, ring, f32 = self._rollout_args(obs, rew, done)
         na = self.num_actions if num_actions is None else int(num_actions)
         rc = self._L.ssd_rollout_random(self._h, na, int(n_steps), int(reset_every), int(step0), po, pr, pd, ring,
@@ -232,15 +264,19 @@ class VecEngine(object):
         if rc:
             _capi.check(rc, self._h)
         self._count_rollout(n_steps, reset_every, step0)
+        if stats is not None:
+            stats.fold(rew, None, step0=step0, n_steps=n_steps, reset_every=reset_every)
 
-    def rollout_actions(self, actions, n_steps, obs, rew=None, done=None, reset_every=0, step0=0, fused=False, order=None):
+    def rollout_actions(self, actions, n_steps, obs, rew=None, done=None, reset_every=0, step0=0, fused=False, order=None,
+                        stats=None):
         """The same call with caller-supplied actions (ssd_rollout_actions): what the reference's callers do, env.step(policy
         actions) per step (visuallizer_rllib.py:121-153), for a recorded sequence / an action chunk of n_steps steps.
         actions: int32 [A,E,N] device tensor (-1 = the agent does not act); step k reads slot (step0 + k) % A.  order: optional
         uint8 [A,E,N], per step the agent indices in action-dict order, 0xFF-terminated (None: index order).  Outputs as
         rollout_random() (fused=True / "auto" as there).  Reuse the same action / output tensors from call to call: the launches'
-        arguments are cached by them."""
+        arguments are cached by them.  stats: as in rollout_random()."""
         torch, dev = self._torch()
+        self._check_stats(stats, rew, n_steps)
         cache = getattr(self, "_act_cache", None)
         if cache is not None and cache[0] is actions and cache[1] is order:
             pa, pord, aring = cache[2]
@@ -257,6 +293,8 @@ class VecEngine(object):
         if rc:
             _capi.check(rc, self._h)
         self._count_rollout(n_steps, reset_every, step0)
+        if stats is not None:
+            stats.fold(rew, None, step0=step0, n_steps=n_steps, reset_every=reset_every)
 
     @staticmethod
     def _fused_flag(fused):

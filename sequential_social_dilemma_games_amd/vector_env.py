@@ -12,6 +12,9 @@ Two surfaces:
   * RLlib `BaseEnv`-style `poll()` / `send_actions()` / `try_reset()` with {env_id: {agent_id: ...}} dicts,
     for code written against that interface (a host round trip per call: use it for compatibility,
     not for speed).
+
+track_episodes=True keeps per-episode statistics on the device (episode_stats.py): the steps write rew / done into the
+slots of a ring, which is folded when it fills, before a reset, and whenever the statistics are read.
 """
 import numpy as np
 
@@ -23,7 +26,8 @@ _NORMALISE = (np.arange(256, dtype=np.float64) - 128.0) / 255.0
 
 class SSDVectorEnv(object):
     def __init__(self, game, num_envs, num_agents, horizon=1000, ascii_map=None, seed=0, device=0,
-                 env_index_base=0, view_len=K.VIEW_LEN, float32_obs=False, return_agent_actions=False):
+                 env_index_base=0, view_len=K.VIEW_LEN, float32_obs=False, return_agent_actions=False, track_episodes=False,
+                 track_ring=64):
         self.engine = VecEngine(game, ascii_map, num_envs=num_envs, num_agents=num_agents, seed=seed, device=device,
                                 env_index_base=env_index_base, view_len=view_len)
         self.num_envs, self.num_agents, self.horizon = num_envs, num_agents, int(horizon)
@@ -38,6 +42,16 @@ class SSDVectorEnv(object):
         self._extras = None
         self._act_buf = None
         self._pending = None
+        # track_episodes: step k writes rew / done into slot k % track_ring of a ring that the episode statistics fold
+        self.stats = None
+        if track_episodes:
+            from .episode_stats import EpisodeStats
+            if int(track_ring) < 1:
+                raise ValueError("track_ring must be >= 1")
+            self.stats = EpisodeStats(num_envs, num_agents, device=device)
+            self._ring_len = int(track_ring)
+            self._ring = self._slot_outs = None
+            self._slot = self._fold_from = self._unfolded = 0
 
     # ------------------------------------------------------------------ tensor API
     def _wrap(self, obs, actions, done):
@@ -46,8 +60,50 @@ class SSDVectorEnv(object):
         self._extras = self.engine.agent_action_obs(actions, done, out=self._extras)
         return {"curr_obs": obs, "other_agent_actions": self._extras[0], "visible_agents": self._extras[1]}
 
-    def reset(self):
+    def _alloc(self):
         self._out = self.engine.alloc_outputs(float32=self.float32_obs)
+        if self.stats is not None:
+            import torch
+            dev = self._out[1].device
+            shape = (self._ring_len, self.num_envs, self.num_agents)
+            self._ring = (torch.zeros(shape, dtype=torch.int32, device=dev), torch.zeros(shape, dtype=torch.uint8, device=dev))
+            self._slot_outs = [(self._out[0], self._ring[0][s], self._ring[1][s]) for s in range(self._ring_len)]
+            self.engine.register_outputs(self._slot_outs)
+            self._slot = self._fold_from = self._unfolded = 0
+            self._out = self._slot_outs[0]
+
+    def _fold(self):
+        """Fold the ring's steps not yet folded (in slot order, episodes ending at done)."""
+        if self.stats is not None and self._unfolded:
+            self.stats.fold(self._ring[0], self._ring[1], step0=self._fold_from, n_steps=self._unfolded)
+            self._fold_from, self._unfolded = self._slot, 0
+
+    def _advance(self):
+        """After a step that wrote slot self._slot: the next step writes the next slot; a full ring is folded first."""
+        if self.stats is None or self._ring is None:
+            return
+        self._unfolded += 1
+        self._slot = (self._slot + 1) % self._ring_len
+        if self._unfolded == self._ring_len:
+            self._fold()
+        self._out = self._slot_outs[self._slot]
+
+    def episode_stats(self):
+        """The EpisodeStats of this batch (track_episodes=True), every step so far folded into it."""
+        if self.stats is None:
+            raise RuntimeError("construct with track_episodes=True")
+        self._fold()
+        return self.stats
+
+    def summary(self):
+        """episode_stats().summary(): RLlib-style means of the episodes that ended since the last read, and clears them."""
+        return self.episode_stats().summary()
+
+    def reset(self):
+        if self.stats is not None and self._ring is not None:
+            self._fold()
+            self.stats.discard()                 # the episodes still open are cut short
+        self._alloc()
         self.engine.reset(obs=self._out[0])
         return self._wrap(self._out[0], None, None)
 
@@ -77,6 +133,7 @@ class SSDVectorEnv(object):
         in_kernel = self._in_kernel()
         obs, rew, done = self.engine.step(actions, order=order, out=self._out, auto_reset=in_kernel)
         self._auto_reset(obs, done, in_kernel)
+        self._advance()
         # (rows of envs whose episode just ended carry a reset's observation: their other_agent_actions are the reset's zeros)
         return self._wrap(obs, actions, done if self.horizon > 0 else None), rew, done
 
@@ -87,6 +144,7 @@ class SSDVectorEnv(object):
             self._act_buf = torch.empty((self.num_envs, self.num_agents), dtype=torch.int32, device=self._out[1].device)
         obs, rew, done = self.engine.step_random(out=self._out, actions_out=self._act_buf, auto_reset=in_kernel)
         self._auto_reset(obs, done, in_kernel)
+        self._advance()
         return self._wrap(obs, self._act_buf, done if self.horizon > 0 else None), rew, done
 
     @staticmethod
@@ -161,7 +219,10 @@ class SSDVectorEnv(object):
         mask = torch.zeros(self.num_envs, dtype=torch.uint8, device=torch.device("cuda", self.engine.device))
         mask[env_id] = 1
         if self._out is None:
-            self._out = self.engine.alloc_outputs(float32=self.float32_obs)
+            self._alloc()
+        elif self.stats is not None:
+            self._fold()
+            self.stats.discard(mask)             # the env's open episode is cut short
         self.engine.reset(mask=mask, obs=self._out[0])
         if self.return_agent_actions:
             n1 = max(self.num_agents - 1, 0)
