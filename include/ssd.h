@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SSD_ABI_VERSION 5   /* 5: episode statistics (ssd_stats_*).  4: the Watershed games (ssd_ws_*).  3: SSD_ROLLOUT_AUTO; SSD_STEP_CHAINS removed.  2: ssd_rollout_actions, ssd_profiler_attached; SSD_ROLLOUT_PIPELINED removed */
+#define SSD_ABI_VERSION 6   /* 6: policy rollouts (ssd_policy_forward, ssd_rollout_policy).  5: episode statistics (ssd_stats_*).  4: the Watershed games (ssd_ws_*).  3: SSD_ROLLOUT_AUTO; SSD_STEP_CHAINS removed.  2: ssd_rollout_actions, ssd_profiler_attached; SSD_ROLLOUT_PIPELINED removed */
 
 enum {
     SSD_OK = 0,
@@ -70,6 +70,8 @@ enum {
                                 observations, index action order and n_steps >= 2 take the fused kernel (SSD_ROLLOUT_FUSED: 3.5 us per
                                 4096-env step against 5.4 through the chains); anything else is dispatched as without the flag.
                                 Same results either way; ssd_rollout_path() says which form ran. */
+    SSD_POLICY_GREEDY = 1u << 8, /* ssd_rollout_policy only: the action is the argmax of the logits (lowest index on ties)
+                                instead of a draw from the S_POLICY stream */
     SSD_OBS_F32 = 1u << 2    /* obs points at float32 [E,N,V,V,3] instead of uint8: the normalisation of map_env.py:199
                                 fused into the kernel (4x the observation bytes; a separate, slower mode) */
 };
@@ -412,6 +414,70 @@ int ssd_stats_discard(ssd_stats *st, const uint8_t *env_mask, void *stream);
 int ssd_stats_drain(ssd_stats *st, int64_t *counts, int64_t *agent_sums, double *metric_sums, int64_t *metric_counts,
                     int64_t *last_len, int64_t *last_ret, double *last_metrics, uint32_t flags, void *stream);
 const char *ssd_stats_last_error(const ssd_stats *st);  /* NULL st: error of the last failed ssd_stats_create */
+
+/* ======================================================================================================================
+ * POLICY ROLLOUTS -- the conv-FC policy network of models/conv_to_fc_net.py:1-51 (Jaques et al. 2019) run on the device and
+ * interleaved with the step kernel, so that a closed-loop rollout (observe, act, step: visuallizer_rllib.py:121-153) is
+ * enqueued by one call (csrc/ssd_policy.hip).  Exact float32 throughout.
+ *
+ * The network, per weight set and observation x = float32((u8 - 128) / 255) of shape [15,15,3] (view_len 7 only):
+ *   conv   6 filters 3x3, stride 1, no padding, ReLU           -> [13,13,6]
+ *   flatten in (row, col, channel) order (TF's flatten of NHWC) -> 1014
+ *   fc1    1014 -> 32, ReLU      fc2  32 -> 32, ReLU            (the trunk)
+ *   logits 32 -> A               value 32 -> 1                  (both on fc2's output)
+ * A weight buffer holds P sets back to back, each SSD_POL_SET_FLOATS(A) floats (a multiple of 64), in this layout (float
+ * offsets within a set; every matrix is [in][out], the layout of a TF checkpoint's kernels):
+ *   conv_w   [3][3][3][6]  (kh, kw, c_in, c_out)      conv_b   [6]
+ *   fc1_w    [1014][32]                               fc1_b    [32]
+ *   fc2_w    [32][32]                                 fc2_b    [32]
+ *   value_w  [32]                                     value_b  [1]    (then 3 floats of padding)
+ *   logits_w [32][A]                                  logits_b [A]    (then padding up to the set stride)
+ * Agent i of an env uses set i when P = N and set 0 when P = 1 (train_baseline.py:87-96: one policy per agent).
+ *
+ * Sampling (ssd_rollout_policy without SSD_POLICY_GREEDY): for the state an action is taken in, with (episode, t) as
+ * ssd_get_state reports them, draw = H(seed, env_index_base + e, episode, t, SSD_S_POLICY, i) and u = (draw >> 8) * 2^-24.
+ * With m = max_a logits[a], e_a = expf(logits[a] - m), s = the float32 sum of e_a in index order and c_a the running float32
+ * sum of e_a / s in index order, the action is the first a with u < c_a, else A - 1.  SSD_POLICY_GREEDY: the first a with
+ * the largest logit.  logp = logits[a] - (m + logf(s)), float32.
+ * ====================================================================================================================== */
+enum { SSD_S_POLICY = 9 };          /* PRNG stream of the policy's action draw (sequential_social_dilemma_games_amd/prng.py) */
+enum {
+    SSD_POL_VIEW = 15, SSD_POL_CONV_OUT = 13, SSD_POL_FILTERS = 6, SSD_POL_HIDDEN = 32, SSD_POL_FLAT = 1014, SSD_POL_MAX_ACTIONS = 15,
+    SSD_POL_CONV_W = 0,             /* 162 */
+    SSD_POL_CONV_B = 162,           /* 6 */
+    SSD_POL_FC1_W = 168,            /* 1014 * 32 */
+    SSD_POL_FC1_B = 32616,          /* 32 */
+    SSD_POL_FC2_W = 32648,          /* 32 * 32 */
+    SSD_POL_FC2_B = 33672,          /* 32 */
+    SSD_POL_VALUE_W = 33704,        /* 32 */
+    SSD_POL_VALUE_B = 33736,        /* 1 */
+    SSD_POL_LOGITS_W = 33740        /* 32 * A, then logits_b [A] at SSD_POL_LOGITS_W + 32 * A */
+};
+#define SSD_POL_LOGITS_B(A) (SSD_POL_LOGITS_W + 32 * (A))
+#define SSD_POL_SET_FLOATS(A) ((SSD_POL_LOGITS_W + 33 * (A) + 63) / 64 * 64)
+
+/* The forward pass alone: obs u8 [B,N,15,15,3] -> logits f32 [B,N,A] and value f32 [B,N] (either may be NULL), device pointers
+ * on device_id, enqueued on `stream`.  weights: P sets as above (P = 1 or N), 4-byte aligned; 1 <= A <= 15; 1 <= N <= 64.
+ * flags: 0.  Bad arguments: SSD_E_INVALID before anything is launched (ssd_policy_last_error says why). */
+int ssd_policy_forward(const float *weights, int32_t num_sets, int32_t num_actions, const uint8_t *obs, int32_t batch,
+                       int32_t num_agents, float *logits, float *value, int32_t device_id, uint32_t flags, void *stream);
+const char *ssd_policy_last_error(void);   /* the calling thread's last ssd_policy_forward error */
+
+/* A closed-loop rollout of n_steps steps in one call (device pointers, enqueued on `stream`, no host synchronisation).  A is the
+ * game's Discrete(n) (8 Harvest, 9 Cleanup); the handle's view_len must be 7.  Step k:
+ *   1. the policy runs on the current observation: obs_in u8 [E,N,15,15,3] for k = 0, else slot (step0 + k - 1) % ring of obs;
+ *   2. it writes actions i32, logp f32, value f32 (and logits f32 [.., A]) into slot s = (step0 + k) % ring of
+ *      actions [ring,E,N], logp [ring,E,N], value [ring,E,N], logits [ring,E,N,A];
+ *   3. the step runs with those actions in index order and SSD_AUTO_RESET (horizon of ssd_set_horizon), writing obs u8
+ *      [ring,E,N,15,15,3], rew i32 [ring,E,N] and done u8 [ring,E,N] into slot s.
+ * After the last step last_value f32 [E,N] holds the value of the final observation (the bootstrap of GAE).  obs and actions
+ * are required; logp, value, logits, rew, done and last_value may be NULL.  ring >= 1, n_steps >= 1, step0 >= 0.
+ * flags: SSD_POLICY_GREEDY or 0.  The same results as n_steps rounds of (ssd_policy_forward, the sampling above,
+ * ssd_step(..., SSD_AUTO_RESET)): a pure function of (state, weights, seed), whatever the ring length or the split into calls.
+ * Two hipLaunchKernel launches per step on `stream` (plus one for last_value). */
+int ssd_rollout_policy(ssd_env *env, const float *weights, int32_t num_sets, const uint8_t *obs_in, int32_t n_steps, int32_t step0,
+                       uint8_t *obs, int32_t *actions, float *logp, float *value, float *logits, int32_t *rew, uint8_t *done,
+                       int32_t ring, float *last_value, uint32_t flags, void *stream);
 
 #ifdef __cplusplus
 }

@@ -4,6 +4,7 @@
     from sequential_social_dilemma_games_amd import VecEngine                  # batched tensor API
     from sequential_social_dilemma_games_amd import WatershedSeqEnv, WatershedSeqCommEnv, WatershedVecEngine
     from sequential_social_dilemma_games_amd import EpisodeStats                # per-episode returns and social metrics
+    from sequential_social_dilemma_games_amd import ConvFCPolicy                # the conv-FC policy net, run in the loop
 
 Everything that steps an env goes through libssd_hip.so (include/ssd.h); importing this package does
 not load it, constructing an env does -- and fails loudly if it is missing.
@@ -27,6 +28,9 @@ def __getattr__(name):
     if name == "EpisodeStats":
         from .episode_stats import EpisodeStats
         return EpisodeStats
+    if name == "ConvFCPolicy":
+        from .policy import ConvFCPolicy
+        return ConvFCPolicy
     if name == "MapEnv":
         from .map_env import MapEnv
         return MapEnv

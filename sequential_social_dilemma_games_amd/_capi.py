@@ -13,14 +13,29 @@ LIB_PATH = os.environ.get("SSD_LIB_PATH") or os.path.join(_PKG, "libssd_hip.so")
 
 SSD_OK, SSD_E_INVALID, SSD_E_DEVICE, SSD_E_NOMEM, SSD_E_STATE = 0, -1, -2, -3, -4
 SSD_HOST_PTRS, SSD_NO_ROTATE, SSD_OBS_F32, SSD_ROLLOUT_FUSED, SSD_AUTO_RESET, SSD_ROLLOUT_AUTO = 1, 2, 4, 8, 16, 128
+SSD_POLICY_GREEDY = 256
 SSD_PATH_AQL, SSD_PATH_COHERENT, SSD_PATH_SPLIT, SSD_PATH_FUSED, SSD_PATH_SYNC, SSD_PATH_QUEUE_DROPPED, SSD_PATH_FORKED = 1, 2, 4, 8, 16, 32, 64
 SSD_ST_BAD_ACTION, SSD_ST_NO_SPAWN, SSD_ST_MOVE_LOOKUP, SSD_ST_WAIT_TIMEOUT = 1, 2, 4, 8
-ABI_VERSION = 5
+ABI_VERSION = 6
 SSD_WS_SEQ, SSD_WS_SEQ_COMM = 0, 1
 SSD_WS_DONE_AGENT, SSD_WS_DONE_ALL, SSD_WS_END, SSD_WS_REW_INT, SSD_WS_REW_F64 = 1, 2, 4, 8, 16
 SSD_ST_NOT_RESET = 16
 SSD_WS_OBS_WIDTH = 12
 SSD_STATS_KEEP = 1
+# the policy network's weight layout (include/ssd.h, SSD_POL_*): float offsets within one weight set
+SSD_S_POLICY = 9
+SSD_POL_VIEW, SSD_POL_CONV_OUT, SSD_POL_FILTERS, SSD_POL_HIDDEN, SSD_POL_FLAT, SSD_POL_MAX_ACTIONS = 15, 13, 6, 32, 1014, 15
+SSD_POL_CONV_W, SSD_POL_CONV_B, SSD_POL_FC1_W, SSD_POL_FC1_B = 0, 162, 168, 32616
+SSD_POL_FC2_W, SSD_POL_FC2_B, SSD_POL_VALUE_W, SSD_POL_VALUE_B, SSD_POL_LOGITS_W = 32648, 33672, 33704, 33736, 33740
+
+
+def SSD_POL_LOGITS_B(num_actions):
+    return SSD_POL_LOGITS_W + 32 * int(num_actions)
+
+
+def SSD_POL_SET_FLOATS(num_actions):
+    return (SSD_POL_LOGITS_W + 33 * int(num_actions) + 63) // 64 * 64
+
 
 # every symbol include/ssd.h declares
 SYMBOLS = ("ssd_create", "ssd_destroy", "ssd_reset", "ssd_step", "ssd_step_random", "ssd_rollout_random", "ssd_rollout_actions", "ssd_rollout_path", "ssd_set_rollout_chains",
@@ -30,7 +45,7 @@ SYMBOLS = ("ssd_create", "ssd_destroy", "ssd_reset", "ssd_step", "ssd_step_rando
            "ssd_ws_create", "ssd_ws_destroy", "ssd_ws_reset", "ssd_ws_step", "ssd_ws_rollout_actions", "ssd_ws_info", "ssd_ws_get_state",
            "ssd_ws_set_state", "ssd_ws_device_status", "ssd_ws_last_error",
            "ssd_stats_create", "ssd_stats_destroy", "ssd_stats_fold", "ssd_stats_set_chunk", "ssd_stats_discard", "ssd_stats_drain",
-           "ssd_stats_last_error")
+           "ssd_stats_last_error", "ssd_policy_forward", "ssd_policy_last_error", "ssd_rollout_policy")
 
 
 class SsdConfig(C.Structure):
@@ -139,6 +154,10 @@ def lib():
         L.ssd_stats_drain.argtypes = [vp] + [vp] * 7 + [u32, vp]
         L.ssd_stats_last_error.argtypes = [vp]
         L.ssd_stats_last_error.restype = C.c_char_p
+        L.ssd_policy_forward.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp, i32, u32, vp]
+        L.ssd_policy_last_error.argtypes = []
+        L.ssd_policy_last_error.restype = C.c_char_p
+        L.ssd_rollout_policy.argtypes = [vp, vp, i32, vp, i32, i32] + [vp] * 7 + [i32, vp, u32, vp]
         for name in SYMBOLS:
             getattr(L, name)
         if L.ssd_abi_version() != ABI_VERSION:
@@ -157,6 +176,12 @@ def stats_check(rc, handle=None):
     if rc != SSD_OK:
         msg = lib().ssd_stats_last_error(handle)
         raise SsdError("libssd_hip episode-statistics call failed (%d): %s" % (rc, msg.decode() if msg else "?"))
+
+
+def policy_check(rc):
+    if rc != SSD_OK:
+        msg = lib().ssd_policy_last_error()
+        raise SsdError("libssd_hip policy call failed (%d): %s" % (rc, msg.decode() if msg else "?"))
 
 
 def check(rc, handle=None):

@@ -23,6 +23,7 @@
 #include "../../include/ssd.h"
 #include "ssd_internal.hpp"
 #include "ssd_aql.hpp"
+#include "ssd_policy.hpp"
 
 using ssd::Params;
 
@@ -1461,6 +1462,57 @@ int ssd_agent_action_obs(ssd_env *env, const int32_t *actions, const uint8_t *do
 int ssd_set_horizon(ssd_env *env, int32_t horizon) {
     if (!env || horizon < 0) return SSD_E_INVALID;
     env->p.horizon = horizon;
+    return SSD_OK;
+}
+
+// A closed-loop rollout: per step one launch of the policy kernel (ssd_policy.hip: forward + action into the ring slot), then the
+// step launch of ssd_step(..., SSD_AUTO_RESET) reading those actions.  Both through hipLaunchKernel on `stream`: the library's
+// AQL chains (ssd_rollout_actions) are not used here.
+int ssd_rollout_policy(ssd_env *env, const float *weights, int32_t num_sets, const uint8_t *obs_in, int32_t n_steps, int32_t step0,
+                       uint8_t *obs, int32_t *actions, float *logp, float *value, float *logits, int32_t *rew, uint8_t *done,
+                       int32_t ring, float *last_value, uint32_t flags, void *stream) {
+    if (!env) return SSD_E_INVALID;
+    auto bad = [&](const char *msg) { env->err = msg; return SSD_E_INVALID; };
+    const int A = env->game == SSD_GAME_HARVEST ? 8 : 9;        // harvest.py:44, cleanup.py:70
+    if (env->view_len != 7 || env->V != SSD_POL_VIEW) return bad("policy rollouts need view_len 7 (15 x 15 observations)");
+    if (env->N < 1) return bad("policy rollouts need at least one agent");
+    if (!weights || !obs_in || !obs || !actions) return bad("weights, obs_in, obs and actions are required");
+    if (reinterpret_cast<uintptr_t>(weights) & 3u) return bad("weights must be 4-byte aligned");
+    if (num_sets != 1 && num_sets != env->N) return bad("num_sets must be 1 or num_agents");
+    if (n_steps < 1) return bad("n_steps must be >= 1");
+    if (ring < 1) return bad("ring must be >= 1");
+    if (step0 < 0) return bad("step0 must be >= 0");
+    if (flags & ~(uint32_t)SSD_POLICY_GREEDY) return bad("flags: only the greedy-policy bit is defined");
+    const size_t en = (size_t)env->E * env->N, ob = en * SSD_POL_VIEW * SSD_POL_VIEW * 3;
+    if (reinterpret_cast<uintptr_t>(obs) & 3u) return bad("obs must be 4-byte aligned");
+    if (ring > 1 && (ob & 3u)) return bad("an observation ring of more than one slot needs E * N to be a multiple of 4 (4-byte aligned slots)");
+    {
+        int cur = -1;
+        if (hipGetDevice(&cur) != hipSuccess || cur != env->device) SSD_HIP(env, hipSetDevice(env->device));
+    }
+    ssd::PolicyArgs pa{};
+    pa.w = weights; pa.P = num_sets; pa.A = A; pa.B = env->E; pa.N = env->N; pa.set_floats = SSD_POL_SET_FLOATS(A);
+    pa.hdr = env->p.hdr; pa.seed_lo = env->p.seed_lo; pa.seed_hi = env->p.seed_hi; pa.env_base = env->p.env_base;
+    pa.greedy = (flags & SSD_POLICY_GREEDY) ? 1 : 0;
+    size_t slot = 0;
+    for (int32_t k = 0; k < n_steps; ++k) {
+        const size_t prev = slot;
+        slot = (size_t)(((int64_t)step0 + k) % ring);
+        pa.obs = k == 0 ? obs_in : obs + prev * ob;
+        pa.actions = actions + slot * en;
+        pa.logp = logp ? logp + slot * en : nullptr;
+        pa.value = value ? value + slot * en : nullptr;
+        pa.logits = logits ? logits + slot * en * A : nullptr;
+        SSD_HIP(env, ssd::launch_policy(pa, stream));
+        const int rc = run(env, ssd::kModeStepAuto, pa.actions, nullptr, nullptr, 0, nullptr, obs + slot * ob, rew ? rew + slot * en : nullptr,
+                           done ? done + slot * en : nullptr, 1, 0, stream);
+        if (rc) return rc;
+    }
+    if (last_value) {
+        pa.obs = obs + slot * ob;
+        pa.actions = nullptr; pa.logp = nullptr; pa.logits = nullptr; pa.value = last_value;
+        SSD_HIP(env, ssd::launch_policy(pa, stream));
+    }
     return SSD_OK;
 }
 

@@ -1,0 +1,262 @@
+// ssd_policy.hip -- the conv-FC policy network of models/conv_to_fc_net.py:1-51 on the device: its forward pass
+// (ssd_policy_forward) and, in ssd_rollout_policy (ssd_capi.hip), its action selection, one launch per step between the step
+// launches.  include/ssd.h states the network, the weight layout and the sampling contract; DESIGN.md section 11 the shape.
+//
+// One workgroup = 16 envs of ONE agent index i, so the weight set (i, or 0 when shared) is uniform across it:
+//   1. the 16 observations (u8, 10.8 KB) go to LDS, with the 256-entry normalisation table float32((u8 - 128) / 255);
+//   2. conv 3x3x3 -> 6 with ReLU on the VALU: a thread per (env, output position) keeps the 6 filters' sums in registers; the
+//      weights are uniform (scalar loads).  The 16 x 1014 outputs stay in LDS in the flatten order (row, col, channel);
+//   3. fc1 (16 x 1014) x (1014 x 32) on the matrix cores, v_mfma_f32_16x16x4_f32 (exact f32: a k-ordered fmaf chain per
+//      accumulator): wave w takes the 16 output columns w & 1 over half of K (w >> 1), two accumulators each; the two halves
+//      are added through LDS.  fc1's weights stream from L2 (130 KB per set, shared by every workgroup of the set);
+//   4. fc2, the logits and the value on the VALU (1.3 kMAC per env);
+//   5. rollouts: one thread per env picks the action (greedy or the S_POLICY draw) and its log-probability.
+// Every sum is in a fixed order, so two calls on the same input agree bit for bit.
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+#include <stdint.h>
+#include <string>
+
+#include "../../include/ssd.h"
+#include "ssd_policy.hpp"
+
+namespace {
+
+constexpr int kTile = 16;          // envs per workgroup: M of the fc1 tile
+constexpr int kThreads = 256;      // 4 waves
+constexpr int kObs = 675;          // 15 * 15 * 3 bytes
+constexpr int kPos = 169;          // 13 * 13 conv outputs per filter
+constexpr int kFlat = 1014;        // 13 * 13 * 6
+constexpr int kPitch = 1017;       // LDS pitch (floats) of a row of conv outputs: 1014 + zero padding, odd against bank conflicts
+constexpr int kKSteps = 254;       // fc1: K = 1014 padded to 1016 = 254 MFMA k-steps of 4
+constexpr int kHalf = kKSteps / 2; // k-steps per wave (odd: 63 pairs and one more)
+constexpr int kHP = 33;            // LDS pitch of the hidden layers
+
+static_assert(kThreads == 256, "one thread per entry of the normalisation table");
+static_assert(SSD_POL_FC1_B == SSD_POL_FC1_W + kFlat * 32 && SSD_POL_FC2_W == SSD_POL_FC1_B + 32 && SSD_POL_FC2_B == SSD_POL_FC2_W + 1024 &&
+              SSD_POL_VALUE_W == SSD_POL_FC2_B + 32 && SSD_POL_VALUE_B == SSD_POL_VALUE_W + 32 && SSD_POL_LOGITS_W >= SSD_POL_VALUE_B + 1,
+              "weight layout of include/ssd.h");
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// shared PRNG (prng.py): the triple32 chain of ssd_kernels.hip
+__device__ __forceinline__ uint32_t mix32(uint32_t x) {
+    x ^= x >> 17; x *= 0xED5AD4BBu;
+    x ^= x >> 11; x *= 0xAC4C1B51u;
+    x ^= x >> 15; x *= 0x31848BABu;
+    x ^= x >> 14;
+    return x;
+}
+__device__ __forceinline__ uint32_t env_key(uint32_t seed_lo, uint32_t seed_hi, uint32_t env, uint32_t episode) {
+    uint32_t h = 0x243F6A88u;
+    h = mix32(h ^ seed_lo);
+    h = mix32(h ^ seed_hi);
+    h = mix32(h ^ env);
+    h = mix32(h ^ episode);
+    return h;
+}
+
+__global__ void __launch_bounds__(kThreads) ssd_policy_kernel(ssd::PolicyArgs a) {
+    __shared__ float s_norm[256];
+    __shared__ float s_conv[kTile * kPitch];
+    __shared__ float s_buf[(kTile * kObs + 3) / 4];   // the observation bytes; after the conv, the small buffers below
+    uint8_t *s_obs = reinterpret_cast<uint8_t *>(s_buf);
+    float *s_part = s_buf;                             // [2][16][16] fc1 partial sums of the second K half
+    float *s_h1 = s_buf + 512;                         // [16][kHP]
+    float *s_h2 = s_h1 + kTile * kHP;                  // [16][kHP]
+    float *s_out = s_h2 + kTile * kHP;                 // [16][16]: logits 0..A-1, value at A
+    static_assert(512 + 2 * kTile * kHP + kTile * 16 <= (kTile * kObs + 3) / 4, "small buffers fit the observation area");
+
+    const int tid = threadIdx.x, i = blockIdx.y, b0 = blockIdx.x * kTile;
+    const int N = a.N, B = a.B, A = a.A;
+    const float *__restrict__ w = a.w + (size_t)(a.P == 1 ? 0 : i) * (size_t)a.set_floats;
+
+    // ---- 1. inputs ----
+    s_norm[tid] = (float)(((double)tid - 128.0) / 255.0);
+    {   // (every load of the thread issued before the first store: one round trip to memory, not 43)
+        constexpr int kLoads = (kTile * kObs + kThreads - 1) / kThreads;
+        uint8_t v[kLoads];
+#pragma unroll
+        for (int u = 0; u < kLoads; ++u) {
+            const int q = tid + u * kThreads, r = q / kObs, o = q - r * kObs, b = b0 + r;
+            v[u] = q < kTile * kObs && b < B ? a.obs[((size_t)b * N + i) * kObs + o] : (uint8_t)128;
+        }
+#pragma unroll
+        for (int u = 0; u < kLoads; ++u)
+            if (tid + u * kThreads < kTile * kObs) s_obs[tid + u * kThreads] = v[u];
+    }
+    if (tid < kTile * (kPitch - kFlat)) s_conv[(tid / 3) * kPitch + kFlat + tid % 3] = 0.f;
+    __syncthreads();
+
+    // ---- 2. conv 3x3, 6 filters, ReLU; output (row, col, channel) ----
+    for (int q = tid; q < kTile * kPos; q += kThreads) {
+        const int r = q / kPos, pos = q - r * kPos, y = pos / 13, x = pos - y * 13;
+        const uint8_t *src = s_obs + r * kObs + (y * 15 + x) * 3;
+        float acc[6];
+#pragma unroll
+        for (int f = 0; f < 6; ++f) acc[f] = 0.f;
+#pragma unroll
+        for (int dy = 0; dy < 3; ++dy) {
+#pragma unroll
+            for (int j = 0; j < 9; ++j) {                   // (dx, c) = (j / 3, j % 3): 9 contiguous bytes of view row y + dy
+                const float v = s_norm[src[dy * 45 + j]];
+#pragma unroll
+                for (int f = 0; f < 6; ++f) acc[f] = fmaf(v, w[SSD_POL_CONV_W + (dy * 9 + j) * 6 + f], acc[f]);
+            }
+        }
+        float *dst = s_conv + r * kPitch + pos * 6;
+#pragma unroll
+        for (int f = 0; f < 6; ++f) dst[f] = fmaxf(acc[f] + w[SSD_POL_CONV_B + f], 0.f);
+    }
+    __syncthreads();
+
+    // ---- 3. fc1 on the matrix cores: A[m][k] = conv row m, B[k][n] = fc1_w[k][n] ----
+    // v_mfma_f32_16x16x4_f32: lane l holds A[l & 15][k = l >> 4] and B[k = l >> 4][l & 15]; D: col l & 15, row 4 (l >> 4) + r
+    const int wave = tid >> 6, lane = tid & 63, nt = wave & 1, kh = wave >> 1;
+    const int l15 = lane & 15, l4 = lane >> 4;
+    const float *a_row = s_conv + l15 * kPitch + l4;
+    const float *w1 = w + SSD_POL_FC1_W + l4 * 32 + nt * 16 + l15;
+    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
+    // (wave half 0: k-steps 0..126; half 1: 127..253, whose last step is peeled -- its rows 1014, 1015 are padding)
+    const int kb = kh * kHalf;
+#pragma unroll 4
+    for (int p = 0; p < (kHalf - 1) / 2; ++p) {
+        const int kk = kb + 2 * p;
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a_row[4 * kk], w1[(size_t)kk * 128], acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a_row[4 * kk + 4], w1[(size_t)kk * 128 + 128], acc1, 0, 0, 0);
+    }
+    {
+        const int kl = kb + kHalf - 1;
+        const float bv = 4 * kl + l4 < kFlat ? w1[(size_t)kl * 128] : 0.f;
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a_row[4 * kl], bv, acc0, 0, 0, 0);
+    }
+    const f32x4 acc = acc0 + acc1;
+    if (kh) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) s_part[(nt * 16 + l4 * 4 + r) * 16 + l15] = acc[r];
+    }
+    __syncthreads();
+    if (!kh) {
+        const int n = nt * 16 + l15;
+        const float bias = w[SSD_POL_FC1_B + n];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int m = l4 * 4 + r;
+            s_h1[m * kHP + n] = fmaxf(acc[r] + s_part[(nt * 16 + m) * 16 + l15] + bias, 0.f);
+        }
+    }
+    __syncthreads();
+
+    // ---- 4. fc2 + ReLU, then the heads ----
+    {
+        const int m = tid >> 4, n = tid & 15;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int nn = n + 16 * h;
+            float s = 0.f;
+#pragma unroll 8
+            for (int k = 0; k < 32; ++k) s = fmaf(s_h1[m * kHP + k], w[SSD_POL_FC2_W + k * 32 + nn], s);
+            s_h2[m * kHP + nn] = fmaxf(s + w[SSD_POL_FC2_B + nn], 0.f);
+        }
+    }
+    __syncthreads();
+    {
+        const int m = tid >> 4, j = tid & 15, b = b0 + m;
+        if (j <= A) {                                       // j < A: logit j; j == A: the value
+            const float *hw = j < A ? w + SSD_POL_LOGITS_W + j : w + SSD_POL_VALUE_W;
+            const int stride = j < A ? A : 1;
+            float s = 0.f;
+#pragma unroll 8
+            for (int k = 0; k < 32; ++k) s = fmaf(s_h2[m * kHP + k], hw[k * stride], s);
+            s += j < A ? w[SSD_POL_LOGITS_W + 32 * A + j] : w[SSD_POL_VALUE_B];
+            s_out[m * 16 + j] = s;
+            if (b < B) {
+                const size_t row = (size_t)b * N + i;
+                if (j < A) {
+                    if (a.logits) a.logits[row * A + j] = s;
+                } else if (a.value) {
+                    a.value[row] = s;
+                }
+            }
+        }
+    }
+    if (!a.actions) return;
+    __syncthreads();
+
+    // ---- 5. the action: argmax, or the first a with u < cumulative softmax (include/ssd.h) ----
+    if (tid < kTile && b0 + tid < B) {
+        const int b = b0 + tid;
+        const float *l = s_out + tid * 16;
+        float mx = l[0];
+        int arg = 0;
+        for (int k = 1; k < A; ++k)
+            if (l[k] > mx) { mx = l[k]; arg = k; }
+        float s = 0.f;
+        for (int k = 0; k < A; ++k) s += expf(l[k] - mx);
+        int act = arg;
+        if (!a.greedy) {
+            const uint4 h = a.hdr[b];                       // {key, t, episode, ...} of the state the action is taken in
+            const uint32_t key = env_key(a.seed_lo, a.seed_hi, a.env_base + (uint32_t)b, h.z);
+            const uint32_t pk = mix32(mix32(key ^ h.y) ^ (uint32_t)SSD_S_POLICY);
+            const float u = (float)(mix32(pk ^ (uint32_t)i) >> 8) * 0x1p-24f;
+            act = A - 1;
+            float c = 0.f;
+            for (int k = 0; k < A; ++k) {
+                c += expf(l[k] - mx) / s;
+                if (u < c) { act = k; break; }
+            }
+        }
+        const size_t row = (size_t)b * N + i;
+        a.actions[row] = act;
+        if (a.logp) a.logp[row] = l[act] - (mx + logf(s));
+    }
+}
+
+thread_local std::string g_policy_error;
+
+int fail(const char *msg) {
+    g_policy_error = msg;
+    return SSD_E_INVALID;
+}
+
+}  // namespace
+
+namespace ssd {
+
+hipError_t launch_policy(const PolicyArgs &a, void *stream) {
+    const dim3 grid((unsigned)((a.B + kTile - 1) / kTile), (unsigned)a.N), block(kThreads);
+    hipLaunchKernelGGL(ssd_policy_kernel, grid, block, 0, static_cast<hipStream_t>(stream), a);
+    return hipGetLastError();
+}
+
+}  // namespace ssd
+
+extern "C" {
+
+const char *ssd_policy_last_error(void) { return g_policy_error.c_str(); }
+
+int ssd_policy_forward(const float *weights, int32_t num_sets, int32_t num_actions, const uint8_t *obs, int32_t batch,
+                       int32_t num_agents, float *logits, float *value, int32_t device_id, uint32_t flags, void *stream) {
+    if (!weights || !obs) return fail("weights and obs are required");
+    if (reinterpret_cast<uintptr_t>(weights) & 3u) return fail("weights must be 4-byte aligned");
+    if (num_agents < 1 || num_agents > 64) return fail("num_agents must be 1..64");
+    if (num_sets != 1 && num_sets != num_agents) return fail("num_sets must be 1 or num_agents");
+    if (num_actions < 1 || num_actions > SSD_POL_MAX_ACTIONS) return fail("num_actions must be 1..15");
+    if (batch < 1) return fail("batch must be >= 1");
+    if (flags) return fail("flags must be 0");
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || device_id < 0 || device_id >= count) return fail("no such HIP device");
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != device_id) {
+        if (hipSetDevice(device_id) != hipSuccess) { g_policy_error = "hipSetDevice failed"; return SSD_E_DEVICE; }
+    }
+    ssd::PolicyArgs a{};
+    a.w = weights; a.P = num_sets; a.A = num_actions; a.B = batch; a.N = num_agents; a.set_floats = SSD_POL_SET_FLOATS(num_actions);
+    a.obs = obs; a.logits = logits; a.value = value;
+    const hipError_t e = ssd::launch_policy(a, stream);
+    if (e != hipSuccess) { g_policy_error = std::string("policy launch: ") + hipGetErrorString(e); return SSD_E_DEVICE; }
+    return SSD_OK;
+}
+
+}  // extern "C"

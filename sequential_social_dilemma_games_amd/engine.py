@@ -304,6 +304,115 @@ class VecEngine(object):
             return _capi.SSD_ROLLOUT_AUTO
         return _capi.SSD_ROLLOUT_FUSED if fused else 0
 
+    # ------------------------------------------------------------------ policy in the loop (include/ssd.h, POLICY ROLLOUTS)
+    def _policy_weights(self, policy):
+        """Checks a ConvFCPolicy against this engine (everything before anything is enqueued); returns its weight-set count."""
+        from .policy import ConvFCPolicy
+        torch, dev = self._torch()
+        if not isinstance(policy, ConvFCPolicy):
+            raise ValueError("policy must be a ConvFCPolicy")
+        if self.V != _capi.SSD_POL_VIEW:
+            raise ValueError("the policy network takes 15 x 15 views (view_len 7); this engine has V = %d" % self.V)
+        if policy.num_actions != self.num_actions:
+            raise ValueError("the policy has %d actions, the game Discrete(%d)" % (policy.num_actions, self.num_actions))
+        if policy.num_sets not in (1, self.N):
+            raise ValueError("the policy has %d weight sets: 1 (shared) or %d (one per agent) expected" % (policy.num_sets, self.N))
+        if policy.conv_w.device != dev:
+            raise ValueError("the policy's parameters are on %s, the engine on %s" % (policy.conv_w.device, dev))
+        if self.N < 1:
+            raise ValueError("a policy needs at least one agent")
+        return policy.num_sets
+
+    def policy_forward(self, policy, obs):
+        """The policy's forward pass on the device (ssd_policy_forward): obs uint8 [..., N, 15, 15, 3] -> (logits float32
+        [..., N, A], value float32 [..., N]), enqueued on the current stream.  The same kernel as rollout_policy()'s."""
+        torch, dev = self._torch()
+        P = self._policy_weights(policy)
+        V, N, A = self.V, self.N, self.num_actions
+        if not isinstance(obs, torch.Tensor) or obs.dtype != torch.uint8 or obs.device != dev or not obs.is_contiguous() \
+                or obs.dim() < 4 or tuple(obs.shape[-4:]) != (N, V, V, 3):
+            raise ValueError("obs must be a contiguous uint8 tensor of shape [..., %d, %d, %d, 3] on %s" % (N, V, V, dev))
+        B = obs.numel() // (N * V * V * 3)
+        if B < 1:
+            raise ValueError("obs holds no observation")
+        lead = tuple(obs.shape[:-3])
+        logits = torch.empty(lead + (A,), dtype=torch.float32, device=dev)
+        value = torch.empty(lead, dtype=torch.float32, device=dev)
+        w = policy.packed()
+        _capi.policy_check(self._L.ssd_policy_forward(self._dp(w), P, A, self._dp(obs), B, N, self._dp(logits), self._dp(value),
+                                                      self.device, 0, self._stream()))
+        return logits, value
+
+    def rollout_policy(self, policy, obs_in, n_steps, obs, actions=None, logp=None, value=None, logits=None, rew=None, done=None,
+                       last_value=None, step0=0, greedy=False, stats=None):
+        """A closed-loop rollout (ssd_rollout_policy): n_steps rounds of (policy forward on the current observation, action, step
+        with automatic reset at the horizon) enqueued by one call, no host synchronisation.  The rings have a leading dimension
+        R and step k writes slot (step0 + k) % R:
+          obs u8 [R,E,N,15,15,3] (required: the next step's policy reads it), actions i32 [R,E,N] (None: a ring of the engine's
+          own), logp / value f32 [R,E,N], logits f32 [R,E,N,A], rew i32 [R,E,N], done u8 [R,E,N];
+        obs_in u8 [E,N,15,15,3] is the observation of the current state (the last reset's or step's); last_value f32 [E,N]
+        receives the value of the final observation.  greedy: argmax actions, else drawn from the S_POLICY stream
+        (include/ssd.h).  stats: an EpisodeStats of this batch folded from rew and done (both required, R >= n_steps)."""
+        torch, dev = self._torch()
+        P = self._policy_weights(policy)
+        n_steps, step0 = int(n_steps), int(step0)
+        if n_steps < 1:
+            raise ValueError("n_steps must be >= 1")
+        if step0 < 0:
+            raise ValueError("step0 must be >= 0")
+        E, N, V, A = self.E, self.N, self.V, self.num_actions
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 6:
+            raise ValueError("obs must be a uint8 ring [R,%d,%d,%d,%d,3]" % (E, N, V, V))
+        R = int(obs.shape[0])
+        if R < 1:
+            raise ValueError("the ring length must be >= 1")
+        self._check_tensor(obs, (R, E, N, V, V, 3), torch.uint8, "obs")
+        if not isinstance(obs_in, torch.Tensor):
+            raise ValueError("obs_in must be a uint8 tensor [%d,%d,%d,%d,3]" % (E, N, V, V))
+        self._check_tensor(obs_in, (E, N, V, V, 3), torch.uint8, "obs_in")
+        if R > 1 and (E * N) % 4:
+            raise ValueError("an observation ring of more than one slot needs num_envs * num_agents to be a multiple of 4")
+        for t, dt, shape, name in ((actions, torch.int32, (R, E, N), "actions"), (logp, torch.float32, (R, E, N), "logp"),
+                                   (value, torch.float32, (R, E, N), "value"), (logits, torch.float32, (R, E, N, A), "logits"),
+                                   (rew, torch.int32, (R, E, N), "rew"), (done, torch.uint8, (R, E, N), "done"),
+                                   (last_value, torch.float32, (E, N), "last_value")):
+            if t is not None:
+                if not isinstance(t, torch.Tensor):
+                    raise ValueError("%s must be a tensor" % name)
+                self._check_tensor(t, shape, dt, name)
+        if stats is not None:
+            self._check_stats(stats, rew, n_steps)
+            if done is None:
+                raise ValueError("stats need the call's done flags: pass done")
+        if actions is None:
+            buf = getattr(self, "_policy_actions", None)
+            if buf is None or tuple(buf.shape) != (R, E, N):
+                buf = torch.empty((R, E, N), dtype=torch.int32, device=dev)
+                self._policy_actions = buf
+            actions = buf
+        w = policy.packed()
+        dp = self._dp
+        rc = self._L.ssd_rollout_policy(self._h, dp(w), P, dp(obs_in), n_steps, step0, dp(obs), dp(actions), dp(logp), dp(value),
+                                        dp(logits), dp(rew), dp(done), R, dp(last_value),
+                                        _capi.SSD_POLICY_GREEDY if greedy else 0, self._stream())
+        if rc:
+            _capi.check(rc, self._h)
+        self._count_auto_steps(n_steps)
+        if stats is not None:
+            stats.fold(rew, done, step0=step0, n_steps=n_steps)
+        return actions
+
+    def _count_auto_steps(self, n):
+        """n steps with SSD_AUTO_RESET: while every env started its episode together, they all reach the horizon together."""
+        s, h = self.steps_since_full_reset, getattr(self, "horizon", 0)
+        if s is None:
+            return
+        if h <= 0:
+            self.steps_since_full_reset = s + n
+            return
+        first = max(h - s, 1)                        # steps until the first reset
+        self.steps_since_full_reset = s + n if n < first else (n - first) % h
+
     def rollout_path(self):
         """How the last rollout call was dispatched (ssd_rollout_path): {"aql", "coherent", "split", "fused", "sync", "forked",
         "queue_dropped": bool, "chains": n, "pool": dispatch queues the device's pool settled on, "agent_match": how the HSA agent

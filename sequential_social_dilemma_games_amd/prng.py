@@ -24,6 +24,8 @@ Streams (the `index` word is given in brackets):
     ACTION      [agent]               random-action rollouts (rollout.py:65)
     SEASON      [0]                   Watershed reset, t = 0: the season, randint(draw, 108)
                                       (replaces watershedOrderedComm.py:69; once per (env, episode))
+    POLICY      [agent]               policy rollouts: the sampled action of the conv-FC policy (policy.py), drawn with
+                                      the (episode, t) of the state the action is taken in
 `cell` is `row * W + col`; `t` is 0 for reset and k for the k-th step after it.
 """
 
@@ -40,6 +42,7 @@ S_WASTE_COIN = 5
 S_WASTE_ORDER = 6
 S_ACTION = 7
 S_SEASON = 8
+S_POLICY = 9
 
 
 def mix32(x):
@@ -123,3 +126,20 @@ def random_actions(seed, env_ids, episodes, t, num_agents, num_actions):
     idx = np.arange(num_agents, dtype=np.uint64)[None, :]
     u = mix32_np(pk[:, None] ^ idx)
     return ((u * np.uint64(num_actions)) >> np.uint64(32)).astype(np.int32)
+
+
+def policy_uniforms(seed, env_ids, episodes, t, num_agents):
+    """u = (draw >> 8) * 2^-24 of the POLICY stream, float32 [E, num_agents]: the uniform a policy rollout compares with the
+    cumulative softmax (include/ssd.h).  env_ids are global env indices; episodes, t: the state's, per env (scalars or [E])."""
+    env_ids = np.asarray(env_ids, dtype=np.uint64)
+    episodes = np.broadcast_to(np.asarray(episodes, dtype=np.uint64), env_ids.shape)
+    t = np.broadcast_to(np.asarray(t, dtype=np.uint64), env_ids.shape)
+    h = np.full(env_ids.shape, H0, dtype=np.uint64)
+    h = mix32_np(h ^ np.uint64(seed & M32))
+    h = mix32_np(h ^ np.uint64((seed >> 32) & M32))
+    h = mix32_np(h ^ (env_ids & M32))
+    h = mix32_np(h ^ (episodes & M32))
+    pk = mix32_np(mix32_np(h ^ (t & M32)) ^ np.uint64(S_POLICY))
+    idx = np.arange(num_agents, dtype=np.uint64)[None, :]
+    d = mix32_np(pk[:, None] ^ idx)
+    return ((d >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24)).astype(np.float32)

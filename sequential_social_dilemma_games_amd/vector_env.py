@@ -147,6 +147,42 @@ class SSDVectorEnv(object):
         self._advance()
         return self._wrap(obs, self._act_buf, done if self.horizon > 0 else None), rew, done
 
+    def sample(self, policy, n_steps, greedy=False):
+        """n_steps closed-loop steps of a ConvFCPolicy on the device in one call (VecEngine.rollout_policy): returns a dict of
+        device tensors obs u8 [K,E,N,15,15,3], actions i32, logp f32, value f32, rew i32, done u8 (all [K,E,N], step k in row
+        k) and last_value f32 [E,N] (the value of the final observation).  Episodes end at the horizon as in step(): a finished
+        env's obs row is its next episode's first.  Afterwards the adapter is where n_steps calls of step() with the sampled
+        actions would have left it; track_episodes keeps counting.  With n_steps > 1, num_envs * num_agents must be a multiple
+        of 4.  Not for float32_obs or return_agent_actions adapters."""
+        import torch
+        if self.float32_obs:
+            raise ValueError("sample() records uint8 observations: construct with float32_obs=False")
+        if self.return_agent_actions:
+            raise ValueError("sample() does not build the agent-action observation extras: construct with return_agent_actions=False")
+        n_steps = int(n_steps)
+        if n_steps < 1:
+            raise ValueError("n_steps must be >= 1")
+        eng = self.engine
+        eng._policy_weights(policy)                  # (every check before anything is enqueued)
+        E, N, V = self.num_envs, self.num_agents, eng.V
+        if n_steps > 1 and (E * N) % 4:
+            raise ValueError("an observation ring of more than one slot needs num_envs * num_agents to be a multiple of 4")
+        if self._out is None:
+            self.reset()
+        dev = self._out[1].device
+        out = {"obs": torch.empty((n_steps, E, N, V, V, 3), dtype=torch.uint8, device=dev),
+               "actions": torch.empty((n_steps, E, N), dtype=torch.int32, device=dev),
+               "logp": torch.empty((n_steps, E, N), dtype=torch.float32, device=dev),
+               "value": torch.empty((n_steps, E, N), dtype=torch.float32, device=dev),
+               "rew": torch.empty((n_steps, E, N), dtype=torch.int32, device=dev),
+               "done": torch.empty((n_steps, E, N), dtype=torch.uint8, device=dev),
+               "last_value": torch.empty((E, N), dtype=torch.float32, device=dev)}
+        self._fold()                                 # the adapter's own ring first: episodes are folded in step order
+        eng.rollout_policy(policy, self._out[0], n_steps, out["obs"], actions=out["actions"], logp=out["logp"], value=out["value"],
+                           rew=out["rew"], done=out["done"], last_value=out["last_value"], greedy=greedy, stats=self.stats)
+        self._out[0].copy_(out["obs"][n_steps - 1])  # the current observation, as step() would have left it
+        return out
+
     @staticmethod
     def to_float(obs):
         """uint8 [E,N,V,V,3] -> float32 NHWC batch [(E*N),V,V,3] with the reference's scaling
