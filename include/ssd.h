@@ -194,7 +194,8 @@ int ssd_rollout_path(const ssd_env *env);
  * THE QUEUE RULE.  A process has about four hardware queues before the device time-slices them, and past that EVERY kernel launch
  * of the process -- the host application's too -- takes ~30 us.  The HIP runtime takes up to GPU_MAX_HW_QUEUES of them (default 4,
  * one per stream in use), RCCL one more stream.  So: the library's pool holds SSD_AQL_QUEUES queues (1..3) if that is set; else
- * 4 - GPU_MAX_HW_QUEUES if the process sets that variable for the HIP runtime (at least 1); else 2.  And whatever the rule says,
+ * 4 - GPU_MAX_HW_QUEUES if the process holds the HIP runtime to 1, 2 or 3 queues; else 2 -- GPU_MAX_HW_QUEUES unset, 4 (the
+ * runtime's own default, which it fills lazily, as streams need queues) or more, 0 or unparsable.  And whatever the rule says,
  * every queue is PROBED when it is created (first rollout call that needs it; the device is synchronised once).  The cliff is about
  * queues that are ACTIVE at the same time, so the probe is a rollout in miniature: 16 dependent one-wave dispatches on every queue
  * of the pool at once, joined through the null stream the way a rollout call is joined, timed against the pool's first queue

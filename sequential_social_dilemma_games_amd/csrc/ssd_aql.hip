@@ -47,6 +47,7 @@
 #include "ssd_internal.hpp"
 #include "ssd_aql.hpp"
 #include "ssd_agent_match.hpp"
+#include "ssd_queue_budget.hpp"
 
 extern "C" const unsigned char ssd_kernels_bundle[];        // ssd_codeobj.S: the clang offload bundle of ssd_kernels.o
 extern "C" const unsigned char ssd_kernels_bundle_end[];
@@ -378,21 +379,15 @@ static Queue *queue_create(DeviceCtx *c) {
 // time-slicing them (every dispatch then waits for its queue's turn: a 20-step rollout that follows an RCCL barrier 320 us instead of
 // 130; measured: the HIP runtime's queues in use + the library's = 4 fine, 5 not -- with 4 queues of the library's beside the
 // runtime's, idle ones included, EVERY launch of the process slowed to ~30 us).  The HIP runtime maps its streams onto at most
-// GPU_MAX_HW_QUEUES queues (default 4, created as streams need them).  The rule (documented in include/ssd.h):
-//   * SSD_AQL_QUEUES (1..3) sets the pool's size;
-//   * else a process that sets GPU_MAX_HW_QUEUES -- bench.py does, to 2, as a rank of a process group -- has told us how many the
-//     runtime takes: the pool gets 4 minus that, at least 1;
-//   * else TWO: a host application with a few torch streams and RCCL's has room for them, not for three;
-//   * and whatever the rule says, a queue that fails its probe when it is created (below) is destroyed again and the pool stays
-//     at the size that was fine (pool_size(device)).
+// GPU_MAX_HW_QUEUES queues (default 4, created as streams need them).  The rule is ssd_queue_budget.hpp's queue_pool_limit()
+// (documented in include/ssd.h): SSD_AQL_QUEUES (1..3) if set; else 4 - GPU_MAX_HW_QUEUES when the process holds the runtime to
+// 1..3 queues; else TWO -- an exported 4, HIP's own default, included.  And whatever the rule says, a queue that fails its probe
+// when it is created (below) is destroyed again and the pool stays at the size that was fine (pool_size(device)).
 static int pool_limit() {
     static const int n = [] {
-        int v = 2;
-        if (const char *h = getenv("GPU_MAX_HW_QUEUES")) { const int hq = atoi(h); if (hq >= 1) v = 4 - hq; }
-        if (const char *o = getenv("SSD_AQL_QUEUES")) v = atoi(o);
         int top = SSD_HOOK("SSD_AQL_POOL_MAX", kPoolQueues);
         top = top < 1 ? 1 : top > kPoolSlots ? kPoolSlots : top;
-        return v < 1 ? 1 : v > top ? top : v;
+        return queue_pool_limit(getenv("GPU_MAX_HW_QUEUES"), getenv("SSD_AQL_QUEUES"), top);
     }();
     return n;
 }

@@ -931,7 +931,7 @@ static int rollout_aql(ssd_env *env, int chains, const ChainJob *jobs, hipStream
     static const bool alternate = SSD_HOOK("SSD_AQL_ALTERNATE", 0) != 0;
     // (measured, us per step: 2048 envs per launch 5.5 split / 5.9 coherent / 6.2 plain; 2730: 9.7 / 8.6 / 8.7; 5461: 19.1 / 15.2 /
     // 14.3 -- once a launch is several rounds of waves the kernel is bandwidth-bound, and re-reading state from an L2 that still
-    // holds it beats fetching it from memory: coherent chains up to 4096 envs per launch, split ones up to 2304)
+    // holds it beats fetching it from memory: coherent chains up to 4096 envs per launch, split ones up to 2304 -- 3072 in a single chain, below)
     const int per_launch = (env->E + chains - 1) / chains;
     // (an explicit action order takes the general kernels: no coherent variant)
     const bool coherent = env_coh != 0 && !key.f32 && !key.order && ssd::fast_profile(env->p, env->game) > 0 && per_launch <= 4096;
@@ -945,8 +945,12 @@ static int rollout_aql(ssd_env *env, int chains, const ChainJob *jobs, hipStream
     // launches per step in one queue -- step, then an observe launch beside the next step -- do not work: kernels of one queue run
     // one after the other on this device even without the barrier bit: two chains' launches in ONE queue take 10.6 us per step, in
     // two queues 5.8.)  SSD_AQL_SPLIT=0 turns it off.
+    // The split cap depends on the chains: with two chains of 2730 envs the split launches no longer fit one round of waves, hence
+    // 2304; a single chain (a pool of one queue) gains from splitting up to 3072 envs and loses at 4096 (measured, Harvest, us per
+    // step split / unsplit: 3072 envs 4.88 / 6.30, 4096 envs 6.96 / 6.54; profiles/r05_ab/).
     static const int env_split = SSD_KNOB("SSD_AQL_SPLIT", 1);
-    key.split = (coherent && env_split != 0 && j0.obs != nullptr && per_launch <= 2304) ? 1 : 0;   // (the argument set holds both forms' launches)
+    const int split_cap = chains == 1 ? 3072 : 2304;
+    key.split = (coherent && env_split != 0 && j0.obs != nullptr && per_launch <= split_cap) ? 1 : 0;   // (the argument set holds both forms' launches)
     const bool split = key.split && j0.n_steps >= 4;
     // (a split set holds its launches for both orientations of the state pair; any other set names the buffer that is current now)
     key.world = key.split ? nullptr : env->p.world;
