@@ -480,6 +480,56 @@ int ssd_rollout_policy(ssd_env *env, const float *weights, int32_t num_sets, con
                        uint8_t *obs, int32_t *actions, float *logp, float *value, float *logits, int32_t *rew, uint8_t *done,
                        int32_t ring, float *last_value, uint32_t flags, void *stream);
 
+/* ======================================================================================================================
+ * RECURRENT POLICY ROLLOUTS -- the policy the reference's Harvest / Cleanup baseline trains (run_scripts/train_baseline.py:146-147,
+ * "use_lstm": True): the trunk above (conv, fc1, fc2) wrapped by RLlib 0.7.6's LSTM, the model of Jaques et al. 2019
+ * (csrc/ssd_policy_lstm.hip).  Exact float32 throughout.
+ *
+ * Per weight set, with x = fc2's output (32 floats, after its ReLU) and a state (c, h) of C cells, C = 64, 128 or 256:
+ *   z = [x, h] @ lstm_w + lstm_b               lstm_w [32 + C][4C] (the x rows first, then the h rows), lstm_b [4C]
+ *   i, j, f, o = the column blocks z[0:C], z[C:2C], z[2C:3C], z[3C:4C]     (TF's LSTMCell / BasicLSTMCell order)
+ *   c' = sigmoid(f + 1) * c + sigmoid(i) * tanh(j)                      (forget bias 1.0; no peepholes, no projection)
+ *   h' = sigmoid(o) * tanh(c')
+ *   logits = h' @ logits_w + logits_b          value = h' @ value_w + value_b      (both heads on the LSTM output)
+ * The trunk's own logits and value heads are not used (RLlib's wrapper reads the inner model's last layer).  A state is f32
+ * [.., 2, C]: c at index 0, h at index 1 (RLlib's state_init order).
+ * Start rule: the state a step uses is zero where the env is at the start of an episode -- the env's t is 0 in a rollout (after
+ * a reset, a masked reset or an automatic reset), starts[row] != 0 in the forward.  Such a row of the state is never read.
+ * A weight set holds the trunk at SSD_POL_CONV_W ... SSD_POL_FC2_B, then the blocks below, each on a 64-float boundary (every
+ * matrix [in][out]); a buffer holds P sets, set p at p * SSD_LSTM_SET_FLOATS(C, A):
+ *   lstm_w [32 + C][4C]   lstm_b [4C]   value_w [C]   value_b [1]   logits_w [C][A]   logits_b [A]
+ * ====================================================================================================================== */
+enum { SSD_LSTM_W = 33728, SSD_LSTM_X = 32, SSD_LSTM_MAX_CELLS = 256 };
+#define SSD_LSTM_ALIGN(n) (((n) + 63) / 64 * 64)
+#define SSD_LSTM_B(C) SSD_LSTM_ALIGN(SSD_LSTM_W + (32 + (C)) * 4 * (C))
+#define SSD_LSTM_VALUE_W(C) SSD_LSTM_ALIGN(SSD_LSTM_B(C) + 4 * (C))
+#define SSD_LSTM_VALUE_B(C) SSD_LSTM_ALIGN(SSD_LSTM_VALUE_W(C) + (C))
+#define SSD_LSTM_LOGITS_W(C) SSD_LSTM_ALIGN(SSD_LSTM_VALUE_B(C) + 1)
+#define SSD_LSTM_LOGITS_B(C, A) SSD_LSTM_ALIGN(SSD_LSTM_LOGITS_W(C) + (C) * (A))
+#define SSD_LSTM_SET_FLOATS(C, A) SSD_LSTM_ALIGN(SSD_LSTM_LOGITS_B(C, A) + (A))
+
+/* The recurrent forward pass alone (device pointers on device_id, enqueued on `stream`): obs u8 [B,N,15,15,3] and state_in f32
+ * [B,N,2,C] -> features f32 [B,N,32] (fc2's output; caller-supplied scratch, required), state_out f32 [B,N,2,C], logits f32
+ * [B,N,A], value f32 [B,N].  state_out, logits and value may be NULL; state_out may equal state_in (updated in place) but must
+ * not overlap it otherwise.  starts: u8 [B,N] or NULL (no row starts).  weights: P sets as above (P = 1 or N), 4-byte
+ * aligned.  flags: 0.  Bad arguments: SSD_E_INVALID before anything is launched (ssd_policy_last_error says why). */
+int ssd_policy_lstm_forward(const float *weights, int32_t num_sets, int32_t num_actions, int32_t cell_size, const uint8_t *obs,
+                            const float *state_in, const uint8_t *starts, int32_t batch, int32_t num_agents, float *features,
+                            float *state_out, float *logits, float *value, int32_t device_id, uint32_t flags, void *stream);
+
+/* ssd_rollout_policy with the recurrent network: the same rings, sampling contract, flags and step order, and besides
+ *   state f32 [E,N,2,C]: the carried state, read and updated in place by every step (zero at every episode start, above);
+ *   state_ring f32 [S,E,N,2,C] or NULL: for call-relative k = 0, state_every, 2 state_every, ... slot k / state_every receives
+ *     the state step k used (after the start rule).  state_every >= 1 and S >= ceil(n_steps / state_every);
+ *   features f32 [E,N,32]: caller-supplied scratch (the call allocates nothing and does not synchronise).
+ * last_value is the value of the final observation under the final state; that pass leaves the carried state as it is.
+ * Three hipLaunchKernel launches per step on `stream` (plus two for last_value). */
+int ssd_rollout_policy_lstm(ssd_env *env, const float *weights, int32_t num_sets, int32_t cell_size, const uint8_t *obs_in,
+                            int32_t n_steps, int32_t step0, float *state, float *state_ring, int32_t state_ring_len,
+                            int32_t state_every, float *features, uint8_t *obs, int32_t *actions, float *logp, float *value,
+                            float *logits, int32_t *rew, uint8_t *done, int32_t ring, float *last_value, uint32_t flags,
+                            void *stream);
+
 #ifdef __cplusplus
 }
 #endif

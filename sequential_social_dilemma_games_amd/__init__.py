@@ -5,6 +5,7 @@
     from sequential_social_dilemma_games_amd import WatershedSeqEnv, WatershedSeqCommEnv, WatershedVecEngine
     from sequential_social_dilemma_games_amd import EpisodeStats                # per-episode returns and social metrics
     from sequential_social_dilemma_games_amd import ConvFCPolicy                # the conv-FC policy net, run in the loop
+    from sequential_social_dilemma_games_amd import ConvLSTMPolicy              # the same trunk under the baseline's LSTM
 
 Everything that steps an env goes through libssd_hip.so (include/ssd.h); importing this package does
 not load it, constructing an env does -- and fails loudly if it is missing.
@@ -28,9 +29,9 @@ def __getattr__(name):
     if name == "EpisodeStats":
         from .episode_stats import EpisodeStats
         return EpisodeStats
-    if name == "ConvFCPolicy":
-        from .policy import ConvFCPolicy
-        return ConvFCPolicy
+    if name in ("ConvFCPolicy", "ConvLSTMPolicy"):
+        from . import policy
+        return getattr(policy, name)
     if name == "MapEnv":
         from .map_env import MapEnv
         return MapEnv

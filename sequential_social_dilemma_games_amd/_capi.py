@@ -37,6 +37,39 @@ def SSD_POL_SET_FLOATS(num_actions):
     return (SSD_POL_LOGITS_W + 33 * int(num_actions) + 63) // 64 * 64
 
 
+# the recurrent policy's weight layout (include/ssd.h, SSD_LSTM_*): the trunk at the SSD_POL_* offsets, then these blocks
+SSD_LSTM_W, SSD_LSTM_X, SSD_LSTM_MAX_CELLS = 33728, 32, 256
+LSTM_CELL_SIZES = (64, 128, 256)
+
+
+def SSD_LSTM_ALIGN(n):
+    return (int(n) + 63) // 64 * 64
+
+
+def SSD_LSTM_B(C):
+    return SSD_LSTM_ALIGN(SSD_LSTM_W + (32 + int(C)) * 4 * int(C))
+
+
+def SSD_LSTM_VALUE_W(C):
+    return SSD_LSTM_ALIGN(SSD_LSTM_B(C) + 4 * int(C))
+
+
+def SSD_LSTM_VALUE_B(C):
+    return SSD_LSTM_ALIGN(SSD_LSTM_VALUE_W(C) + int(C))
+
+
+def SSD_LSTM_LOGITS_W(C):
+    return SSD_LSTM_ALIGN(SSD_LSTM_VALUE_B(C) + 1)
+
+
+def SSD_LSTM_LOGITS_B(C, A):
+    return SSD_LSTM_ALIGN(SSD_LSTM_LOGITS_W(C) + int(C) * int(A))
+
+
+def SSD_LSTM_SET_FLOATS(C, A):
+    return SSD_LSTM_ALIGN(SSD_LSTM_LOGITS_B(C, A) + int(A))
+
+
 # every symbol include/ssd.h declares
 SYMBOLS = ("ssd_create", "ssd_destroy", "ssd_reset", "ssd_step", "ssd_step_random", "ssd_rollout_random", "ssd_rollout_actions", "ssd_rollout_path", "ssd_set_rollout_chains",
            "ssd_profiler_attached", "ssd_observe",
@@ -45,7 +78,10 @@ SYMBOLS = ("ssd_create", "ssd_destroy", "ssd_reset", "ssd_step", "ssd_step_rando
            "ssd_ws_create", "ssd_ws_destroy", "ssd_ws_reset", "ssd_ws_step", "ssd_ws_rollout_actions", "ssd_ws_info", "ssd_ws_get_state",
            "ssd_ws_set_state", "ssd_ws_device_status", "ssd_ws_last_error",
            "ssd_stats_create", "ssd_stats_destroy", "ssd_stats_fold", "ssd_stats_set_chunk", "ssd_stats_discard", "ssd_stats_drain",
-           "ssd_stats_last_error", "ssd_policy_forward", "ssd_policy_last_error", "ssd_rollout_policy")
+           "ssd_stats_last_error", "ssd_policy_forward", "ssd_policy_last_error", "ssd_rollout_policy",
+           "ssd_policy_lstm_forward", "ssd_rollout_policy_lstm")
+# added after ABI 6 without a version bump (the calls are additive): a library built before them lacks them
+LSTM_SYMBOLS = ("ssd_policy_lstm_forward", "ssd_rollout_policy_lstm")
 
 
 class SsdConfig(C.Structure):
@@ -158,6 +194,12 @@ def lib():
         L.ssd_policy_last_error.argtypes = []
         L.ssd_policy_last_error.restype = C.c_char_p
         L.ssd_rollout_policy.argtypes = [vp, vp, i32, vp, i32, i32] + [vp] * 7 + [i32, vp, u32, vp]
+        missing = [name for name in LSTM_SYMBOLS if not hasattr(L, name)]
+        if missing:
+            raise SsdError("%s lacks %s (built before the recurrent policy calls): rebuild it with `python -c 'import "
+                           "__graft_entry__ as g; g.build()'`" % (LIB_PATH, ", ".join(missing)))
+        L.ssd_policy_lstm_forward.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, u32, vp]
+        L.ssd_rollout_policy_lstm.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, vp, i32, i32] + [vp] * 8 + [i32, vp, u32, vp]
         for name in SYMBOLS:
             getattr(L, name)
         if L.ssd_abi_version() != ABI_VERSION:

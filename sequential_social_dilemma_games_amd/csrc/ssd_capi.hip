@@ -1520,6 +1520,70 @@ int ssd_rollout_policy(ssd_env *env, const float *weights, int32_t num_sets, con
     return SSD_OK;
 }
 
+int ssd_rollout_policy_lstm(ssd_env *env, const float *weights, int32_t num_sets, int32_t cell_size, const uint8_t *obs_in,
+                            int32_t n_steps, int32_t step0, float *state, float *state_ring, int32_t state_ring_len,
+                            int32_t state_every, float *features, uint8_t *obs, int32_t *actions, float *logp, float *value,
+                            float *logits, int32_t *rew, uint8_t *done, int32_t ring, float *last_value, uint32_t flags,
+                            void *stream) {
+    if (!env) return SSD_E_INVALID;
+    auto bad = [&](const char *msg) { env->err = msg; return SSD_E_INVALID; };
+    const int A = env->game == SSD_GAME_HARVEST ? 8 : 9;        // harvest.py:44, cleanup.py:70
+    if (env->view_len != 7 || env->V != SSD_POL_VIEW) return bad("policy rollouts need view_len 7 (15 x 15 observations)");
+    if (env->N < 1) return bad("policy rollouts need at least one agent");
+    if (!weights || !obs_in || !obs || !actions || !state || !features)
+        return bad("weights, obs_in, obs, actions, state and features are required");
+    if (reinterpret_cast<uintptr_t>(weights) & 3u) return bad("weights must be 4-byte aligned");
+    if (cell_size != 64 && cell_size != 128 && cell_size != 256) return bad("cell_size must be 64, 128 or 256");
+    if (num_sets != 1 && num_sets != env->N) return bad("num_sets must be 1 or num_agents");
+    if (n_steps < 1) return bad("n_steps must be >= 1");
+    if (ring < 1) return bad("ring must be >= 1");
+    if (step0 < 0) return bad("step0 must be >= 0");
+    if (state_ring) {
+        if (state_every < 1) return bad("state_every must be >= 1");
+        if ((int64_t)state_ring_len * state_every < n_steps) return bad("the state ring needs ceil(n_steps / state_every) slots");
+    }
+    if (flags & ~(uint32_t)SSD_POLICY_GREEDY) return bad("flags: only the greedy-policy bit is defined");
+    const size_t en = (size_t)env->E * env->N, ob = en * SSD_POL_VIEW * SSD_POL_VIEW * 3, sn = en * 2 * cell_size;
+    if (reinterpret_cast<uintptr_t>(obs) & 3u) return bad("obs must be 4-byte aligned");
+    if (ring > 1 && (ob & 3u)) return bad("an observation ring of more than one slot needs E * N to be a multiple of 4 (4-byte aligned slots)");
+    {
+        int cur = -1;
+        if (hipGetDevice(&cur) != hipSuccess || cur != env->device) SSD_HIP(env, hipSetDevice(env->device));
+    }
+    ssd::PolicyArgs tr{};                       // the trunk, features mode
+    tr.w = weights; tr.P = num_sets; tr.A = A; tr.B = env->E; tr.N = env->N; tr.set_floats = SSD_LSTM_SET_FLOATS(cell_size, A);
+    tr.feat = features;
+    ssd::LstmArgs la{};
+    la.w = weights; la.P = num_sets; la.A = A; la.B = env->E; la.N = env->N; la.C = cell_size; la.set_floats = tr.set_floats;
+    la.feat = features; la.state_in = state; la.state_out = state;
+    la.hdr = env->p.hdr; la.seed_lo = env->p.seed_lo; la.seed_hi = env->p.seed_hi; la.env_base = env->p.env_base;
+    la.greedy = (flags & SSD_POLICY_GREEDY) ? 1 : 0;
+    size_t slot = 0;
+    for (int32_t k = 0; k < n_steps; ++k) {
+        const size_t prev = slot;
+        slot = (size_t)(((int64_t)step0 + k) % ring);
+        tr.obs = k == 0 ? obs_in : obs + prev * ob;
+        SSD_HIP(env, ssd::launch_policy_features(tr, stream));
+        la.state_used = state_ring && k % state_every == 0 ? state_ring + (size_t)(k / state_every) * sn : nullptr;
+        la.actions = actions + slot * en;
+        la.logp = logp ? logp + slot * en : nullptr;
+        la.value = value ? value + slot * en : nullptr;
+        la.logits = logits ? logits + slot * en * A : nullptr;
+        SSD_HIP(env, ssd::launch_policy_lstm(la, stream));
+        const int rc = run(env, ssd::kModeStepAuto, la.actions, nullptr, nullptr, 0, nullptr, obs + slot * ob, rew ? rew + slot * en : nullptr,
+                           done ? done + slot * en : nullptr, 1, 0, stream);
+        if (rc) return rc;
+    }
+    if (last_value) {                           // the final observation under the final state; the state stays as it is
+        tr.obs = obs + slot * ob;
+        SSD_HIP(env, ssd::launch_policy_features(tr, stream));
+        la.state_out = nullptr; la.state_used = nullptr;
+        la.actions = nullptr; la.logp = nullptr; la.logits = nullptr; la.value = last_value;
+        SSD_HIP(env, ssd::launch_policy_lstm(la, stream));
+    }
+    return SSD_OK;
+}
+
 int ssd_rollout_path(const ssd_env *env) { return env ? env->last_path : SSD_E_INVALID; }
 
 int ssd_set_rollout_chains(ssd_env *env, int32_t chains) {

@@ -11,7 +11,8 @@
 //      are added through LDS.  fc1's weights stream from L2 (130 KB per set, shared by every workgroup of the set);
 //   4. fc2, the logits and the value on the VALU (1.3 kMAC per env);
 //   5. rollouts: one thread per env picks the action (greedy or the S_POLICY draw) and its log-probability.
-// Every sum is in a fixed order, so two calls on the same input agree bit for bit.
+// Every sum is in a fixed order, so two calls on the same input agree bit for bit.  The <true> instantiation stops after fc2
+// and writes its output instead: the trunk of the recurrent policy (ssd_policy_lstm.hip).
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -40,23 +41,8 @@ static_assert(SSD_POL_FC1_B == SSD_POL_FC1_W + kFlat * 32 && SSD_POL_FC2_W == SS
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// shared PRNG (prng.py): the triple32 chain of ssd_kernels.hip
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-    x ^= x >> 17; x *= 0xED5AD4BBu;
-    x ^= x >> 11; x *= 0xAC4C1B51u;
-    x ^= x >> 15; x *= 0x31848BABu;
-    x ^= x >> 14;
-    return x;
-}
-__device__ __forceinline__ uint32_t env_key(uint32_t seed_lo, uint32_t seed_hi, uint32_t env, uint32_t episode) {
-    uint32_t h = 0x243F6A88u;
-    h = mix32(h ^ seed_lo);
-    h = mix32(h ^ seed_hi);
-    h = mix32(h ^ env);
-    h = mix32(h ^ episode);
-    return h;
-}
-
+// kFeatures: stop after fc2 and write its output to a.feat (the trunk of the recurrent policy, ssd_policy_lstm.hip)
+template <bool kFeatures>
 __global__ void __launch_bounds__(kThreads) ssd_policy_kernel(ssd::PolicyArgs a) {
     __shared__ float s_norm[256];
     __shared__ float s_conv[kTile * kPitch];
@@ -157,9 +143,15 @@ __global__ void __launch_bounds__(kThreads) ssd_policy_kernel(ssd::PolicyArgs a)
             float s = 0.f;
 #pragma unroll 8
             for (int k = 0; k < 32; ++k) s = fmaf(s_h1[m * kHP + k], w[SSD_POL_FC2_W + k * 32 + nn], s);
-            s_h2[m * kHP + nn] = fmaxf(s + w[SSD_POL_FC2_B + nn], 0.f);
+            const float hv = fmaxf(s + w[SSD_POL_FC2_B + nn], 0.f);
+            if (kFeatures) {
+                if (b0 + m < B) a.feat[((size_t)(b0 + m) * N + i) * 32 + nn] = hv;
+            } else {
+                s_h2[m * kHP + nn] = hv;
+            }
         }
     }
+    if (kFeatures) return;
     __syncthreads();
     {
         const int m = tid >> 4, j = tid & 15, b = b0 + m;
@@ -187,29 +179,12 @@ __global__ void __launch_bounds__(kThreads) ssd_policy_kernel(ssd::PolicyArgs a)
     // ---- 5. the action: argmax, or the first a with u < cumulative softmax (include/ssd.h) ----
     if (tid < kTile && b0 + tid < B) {
         const int b = b0 + tid;
-        const float *l = s_out + tid * 16;
-        float mx = l[0];
-        int arg = 0;
-        for (int k = 1; k < A; ++k)
-            if (l[k] > mx) { mx = l[k]; arg = k; }
-        float s = 0.f;
-        for (int k = 0; k < A; ++k) s += expf(l[k] - mx);
-        int act = arg;
-        if (!a.greedy) {
-            const uint4 h = a.hdr[b];                       // {key, t, episode, ...} of the state the action is taken in
-            const uint32_t key = env_key(a.seed_lo, a.seed_hi, a.env_base + (uint32_t)b, h.z);
-            const uint32_t pk = mix32(mix32(key ^ h.y) ^ (uint32_t)SSD_S_POLICY);
-            const float u = (float)(mix32(pk ^ (uint32_t)i) >> 8) * 0x1p-24f;
-            act = A - 1;
-            float c = 0.f;
-            for (int k = 0; k < A; ++k) {
-                c += expf(l[k] - mx) / s;
-                if (u < c) { act = k; break; }
-            }
-        }
+        float lp;
+        const int act = ssd::policy_pick(s_out + tid * 16, A, a.greedy, a.greedy ? uint4{} : a.hdr[b], a.seed_lo, a.seed_hi,
+                                         a.env_base + (uint32_t)b, (uint32_t)i, &lp);
         const size_t row = (size_t)b * N + i;
         a.actions[row] = act;
-        if (a.logp) a.logp[row] = l[act] - (mx + logf(s));
+        if (a.logp) a.logp[row] = lp;
     }
 }
 
@@ -226,9 +201,18 @@ namespace ssd {
 
 hipError_t launch_policy(const PolicyArgs &a, void *stream) {
     const dim3 grid((unsigned)((a.B + kTile - 1) / kTile), (unsigned)a.N), block(kThreads);
-    hipLaunchKernelGGL(ssd_policy_kernel, grid, block, 0, static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(ssd_policy_kernel<false>, grid, block, 0, static_cast<hipStream_t>(stream), a);
     return hipGetLastError();
 }
+
+hipError_t launch_policy_features(const PolicyArgs &a, void *stream) {
+    const dim3 grid((unsigned)((a.B + kTile - 1) / kTile), (unsigned)a.N), block(kThreads);
+    hipLaunchKernelGGL(ssd_policy_kernel<true>, grid, block, 0, static_cast<hipStream_t>(stream), a);
+    return hipGetLastError();
+}
+
+int policy_fail(const char *msg) { return fail(msg); }
+void policy_set_error(const char *msg) { g_policy_error = msg; }
 
 }  // namespace ssd
 

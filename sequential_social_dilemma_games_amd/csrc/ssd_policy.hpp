@@ -1,13 +1,17 @@
-// csrc/ssd_policy.hpp -- the policy kernel's argument block, shared by ssd_policy.hip (kernel, ssd_policy_forward) and
-// ssd_capi.hip (ssd_rollout_policy, which interleaves it with the step kernel).
+// csrc/ssd_policy.hpp -- the policy kernels' argument blocks and the action selection they share, used by ssd_policy.hip (trunk
+// kernel, ssd_policy_forward), ssd_policy_lstm.hip (recurrent cell, ssd_policy_lstm_forward) and ssd_capi.hip (the rollouts, which
+// interleave them with the step kernel).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
+
+#include "../../include/ssd.h"
 
 namespace ssd {
 
 struct PolicyArgs {
-    const float *w;                // P weight sets of set_floats floats each (include/ssd.h, SSD_POL_*)
+    const float *w;                // P weight sets of set_floats floats each (include/ssd.h, SSD_POL_* / SSD_LSTM_*)
     int32_t P, A, B, N, set_floats;
     const uint8_t *obs;            // u8 [B][N][15][15][3]
     float *logits;                 // [B][N][A] or null
@@ -18,9 +22,73 @@ struct PolicyArgs {
     const uint4 *hdr;              // [B] the engine's per-env header {key, t, episode, ...}: (episode, t) of the state acted in
     uint32_t seed_lo, seed_hi, env_base;
     int32_t greedy;
+    float *feat;                   // launch_policy_features only: fc2's output [B][N][32] (the heads are not computed)
+};
+
+struct LstmArgs {
+    const float *w;                // P weight sets of set_floats floats each (SSD_LSTM_SET_FLOATS(C, A))
+    int32_t P, A, B, N, C, set_floats;
+    const float *feat;             // [B][N][32] the trunk's output
+    const float *state_in;         // [B][N][2][C]
+    float *state_out;              // [B][N][2][C], null, or state_in itself
+    float *state_used;             // [B][N][2][C] the state the step used (after the start rule), or null
+    const uint8_t *starts;         // [B][N] start rows (the forward), or null
+    const uint4 *hdr;              // [B] start where t == 0 (rollouts), or null; also (episode, t) of the action draw
+    float *logits;                 // [B][N][A] or null
+    float *value;                  // [B][N] or null
+    int32_t *actions;              // [B][N] or null (no action selection)
+    float *logp;                   // [B][N] or null
+    uint32_t seed_lo, seed_hi, env_base;
+    int32_t greedy;
 };
 
 // hipLaunchKernel of the policy kernel on `stream` (arguments already checked); returns the launch's error code.
 hipError_t launch_policy(const PolicyArgs &a, void *stream);
+// The same kernel up to fc2: writes a.feat instead of the heads (logits, value, actions unused).
+hipError_t launch_policy_features(const PolicyArgs &a, void *stream);
+// The recurrent cell and heads (ssd_policy_lstm.hip); a.C in {64, 128, 256}.
+hipError_t launch_policy_lstm(const LstmArgs &a, void *stream);
+// The calling thread's ssd_policy_last_error text; returns SSD_E_INVALID.
+int policy_fail(const char *msg);
+void policy_set_error(const char *msg);
+
+// shared PRNG (prng.py): the triple32 chain of ssd_kernels.hip
+__device__ __forceinline__ uint32_t pol_mix32(uint32_t x) {
+    x ^= x >> 17; x *= 0xED5AD4BBu;
+    x ^= x >> 11; x *= 0xAC4C1B51u;
+    x ^= x >> 15; x *= 0x31848BABu;
+    x ^= x >> 14;
+    return x;
+}
+
+// The action of agent i of env b from its logits l[0..A-1]: argmax (greedy), or the first a with u < cumulative softmax, u from
+// the S_POLICY draw of the env's (episode, t) in h = hdr[b] (include/ssd.h); *logp its log-probability.
+__device__ __forceinline__ int policy_pick(const float *l, int A, int greedy, uint4 h, uint32_t seed_lo, uint32_t seed_hi,
+                                           uint32_t env, uint32_t i, float *logp) {
+    float mx = l[0];
+    int arg = 0;
+    for (int k = 1; k < A; ++k)
+        if (l[k] > mx) { mx = l[k]; arg = k; }
+    float s = 0.f;
+    for (int k = 0; k < A; ++k) s += expf(l[k] - mx);
+    int act = arg;
+    if (!greedy) {
+        uint32_t key = 0x243F6A88u;
+        key = pol_mix32(key ^ seed_lo);
+        key = pol_mix32(key ^ seed_hi);
+        key = pol_mix32(key ^ env);
+        key = pol_mix32(key ^ h.z);
+        const uint32_t pk = pol_mix32(pol_mix32(key ^ h.y) ^ (uint32_t)SSD_S_POLICY);
+        const float u = (float)(pol_mix32(pk ^ i) >> 8) * 0x1p-24f;
+        act = A - 1;
+        float c = 0.f;
+        for (int k = 0; k < A; ++k) {
+            c += expf(l[k] - mx) / s;
+            if (u < c) { act = k; break; }
+        }
+    }
+    *logp = l[act] - (mx + logf(s));
+    return act;
+}
 
 }  // namespace ssd

@@ -306,11 +306,12 @@ class VecEngine(object):
 
     # ------------------------------------------------------------------ policy in the loop (include/ssd.h, POLICY ROLLOUTS)
     def _policy_weights(self, policy):
-        """Checks a ConvFCPolicy against this engine (everything before anything is enqueued); returns its weight-set count."""
-        from .policy import ConvFCPolicy
+        """Checks a ConvFCPolicy or ConvLSTMPolicy against this engine (everything before anything is enqueued); returns its
+        weight-set count."""
+        from .policy import ConvFCPolicy, ConvLSTMPolicy
         torch, dev = self._torch()
-        if not isinstance(policy, ConvFCPolicy):
-            raise ValueError("policy must be a ConvFCPolicy")
+        if not isinstance(policy, (ConvFCPolicy, ConvLSTMPolicy)):
+            raise ValueError("policy must be a ConvFCPolicy or a ConvLSTMPolicy")
         if self.V != _capi.SSD_POL_VIEW:
             raise ValueError("the policy network takes 15 x 15 views (view_len 7); this engine has V = %d" % self.V)
         if policy.num_actions != self.num_actions:
@@ -323,9 +324,25 @@ class VecEngine(object):
             raise ValueError("a policy needs at least one agent")
         return policy.num_sets
 
-    def policy_forward(self, policy, obs):
+    @staticmethod
+    def _is_recurrent(policy):
+        from .policy import ConvLSTMPolicy
+        return isinstance(policy, ConvLSTMPolicy)
+
+    def _features(self, rows):
+        """The engine's trunk-feature scratch of the recurrent policy: f32 [rows, 32], reused between calls."""
+        torch, dev = self._torch()
+        buf = getattr(self, "_feat_buf", None)
+        if buf is None or buf.shape[0] < rows:
+            buf = torch.empty((rows, _capi.SSD_LSTM_X), dtype=torch.float32, device=dev)
+            self._feat_buf = buf
+        return buf
+
+    def policy_forward(self, policy, obs, state=None, starts=None):
         """The policy's forward pass on the device (ssd_policy_forward): obs uint8 [..., N, 15, 15, 3] -> (logits float32
-        [..., N, A], value float32 [..., N]), enqueued on the current stream.  The same kernel as rollout_policy()'s."""
+        [..., N, A], value float32 [..., N]), enqueued on the current stream.  The same kernel as rollout_policy()'s.
+        A ConvLSTMPolicy (ssd_policy_lstm_forward) takes state float32 [..., N, 2, C] (required) and starts bool / uint8
+        [..., N] (rows whose state is taken as zero; None: none) and returns (logits, value, new state [..., N, 2, C])."""
         torch, dev = self._torch()
         P = self._policy_weights(policy)
         V, N, A = self.V, self.N, self.num_actions
@@ -336,15 +353,36 @@ class VecEngine(object):
         if B < 1:
             raise ValueError("obs holds no observation")
         lead = tuple(obs.shape[:-3])
+        recurrent = self._is_recurrent(policy)
+        if not recurrent:
+            if state is not None or starts is not None:
+                raise ValueError("state and starts belong to a ConvLSTMPolicy; a ConvFCPolicy has no state")
+        else:
+            C = policy.cell_size
+            if not isinstance(state, torch.Tensor):
+                raise ValueError("a ConvLSTMPolicy needs state: a float32 tensor %s" % ((lead + (2, C)),))
+            self._check_tensor(state, lead + (2, C), torch.float32, "state")
+            if starts is not None:
+                if not isinstance(starts, torch.Tensor) or starts.dtype not in (torch.bool, torch.uint8):
+                    raise ValueError("starts must be a bool or uint8 tensor of shape %s" % (lead,))
+                self._check_tensor(starts, lead, starts.dtype, "starts")
+                starts = starts.view(torch.uint8)
         logits = torch.empty(lead + (A,), dtype=torch.float32, device=dev)
         value = torch.empty(lead, dtype=torch.float32, device=dev)
         w = policy.packed()
-        _capi.policy_check(self._L.ssd_policy_forward(self._dp(w), P, A, self._dp(obs), B, N, self._dp(logits), self._dp(value),
-                                                      self.device, 0, self._stream()))
-        return logits, value
+        if not recurrent:
+            _capi.policy_check(self._L.ssd_policy_forward(self._dp(w), P, A, self._dp(obs), B, N, self._dp(logits), self._dp(value),
+                                                          self.device, 0, self._stream()))
+            return logits, value
+        new_state = torch.empty_like(state)
+        feat = self._features(B * N)
+        _capi.policy_check(self._L.ssd_policy_lstm_forward(self._dp(w), P, A, C, self._dp(obs), self._dp(state), self._dp(starts), B, N,
+                                                           self._dp(feat), self._dp(new_state), self._dp(logits), self._dp(value),
+                                                           self.device, 0, self._stream()))
+        return logits, value, new_state
 
     def rollout_policy(self, policy, obs_in, n_steps, obs, actions=None, logp=None, value=None, logits=None, rew=None, done=None,
-                       last_value=None, step0=0, greedy=False, stats=None):
+                       last_value=None, step0=0, greedy=False, stats=None, state=None, state_ring=None, state_every=1):
         """A closed-loop rollout (ssd_rollout_policy): n_steps rounds of (policy forward on the current observation, action, step
         with automatic reset at the horizon) enqueued by one call, no host synchronisation.  The rings have a leading dimension
         R and step k writes slot (step0 + k) % R:
@@ -352,9 +390,13 @@ class VecEngine(object):
           own), logp / value f32 [R,E,N], logits f32 [R,E,N,A], rew i32 [R,E,N], done u8 [R,E,N];
         obs_in u8 [E,N,15,15,3] is the observation of the current state (the last reset's or step's); last_value f32 [E,N]
         receives the value of the final observation.  greedy: argmax actions, else drawn from the S_POLICY stream
-        (include/ssd.h).  stats: an EpisodeStats of this batch folded from rew and done (both required, R >= n_steps)."""
+        (include/ssd.h).  stats: an EpisodeStats of this batch folded from rew and done (both required, R >= n_steps).
+        A ConvLSTMPolicy (ssd_rollout_policy_lstm) also takes state float32 [E,N,2,C] (required), the carried state, updated in
+        place and zero at every episode start; state_ring float32 [S,E,N,2,C] receives the state call-relative step k used in
+        slot k // state_every for every k that is a multiple of state_every (S >= ceil(n_steps / state_every))."""
         torch, dev = self._torch()
         P = self._policy_weights(policy)
+        recurrent = self._is_recurrent(policy)
         n_steps, step0 = int(n_steps), int(step0)
         if n_steps < 1:
             raise ValueError("n_steps must be >= 1")
@@ -384,6 +426,27 @@ class VecEngine(object):
             self._check_stats(stats, rew, n_steps)
             if done is None:
                 raise ValueError("stats need the call's done flags: pass done")
+        if not recurrent:
+            if state is not None or state_ring is not None:
+                raise ValueError("state and state_ring belong to a ConvLSTMPolicy; a ConvFCPolicy has no state")
+        else:
+            C = policy.cell_size
+            if not isinstance(state, torch.Tensor):
+                raise ValueError("a ConvLSTMPolicy needs state: a float32 tensor [%d,%d,2,%d]" % (E, N, C))
+            self._check_tensor(state, (E, N, 2, C), torch.float32, "state")
+            state_every = int(state_every)
+            S = 0
+            if state_ring is not None:
+                if state_every < 1:
+                    raise ValueError("state_every must be >= 1")
+                if not isinstance(state_ring, torch.Tensor) or state_ring.dim() != 5:
+                    raise ValueError("state_ring must be a float32 ring [S,%d,%d,2,%d]" % (E, N, C))
+                S = int(state_ring.shape[0])
+                self._check_tensor(state_ring, (S, E, N, 2, C), torch.float32, "state_ring")
+                if S < -(-n_steps // state_every):
+                    raise ValueError("state_ring needs ceil(n_steps / state_every) = %d slots, has %d" % (-(-n_steps // state_every), S))
+                if state_ring.data_ptr() < state.data_ptr() + state.numel() * 4 and state.data_ptr() < state_ring.data_ptr() + state_ring.numel() * 4:
+                    raise ValueError("state_ring must not overlap state")
         if actions is None:
             buf = getattr(self, "_policy_actions", None)
             if buf is None or tuple(buf.shape) != (R, E, N):
@@ -392,9 +455,15 @@ class VecEngine(object):
             actions = buf
         w = policy.packed()
         dp = self._dp
-        rc = self._L.ssd_rollout_policy(self._h, dp(w), P, dp(obs_in), n_steps, step0, dp(obs), dp(actions), dp(logp), dp(value),
-                                        dp(logits), dp(rew), dp(done), R, dp(last_value),
-                                        _capi.SSD_POLICY_GREEDY if greedy else 0, self._stream())
+        if recurrent:
+            rc = self._L.ssd_rollout_policy_lstm(self._h, dp(w), P, C, dp(obs_in), n_steps, step0, dp(state), dp(state_ring), S,
+                                                 state_every, dp(self._features(E * N)), dp(obs), dp(actions), dp(logp), dp(value),
+                                                 dp(logits), dp(rew), dp(done), R, dp(last_value),
+                                                 _capi.SSD_POLICY_GREEDY if greedy else 0, self._stream())
+        else:
+            rc = self._L.ssd_rollout_policy(self._h, dp(w), P, dp(obs_in), n_steps, step0, dp(obs), dp(actions), dp(logp), dp(value),
+                                            dp(logits), dp(rew), dp(done), R, dp(last_value),
+                                            _capi.SSD_POLICY_GREEDY if greedy else 0, self._stream())
         if rc:
             _capi.check(rc, self._h)
         self._count_auto_steps(n_steps)

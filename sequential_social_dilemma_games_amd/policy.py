@@ -1,5 +1,6 @@
 """The conv-FC policy network of the reference (models/conv_to_fc_net.py:1-51, ConvToFCNet: the model of Jaques et al. 2019)
-as a torch module whose weights the device kernels read (include/ssd.h, SSD_POL_*; csrc/ssd_policy.hip).
+as a torch module whose weights the device kernels read (include/ssd.h, SSD_POL_*; csrc/ssd_policy.hip), and ConvLSTMPolicy, the
+same trunk under RLlib's LSTM (SSD_LSTM_*; csrc/ssd_policy_lstm.hip).
 
     policy = ConvFCPolicy(num_actions=8, num_sets=5).cuda()       # one weight set per agent, as train_baseline.py:87-96
     logits, value = policy(obs_u8)                                # [..., N, 15, 15, 3] -> [..., N, A], [..., N]
@@ -98,27 +99,133 @@ class ConvFCPolicy(torch.nn.Module):
 
     def forward(self, obs):
         P, A = self.num_sets, self.num_actions
-        if obs.shape[-3:] != (VIEW, VIEW, 3):
-            raise ValueError("observations must end in (15, 15, 3), got %s" % (tuple(obs.shape),))
-        if P > 1 and (obs.dim() < 4 or obs.shape[-4] != P):
-            raise ValueError("with %d weight sets the observations need an agent axis of %d: [..., %d, 15, 15, 3]" % (P, P, P))
-        lead = obs.shape[:-3]
-        dt = self.conv_w.dtype
-        key = (obs.device, dt)
-        if key not in self._tables:                                  # float((u8 - 128) / 255), from the float64 values
-            self._tables[key] = torch.from_numpy(_NORMALISE).to(dt).to(obs.device)
-        x = self._tables[key][obs.long()]
-        x = x.reshape(-1, P, VIEW, VIEW, 3)
-        M = x.shape[0]
-        x = x.permute(0, 1, 4, 2, 3).reshape(M, P * 3, VIEW, VIEW)    # NHWC -> NCHW, the sets as conv groups
-        wc = self.conv_w.permute(0, 4, 3, 1, 2).reshape(P * FILTERS, 3, 3, 3)
-        h = torch.relu(torch.nn.functional.conv2d(x, wc, self.conv_b.reshape(P * FILTERS), groups=P))
-        h = h.reshape(M, P, FILTERS, 13, 13).permute(0, 1, 3, 4, 2).reshape(M, P, FLAT)   # flatten (row, col, channel)
-        h = torch.relu(torch.einsum("mpk,pkj->mpj", h, self.fc1_w) + self.fc1_b)
-        h = torch.relu(torch.einsum("mpk,pkj->mpj", h, self.fc2_w) + self.fc2_b)
+        h, lead = _trunk(self, obs)
         logits = torch.einsum("mpk,pkj->mpj", h, self.logits_w) + self.logits_b
         value = (torch.einsum("mpk,pkj->mpj", h, self.value_w) + self.value_b)[..., 0]
         return logits.reshape(lead + (A,)), value.reshape(lead)
+
+
+def _trunk(module, obs):
+    """The conv-FC trunk shared by both policies: uint8 observations [..., (P,) 15, 15, 3] -> (fc2's output [M, P, 32], the
+    leading shape of one row per observation)."""
+    P = module.num_sets
+    if obs.shape[-3:] != (VIEW, VIEW, 3):
+        raise ValueError("observations must end in (15, 15, 3), got %s" % (tuple(obs.shape),))
+    if P > 1 and (obs.dim() < 4 or obs.shape[-4] != P):
+        raise ValueError("with %d weight sets the observations need an agent axis of %d: [..., %d, 15, 15, 3]" % (P, P, P))
+    lead = obs.shape[:-3]
+    dt = module.conv_w.dtype
+    key = (obs.device, dt)
+    if key not in module._tables:                                # float((u8 - 128) / 255), from the float64 values
+        module._tables[key] = torch.from_numpy(_NORMALISE).to(dt).to(obs.device)
+    x = module._tables[key][obs.long()]
+    x = x.reshape(-1, P, VIEW, VIEW, 3)
+    M = x.shape[0]
+    x = x.permute(0, 1, 4, 2, 3).reshape(M, P * 3, VIEW, VIEW)    # NHWC -> NCHW, the sets as conv groups
+    wc = module.conv_w.permute(0, 4, 3, 1, 2).reshape(P * FILTERS, 3, 3, 3)
+    h = torch.relu(torch.nn.functional.conv2d(x, wc, module.conv_b.reshape(P * FILTERS), groups=P))
+    h = h.reshape(M, P, FILTERS, 13, 13).permute(0, 1, 3, 4, 2).reshape(M, P, FLAT)   # flatten (row, col, channel)
+    h = torch.relu(torch.einsum("mpk,pkj->mpj", h, module.fc1_w) + module.fc1_b)
+    h = torch.relu(torch.einsum("mpk,pkj->mpj", h, module.fc2_w) + module.fc2_b)
+    return h, lead
+
+
+class ConvLSTMPolicy(torch.nn.Module):
+    """The baseline's recurrent policy (run_scripts/train_baseline.py:146-147, "use_lstm": True): the trunk of ConvFCPolicy
+    (conv, fc1, fc2) and RLlib 0.7.6's LSTM of cell_size C cells on fc2's output, with the logits and the value on the LSTM's
+    output h' (include/ssd.h, RECURRENT POLICY ROLLOUTS).  The cell is TF's LSTMCell: z = [x, h] @ lstm_w + lstm_b split into
+    (i, j, f, o); c' = sigmoid(f + 1) c + sigmoid(i) tanh(j); h' = sigmoid(o) tanh(c').  A state is [..., 2, C] (c, then h).
+
+        policy = ConvLSTMPolicy(8, num_sets=5, cell_size=128).cuda()
+        state = policy.initial_state((E, 5))
+        logits, value, state = policy(obs_u8, state, starts)            # starts: rows whose episode begins (state zeroed)
+        logits, value, final = policy.forward_sequence(obs_seq, state_in, resets)   # the learner's BPTT path
+
+    Parameters in TF's layouts with a leading weight-set axis: the trunk's, lstm_w [P, 32 + C, 4C], lstm_b [P, 4C], logits_w
+    [P, C, A], logits_b [P, A], value_w [P, C, 1], value_b [P, 1]."""
+
+    def __init__(self, num_actions, num_sets=1, cell_size=128, seed=0):
+        super().__init__()
+        A, P, C = int(num_actions), int(num_sets), int(cell_size)
+        if not 1 <= A <= _capi.SSD_POL_MAX_ACTIONS:
+            raise ValueError("num_actions must be 1..%d" % _capi.SSD_POL_MAX_ACTIONS)
+        if not 1 <= P <= 64:
+            raise ValueError("num_sets must be 1..64")
+        if C not in _capi.LSTM_CELL_SIZES:
+            raise ValueError("cell_size must be one of %s" % (_capi.LSTM_CELL_SIZES,))
+        self.num_actions, self.num_sets, self.cell_size = A, P, C
+        g = torch.Generator().manual_seed(int(seed))
+        limit = float(np.sqrt(6.0 / (27 + 9 * FILTERS)))        # slim.conv2d's default initializer: Glorot uniform
+        lstm_limit = float(np.sqrt(6.0 / ((HIDDEN + C) + 4 * C)))   # TF's default kernel initializer: Glorot uniform
+        init = {"conv_w": (torch.rand((P, 3, 3, 3, FILTERS), generator=g, dtype=torch.float64) * 2 - 1) * limit,
+                "fc1_w": normc((P, FLAT, HIDDEN), 1.0, g), "fc2_w": normc((P, HIDDEN, HIDDEN), 1.0, g),
+                "lstm_w": (torch.rand((P, HIDDEN + C, 4 * C), generator=g, dtype=torch.float64) * 2 - 1) * lstm_limit,
+                "value_w": normc((P, C, 1), 1.0, g), "logits_w": normc((P, C, A), 0.01, g)}
+        for name, shape, _ in self.layout():
+            t = init.get(name)
+            if t is None:
+                t = torch.zeros((P,) + shape, dtype=torch.float64)       # biases start at zero
+            self.register_parameter(name, torch.nn.Parameter(t.to(torch.float32)))
+        self._packed = None
+        self._tables = {}
+
+    def layout(self):
+        """(name, shape of one set, float offset within a packed set) of every parameter, in packed order."""
+        A, C = self.num_actions, self.cell_size
+        return _FIXED[:6] + (("lstm_w", (HIDDEN + C, 4 * C), _capi.SSD_LSTM_W), ("lstm_b", (4 * C,), _capi.SSD_LSTM_B(C)),
+                             ("value_w", (C, 1), _capi.SSD_LSTM_VALUE_W(C)), ("value_b", (1,), _capi.SSD_LSTM_VALUE_B(C)),
+                             ("logits_w", (C, A), _capi.SSD_LSTM_LOGITS_W(C)), ("logits_b", (A,), _capi.SSD_LSTM_LOGITS_B(C, A)))
+
+    load_arrays = ConvFCPolicy.load_arrays
+    packed = ConvFCPolicy.packed
+
+    @property
+    def set_floats(self):
+        return _capi.SSD_LSTM_SET_FLOATS(self.cell_size, self.num_actions)
+
+    def initial_state(self, lead, device=None):
+        """A zero state [*lead, 2, C] (float32, on the parameters' device unless given)."""
+        lead = (int(lead),) if isinstance(lead, int) else tuple(int(n) for n in lead)
+        return torch.zeros(lead + (2, self.cell_size), dtype=self.lstm_w.dtype,
+                           device=self.lstm_w.device if device is None else device)
+
+    def forward(self, obs, state, starts=None):
+        """obs u8 [..., (P,) 15, 15, 3], state [..., 2, C] (the same leading shape), starts bool [...] or None: rows whose state
+        is replaced by zero (selected, not multiplied: whatever the state holds there is never used).  Returns (logits [..., A],
+        value [...], new state [..., 2, C])."""
+        P, A, C = self.num_sets, self.num_actions, self.cell_size
+        x, lead = _trunk(self, obs)
+        M = x.shape[0]
+        if tuple(state.shape) != tuple(lead) + (2, C):
+            raise ValueError("state must have shape %s, got %s" % (tuple(lead) + (2, C), tuple(state.shape)))
+        st = state.to(x.dtype).reshape(M, P, 2, C)
+        if starts is not None:
+            if tuple(starts.shape) != tuple(lead):
+                raise ValueError("starts must have shape %s, got %s" % (tuple(lead), tuple(starts.shape)))
+            st = torch.where(starts.to(torch.bool).reshape(M, P, 1, 1).to(st.device), torch.zeros((), dtype=st.dtype, device=st.device), st)
+        c, h = st[:, :, 0], st[:, :, 1]
+        z = torch.einsum("mpk,pkj->mpj", torch.cat([x, h], dim=-1), self.lstm_w) + self.lstm_b
+        zi, zj, zf, zo = z[..., :C], z[..., C:2 * C], z[..., 2 * C:3 * C], z[..., 3 * C:]
+        c2 = torch.sigmoid(zf + 1.0) * c + torch.sigmoid(zi) * torch.tanh(zj)
+        h2 = torch.sigmoid(zo) * torch.tanh(c2)
+        logits = torch.einsum("mpk,pkj->mpj", h2, self.logits_w) + self.logits_b
+        value = (torch.einsum("mpk,pkj->mpj", h2, self.value_w) + self.value_b)[..., 0]
+        new_state = torch.stack([c2, h2], dim=2)
+        return logits.reshape(tuple(lead) + (A,)), value.reshape(lead), new_state.reshape(tuple(lead) + (2, C))
+
+    def forward_sequence(self, obs, state, resets=None):
+        """T steps for truncated BPTT: obs u8 [T, ..., (P,) 15, 15, 3], state [..., 2, C] before step 0, resets bool [T, ...] or
+        None (resets[t]: the state step t uses is zero, as the start rule of forward()).  Differentiable.  Returns (logits
+        [T, ..., A], value [T, ...], the state after step T - 1)."""
+        T = int(obs.shape[0])
+        if resets is not None and int(resets.shape[0]) != T:
+            raise ValueError("resets must have T = %d rows" % T)
+        logits, values = [], []
+        for t in range(T):
+            lg, v, state = self.forward(obs[t], state, None if resets is None else resets[t])
+            logits.append(lg)
+            values.append(v)
+        return torch.stack(logits), torch.stack(values), state
 
 
 def sample_host(logits, u, greedy=False):
