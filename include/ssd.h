@@ -530,6 +530,87 @@ int ssd_rollout_policy_lstm(ssd_env *env, const float *weights, int32_t num_sets
                             float *logits, int32_t *rew, uint8_t *done, int32_t ring, float *last_value, uint32_t flags,
                             void *stream);
 
+/* ======================================================================================================================
+ * MOA POLICY ROLLOUTS -- the causal-influence policy of run_scripts/train_moa.py:64-155 (MOA_LSTM, models/moa_model.py:121-311)
+ * with the social-influence reward of Jaques et al. 2019 (algorithms/common_funcs.py:134-195), on the device
+ * (csrc/ssd_policy_moa.hip).  Exact float32 throughout.  N agents, 2 <= N <= SSD_MOA_MAX_AGENTS.
+ *
+ * Per weight set, with x the normalised observation of the trunk above (view_len 7):
+ *   conv at SSD_POL_CONV_W / SSD_POL_CONV_B, ReLU, flatten (row, col, channel) to 1014 -- the trunk's conv, run once;
+ *   two FC stacks on it, s = 0 (actions) and s = 1 (MOA): y_s = tanh(tanh(x @ fc1_w + fc1_b) @ fc2_w + fc2_b), 32 floats
+ *     (RLlib's default fcnet_activation "tanh": train_moa.py:138-144 does not set it);
+ *   Keras LSTMs of C cells, C = 64, 128 or 256: z = in @ kernel + h @ recurrent_kernel + bias, gate blocks (i, f, c, o):
+ *     c' = sigmoid(f) * c + sigmoid(i) * tanh(c~),  h' = sigmoid(o) * tanh(c')   (no +1 on f at run time; not RLlib's cell)
+ *   actions LSTM on y_0: logits = h1' @ logits_w + logits_b, value = h1' @ value_w + value_b;
+ *   MOA LSTM on in = [y_1, the N previous actions as floats, own first] -> pred = h2' @ pred_w + pred_b, read as [N-1][A].
+ * A state is f32 [.., 4, C] = (h1, c1, h2, c2) (moa_model.py:114-118).  The previous actions of row (e, i) are agent i's, then
+ * the other agents' in the order of their ids sorted AS STRINGS ('agent-10' < 'agent-2', as ssd_agent_action_obs); the j of
+ * pred [j][a] is the j-th of those others.  Start rule: where the env's t is 0 (rollouts) or starts[row] != 0 (the forward),
+ * the state and the previous-action vector of the row are zero; they are selected, never read.
+ * Counterfactuals: with z the MOA gates of the true input and a_prev the own previous action (0 at a start),
+ * cf[a] = pred of the cell update from z + (a - a_prev) * kernel[32] (kernel row 32 is the own-action input; a = 0 .. A-1),
+ * in float32 as written: (z + bias) + (float)(a - a_prev) * row.  moa_logits IS cf[a_prev] (bitwise); the state advances with
+ * the true input only.
+ * Influence of row (e, i), with a_t the action chosen from this step's logits (common_funcs.py:140-157) and pi their softmax:
+ *   for each other agent j: log p = log_softmax(cf[a_t][j]), log q = logsumexp over a of (log pi(a) + log_softmax(cf[a][j]));
+ *   KL_j = sum over k with p_k != 0 of p_k (log p_k - log q_k);  influence = clip(sum_j KL_j, -clip, clip).
+ * A non-finite sum gives 0 for that row (the reference zeroes the whole trajectory, common_funcs.py:62-66).  The visibility
+ * factor is 1 (visible agents are all ones, above) and is not read.  The shaped reward is rew + w * influence.
+ *
+ * Weight set (floats, every block on a 64-float boundary, matrices [in][out]); a buffer holds P = 1 or N sets, set p at
+ * p * SSD_MOA_SET_FLOATS(C, A, N).  Stack s's fc1_w [1014][32], fc1_b, fc2_w [32][32], fc2_b sit at SSD_MOA_FC(s) + the trunk's
+ * relative offsets (SSD_POL_FC1_W ... SSD_POL_FC2_B minus SSD_POL_FC1_W).  Each (kernel, recurrent_kernel) pair is one matrix
+ * with the input rows first: lstm [32 + C][4C]; moa [48 + C][4C] whose rows 32 + N .. 47 are zero.
+ * ====================================================================================================================== */
+enum { SSD_MOA_FC = 33728, SSD_MOA_FC_STRIDE = 33536, SSD_MOA_X = 32, SSD_MOA_XM = 48, SSD_MOA_MAX_AGENTS = 16 };
+#define SSD_MOA_ALIGN(n) (((n) + 63) / 64 * 64)
+#define SSD_MOA_FC1_W(s) (SSD_MOA_FC + (s) * SSD_MOA_FC_STRIDE)
+#define SSD_MOA_FC1_B(s) (SSD_MOA_FC1_W(s) + (SSD_POL_FC1_B - SSD_POL_FC1_W))
+#define SSD_MOA_FC2_W(s) (SSD_MOA_FC1_W(s) + (SSD_POL_FC2_W - SSD_POL_FC1_W))
+#define SSD_MOA_FC2_B(s) (SSD_MOA_FC1_W(s) + (SSD_POL_FC2_B - SSD_POL_FC1_W))
+#define SSD_MOA_LSTM_W(C) (SSD_MOA_FC + 2 * SSD_MOA_FC_STRIDE)
+#define SSD_MOA_LSTM_B(C) SSD_MOA_ALIGN(SSD_MOA_LSTM_W(C) + (32 + (C)) * 4 * (C))
+#define SSD_MOA_VALUE_W(C) SSD_MOA_ALIGN(SSD_MOA_LSTM_B(C) + 4 * (C))
+#define SSD_MOA_VALUE_B(C) SSD_MOA_ALIGN(SSD_MOA_VALUE_W(C) + (C))
+#define SSD_MOA_LOGITS_W(C) SSD_MOA_ALIGN(SSD_MOA_VALUE_B(C) + 1)
+#define SSD_MOA_LOGITS_B(C, A) SSD_MOA_ALIGN(SSD_MOA_LOGITS_W(C) + (C) * (A))
+#define SSD_MOA_MW(C, A) SSD_MOA_ALIGN(SSD_MOA_LOGITS_B(C, A) + (A))
+#define SSD_MOA_MB(C, A) SSD_MOA_ALIGN(SSD_MOA_MW(C, A) + (SSD_MOA_XM + (C)) * 4 * (C))
+#define SSD_MOA_PRED_W(C, A) SSD_MOA_ALIGN(SSD_MOA_MB(C, A) + 4 * (C))
+#define SSD_MOA_PRED_B(C, A, N) SSD_MOA_ALIGN(SSD_MOA_PRED_W(C, A) + (C) * ((N) - 1) * (A))
+#define SSD_MOA_SET_FLOATS(C, A, N) SSD_MOA_ALIGN(SSD_MOA_PRED_B(C, A, N) + ((N) - 1) * (A))
+/* Caller scratch of both calls, in floats, for rows = B * N (or E * N): features [rows][2][32], then logits [rows][16] (this
+ * step's, for the MOA cell), then two i32 [rows] buffers of joint actions (the rollout's ping-pong). */
+#define SSD_MOA_SCRATCH_FLOATS(rows) (82 * (size_t)(rows))
+
+/* The MOA forward pass alone (device pointers on device_id, enqueued on `stream`): obs u8 [B,N,15,15,3], prev_actions i32 [B,N]
+ * (the previous joint action of each row's env, by agent index), state_in f32 [B,N,4,C] and starts u8 [B,N] or NULL ->
+ * state_out f32 [B,N,4,C], logits f32 [B,N,A], value f32 [B,N], moa_logits f32 [B,N,N-1,A], cf_logits f32 [B,N,A,N-1,A].
+ * Every output may be NULL; state_out may equal state_in (in place) but must not overlap it otherwise.  With actions i32
+ * [B,N] (this step's, as chosen from these logits) it also writes influence f32 [B,N] with the given clip (finite, >= 0).
+ * scratch: SSD_MOA_SCRATCH_FLOATS(B * N) floats, required.  weights: P sets (P = 1 or N), 4-byte aligned.  flags: 0.
+ * Bad arguments: SSD_E_INVALID before anything is launched (ssd_policy_last_error says why). */
+int ssd_policy_moa_forward(const float *weights, int32_t num_sets, int32_t num_actions, int32_t cell_size, const uint8_t *obs,
+                           const int32_t *prev_actions, const float *state_in, const uint8_t *starts, int32_t batch,
+                           int32_t num_agents, float *scratch, float *state_out, float *logits, float *value, float *moa_logits,
+                           float *cf_logits, const int32_t *actions, float *influence, float influence_clip, int32_t device_id,
+                           uint32_t flags, void *stream);
+
+/* ssd_rollout_policy_lstm with the MOA network: the same rings, sampling contract, flags and step order, state [E,N,4,C] and
+ * state ring (of the 4-row state), and besides
+ *   prev_actions i32 [E,N]: the carried previous joint action, read by step 0 and left holding the last step's actions;
+ *   prev_actions_ring i32 [R,E,N] or NULL: slot (step0 + k) % R receives what step k's MOA read (zero where t was 0);
+ *   influence f32 [R,E,N] or NULL: slot (step0 + k) % R receives step k's influence (clip: influence_clip, finite, >= 0);
+ *   scratch: SSD_MOA_SCRATCH_FLOATS(E * N) floats (the call allocates nothing and does not synchronise).
+ * Four hipLaunchKernel launches per step on `stream` (trunk, actions cell, MOA cell with the influence, env step), one
+ * device-to-device copy of the joint action at the end, and two launches for last_value, which leaves the state alone. */
+int ssd_rollout_policy_moa(ssd_env *env, const float *weights, int32_t num_sets, int32_t cell_size, const uint8_t *obs_in,
+                           int32_t n_steps, int32_t step0, float *state, float *state_ring, int32_t state_ring_len,
+                           int32_t state_every, int32_t *prev_actions, int32_t *prev_actions_ring, float *influence,
+                           float influence_clip, float *scratch, uint8_t *obs, int32_t *actions, float *logp, float *value,
+                           float *logits, int32_t *rew, uint8_t *done, int32_t ring, float *last_value, uint32_t flags,
+                           void *stream);
+
 #ifdef __cplusplus
 }
 #endif

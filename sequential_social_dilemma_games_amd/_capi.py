@@ -70,6 +70,76 @@ def SSD_LSTM_SET_FLOATS(C, A):
     return SSD_LSTM_ALIGN(SSD_LSTM_LOGITS_B(C, A) + int(A))
 
 
+# the MOA policy's weight layout (include/ssd.h, SSD_MOA_*): the trunk's conv, two FC stacks, the actions LSTM with its heads,
+# the MOA LSTM with pred
+SSD_MOA_FC, SSD_MOA_FC_STRIDE, SSD_MOA_X, SSD_MOA_XM, SSD_MOA_MAX_AGENTS = 33728, 33536, 32, 48, 16
+SSD_MOA_ALIGN = SSD_LSTM_ALIGN
+
+
+def SSD_MOA_FC1_W(s):
+    return SSD_MOA_FC + int(s) * SSD_MOA_FC_STRIDE
+
+
+def SSD_MOA_FC1_B(s):
+    return SSD_MOA_FC1_W(s) + (SSD_POL_FC1_B - SSD_POL_FC1_W)
+
+
+def SSD_MOA_FC2_W(s):
+    return SSD_MOA_FC1_W(s) + (SSD_POL_FC2_W - SSD_POL_FC1_W)
+
+
+def SSD_MOA_FC2_B(s):
+    return SSD_MOA_FC1_W(s) + (SSD_POL_FC2_B - SSD_POL_FC1_W)
+
+
+def SSD_MOA_LSTM_W(C):
+    return SSD_MOA_FC + 2 * SSD_MOA_FC_STRIDE
+
+
+def SSD_MOA_LSTM_B(C):
+    return SSD_MOA_ALIGN(SSD_MOA_LSTM_W(C) + (32 + int(C)) * 4 * int(C))
+
+
+def SSD_MOA_VALUE_W(C):
+    return SSD_MOA_ALIGN(SSD_MOA_LSTM_B(C) + 4 * int(C))
+
+
+def SSD_MOA_VALUE_B(C):
+    return SSD_MOA_ALIGN(SSD_MOA_VALUE_W(C) + int(C))
+
+
+def SSD_MOA_LOGITS_W(C):
+    return SSD_MOA_ALIGN(SSD_MOA_VALUE_B(C) + 1)
+
+
+def SSD_MOA_LOGITS_B(C, A):
+    return SSD_MOA_ALIGN(SSD_MOA_LOGITS_W(C) + int(C) * int(A))
+
+
+def SSD_MOA_MW(C, A):
+    return SSD_MOA_ALIGN(SSD_MOA_LOGITS_B(C, A) + int(A))
+
+
+def SSD_MOA_MB(C, A):
+    return SSD_MOA_ALIGN(SSD_MOA_MW(C, A) + (SSD_MOA_XM + int(C)) * 4 * int(C))
+
+
+def SSD_MOA_PRED_W(C, A):
+    return SSD_MOA_ALIGN(SSD_MOA_MB(C, A) + 4 * int(C))
+
+
+def SSD_MOA_PRED_B(C, A, N):
+    return SSD_MOA_ALIGN(SSD_MOA_PRED_W(C, A) + int(C) * (int(N) - 1) * int(A))
+
+
+def SSD_MOA_SET_FLOATS(C, A, N):
+    return SSD_MOA_ALIGN(SSD_MOA_PRED_B(C, A, N) + (int(N) - 1) * int(A))
+
+
+def SSD_MOA_SCRATCH_FLOATS(rows):
+    return 82 * int(rows)
+
+
 # every symbol include/ssd.h declares
 SYMBOLS = ("ssd_create", "ssd_destroy", "ssd_reset", "ssd_step", "ssd_step_random", "ssd_rollout_random", "ssd_rollout_actions", "ssd_rollout_path", "ssd_set_rollout_chains",
            "ssd_profiler_attached", "ssd_observe",
@@ -79,9 +149,10 @@ SYMBOLS = ("ssd_create", "ssd_destroy", "ssd_reset", "ssd_step", "ssd_step_rando
            "ssd_ws_set_state", "ssd_ws_device_status", "ssd_ws_last_error",
            "ssd_stats_create", "ssd_stats_destroy", "ssd_stats_fold", "ssd_stats_set_chunk", "ssd_stats_discard", "ssd_stats_drain",
            "ssd_stats_last_error", "ssd_policy_forward", "ssd_policy_last_error", "ssd_rollout_policy",
-           "ssd_policy_lstm_forward", "ssd_rollout_policy_lstm")
+           "ssd_policy_lstm_forward", "ssd_rollout_policy_lstm", "ssd_policy_moa_forward", "ssd_rollout_policy_moa")
 # added after ABI 6 without a version bump (the calls are additive): a library built before them lacks them
 LSTM_SYMBOLS = ("ssd_policy_lstm_forward", "ssd_rollout_policy_lstm")
+MOA_SYMBOLS = ("ssd_policy_moa_forward", "ssd_rollout_policy_moa")
 
 
 class SsdConfig(C.Structure):
@@ -194,12 +265,15 @@ def lib():
         L.ssd_policy_last_error.argtypes = []
         L.ssd_policy_last_error.restype = C.c_char_p
         L.ssd_rollout_policy.argtypes = [vp, vp, i32, vp, i32, i32] + [vp] * 7 + [i32, vp, u32, vp]
-        missing = [name for name in LSTM_SYMBOLS if not hasattr(L, name)]
+        missing = [name for name in LSTM_SYMBOLS + MOA_SYMBOLS if not hasattr(L, name)]
         if missing:
-            raise SsdError("%s lacks %s (built before the recurrent policy calls): rebuild it with `python -c 'import "
+            raise SsdError("%s lacks %s (built before the recurrent or MOA policy calls): rebuild it with `python -c 'import "
                            "__graft_entry__ as g; g.build()'`" % (LIB_PATH, ", ".join(missing)))
         L.ssd_policy_lstm_forward.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, u32, vp]
         L.ssd_rollout_policy_lstm.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, vp, i32, i32] + [vp] * 8 + [i32, vp, u32, vp]
+        L.ssd_policy_moa_forward.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, i32, i32] + [vp] * 8 + [C.c_float, i32, u32, vp]
+        L.ssd_rollout_policy_moa.argtypes = ([vp, vp, i32, i32, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp, C.c_float] + [vp] * 8
+                                             + [i32, vp, u32, vp])
         for name in SYMBOLS:
             getattr(L, name)
         if L.ssd_abi_version() != ABI_VERSION:

@@ -1584,6 +1584,84 @@ int ssd_rollout_policy_lstm(ssd_env *env, const float *weights, int32_t num_sets
     return SSD_OK;
 }
 
+int ssd_rollout_policy_moa(ssd_env *env, const float *weights, int32_t num_sets, int32_t cell_size, const uint8_t *obs_in,
+                           int32_t n_steps, int32_t step0, float *state, float *state_ring, int32_t state_ring_len,
+                           int32_t state_every, int32_t *prev_actions, int32_t *prev_actions_ring, float *influence,
+                           float influence_clip, float *scratch, uint8_t *obs, int32_t *actions, float *logp, float *value,
+                           float *logits, int32_t *rew, uint8_t *done, int32_t ring, float *last_value, uint32_t flags,
+                           void *stream) {
+    if (!env) return SSD_E_INVALID;
+    auto bad = [&](const char *msg) { env->err = msg; return SSD_E_INVALID; };
+    const int A = env->game == SSD_GAME_HARVEST ? 8 : 9;        // harvest.py:44, cleanup.py:70
+    if (env->view_len != 7 || env->V != SSD_POL_VIEW) return bad("policy rollouts need view_len 7 (15 x 15 observations)");
+    if (env->N < 2 || env->N > SSD_MOA_MAX_AGENTS) return bad("the MOA policy needs 2..16 agents");
+    if (!weights || !obs_in || !obs || !actions || !state || !prev_actions || !scratch)
+        return bad("weights, obs_in, obs, actions, state, prev_actions and scratch are required");
+    if (reinterpret_cast<uintptr_t>(weights) & 3u) return bad("weights must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(scratch) & 3u) return bad("scratch must be 4-byte aligned");
+    if (cell_size != 64 && cell_size != 128 && cell_size != 256) return bad("cell_size must be 64, 128 or 256");
+    if (num_sets != 1 && num_sets != env->N) return bad("num_sets must be 1 or num_agents");
+    if (n_steps < 1) return bad("n_steps must be >= 1");
+    if (ring < 1) return bad("ring must be >= 1");
+    if (step0 < 0) return bad("step0 must be >= 0");
+    if (state_ring) {
+        if (state_every < 1) return bad("state_every must be >= 1");
+        if ((int64_t)state_ring_len * state_every < n_steps) return bad("the state ring needs ceil(n_steps / state_every) slots");
+    }
+    if (influence && !(influence_clip >= 0.f && influence_clip <= 3.0e38f)) return bad("influence_clip must be finite and >= 0");
+    if (flags & ~(uint32_t)SSD_POLICY_GREEDY) return bad("flags: only the greedy-policy bit is defined");
+    const size_t en = (size_t)env->E * env->N, ob = en * SSD_POL_VIEW * SSD_POL_VIEW * 3, sn = en * 4 * cell_size;
+    if (reinterpret_cast<uintptr_t>(obs) & 3u) return bad("obs must be 4-byte aligned");
+    if (ring > 1 && (ob & 3u)) return bad("an observation ring of more than one slot needs E * N to be a multiple of 4 (4-byte aligned slots)");
+    {
+        int cur = -1;
+        if (hipGetDevice(&cur) != hipSuccess || cur != env->device) SSD_HIP(env, hipSetDevice(env->device));
+    }
+    // scratch (include/ssd.h): features [en][2][32], logits [en][16], the joint-action ping-pong i32 [2][en]
+    int32_t *pp[2] = {reinterpret_cast<int32_t *>(scratch + 80 * en), reinterpret_cast<int32_t *>(scratch + 81 * en)};
+    ssd::PolicyArgs tr{};                       // the trunk, MOA mode
+    tr.w = weights; tr.P = num_sets; tr.A = A; tr.B = env->E; tr.N = env->N;
+    tr.set_floats = SSD_MOA_SET_FLOATS(cell_size, A, env->N); tr.feat = scratch;
+    ssd::MoaArgs ma{};
+    ma.w = weights; ma.P = num_sets; ma.A = A; ma.B = env->E; ma.N = env->N; ma.C = cell_size; ma.set_floats = tr.set_floats;
+    ma.feat = scratch; ma.state_in = state; ma.state_out = state; ma.logits_scratch = scratch + 64 * en;
+    ma.hdr = env->p.hdr; ma.seed_lo = env->p.seed_lo; ma.seed_hi = env->p.seed_hi; ma.env_base = env->p.env_base;
+    ma.greedy = (flags & SSD_POLICY_GREEDY) ? 1 : 0;
+    ma.pi_logits = ma.logits_scratch; ma.pi_stride = 16; ma.clip = influence_clip;
+    size_t slot = 0;
+    for (int32_t k = 0; k < n_steps; ++k) {
+        const size_t prev = slot;
+        slot = (size_t)(((int64_t)step0 + k) % ring);
+        tr.obs = k == 0 ? obs_in : obs + prev * ob;
+        SSD_HIP(env, ssd::launch_policy_moa_features(tr, stream));
+        ma.state_used = state_ring && k % state_every == 0 ? state_ring + (size_t)(k / state_every) * sn : nullptr;
+        ma.actions = actions + slot * en;
+        ma.actions_copy = pp[(k + 1) & 1];      // the next step's previous joint action: never the buffer this step reads
+        ma.logp = logp ? logp + slot * en : nullptr;
+        ma.value = value ? value + slot * en : nullptr;
+        ma.logits = logits ? logits + slot * en * A : nullptr;
+        SSD_HIP(env, ssd::launch_policy_moa_actions(ma, stream));
+        ma.prev = k == 0 ? prev_actions : pp[k & 1];
+        ma.prev_used = prev_actions_ring ? prev_actions_ring + slot * en : nullptr;
+        ma.taken = influence ? ma.actions : nullptr;
+        ma.influence = influence ? influence + slot * en : nullptr;
+        SSD_HIP(env, ssd::launch_policy_moa_cell(ma, stream));
+        const int rc = run(env, ssd::kModeStepAuto, ma.actions, nullptr, nullptr, 0, nullptr, obs + slot * ob, rew ? rew + slot * en : nullptr,
+                           done ? done + slot * en : nullptr, 1, 0, stream);
+        if (rc) return rc;
+    }
+    SSD_HIP(env, hipMemcpyAsync(prev_actions, pp[n_steps & 1], en * sizeof(int32_t), hipMemcpyDeviceToDevice,
+                                static_cast<hipStream_t>(stream)));
+    if (last_value) {                           // the final observation under the final state; the state stays as it is
+        tr.obs = obs + slot * ob;
+        SSD_HIP(env, ssd::launch_policy_moa_features(tr, stream));
+        ma.state_out = nullptr; ma.state_used = nullptr; ma.actions = nullptr; ma.actions_copy = nullptr; ma.logp = nullptr;
+        ma.logits = nullptr; ma.logits_scratch = nullptr; ma.value = last_value;
+        SSD_HIP(env, ssd::launch_policy_moa_actions(ma, stream));
+    }
+    return SSD_OK;
+}
+
 int ssd_rollout_path(const ssd_env *env) { return env ? env->last_path : SSD_E_INVALID; }
 
 int ssd_set_rollout_chains(ssd_env *env, int32_t chains) {

@@ -11,8 +11,9 @@
 //      are added through LDS.  fc1's weights stream from L2 (130 KB per set, shared by every workgroup of the set);
 //   4. fc2, the logits and the value on the VALU (1.3 kMAC per env);
 //   5. rollouts: one thread per env picks the action (greedy or the S_POLICY draw) and its log-probability.
-// Every sum is in a fixed order, so two calls on the same input agree bit for bit.  The <true> instantiation stops after fc2
-// and writes its output instead: the trunk of the recurrent policy (ssd_policy_lstm.hip).
+// Every sum is in a fixed order, so two calls on the same input agree bit for bit.  kModeFeatures stops after fc2 and writes its
+// output instead: the trunk of the recurrent policy (ssd_policy_lstm.hip).  kModeMoa runs steps 3 and 4 (to fc2) once per FC
+// stack of the MOA policy, with tanh for ReLU, on the same conv output and writes both outputs (ssd_policy_moa.hip).
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -41,9 +42,63 @@ static_assert(SSD_POL_FC1_B == SSD_POL_FC1_W + kFlat * 32 && SSD_POL_FC2_W == SS
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// kFeatures: stop after fc2 and write its output to a.feat (the trunk of the recurrent policy, ssd_policy_lstm.hip)
-template <bool kFeatures>
+constexpr int kModeHeads = 0, kModeFeatures = 1, kModeMoa = 2;
+
+// The MOA policy's FC stack s on the conv output of s_conv (steps 3 and 4 of ssd_policy_kernel with tanh, stack s's weights at
+// SSD_MOA_FC1_W(s), the trunk's relative offsets): writes feat [B][N][2][32] at stack s.
+__device__ __forceinline__ void moa_stack(const ssd::PolicyArgs &a, const float *__restrict__ w, int s, const float *s_conv,
+                                          float *s_part, float *s_h1, int tid, int i, int b0) {
+    const float *ws = w + (SSD_MOA_FC1_W(s) - SSD_POL_FC1_W);
+    const int wave = tid >> 6, lane = tid & 63, nt = wave & 1, kh = wave >> 1;
+    const int l15 = lane & 15, l4 = lane >> 4;
+    const float *a_row = s_conv + l15 * kPitch + l4;
+    const float *w1 = ws + SSD_POL_FC1_W + l4 * 32 + nt * 16 + l15;
+    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
+    const int kb = kh * kHalf;
+#pragma unroll 4
+    for (int p = 0; p < (kHalf - 1) / 2; ++p) {
+        const int kk = kb + 2 * p;
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a_row[4 * kk], w1[(size_t)kk * 128], acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a_row[4 * kk + 4], w1[(size_t)kk * 128 + 128], acc1, 0, 0, 0);
+    }
+    {
+        const int kl = kb + kHalf - 1;
+        const float bv = 4 * kl + l4 < kFlat ? w1[(size_t)kl * 128] : 0.f;
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a_row[4 * kl], bv, acc0, 0, 0, 0);
+    }
+    const f32x4 acc = acc0 + acc1;
+    if (kh) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) s_part[(nt * 16 + l4 * 4 + r) * 16 + l15] = acc[r];
+    }
+    __syncthreads();
+    if (!kh) {
+        const int n = nt * 16 + l15;
+        const float bias = ws[SSD_POL_FC1_B + n];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int m = l4 * 4 + r;
+            s_h1[m * kHP + n] = tanhf(acc[r] + s_part[(nt * 16 + m) * 16 + l15] + bias);
+        }
+    }
+    __syncthreads();
+    const int m = tid >> 4, n = tid & 15;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int nn = n + 16 * h;
+        float acc2 = 0.f;
+#pragma unroll 8
+        for (int k = 0; k < 32; ++k) acc2 = fmaf(s_h1[m * kHP + k], ws[SSD_POL_FC2_W + k * 32 + nn], acc2);
+        if (b0 + m < a.B) a.feat[(((size_t)(b0 + m) * a.N + i) * 2 + s) * 32 + nn] = tanhf(acc2 + ws[SSD_POL_FC2_B + nn]);
+    }
+    __syncthreads();                                    // s_part and s_h1 are the next stack's
+}
+
+// kModeFeatures: stop after fc2 and write its output to a.feat (the trunk of the recurrent policy, ssd_policy_lstm.hip).
+// kModeMoa: both FC stacks of the MOA policy after the conv (moa_stack).
+template <int kMode>
 __global__ void __launch_bounds__(kThreads) ssd_policy_kernel(ssd::PolicyArgs a) {
+    constexpr bool kFeatures = kMode != kModeHeads;
     __shared__ float s_norm[256];
     __shared__ float s_conv[kTile * kPitch];
     __shared__ float s_buf[(kTile * kObs + 3) / 4];   // the observation bytes; after the conv, the small buffers below
@@ -96,6 +151,11 @@ __global__ void __launch_bounds__(kThreads) ssd_policy_kernel(ssd::PolicyArgs a)
         for (int f = 0; f < 6; ++f) dst[f] = fmaxf(acc[f] + w[SSD_POL_CONV_B + f], 0.f);
     }
     __syncthreads();
+    if constexpr (kMode == kModeMoa) {
+        moa_stack(a, w, 0, s_conv, s_part, s_h1, tid, i, b0);
+        moa_stack(a, w, 1, s_conv, s_part, s_h1, tid, i, b0);
+        return;
+    } else {
 
     // ---- 3. fc1 on the matrix cores: A[m][k] = conv row m, B[k][n] = fc1_w[k][n] ----
     // v_mfma_f32_16x16x4_f32: lane l holds A[l & 15][k = l >> 4] and B[k = l >> 4][l & 15]; D: col l & 15, row 4 (l >> 4) + r
@@ -186,6 +246,7 @@ __global__ void __launch_bounds__(kThreads) ssd_policy_kernel(ssd::PolicyArgs a)
         a.actions[row] = act;
         if (a.logp) a.logp[row] = lp;
     }
+    }  // (kMode != kModeMoa)
 }
 
 thread_local std::string g_policy_error;
@@ -201,13 +262,19 @@ namespace ssd {
 
 hipError_t launch_policy(const PolicyArgs &a, void *stream) {
     const dim3 grid((unsigned)((a.B + kTile - 1) / kTile), (unsigned)a.N), block(kThreads);
-    hipLaunchKernelGGL(ssd_policy_kernel<false>, grid, block, 0, static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(ssd_policy_kernel<kModeHeads>, grid, block, 0, static_cast<hipStream_t>(stream), a);
     return hipGetLastError();
 }
 
 hipError_t launch_policy_features(const PolicyArgs &a, void *stream) {
     const dim3 grid((unsigned)((a.B + kTile - 1) / kTile), (unsigned)a.N), block(kThreads);
-    hipLaunchKernelGGL(ssd_policy_kernel<true>, grid, block, 0, static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(ssd_policy_kernel<kModeFeatures>, grid, block, 0, static_cast<hipStream_t>(stream), a);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_moa_features(const PolicyArgs &a, void *stream) {
+    const dim3 grid((unsigned)((a.B + kTile - 1) / kTile), (unsigned)a.N), block(kThreads);
+    hipLaunchKernelGGL(ssd_policy_kernel<kModeMoa>, grid, block, 0, static_cast<hipStream_t>(stream), a);
     return hipGetLastError();
 }
 

@@ -22,7 +22,8 @@ struct PolicyArgs {
     const uint4 *hdr;              // [B] the engine's per-env header {key, t, episode, ...}: (episode, t) of the state acted in
     uint32_t seed_lo, seed_hi, env_base;
     int32_t greedy;
-    float *feat;                   // launch_policy_features only: fc2's output [B][N][32] (the heads are not computed)
+    float *feat;                   // launch_policy_features only: fc2's output [B][N][32] (the heads are not computed);
+                                   // launch_policy_moa_features: both FC stacks' outputs [B][N][2][32]
 };
 
 struct LstmArgs {
@@ -46,8 +47,44 @@ struct LstmArgs {
 hipError_t launch_policy(const PolicyArgs &a, void *stream);
 // The same kernel up to fc2: writes a.feat instead of the heads (logits, value, actions unused).
 hipError_t launch_policy_features(const PolicyArgs &a, void *stream);
+// The same kernel with the MOA policy's two tanh FC stacks (SSD_MOA_FC1_W(s)): writes a.feat [B][N][2][32].
+hipError_t launch_policy_moa_features(const PolicyArgs &a, void *stream);
 // The recurrent cell and heads (ssd_policy_lstm.hip); a.C in {64, 128, 256}.
 hipError_t launch_policy_lstm(const LstmArgs &a, void *stream);
+struct MoaArgs {
+    const float *w;                // P weight sets of set_floats floats each (SSD_MOA_SET_FLOATS(C, A, N))
+    int32_t P, A, B, N, C, set_floats;
+    const float *feat;             // [B][N][2][32] the FC stacks' outputs
+    const float *state_in;         // [B][N][4][C] (h1, c1, h2, c2)
+    float *state_out;              // [B][N][4][C], null, or state_in itself
+    float *state_used;             // [B][N][4][C] the state the step used (after the start rule), or null
+    const uint8_t *starts;         // [B][N] start rows (the forward), or null
+    const uint4 *hdr;              // [B] start where t == 0 (rollouts), or null; also (episode, t) of the action draw
+    // actions cell (launch_policy_moa_actions)
+    float *logits;                 // [B][N][A] or null
+    float *logits_scratch;         // [B][N][16] this step's logits for the MOA cell, or null
+    float *value;                  // [B][N] or null
+    int32_t *actions;              // [B][N] or null (no action selection)
+    int32_t *actions_copy;         // [B][N] a second copy of the actions (the next step's previous joint action), or null
+    float *logp;                   // [B][N] or null
+    uint32_t seed_lo, seed_hi, env_base;
+    int32_t greedy;
+    // MOA cell (launch_policy_moa_cell)
+    const int32_t *prev;           // [B][N] the previous joint action by agent index (read where the row does not start)
+    int32_t *prev_used;            // [B][N] what the MOA read (zero at a start), or null
+    const float *pi_logits;        // [B][N][pi_stride] this step's action logits (for the influence), or null
+    int32_t pi_stride;
+    const int32_t *taken;          // [B][N] this step's actions (for the influence), or null: no influence
+    float *moa_logits;             // [B][N][N-1][A] or null
+    float *cf_logits;              // [B][N][A][N-1][A] or null
+    float *influence;              // [B][N] or null
+    float clip;
+};
+
+// The MOA policy's actions cell: the Keras LSTM on stack 0, the heads and the action (ssd_policy_moa.hip).
+hipError_t launch_policy_moa_actions(const MoaArgs &a, void *stream);
+// The MOA cell: gates, the A counterfactual updates and predictions, moa_logits and the influence (ssd_policy_moa.hip).
+hipError_t launch_policy_moa_cell(const MoaArgs &a, void *stream);
 // The calling thread's ssd_policy_last_error text; returns SSD_E_INVALID.
 int policy_fail(const char *msg);
 void policy_set_error(const char *msg);

@@ -306,12 +306,14 @@ class VecEngine(object):
 
     # ------------------------------------------------------------------ policy in the loop (include/ssd.h, POLICY ROLLOUTS)
     def _policy_weights(self, policy):
-        """Checks a ConvFCPolicy or ConvLSTMPolicy against this engine (everything before anything is enqueued); returns its
-        weight-set count."""
-        from .policy import ConvFCPolicy, ConvLSTMPolicy
+        """Checks a ConvFCPolicy, ConvLSTMPolicy or ConvMOAPolicy against this engine (everything before anything is enqueued);
+        returns its weight-set count."""
+        from .policy import ConvFCPolicy, ConvLSTMPolicy, ConvMOAPolicy
         torch, dev = self._torch()
-        if not isinstance(policy, (ConvFCPolicy, ConvLSTMPolicy)):
-            raise ValueError("policy must be a ConvFCPolicy or a ConvLSTMPolicy")
+        if not isinstance(policy, (ConvFCPolicy, ConvLSTMPolicy, ConvMOAPolicy)):
+            raise ValueError("policy must be a ConvFCPolicy, a ConvLSTMPolicy or a ConvMOAPolicy")
+        if isinstance(policy, ConvMOAPolicy) and policy.num_agents != self.N:
+            raise ValueError("the MOA policy is built for %d agents, the engine has %d" % (policy.num_agents, self.N))
         if self.V != _capi.SSD_POL_VIEW:
             raise ValueError("the policy network takes 15 x 15 views (view_len 7); this engine has V = %d" % self.V)
         if policy.num_actions != self.num_actions:
@@ -329,6 +331,55 @@ class VecEngine(object):
         from .policy import ConvLSTMPolicy
         return isinstance(policy, ConvLSTMPolicy)
 
+    @staticmethod
+    def _is_moa(policy):
+        from .policy import ConvMOAPolicy
+        return isinstance(policy, ConvMOAPolicy)
+
+    def _moa_scratch(self, rows):
+        """The engine's scratch of the MOA policy's calls: SSD_MOA_SCRATCH_FLOATS(rows) floats, reused between calls."""
+        torch, dev = self._torch()
+        n = _capi.SSD_MOA_SCRATCH_FLOATS(rows)
+        buf = getattr(self, "_moa_buf", None)
+        if buf is None or buf.numel() < n:
+            buf = torch.empty(n, dtype=torch.float32, device=dev)
+            self._moa_buf = buf
+        return buf
+
+    def _check_actions_like(self, t, shape, name):
+        torch, dev = self._torch()
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s must be an int32 tensor of shape %s" % (name, tuple(shape)))
+        self._check_tensor(t, tuple(shape), torch.int32, name)
+
+    def _policy_forward_moa(self, policy, obs, lead, B, state, starts, prev_actions, actions, influence_clip):
+        torch, dev = self._torch()
+        N, A, C = self.N, self.num_actions, policy.cell_size
+        if not isinstance(state, torch.Tensor):
+            raise ValueError("a ConvMOAPolicy needs state: a float32 tensor %s" % ((lead + (4, C)),))
+        self._check_tensor(state, lead + (4, C), torch.float32, "state")
+        self._check_actions_like(prev_actions, lead, "prev_actions")
+        if actions is not None:
+            self._check_actions_like(actions, lead, "actions")
+        if starts is not None:
+            if not isinstance(starts, torch.Tensor) or starts.dtype not in (torch.bool, torch.uint8):
+                raise ValueError("starts must be a bool or uint8 tensor of shape %s" % (lead,))
+            self._check_tensor(starts, lead, starts.dtype, "starts")
+            starts = starts.view(torch.uint8)
+        clip = float(influence_clip)
+        if not (0.0 <= clip < float("inf")):
+            raise ValueError("influence_clip must be finite and >= 0")
+        e = lambda shape: torch.empty(lead + shape, dtype=torch.float32, device=dev)   # noqa: E731
+        logits, value, moa, cf, new_state = e((A,)), e(()), e((N - 1, A)), e((A, N - 1, A)), torch.empty_like(state)
+        infl = e(()) if actions is not None else None
+        w = policy.packed()
+        dp = self._dp
+        _capi.policy_check(self._L.ssd_policy_moa_forward(dp(w), policy.num_sets, A, C, dp(obs), dp(prev_actions), dp(state),
+                                                          dp(starts), B, N, dp(self._moa_scratch(B * N)), dp(new_state),
+                                                          dp(logits), dp(value), dp(moa), dp(cf), dp(actions), dp(infl), clip,
+                                                          self.device, 0, self._stream()))
+        return logits, value, moa, cf, new_state, infl
+
     def _features(self, rows):
         """The engine's trunk-feature scratch of the recurrent policy: f32 [rows, 32], reused between calls."""
         torch, dev = self._torch()
@@ -338,11 +389,14 @@ class VecEngine(object):
             self._feat_buf = buf
         return buf
 
-    def policy_forward(self, policy, obs, state=None, starts=None):
+    def policy_forward(self, policy, obs, state=None, starts=None, prev_actions=None, actions=None, influence_clip=10.0):
         """The policy's forward pass on the device (ssd_policy_forward): obs uint8 [..., N, 15, 15, 3] -> (logits float32
         [..., N, A], value float32 [..., N]), enqueued on the current stream.  The same kernel as rollout_policy()'s.
         A ConvLSTMPolicy (ssd_policy_lstm_forward) takes state float32 [..., N, 2, C] (required) and starts bool / uint8
-        [..., N] (rows whose state is taken as zero; None: none) and returns (logits, value, new state [..., N, 2, C])."""
+        [..., N] (rows whose state is taken as zero; None: none) and returns (logits, value, new state [..., N, 2, C]).
+        A ConvMOAPolicy (ssd_policy_moa_forward) takes state float32 [..., N, 4, C] and prev_actions int32 [..., N] (both
+        required), starts as above and, for the influence, actions int32 [..., N] (this step's) and influence_clip; it returns
+        (logits, value, moa_logits [..., N, N-1, A], cf_logits [..., N, A, N-1, A], new state, influence [..., N] or None)."""
         torch, dev = self._torch()
         P = self._policy_weights(policy)
         V, N, A = self.V, self.N, self.num_actions
@@ -353,6 +407,10 @@ class VecEngine(object):
         if B < 1:
             raise ValueError("obs holds no observation")
         lead = tuple(obs.shape[:-3])
+        if self._is_moa(policy):
+            return self._policy_forward_moa(policy, obs, lead, B, state, starts, prev_actions, actions, influence_clip)
+        if prev_actions is not None or actions is not None:
+            raise ValueError("prev_actions and actions belong to a ConvMOAPolicy")
         recurrent = self._is_recurrent(policy)
         if not recurrent:
             if state is not None or starts is not None:
@@ -382,7 +440,8 @@ class VecEngine(object):
         return logits, value, new_state
 
     def rollout_policy(self, policy, obs_in, n_steps, obs, actions=None, logp=None, value=None, logits=None, rew=None, done=None,
-                       last_value=None, step0=0, greedy=False, stats=None, state=None, state_ring=None, state_every=1):
+                       last_value=None, step0=0, greedy=False, stats=None, state=None, state_ring=None, state_every=1,
+                       prev_actions=None, prev_actions_ring=None, influence=None, influence_clip=10.0):
         """A closed-loop rollout (ssd_rollout_policy): n_steps rounds of (policy forward on the current observation, action, step
         with automatic reset at the horizon) enqueued by one call, no host synchronisation.  The rings have a leading dimension
         R and step k writes slot (step0 + k) % R:
@@ -393,10 +452,16 @@ class VecEngine(object):
         (include/ssd.h).  stats: an EpisodeStats of this batch folded from rew and done (both required, R >= n_steps).
         A ConvLSTMPolicy (ssd_rollout_policy_lstm) also takes state float32 [E,N,2,C] (required), the carried state, updated in
         place and zero at every episode start; state_ring float32 [S,E,N,2,C] receives the state call-relative step k used in
-        slot k // state_every for every k that is a multiple of state_every (S >= ceil(n_steps / state_every))."""
+        slot k // state_every for every k that is a multiple of state_every (S >= ceil(n_steps / state_every)).
+        A ConvMOAPolicy (ssd_rollout_policy_moa) takes state [E,N,4,C] and state_ring [S,E,N,4,C] as above, prev_actions int32
+        [E,N] (required: the carried previous joint action, read by step 0 and left holding the last step's), and the rings
+        prev_actions_ring int32 [R,E,N] (what each step's MOA read) and influence float32 [R,E,N] (each step's influence reward,
+        clipped to influence_clip)."""
         torch, dev = self._torch()
         P = self._policy_weights(policy)
-        recurrent = self._is_recurrent(policy)
+        moa = self._is_moa(policy)
+        recurrent = self._is_recurrent(policy) or moa
+        SR = 4 if moa else 2
         n_steps, step0 = int(n_steps), int(step0)
         if n_steps < 1:
             raise ValueError("n_steps must be >= 1")
@@ -432,21 +497,34 @@ class VecEngine(object):
         else:
             C = policy.cell_size
             if not isinstance(state, torch.Tensor):
-                raise ValueError("a ConvLSTMPolicy needs state: a float32 tensor [%d,%d,2,%d]" % (E, N, C))
-            self._check_tensor(state, (E, N, 2, C), torch.float32, "state")
+                raise ValueError("a recurrent policy needs state: a float32 tensor [%d,%d,%d,%d]" % (E, N, SR, C))
+            self._check_tensor(state, (E, N, SR, C), torch.float32, "state")
             state_every = int(state_every)
             S = 0
             if state_ring is not None:
                 if state_every < 1:
                     raise ValueError("state_every must be >= 1")
                 if not isinstance(state_ring, torch.Tensor) or state_ring.dim() != 5:
-                    raise ValueError("state_ring must be a float32 ring [S,%d,%d,2,%d]" % (E, N, C))
+                    raise ValueError("state_ring must be a float32 ring [S,%d,%d,%d,%d]" % (E, N, SR, C))
                 S = int(state_ring.shape[0])
-                self._check_tensor(state_ring, (S, E, N, 2, C), torch.float32, "state_ring")
+                self._check_tensor(state_ring, (S, E, N, SR, C), torch.float32, "state_ring")
                 if S < -(-n_steps // state_every):
                     raise ValueError("state_ring needs ceil(n_steps / state_every) = %d slots, has %d" % (-(-n_steps // state_every), S))
                 if state_ring.data_ptr() < state.data_ptr() + state.numel() * 4 and state.data_ptr() < state_ring.data_ptr() + state_ring.numel() * 4:
                     raise ValueError("state_ring must not overlap state")
+        if moa:
+            self._check_actions_like(prev_actions, (E, N), "prev_actions")
+            if prev_actions_ring is not None:
+                self._check_actions_like(prev_actions_ring, (R, E, N), "prev_actions_ring")
+            if influence is not None:
+                if not isinstance(influence, torch.Tensor):
+                    raise ValueError("influence must be a float32 ring [R,%d,%d]" % (E, N))
+                self._check_tensor(influence, (R, E, N), torch.float32, "influence")
+            clip = float(influence_clip)
+            if not (0.0 <= clip < float("inf")):
+                raise ValueError("influence_clip must be finite and >= 0")
+        elif prev_actions is not None or prev_actions_ring is not None or influence is not None:
+            raise ValueError("prev_actions, prev_actions_ring and influence belong to a ConvMOAPolicy")
         if actions is None:
             buf = getattr(self, "_policy_actions", None)
             if buf is None or tuple(buf.shape) != (R, E, N):
@@ -455,7 +533,13 @@ class VecEngine(object):
             actions = buf
         w = policy.packed()
         dp = self._dp
-        if recurrent:
+        if moa:
+            rc = self._L.ssd_rollout_policy_moa(self._h, dp(w), P, C, dp(obs_in), n_steps, step0, dp(state), dp(state_ring), S,
+                                                state_every, dp(prev_actions), dp(prev_actions_ring), dp(influence), clip,
+                                                dp(self._moa_scratch(E * N)), dp(obs), dp(actions), dp(logp), dp(value),
+                                                dp(logits), dp(rew), dp(done), R, dp(last_value),
+                                                _capi.SSD_POLICY_GREEDY if greedy else 0, self._stream())
+        elif recurrent:
             rc = self._L.ssd_rollout_policy_lstm(self._h, dp(w), P, C, dp(obs_in), n_steps, step0, dp(state), dp(state_ring), S,
                                                  state_every, dp(self._features(E * N)), dp(obs), dp(actions), dp(logp), dp(value),
                                                  dp(logits), dp(rew), dp(done), R, dp(last_value),

@@ -1,6 +1,7 @@
 """The conv-FC policy network of the reference (models/conv_to_fc_net.py:1-51, ConvToFCNet: the model of Jaques et al. 2019)
-as a torch module whose weights the device kernels read (include/ssd.h, SSD_POL_*; csrc/ssd_policy.hip), and ConvLSTMPolicy, the
-same trunk under RLlib's LSTM (SSD_LSTM_*; csrc/ssd_policy_lstm.hip).
+as a torch module whose weights the device kernels read (include/ssd.h, SSD_POL_*; csrc/ssd_policy.hip), ConvLSTMPolicy, the
+same trunk under RLlib's LSTM (SSD_LSTM_*; csrc/ssd_policy_lstm.hip), and ConvMOAPolicy, the causal-influence policy of
+train_moa.py with its social-influence reward, influence() (SSD_MOA_*; csrc/ssd_policy_moa.hip).
 
     policy = ConvFCPolicy(num_actions=8, num_sets=5).cuda()       # one weight set per agent, as train_baseline.py:87-96
     logits, value = policy(obs_u8)                                # [..., N, 15, 15, 3] -> [..., N, A], [..., N]
@@ -271,3 +272,242 @@ def cdf_margin(logits, u):
         c = (c + (e[..., a] / s).astype(np.float32)).astype(np.float32)
         margin = np.minimum(margin, np.abs(np.asarray(u, np.float64) - c.astype(np.float64)))
     return margin
+
+
+def _glorot(shape, fan_in, fan_out, generator):
+    limit = float(np.sqrt(6.0 / (fan_in + fan_out)))
+    return (torch.rand(shape, generator=generator, dtype=torch.float64) * 2 - 1) * limit
+
+
+def _orthogonal(P, rows, cols, generator):
+    """Keras' Orthogonal initializer for [rows, cols] kernels (rows <= cols), one per weight set."""
+    out = torch.empty((P, rows, cols), dtype=torch.float64)
+    for p in range(P):
+        q, r = torch.linalg.qr(torch.randn((cols, rows), generator=generator, dtype=torch.float64))
+        out[p] = (q * torch.sign(torch.diagonal(r))).T
+    return out
+
+
+def agent_order(num_agents):
+    """Agent indices in the order of their ids sorted as strings ('agent-10' < 'agent-2'): map_env.py:202's order."""
+    return sorted(range(int(num_agents)), key=lambda n: "agent-%d" % n)
+
+
+def other_agents(num_agents):
+    """others [N, N-1]: row i lists the agents other than i in string-sorted id order (the j of the MOA's predictions)."""
+    order = agent_order(num_agents)
+    return np.array([[n for n in order if n != i] for i in range(int(num_agents))], dtype=np.int64).reshape(int(num_agents), -1)
+
+
+def keras_lstm(x, h, c, kernel, recurrent, bias):
+    """One Keras LSTM step (TF 2.0): z = x @ kernel + h @ recurrent + bias, gates (i, f, c, o), no forget bias at run time."""
+    C = h.shape[-1]
+    z = x @ kernel + h @ recurrent + bias
+    zi, zf, zc, zo = z[..., :C], z[..., C:2 * C], z[..., 2 * C:3 * C], z[..., 3 * C:]
+    c2 = torch.sigmoid(zf) * c + torch.sigmoid(zi) * torch.tanh(zc)
+    return torch.sigmoid(zo) * torch.tanh(c2), c2
+
+
+class ConvMOAPolicy(torch.nn.Module):
+    """The causal-influence policy of run_scripts/train_moa.py (MOA_LSTM, models/moa_model.py:121-311): the trunk's conv, two
+    tanh FC stacks (32, 32), a Keras LSTM of cell_size C cells for the actions (logits and value on its output) and one for the
+    model of other agents (MOA), whose input is the MOA stack's output and the N previous actions, own first and the others in
+    string-sorted id order, and whose output predicts the others' next actions, pred [N-1, A] (include/ssd.h, MOA POLICY
+    ROLLOUTS).  A state is [..., 4, C]: (h1, c1, h2, c2).
+
+        policy = ConvMOAPolicy(8, num_agents=5, num_sets=5).cuda()
+        state = policy.initial_state((E, 5))
+        logits, value, moa_logits, cf_logits, state = policy(obs_u8, prev_actions, state, starts)
+        r = influence(logits, cf_logits, actions, clip=10.0)             # the social-influence reward of each row
+
+    Parameters in Keras' layouts with a leading weight-set axis: conv_w, conv_b; a_fc1_w [1014, 32] ... a_fc2_b (actions stack),
+    m_fc1_w ... m_fc2_b (MOA stack); lstm_kernel [32, 4C], lstm_recurrent [C, 4C], lstm_bias [4C], logits_w [C, A], logits_b,
+    value_w [C, 1], value_b; moa_kernel [32 + N, 4C], moa_recurrent [C, 4C], moa_bias [4C], pred_w [C, (N-1) A], pred_b."""
+
+    def __init__(self, num_actions, num_agents, num_sets=1, cell_size=128, seed=0):
+        super().__init__()
+        A, N, P, C = int(num_actions), int(num_agents), int(num_sets), int(cell_size)
+        if not 1 <= A <= _capi.SSD_POL_MAX_ACTIONS:
+            raise ValueError("num_actions must be 1..%d" % _capi.SSD_POL_MAX_ACTIONS)
+        if not 2 <= N <= _capi.SSD_MOA_MAX_AGENTS:
+            raise ValueError("the MOA policy needs 2..%d agents" % _capi.SSD_MOA_MAX_AGENTS)
+        if P not in (1, N):
+            raise ValueError("num_sets must be 1 or num_agents")
+        if C not in _capi.LSTM_CELL_SIZES:
+            raise ValueError("cell_size must be one of %s" % (_capi.LSTM_CELL_SIZES,))
+        self.num_actions, self.num_agents, self.num_sets, self.cell_size = A, N, P, C
+        g = torch.Generator().manual_seed(int(seed))
+        init = {"conv_w": _glorot((P, 3, 3, 3, FILTERS), 27, 9 * FILTERS, g),
+                "lstm_kernel": _glorot((P, HIDDEN, 4 * C), HIDDEN, 4 * C, g), "lstm_recurrent": _orthogonal(P, C, 4 * C, g),
+                "logits_w": _glorot((P, C, A), C, A, g), "value_w": normc((P, C, 1), 0.01, g),
+                "moa_kernel": _glorot((P, HIDDEN + N, 4 * C), HIDDEN + N, 4 * C, g), "moa_recurrent": _orthogonal(P, C, 4 * C, g),
+                "pred_w": _glorot((P, C, (N - 1) * A), C, (N - 1) * A, g)}
+        for s in ("a", "m"):
+            init[s + "_fc1_w"] = normc((P, FLAT, HIDDEN), 1.0, g)
+            init[s + "_fc2_w"] = normc((P, HIDDEN, HIDDEN), 1.0, g)
+        for name in ("lstm_bias", "moa_bias"):                  # Keras' unit_forget_bias: 1 in the forget block
+            b = torch.zeros((P, 4 * C), dtype=torch.float64)
+            b[:, C:2 * C] = 1.0
+            init[name] = b
+        for name, shape, _ in self.layout():
+            t = init.get(name)
+            if t is None:
+                t = torch.zeros((P,) + shape, dtype=torch.float64)       # the other biases start at zero
+            self.register_parameter(name, torch.nn.Parameter(t.to(torch.float32)))
+        self._packed = None
+        self._tables = {}
+        self.register_buffer("_others", torch.from_numpy(other_agents(N)), persistent=False)
+
+    def layout(self):
+        """(name, shape of one set, float offset within a packed set) of every parameter, in packed order."""
+        A, N, C = self.num_actions, self.num_agents, self.cell_size
+        out = list(_FIXED[:2])
+        for s, p in ((0, "a"), (1, "m")):
+            out += [(p + "_fc1_w", (FLAT, HIDDEN), _capi.SSD_MOA_FC1_W(s)), (p + "_fc1_b", (HIDDEN,), _capi.SSD_MOA_FC1_B(s)),
+                    (p + "_fc2_w", (HIDDEN, HIDDEN), _capi.SSD_MOA_FC2_W(s)), (p + "_fc2_b", (HIDDEN,), _capi.SSD_MOA_FC2_B(s))]
+        lw, mw = _capi.SSD_MOA_LSTM_W(C), _capi.SSD_MOA_MW(C, A)
+        out += [("lstm_kernel", (HIDDEN, 4 * C), lw), ("lstm_recurrent", (C, 4 * C), lw + HIDDEN * 4 * C),
+                ("lstm_bias", (4 * C,), _capi.SSD_MOA_LSTM_B(C)),
+                ("value_w", (C, 1), _capi.SSD_MOA_VALUE_W(C)), ("value_b", (1,), _capi.SSD_MOA_VALUE_B(C)),
+                ("logits_w", (C, A), _capi.SSD_MOA_LOGITS_W(C)), ("logits_b", (A,), _capi.SSD_MOA_LOGITS_B(C, A)),
+                ("moa_kernel", (HIDDEN + N, 4 * C), mw), ("moa_recurrent", (C, 4 * C), mw + _capi.SSD_MOA_XM * 4 * C),
+                ("moa_bias", (4 * C,), _capi.SSD_MOA_MB(C, A)),
+                ("pred_w", (C, (N - 1) * A), _capi.SSD_MOA_PRED_W(C, A)), ("pred_b", ((N - 1) * A,), _capi.SSD_MOA_PRED_B(C, A, N))]
+        return tuple(out)
+
+    load_arrays = ConvFCPolicy.load_arrays
+    packed = ConvFCPolicy.packed                                 # (the MOA input's zero rows 32 + N .. 47 are never written)
+
+    @property
+    def set_floats(self):
+        return _capi.SSD_MOA_SET_FLOATS(self.cell_size, self.num_actions, self.num_agents)
+
+    def initial_state(self, lead, device=None):
+        """A zero state [*lead, 4, C] (float32, on the parameters' device unless given)."""
+        lead = (int(lead),) if isinstance(lead, int) else tuple(int(n) for n in lead)
+        return torch.zeros(lead + (4, self.cell_size), dtype=self.lstm_kernel.dtype,
+                           device=self.lstm_kernel.device if device is None else device)
+
+    def _per_agent(self, name):
+        """Parameter `name` with one entry per agent [N, ...] (set i, or set 0 for all when shared)."""
+        t = getattr(self, name)
+        return t.expand((self.num_agents,) + tuple(t.shape[1:])) if self.num_sets == 1 else t
+
+    def _stacks(self, obs):
+        """u8 [..., N, 15, 15, 3] -> (actions-stack output [M, N, 32], MOA-stack output [M, N, 32], leading shape [..., N])."""
+        N = self.num_agents
+        if obs.shape[-3:] != (VIEW, VIEW, 3) or obs.dim() < 4 or obs.shape[-4] != N:
+            raise ValueError("observations must be [..., %d, 15, 15, 3], got %s" % (N, tuple(obs.shape)))
+        lead = tuple(obs.shape[:-3])
+        dt = self.conv_w.dtype
+        key = (obs.device, dt)
+        if key not in self._tables:
+            self._tables[key] = torch.from_numpy(_NORMALISE).to(dt).to(obs.device)
+        x = self._tables[key][obs.long()].reshape(-1, N, VIEW, VIEW, 3)
+        M = x.shape[0]
+        x = x.permute(0, 1, 4, 2, 3).reshape(M, N * 3, VIEW, VIEW)
+        wc = self._per_agent("conv_w").permute(0, 4, 3, 1, 2).reshape(N * FILTERS, 3, 3, 3)
+        h = torch.relu(torch.nn.functional.conv2d(x, wc, self._per_agent("conv_b").reshape(N * FILTERS), groups=N))
+        h = h.reshape(M, N, FILTERS, 13, 13).permute(0, 1, 3, 4, 2).reshape(M, N, FLAT)
+        out = []
+        for p in ("a", "m"):
+            y = torch.tanh(torch.einsum("mnk,nkj->mnj", h, self._per_agent(p + "_fc1_w")) + self._per_agent(p + "_fc1_b"))
+            out.append(torch.tanh(torch.einsum("mnk,nkj->mnj", y, self._per_agent(p + "_fc2_w")) + self._per_agent(p + "_fc2_b")))
+        return out[0], out[1], lead
+
+    def _step(self, obs, prev_actions, state, starts, counterfactuals):
+        N, A, C = self.num_agents, self.num_actions, self.cell_size
+        ya, ym, lead = self._stacks(obs)
+        M = ya.shape[0]
+        if tuple(state.shape) != lead + (4, C):
+            raise ValueError("state must have shape %s, got %s" % (lead + (4, C), tuple(state.shape)))
+        if tuple(prev_actions.shape) != lead:
+            raise ValueError("prev_actions must have shape %s, got %s" % (lead, tuple(prev_actions.shape)))
+        st = state.to(ya.dtype).reshape(M, N, 4, C)
+        prev = prev_actions.reshape(M, N).to(ya.device)
+        s = None
+        if starts is not None:
+            if tuple(starts.shape) != lead:
+                raise ValueError("starts must have shape %s, got %s" % (lead, tuple(starts.shape)))
+            s = starts.to(torch.bool).reshape(M, N).to(st.device)
+            st = torch.where(s[..., None, None], torch.zeros((), dtype=st.dtype, device=st.device), st)
+        h1, c1 = keras_lstm(ya[:, :, None, :], st[:, :, 0, None], st[:, :, 1, None], self._per_agent("lstm_kernel"),
+                            self._per_agent("lstm_recurrent"), self._per_agent("lstm_bias")[:, None])
+        h1, c1 = h1[:, :, 0], c1[:, :, 0]
+        logits = torch.einsum("mnk,nkj->mnj", h1, self._per_agent("logits_w")) + self._per_agent("logits_b")
+        value = (torch.einsum("mnk,nkj->mnj", h1, self._per_agent("value_w")) + self._per_agent("value_b"))[..., 0]
+        # the MOA input of row (m, i): own previous action, then the others' in string order (zero at a start)
+        others = prev[:, self._others.to(prev.device)]                           # [M, N, N-1]
+        acts = torch.cat([prev[..., None], others], dim=-1)                      # [M, N, N]
+        if s is not None:                                       # a starting row's whole vector is zero (selected)
+            acts = torch.where(s[..., None], torch.zeros_like(acts), acts)
+        acts = acts.to(ya.dtype)
+        mk, mr, mb = self._per_agent("moa_kernel"), self._per_agent("moa_recurrent"), self._per_agent("moa_bias")[:, None]
+        h2s, c2s = st[:, :, 2, None], st[:, :, 3, None]
+        if counterfactuals:                                     # own slot replaced by a = 0 .. A-1: [M, N, A, 32 + N]
+            cf_acts = acts[:, :, None, :].repeat(1, 1, A, 1)
+            cf_acts[..., 0] = torch.arange(A, dtype=ya.dtype, device=ya.device)
+            inp = torch.cat([ym[:, :, None, :].expand(M, N, A, HIDDEN), cf_acts], dim=-1)
+            hcf, _ = keras_lstm(inp, h2s.expand(M, N, A, C), c2s.expand(M, N, A, C), mk, mr, mb)
+            cf = torch.einsum("mnak,nkj->mnaj", hcf, self._per_agent("pred_w")) + self._per_agent("pred_b")[:, None]
+            cf = cf.reshape(M, N, A, N - 1, A)
+            own = acts[..., 0].long().clamp(0, A - 1)
+            moa = torch.gather(cf, 2, own[:, :, None, None, None].expand(M, N, 1, N - 1, A))[:, :, 0]
+        h2, c2 = keras_lstm(torch.cat([ym, acts], dim=-1)[:, :, None, :], h2s, c2s, mk, mr, mb)
+        h2, c2 = h2[:, :, 0], c2[:, :, 0]
+        if not counterfactuals:
+            moa = (torch.einsum("mnk,nkj->mnj", h2, self._per_agent("pred_w")) + self._per_agent("pred_b")).reshape(M, N, N - 1, A)
+            cf = None
+        new_state = torch.stack([h1, c1, h2, c2], dim=2)
+        out = (logits.reshape(lead + (A,)), value.reshape(lead), moa.reshape(lead + (N - 1, A)),
+               None if cf is None else cf.reshape(lead + (A, N - 1, A)), new_state.reshape(lead + (4, C)))
+        return out
+
+    def forward(self, obs, prev_actions, state, starts=None):
+        """obs u8 [..., N, 15, 15, 3], prev_actions int [..., N] (the previous joint action of each row's env, by agent
+        index), state [..., N, 4, C], starts bool [..., N] or None: rows whose state and previous actions are taken as zero
+        (selected: whatever they hold there is never used).  Returns (logits [..., N, A], value [..., N], moa_logits
+        [..., N, N-1, A], cf_logits [..., N, A, N-1, A], new state [..., N, 4, C]); moa_logits is cf_logits at the own
+        previous action."""
+        return self._step(obs, prev_actions, state, starts, True)
+
+    def forward_sequence(self, obs, prev_actions, state, resets=None):
+        """T steps for truncated BPTT, without counterfactuals: obs u8 [T, ..., N, 15, 15, 3], prev_actions [T, ..., N],
+        state [..., N, 4, C] before step 0, resets bool [T, ..., N] or None (the start rule of forward()).  Differentiable.
+        Returns (logits [T, ..., N, A], value [T, ..., N], moa_logits [T, ..., N, N-1, A], the state after step T - 1)."""
+        T = int(obs.shape[0])
+        if int(prev_actions.shape[0]) != T or (resets is not None and int(resets.shape[0]) != T):
+            raise ValueError("prev_actions and resets must have T = %d rows" % T)
+        logits, values, moas = [], [], []
+        for t in range(T):
+            lg, v, moa, _, state = self._step(obs[t], prev_actions[t], state, None if resets is None else resets[t], False)
+            logits.append(lg)
+            values.append(v)
+            moas.append(moa)
+        return torch.stack(logits), torch.stack(values), torch.stack(moas), state
+
+    def moa_loss(self, moa_logits, actions, weight=1.0):
+        """MOALoss (algorithms/common_funcs.py:70-95): the mean over rows and other agents of the cross-entropy of moa_logits
+        [..., N, N-1, A] against the other agents' actions [..., N] taken at the SAME step (the reference pairs row t with row
+        t + 1's other_agent_actions and drops the last row; here the targets are in the same actions ring), times weight."""
+        N, A = self.num_agents, self.num_actions
+        others = actions.long()[..., self._others.to(actions.device)]            # [..., N, N-1]
+        ce = torch.nn.functional.cross_entropy(moa_logits.reshape(-1, A), others.reshape(-1), reduction="mean")
+        return ce * weight
+
+
+def influence(logits, cf_logits, actions, clip=10.0):
+    """The social-influence reward of each row (include/ssd.h): logits [..., A] of this step's action distribution pi,
+    cf_logits [..., A, N-1, A] the counterfactual predictions, actions [...] the actions taken.  For each other agent j,
+    KL(p || q) with p = softmax(cf[a_t][j]) and q = sum_a pi(a) softmax(cf[a][j]), in log space; summed over j, clipped to
+    [-clip, clip]; a non-finite row gives 0."""
+    logits, cf = logits.to(torch.float32), cf_logits.to(torch.float32)
+    lpi = torch.log_softmax(logits, dim=-1)                                       # [..., A]
+    ls = torch.log_softmax(cf, dim=-1)                                            # [..., A, N-1, A]
+    idx = actions.long()[..., None, None, None].expand(ls.shape[:-3] + (1,) + ls.shape[-2:])
+    lp = torch.gather(ls, -3, idx)[..., 0, :, :]                                  # [..., N-1, A]
+    lq = torch.logsumexp(lpi[..., :, None, None] + ls, dim=-3)
+    p = lp.exp()
+    kl = torch.where(p != 0, p * (lp - lq), torch.zeros((), dtype=p.dtype, device=p.device)).sum(-1).sum(-1)
+    kl = torch.where(torch.isfinite(kl), kl, torch.zeros((), dtype=kl.dtype, device=kl.device))
+    return kl.clamp(-float(clip), float(clip))

@@ -43,6 +43,8 @@ class SSDVectorEnv(object):
         self._act_buf = None
         self._pending = None
         self._lstm_state = None                  # the recurrent policy's state [E,N,2,C] carried across sample() calls
+        self._moa_state = None                   # the MOA policy's state [E,N,4,C] and previous joint action [E,N], likewise
+        self._moa_prev = None
         # track_episodes: step k writes rew / done into slot k % track_ring of a ring that the episode statistics fold
         self.stats = None
         if track_episodes:
@@ -106,6 +108,7 @@ class SSDVectorEnv(object):
             self.stats.discard()                 # the episodes still open are cut short
         self._alloc()
         self._lstm_state = None
+        self._moa_state = self._moa_prev = None
         self.engine.reset(obs=self._out[0])
         return self._wrap(self._out[0], None, None)
 
@@ -149,7 +152,7 @@ class SSDVectorEnv(object):
         self._advance()
         return self._wrap(obs, self._act_buf, done if self.horizon > 0 else None), rew, done
 
-    def sample(self, policy, n_steps, greedy=False, state_every=None):
+    def sample(self, policy, n_steps, greedy=False, state_every=None, influence_weight=1.0):
         """n_steps closed-loop steps of a ConvFCPolicy or a ConvLSTMPolicy on the device in one call (VecEngine.rollout_policy): returns a dict of
         device tensors obs u8 [K,E,N,15,15,3], actions i32, logp f32, value f32, rew i32, done u8 (all [K,E,N], step k in row
         k) and last_value f32 [E,N] (the value of the final observation).  Episodes end at the horizon as in step(): a finished
@@ -159,7 +162,11 @@ class SSDVectorEnv(object):
         A ConvLSTMPolicy's state [E,N,2,C] is kept by the adapter across calls (zero after reset(), and at every episode start)
         and the dict gains "state_in" f32 [E,N,2,C], the state step 0 used; with state_every, "state" f32 [S,E,N,2,C] too, the
         state of steps 0, state_every, 2 state_every, ... (S = ceil(n_steps / state_every)).  A policy of another cell size than
-        the state held raises until reset()."""
+        the state held raises until reset().
+        A ConvMOAPolicy's state [E,N,4,C] and previous joint action [E,N] are kept the same way (both zero after reset() and
+        at every episode start), and the dict gains "state_in", "state" (with state_every), "influence" f32 [K,E,N],
+        "prev_actions" i32 [K,E,N] (what each step's MOA read) and "rewards" f32 [K,E,N] = rew + influence_weight *
+        influence."""
         import torch
         if self.float32_obs:
             raise ValueError("sample() records uint8 observations: construct with float32_obs=False")
@@ -170,13 +177,15 @@ class SSDVectorEnv(object):
             raise ValueError("n_steps must be >= 1")
         eng = self.engine
         eng._policy_weights(policy)                  # (every check before anything is enqueued)
-        recurrent = eng._is_recurrent(policy)
+        moa = eng._is_moa(policy)
+        recurrent = eng._is_recurrent(policy) or moa
         if not recurrent and state_every is not None:
             raise ValueError("state_every belongs to a ConvLSTMPolicy")
         if recurrent:
-            if self._lstm_state is not None and self._lstm_state.shape[-1] != policy.cell_size:
+            held = self._moa_state if moa else self._lstm_state
+            if held is not None and held.shape[-1] != policy.cell_size:
                 raise ValueError("the adapter holds the state of a %d-cell policy, this one has %d cells: reset() first"
-                                 % (self._lstm_state.shape[-1], policy.cell_size))
+                                 % (held.shape[-1], policy.cell_size))
             every = n_steps if state_every is None else int(state_every)
             if every < 1:
                 raise ValueError("state_every must be >= 1")
@@ -194,7 +203,19 @@ class SSDVectorEnv(object):
                "done": torch.empty((n_steps, E, N), dtype=torch.uint8, device=dev),
                "last_value": torch.empty((E, N), dtype=torch.float32, device=dev)}
         kw = {}
-        if recurrent:
+        if moa:
+            if self._moa_state is None:
+                self._moa_state = torch.zeros((E, N, 4, policy.cell_size), dtype=torch.float32, device=dev)
+                self._moa_prev = torch.zeros((E, N), dtype=torch.int32, device=dev)
+            ring = torch.empty((-(-n_steps // every), E, N, 4, policy.cell_size), dtype=torch.float32, device=dev)
+            out["influence"] = torch.empty((n_steps, E, N), dtype=torch.float32, device=dev)
+            out["prev_actions"] = torch.empty((n_steps, E, N), dtype=torch.int32, device=dev)
+            kw = dict(state=self._moa_state, state_ring=ring, state_every=every, prev_actions=self._moa_prev,
+                      prev_actions_ring=out["prev_actions"], influence=out["influence"])
+            out["state_in"] = ring[0]
+            if state_every is not None:
+                out["state"] = ring
+        elif recurrent:
             if self._lstm_state is None:
                 self._lstm_state = torch.zeros((E, N, 2, policy.cell_size), dtype=torch.float32, device=dev)
             ring = torch.empty((-(-n_steps // every), E, N, 2, policy.cell_size), dtype=torch.float32, device=dev)
@@ -206,6 +227,8 @@ class SSDVectorEnv(object):
         eng.rollout_policy(policy, self._out[0], n_steps, out["obs"], actions=out["actions"], logp=out["logp"], value=out["value"],
                            rew=out["rew"], done=out["done"], last_value=out["last_value"], greedy=greedy, stats=self.stats, **kw)
         self._out[0].copy_(out["obs"][n_steps - 1])  # the current observation, as step() would have left it
+        if moa:
+            out["rewards"] = out["rew"].to(torch.float32) + float(influence_weight) * out["influence"]
         return out
 
     @staticmethod
