@@ -611,6 +611,84 @@ int ssd_rollout_policy_moa(ssd_env *env, const float *weights, int32_t num_sets,
                            float *logits, int32_t *rew, uint8_t *done, int32_t ring, float *last_value, uint32_t flags,
                            void *stream);
 
+/* ======================================================================================================================
+ * WATERSHED POLICY ROLLOUTS -- LSTMFCNet (models/watershed_nets.py:94-177), the policy of every agent of the Watershed
+ * baselines (run_scripts/train_watershed_baseline.py:119,162, train_watershed_comm_baseline.py:97-127) and of the comm
+ * agents of train_watershed_comm_moa.py:115,124, on the device between the phases of the Watershed engine above
+ * (csrc/ssd_ws_policy.hip).  Exact float32 throughout, every sum in a fixed order: a sum over k is
+ * s = 0, s = fmaf(in[k], w[k][j], s) for k ascending, then s + bias.
+ *
+ * One weight set per agent id: num_sets = 4 for SSD_WS_SEQ, 8 for SSD_WS_SEQ_COMM.  The row that acts uses the set of its
+ * agent.  Per set, with x0 the engine's observation row f32 [12] (zero-padded: rows of dense0_w beyond the agent's
+ * observation length meet zeros) and a state (h, c) of C cells, C = 64, 128 or 256:
+ *   d0 = relu(x0 @ dense0_w + dense0_b)   [12][16]        d1 = relu(d0 @ dense1_w + dense1_b)   [16][16]
+ *   z  = [d1, h] @ lstm_w + lstm_b        lstm_w [16 + C][4C]: Keras' kernel rows, then its recurrent_kernel rows
+ *   i, f, g, o = the column blocks z[0:C], z[C:2C], z[2C:3C], z[3C:4C]          (Keras' order; no forget bias at run time)
+ *   c' = sigmoid(f) * c + sigmoid(i) * tanh(g)            h' = sigmoid(o) * tanh(c')
+ *   dist = h' @ out_w + out_b   [C][5]                    value = h' @ value_w + value_b   [C]
+ * sigmoid(x) = 1 / (1 + expf(-x)).  A state is f32 [.., 2, C]: h at index 0, c at index 1 (Keras' order).
+ * Weight set (floats, every block on a 64-float boundary, matrices [in][out]); set p at p * SSD_WSP_SET_FLOATS(C):
+ *   dense0_w [12][16]  dense0_b [16]  dense1_w [16][16]  dense1_b [16]  lstm_w [16 + C][4C]  lstm_b [4C]  out_w [C][5]
+ *   out_b [5]  value_w [C]  value_b [1]
+ *
+ * The action distribution follows from (variant, agent id):
+ *   comm agents (SSD_WS_SEQ_COMM ids 0-3): Categorical over dist[0:5] by the POLICY ROLLOUTS rule above (the first a with
+ *     u < the running float32 softmax sum; greedy: the first maximal logit; logp = l_a - (m + logf(s))); the action is
+ *     recorded as a float;
+ *   action agents (SSD_WS_SEQ ids 0-3, SSD_WS_SEQ_COMM ids 4-7): RLlib's DiagGaussian, mean = dist[0], log_std = dist[1]
+ *     (dist[2:5] are computed and written, and unused): std = expf(log_std), a = mean + std * n,
+ *     z = (a - mean) / std, logp = ((-0.5f * (z * z)) - log_std) - 0.9189385f.  Greedy: n = 0, i.e. a = mean (bitwise).
+ *     The rings record the unclipped a; the env steps with fminf(fmaxf(a, 0), 1) (RLlib's clip_actions; a NaN gives 0).
+ * Draws: with (episode, t) of the state the action is taken in, t = round * P + phase - 1 (P = 4 / 12; round and phase as
+ * ssd_ws_get_state reports them; 0 for the first action after a reset) and i the acting agent's id,
+ *   d1 = H(seed, env_index_base + e, episode, t, SSD_S_POLICY, i),  d2 = H(.., i + 16),
+ *   categorical: u = (d1 >> 8) * 2^-24;
+ *   Gaussian: u1 = ((d1 >> 8) + 1) * 2^-24 in (0, 1], u2 = (d2 >> 8) * 2^-24, n = sqrtf(-2 * logf(u1)) * cosf(6.2831855f * u2).
+ * Start rule: the state an agent uses at its first action of an episode is zero, and such a row is never read.  In a
+ * rollout that is round == 0, and for SSD_WS_SEQ_COMM besides phase <= 4 or phase >= 9 (phases 5-8 are the comm agents'
+ * second message); in the forward call it is starts[row] != 0.
+ * ====================================================================================================================== */
+enum { SSD_WSP_X = 16, SSD_WSP_OUT = 5, SSD_WSP_D0_W = 0, SSD_WSP_D0_B = 192, SSD_WSP_D1_W = 256, SSD_WSP_D1_B = 512, SSD_WSP_LSTM_W = 576 };
+#define SSD_WSP_ALIGN(n) (((n) + 63) / 64 * 64)
+#define SSD_WSP_LSTM_B(C) SSD_WSP_ALIGN(SSD_WSP_LSTM_W + (16 + (C)) * 4 * (C))
+#define SSD_WSP_OUT_W(C) SSD_WSP_ALIGN(SSD_WSP_LSTM_B(C) + 4 * (C))
+#define SSD_WSP_OUT_B(C) SSD_WSP_ALIGN(SSD_WSP_OUT_W(C) + 5 * (C))
+#define SSD_WSP_VALUE_W(C) SSD_WSP_ALIGN(SSD_WSP_OUT_B(C) + 5)
+#define SSD_WSP_VALUE_B(C) SSD_WSP_ALIGN(SSD_WSP_VALUE_W(C) + (C))
+#define SSD_WSP_SET_FLOATS(C) SSD_WSP_ALIGN(SSD_WSP_VALUE_B(C) + 1)
+
+/* The forward pass alone (device pointers on device_id, enqueued on `stream`): obs f32 [B,12], agent i8 [B] (row b uses weight
+ * set agent[b]; ids mix freely) and state_in f32 [B,2,C] -> state_out f32 [B,2,C], dist f32 [B,5], value f32 [B].  state_out,
+ * dist and value may be NULL; state_out may equal state_in (in place) but must not overlap it otherwise.  starts: u8 [B] or
+ * NULL (no row starts).  A row whose agent is outside 0 .. num_sets - 1 gets zero outputs and its state_out row is not written.
+ * weights: num_sets sets as above, 4-byte aligned; variant fixes num_sets.  flags: 0.  Bad arguments: SSD_E_INVALID before
+ * anything is launched (ssd_policy_last_error says why). */
+int ssd_ws_policy_forward(const float *weights, int32_t num_sets, int32_t cell_size, int32_t variant, const float *obs,
+                          const int8_t *agent, const float *state_in, const uint8_t *starts, int32_t batch, float *state_out,
+                          float *dist, float *value, int32_t device_id, uint32_t flags, void *stream);
+
+/* A closed-loop rollout of n_steps phases in one call (device pointers, enqueued on `stream`; the call allocates nothing and
+ * never synchronises).  Step k:
+ *   1. the policy reads the current observation and its agent: obs_in f32 [E,12] / agent_in i8 [E] (what the engine last
+ *      returned) for k = 0, else slot (step0 + k - 1) % ring of obs / agent.  It uses and updates row [e, agent] of
+ *      state f32 [E,NA,2,C] (NA = num_sets) and leaves the other agents' rows as they are;
+ *   2. it writes actor i8 (= that agent), actions f32, logp f32, value f32 (all [ring,E]), dist f32 [ring,E,5] and
+ *      state_ring f32 [ring,E,2,C] (the state it used, after the start rule) into slot s = (step0 + k) % ring, and the
+ *      clipped action into scratch f32 [E] (caller-supplied);
+ *   3. one phase of the env with scratch as its actions and SSD_AUTO_RESET writes obs f32 [ring,E,12], agent i8 [ring,E],
+ *      rew f64 [ring,E] and done u8 [ring,E] into slot s, exactly as the step call of the Watershed section does.
+ * After the last step last_value f32 [E] holds the value of the final observation under its observer's state; that pass
+ * leaves `state` alone.  obs, agent and actions are required (obs rows 16-byte aligned); state_ring, rew, done, actor, logp,
+ * value, dist and last_value may be NULL.  A never-reset env (phase 0) is left alone as by SSD_ST_NOT_RESET: zero outputs,
+ * state untouched.  ring >= 1, n_steps >= 1, step0 >= 0.  flags: SSD_POLICY_GREEDY or 0.  A pure function of (env state,
+ * policy state, weights, seed), whatever the ring length or the split into calls.  Bad arguments: SSD_E_INVALID before
+ * anything is launched, engine and state untouched (ssd_ws_last_error says why).  Two launches per step on `stream`, one more
+ * for last_value. */
+int ssd_ws_rollout_policy(ssd_ws_env *env, const float *weights, int32_t num_sets, int32_t cell_size, const float *obs_in,
+                          const int8_t *agent_in, int32_t n_steps, int32_t step0, float *state, float *state_ring, float *scratch,
+                          float *obs, int8_t *agent, double *rew, uint8_t *done, int8_t *actor, float *actions, float *logp,
+                          float *value, float *dist, int32_t ring, float *last_value, uint32_t flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@
     from sequential_social_dilemma_games_amd import ConvFCPolicy                # the conv-FC policy net, run in the loop
     from sequential_social_dilemma_games_amd import ConvLSTMPolicy              # the same trunk under the baseline's LSTM
     from sequential_social_dilemma_games_amd import ConvMOAPolicy               # the causal-influence (MOA) policy
+    from sequential_social_dilemma_games_amd import WatershedLSTMPolicy         # the Watershed baselines' LSTM-FC policy
 
 Everything that steps an env goes through libssd_hip.so (include/ssd.h); importing this package does
 not load it, constructing an env does -- and fails loudly if it is missing.
@@ -30,7 +31,7 @@ def __getattr__(name):
     if name == "EpisodeStats":
         from .episode_stats import EpisodeStats
         return EpisodeStats
-    if name in ("ConvFCPolicy", "ConvLSTMPolicy", "ConvMOAPolicy"):
+    if name in ("ConvFCPolicy", "ConvLSTMPolicy", "ConvMOAPolicy", "WatershedLSTMPolicy"):
         from . import policy
         return getattr(policy, name)
     if name == "MapEnv":

@@ -140,6 +140,35 @@ def SSD_MOA_SCRATCH_FLOATS(rows):
     return 82 * int(rows)
 
 
+# the Watershed policy's weight layout (include/ssd.h, SSD_WSP_*): dense0, dense1, the Keras LSTM, the dist and value heads
+SSD_WSP_X, SSD_WSP_OUT, SSD_WSP_D0_W, SSD_WSP_D0_B, SSD_WSP_D1_W, SSD_WSP_D1_B, SSD_WSP_LSTM_W = 16, 5, 0, 192, 256, 512, 576
+SSD_WSP_ALIGN = SSD_LSTM_ALIGN
+
+
+def SSD_WSP_LSTM_B(C):
+    return SSD_WSP_ALIGN(SSD_WSP_LSTM_W + (16 + int(C)) * 4 * int(C))
+
+
+def SSD_WSP_OUT_W(C):
+    return SSD_WSP_ALIGN(SSD_WSP_LSTM_B(C) + 4 * int(C))
+
+
+def SSD_WSP_OUT_B(C):
+    return SSD_WSP_ALIGN(SSD_WSP_OUT_W(C) + 5 * int(C))
+
+
+def SSD_WSP_VALUE_W(C):
+    return SSD_WSP_ALIGN(SSD_WSP_OUT_B(C) + 5)
+
+
+def SSD_WSP_VALUE_B(C):
+    return SSD_WSP_ALIGN(SSD_WSP_VALUE_W(C) + int(C))
+
+
+def SSD_WSP_SET_FLOATS(C):
+    return SSD_WSP_ALIGN(SSD_WSP_VALUE_B(C) + 1)
+
+
 # every symbol include/ssd.h declares
 SYMBOLS = ("ssd_create", "ssd_destroy", "ssd_reset", "ssd_step", "ssd_step_random", "ssd_rollout_random", "ssd_rollout_actions", "ssd_rollout_path", "ssd_set_rollout_chains",
            "ssd_profiler_attached", "ssd_observe",
@@ -149,10 +178,12 @@ SYMBOLS = ("ssd_create", "ssd_destroy", "ssd_reset", "ssd_step", "ssd_step_rando
            "ssd_ws_set_state", "ssd_ws_device_status", "ssd_ws_last_error",
            "ssd_stats_create", "ssd_stats_destroy", "ssd_stats_fold", "ssd_stats_set_chunk", "ssd_stats_discard", "ssd_stats_drain",
            "ssd_stats_last_error", "ssd_policy_forward", "ssd_policy_last_error", "ssd_rollout_policy",
-           "ssd_policy_lstm_forward", "ssd_rollout_policy_lstm", "ssd_policy_moa_forward", "ssd_rollout_policy_moa")
+           "ssd_policy_lstm_forward", "ssd_rollout_policy_lstm", "ssd_policy_moa_forward", "ssd_rollout_policy_moa",
+           "ssd_ws_policy_forward", "ssd_ws_rollout_policy")
 # added after ABI 6 without a version bump (the calls are additive): a library built before them lacks them
 LSTM_SYMBOLS = ("ssd_policy_lstm_forward", "ssd_rollout_policy_lstm")
 MOA_SYMBOLS = ("ssd_policy_moa_forward", "ssd_rollout_policy_moa")
+WS_POLICY_SYMBOLS = ("ssd_ws_policy_forward", "ssd_ws_rollout_policy")
 
 
 class SsdConfig(C.Structure):
@@ -265,15 +296,17 @@ def lib():
         L.ssd_policy_last_error.argtypes = []
         L.ssd_policy_last_error.restype = C.c_char_p
         L.ssd_rollout_policy.argtypes = [vp, vp, i32, vp, i32, i32] + [vp] * 7 + [i32, vp, u32, vp]
-        missing = [name for name in LSTM_SYMBOLS + MOA_SYMBOLS if not hasattr(L, name)]
+        missing = [name for name in LSTM_SYMBOLS + MOA_SYMBOLS + WS_POLICY_SYMBOLS if not hasattr(L, name)]
         if missing:
-            raise SsdError("%s lacks %s (built before the recurrent or MOA policy calls): rebuild it with `python -c 'import "
+            raise SsdError("%s lacks %s (built before the recurrent, MOA or Watershed policy calls): rebuild it with `python -c 'import "
                            "__graft_entry__ as g; g.build()'`" % (LIB_PATH, ", ".join(missing)))
         L.ssd_policy_lstm_forward.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, u32, vp]
         L.ssd_rollout_policy_lstm.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, vp, i32, i32] + [vp] * 8 + [i32, vp, u32, vp]
         L.ssd_policy_moa_forward.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, i32, i32] + [vp] * 8 + [C.c_float, i32, u32, vp]
         L.ssd_rollout_policy_moa.argtypes = ([vp, vp, i32, i32, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp, C.c_float] + [vp] * 8
                                              + [i32, vp, u32, vp])
+        L.ssd_ws_policy_forward.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, u32, vp]
+        L.ssd_ws_rollout_policy.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32] + [vp] * 12 + [i32, vp, u32, vp]
         for name in SYMBOLS:
             getattr(L, name)
         if L.ssd_abi_version() != ABI_VERSION:

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/ssd.h"
+#include "ssd_ws_policy.hpp"
 #include "ssd_ws_square.hpp"
 
 namespace {
@@ -397,6 +398,25 @@ void for_each_field(ssd_ws_env *env, const ssd_ws_state *st, F f) {
 }
 
 }  // namespace
+
+// ssd_ws_policy.hpp: the policy rollouts' read-only view of a handle (host code; no kernel of this file knows of it)
+namespace ssd {
+
+void ws_policy_view(const ssd_ws_env *env, WsPolicyView *v) {
+    const WsParams &p = env->p;
+    v->phase = p.d.phase; v->round = p.d.round; v->episode = p.d.episode;
+    v->E = p.E; v->variant = p.variant; v->device = env->device;
+    v->seed_lo = p.seed_lo; v->seed_hi = p.seed_hi; v->env_base = p.env_base;
+}
+
+int ws_fail_invalid(ssd_ws_env *env, const char *msg) {
+    env->err = msg;
+    return SSD_E_INVALID;
+}
+
+int ws_fail_device(ssd_ws_env *env, const char *what, int hip_error) { return ws_fail(env, what, (hipError_t)hip_error); }
+
+}  // namespace ssd
 
 extern "C" {
 

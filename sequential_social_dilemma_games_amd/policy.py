@@ -1,7 +1,8 @@
 """The conv-FC policy network of the reference (models/conv_to_fc_net.py:1-51, ConvToFCNet: the model of Jaques et al. 2019)
 as a torch module whose weights the device kernels read (include/ssd.h, SSD_POL_*; csrc/ssd_policy.hip), ConvLSTMPolicy, the
 same trunk under RLlib's LSTM (SSD_LSTM_*; csrc/ssd_policy_lstm.hip), and ConvMOAPolicy, the causal-influence policy of
-train_moa.py with its social-influence reward, influence() (SSD_MOA_*; csrc/ssd_policy_moa.hip).
+train_moa.py with its social-influence reward, influence() (SSD_MOA_*; csrc/ssd_policy_moa.hip).  WatershedLSTMPolicy, at the
+end of the file, is the LSTM-FC network of the Watershed launchers (SSD_WSP_*; csrc/ssd_ws_policy.hip).
 
     policy = ConvFCPolicy(num_actions=8, num_sets=5).cuda()       # one weight set per agent, as train_baseline.py:87-96
     logits, value = policy(obs_u8)                                # [..., N, 15, 15, 3] -> [..., N, A], [..., N]
@@ -511,3 +512,206 @@ def influence(logits, cf_logits, actions, clip=10.0):
     kl = torch.where(p != 0, p * (lp - lq), torch.zeros((), dtype=p.dtype, device=p.device)).sum(-1).sum(-1)
     kl = torch.where(torch.isfinite(kl), kl, torch.zeros((), dtype=kl.dtype, device=kl.device))
     return kl.clamp(-float(clip), float(clip))
+
+
+# ---- the Watershed baselines' policy (include/ssd.h, WATERSHED POLICY ROLLOUTS; csrc/ssd_ws_policy.hip) ----
+
+WS_OBS = _capi.SSD_WS_OBS_WIDTH
+WS_X = _capi.SSD_WSP_X
+WS_OUT = _capi.SSD_WSP_OUT
+
+
+def ws_is_comm(variant, agent):
+    """True where `agent` (ids, scalar or array) is a comm agent: its action is Categorical(5), not the Gaussian."""
+    return (int(variant) == _capi.SSD_WS_SEQ_COMM) & (np.asarray(agent) < 4)
+
+
+def ws_policy_start(variant, rnd, phase):
+    """The start rule as a function of the engine's (round, phase) before an action: True where the acting agent acts for the
+    first time in its episode, so that the state it uses is zero.  Every agent acts in round 0; a comm agent of SeqComm acts
+    there twice, and phases 5-8 are its second message."""
+    rnd, phase = np.asarray(rnd), np.asarray(phase)
+    first = rnd == 0
+    if int(variant) == _capi.SSD_WS_SEQ_COMM:
+        first = first & ((phase <= 4) | (phase >= 9))
+    return first
+
+
+def ws_policy_t(variant, rnd, phase):
+    """The t of the action draw: round * P + phase - 1 (0 for the first action after a reset)."""
+    P = 4 if int(variant) == _capi.SSD_WS_SEQ else 12
+    return np.asarray(rnd, np.int64) * P + np.asarray(phase, np.int64) - 1
+
+
+def sample_gaussian_host(mean, log_std, u1, u2, greedy=False, dtype=np.float32):
+    """The rollout's Gaussian action in NumPy (include/ssd.h), float32 as the device computes it (or dtype=np.float64 for the
+    same expressions evaluated exactly enough to judge the float32 ones): n = sqrt(-2 log u1) cos(2 pi u2), a = mean + std n
+    with std = exp(log_std), logp = -0.5 ((a - mean) / std)^2 - log_std - 0.9189385.  greedy: a = mean.  Returns (a, logp,
+    the clipped action min(max(a, 0), 1) the env steps with, a NaN giving 0)."""
+    f = np.dtype(dtype).type
+    mean, log_std = np.asarray(mean, dtype=dtype), np.asarray(log_std, dtype=dtype)
+    sd = np.exp(log_std).astype(dtype)
+    if greedy:
+        a = mean.copy()
+    else:
+        u1, u2 = np.asarray(u1, dtype=dtype), np.asarray(u2, dtype=dtype)
+        r = np.sqrt((f(-2.0) * np.log(u1).astype(dtype)).astype(dtype)).astype(dtype)
+        n = (r * np.cos((f(np.float32(6.2831855)) * u2).astype(dtype)).astype(dtype)).astype(dtype)
+        a = (mean + (sd * n).astype(dtype)).astype(dtype)
+    z = ((a - mean).astype(dtype) / sd).astype(dtype)
+    logp = (((f(-0.5) * (z * z).astype(dtype)).astype(dtype) - log_std).astype(dtype) - f(np.float32(0.9189385))).astype(dtype)
+    return a, logp, np.fmin(np.fmax(a, f(0.0)), f(1.0)).astype(dtype)
+
+
+class WatershedLSTMPolicy(torch.nn.Module):
+    """LSTMFCNet of the reference's Watershed launchers (models/watershed_nets.py:94-177): per agent id its own weight set of
+    dense0 (obs -> 16, ReLU), dense1 (16 -> 16, ReLU), a Keras LSTM of cell_size C cells and, on its output, a 5-wide
+    distribution head and a value head.  One agent acts per env and phase; a row uses the set of its acting agent.
+
+        policy = WatershedLSTMPolicy(SEQ_COMM, cell_size=128).cuda()         # 8 weight sets
+        out = eng.sample(policy, 131)                                        # the closed loop on the device
+        dist, value, state = policy(obs, agent, state, starts)               # the same network in torch
+        dist, value, final = policy.forward_sequence(5, obs_seq, state_in)   # BPTT over agent 5's own steps
+
+    dist is the input of the action distribution: the five logits of a comm agent's Categorical, or (mean, log_std, 3 unused) of
+    an action agent's DiagGaussian.  A state is [..., 2, C]: (h, c).  Parameters in Keras' layouts with a leading weight-set
+    axis: dense0_w [S, 12, 16] (the rows beyond an agent's observation length meet the zero padding of the engine's rows),
+    dense0_b, dense1_w [S, 16, 16], dense1_b, lstm_kernel [S, 16, 4C], lstm_recurrent [S, C, 4C], lstm_bias [S, 4C], out_w
+    [S, C, 5], out_b, value_w [S, C, 1], value_b.  share_comm_layer: dense1 of agents k and k + 4 is ONE layer (the
+    reference's shared_layers[id % 4]): dense1_w / dense1_b have 4 entries, and packed() writes each into both sets."""
+
+    def __init__(self, variant, local_obs=False, cell_size=128, share_comm_layer=False, seed=0):
+        super().__init__()
+        from .watershed import obs_len
+        V, C = int(variant), int(cell_size)
+        if V not in (_capi.SSD_WS_SEQ, _capi.SSD_WS_SEQ_COMM):
+            raise ValueError("variant must be SEQ or SEQ_COMM")
+        if C not in _capi.LSTM_CELL_SIZES:
+            raise ValueError("cell_size must be one of %s" % (_capi.LSTM_CELL_SIZES,))
+        S = 4 if V == _capi.SSD_WS_SEQ else 8
+        self.variant, self.local_obs, self.cell_size, self.num_sets = V, bool(local_obs), C, S
+        self.share_comm_layer = bool(share_comm_layer)
+        self.num_dense1 = 4 if self.share_comm_layer else S
+        self.obs_lens = tuple(obs_len(V, self.local_obs, i) for i in range(S))
+        g = torch.Generator().manual_seed(int(seed))
+        d0 = torch.zeros((S, WS_OBS, WS_X), dtype=torch.float64)
+        for i, n in enumerate(self.obs_lens):                    # Keras' Glorot uniform on the [n, 16] kernel the agent has
+            d0[i, :n] = _glorot((n, WS_X), n, WS_X, g)
+        init = {"dense0_w": d0, "dense1_w": normc((self.num_dense1, WS_X, WS_X), 1.0, g),
+                "lstm_kernel": _glorot((S, WS_X, 4 * C), WS_X, 4 * C, g), "lstm_recurrent": _orthogonal(S, C, 4 * C, g),
+                "out_w": _glorot((S, C, WS_OUT), C, WS_OUT, g), "value_w": _glorot((S, C, 1), C, 1, g)}
+        for name, shape, _ in self.layout():
+            t = init.get(name)
+            n = self.num_dense1 if name.startswith("dense1") else S
+            if t is None:
+                t = torch.zeros((n,) + shape, dtype=torch.float64)       # Keras' bias_initializer "zeros"
+            self.register_parameter(name, torch.nn.Parameter(t.to(torch.float32)))
+        self._packed = None
+
+    def layout(self):
+        """(name, shape of one set, float offset within a packed set) of every parameter, in packed order."""
+        C = self.cell_size
+        lw = _capi.SSD_WSP_LSTM_W
+        return (("dense0_w", (WS_OBS, WS_X), _capi.SSD_WSP_D0_W), ("dense0_b", (WS_X,), _capi.SSD_WSP_D0_B),
+                ("dense1_w", (WS_X, WS_X), _capi.SSD_WSP_D1_W), ("dense1_b", (WS_X,), _capi.SSD_WSP_D1_B),
+                ("lstm_kernel", (WS_X, 4 * C), lw), ("lstm_recurrent", (C, 4 * C), lw + WS_X * 4 * C),
+                ("lstm_bias", (4 * C,), _capi.SSD_WSP_LSTM_B(C)),
+                ("out_w", (C, WS_OUT), _capi.SSD_WSP_OUT_W(C)), ("out_b", (WS_OUT,), _capi.SSD_WSP_OUT_B(C)),
+                ("value_w", (C, 1), _capi.SSD_WSP_VALUE_W(C)), ("value_b", (1,), _capi.SSD_WSP_VALUE_B(C)))
+
+    load_arrays = ConvFCPolicy.load_arrays
+
+    @property
+    def set_floats(self):
+        return _capi.SSD_WSP_SET_FLOATS(self.cell_size)
+
+    def _set(self, name, i):
+        """Parameter `name` of agent id i (a shared dense1 is entry i % 4)."""
+        t = getattr(self, name)
+        return t[i % t.shape[0]]
+
+    def packed(self):
+        """All weight sets as ONE contiguous float32 tensor on the parameters' device, in the layout of include/ssd.h: set p
+        at p * SSD_WSP_SET_FLOATS(C).  Rebuilt from the parameters on every call by device copies on the current stream (no
+        host synchronisation), so an optimiser's update takes effect on the next call.  The buffer is reused between calls."""
+        S, F = self.num_sets, self.set_floats
+        dev = self.dense0_w.device
+        if self._packed is None or self._packed.device != dev:
+            self._packed = torch.zeros(S * F, dtype=torch.float32, device=dev)
+        v = self._packed.view(S, F)
+        with torch.no_grad():
+            for name, shape, off in self.layout():
+                n = int(np.prod(shape))
+                t = getattr(self, name).reshape(-1, n)
+                if t.shape[0] != S:                              # the shared dense1: entry k serves sets k and k + 4
+                    t = t.repeat(S // t.shape[0], 1)
+                v[:, off:off + n].copy_(t)
+        return self._packed
+
+    def initial_state(self, lead, device=None):
+        """A zero state [*lead, 2, C] (the parameters' dtype, on their device unless given); a rollout's carried state is
+        initial_state((E, num_sets))."""
+        lead = (int(lead),) if isinstance(lead, int) else tuple(int(n) for n in lead)
+        return torch.zeros(lead + (2, self.cell_size), dtype=self.dense0_w.dtype,
+                           device=self.dense0_w.device if device is None else device)
+
+    def _cell(self, i, x, h, c):
+        """Set i on rows x [M, 12], (h, c) [M, C] -> (dist [M, 5], value [M], h', c')."""
+        d0 = torch.relu(x @ self._set("dense0_w", i) + self._set("dense0_b", i))
+        d1 = torch.relu(d0 @ self._set("dense1_w", i) + self._set("dense1_b", i))
+        h2, c2 = keras_lstm(d1, h, c, self.lstm_kernel[i], self.lstm_recurrent[i], self.lstm_bias[i])
+        return h2 @ self.out_w[i] + self.out_b[i], (h2 @ self.value_w[i] + self.value_b[i])[..., 0], h2, c2
+
+    def forward(self, obs, agent, state, starts=None):
+        """obs [..., 12], agent int [...] (the acting agent of each row, ids may mix), state [..., 2, C] (each row's OWN state:
+        that of its acting agent), starts bool [...] or None: rows whose state is taken as zero (selected: whatever it holds is
+        never used).  Returns (dist [..., 5], value [...], new state [..., 2, C]).  A row whose agent is no id of this variant
+        gets zeros and keeps its state.  (The rows of each id are gathered by index, which synchronises with the device.)"""
+        C = self.cell_size
+        lead = tuple(agent.shape)
+        if tuple(obs.shape) != lead + (WS_OBS,) or tuple(state.shape) != lead + (2, C):
+            raise ValueError("obs must be %s and state %s, got %s and %s" % (lead + (WS_OBS,), lead + (2, C), tuple(obs.shape),
+                                                                              tuple(state.shape)))
+        dt = self.dense0_w.dtype
+        x, st, ag = obs.to(dt).reshape(-1, WS_OBS), state.to(dt).reshape(-1, 2, C), agent.reshape(-1).long()
+        new_state = st
+        if starts is not None:
+            if tuple(starts.shape) != lead:
+                raise ValueError("starts must have shape %s, got %s" % (lead, tuple(starts.shape)))
+            st = torch.where(starts.to(torch.bool).reshape(-1, 1, 1).to(st.device), torch.zeros((), dtype=dt, device=st.device), st)
+        M = x.shape[0]
+        dist = torch.zeros((M, WS_OUT), dtype=dt, device=x.device)
+        value = torch.zeros((M,), dtype=dt, device=x.device)
+        for i in range(self.num_sets):
+            idx = torch.nonzero(ag == i)[:, 0]
+            if idx.numel() == 0:
+                continue
+            d, v, h2, c2 = self._cell(i, x[idx], st[idx, 0], st[idx, 1])
+            dist = dist.index_copy(0, idx, d)
+            value = value.index_copy(0, idx, v)
+            new_state = new_state.index_copy(0, idx, torch.stack([h2, c2], dim=1))
+        return dist.reshape(lead + (WS_OUT,)), value.reshape(lead), new_state.reshape(lead + (2, C))
+
+    def forward_sequence(self, agent_id, obs, state, resets=None):
+        """T of agent agent_id's own steps for truncated BPTT: obs [T, ..., 12] (the observations it acted on, in order), state
+        [..., 2, C] before step 0, resets bool [T, ...] or None (resets[t]: the state step t uses is zero, as the start rule).
+        Differentiable.  Returns (dist [T, ..., 5], value [T, ...], the state after step T - 1)."""
+        i, C, T = int(agent_id), self.cell_size, int(obs.shape[0])
+        if not 0 <= i < self.num_sets:
+            raise ValueError("agent_id must be 0..%d" % (self.num_sets - 1))
+        if resets is not None and int(resets.shape[0]) != T:
+            raise ValueError("resets must have T = %d rows" % T)
+        lead = tuple(obs.shape[1:-1])
+        dt = self.dense0_w.dtype
+        st = state.to(dt).reshape(-1, 2, C)
+        h, c = st[:, 0], st[:, 1]
+        dists, values = [], []
+        for t in range(T):
+            if resets is not None:
+                keep = ~resets[t].to(torch.bool).reshape(-1, 1).to(h.device)
+                zero = torch.zeros((), dtype=dt, device=h.device)
+                h, c = torch.where(keep, h, zero), torch.where(keep, c, zero)
+            d, v, h, c = self._cell(i, obs[t].to(dt).reshape(-1, WS_OBS), h, c)
+            dists.append(d.reshape(lead + (WS_OUT,)))
+            values.append(v.reshape(lead))
+        return torch.stack(dists), torch.stack(values), torch.stack([h, c], dim=1).reshape(lead + (2, C))

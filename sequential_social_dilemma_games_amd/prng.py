@@ -26,6 +26,8 @@ Streams (the `index` word is given in brackets):
                                       (replaces watershedOrderedComm.py:69; once per (env, episode))
     POLICY      [agent]               policy rollouts: the sampled action of the conv-FC policy (policy.py), drawn with
                                       the (episode, t) of the state the action is taken in
+    POLICY      [agent], [agent + 16] Watershed policy rollouts (ws_policy_draws): d1 picks a comm agent's message or, with
+                                      d2, makes an action agent's normal deviate (Box-Muller); t = round * P + phase - 1
 `cell` is `row * W + col`; `t` is 0 for reset and k for the k-th step after it.
 """
 
@@ -143,3 +145,32 @@ def policy_uniforms(seed, env_ids, episodes, t, num_agents):
     idx = np.arange(num_agents, dtype=np.uint64)[None, :]
     d = mix32_np(pk[:, None] ^ idx)
     return ((d >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24)).astype(np.float32)
+
+
+def ws_policy_draws(seed, env_ids, episodes, t, agent):
+    """(d1, d2) = H(.., POLICY, agent), H(.., POLICY, agent + 16) of a Watershed policy rollout, uint32 arrays shaped like
+    env_ids (global env indices); episodes, t (= round * P + phase - 1 of the state acted in) and agent (the acting agent's
+    id): scalars or arrays of that shape."""
+    env_ids = np.asarray(env_ids, dtype=np.uint64)
+    episodes = np.broadcast_to(np.asarray(episodes, dtype=np.uint64), env_ids.shape)
+    t = np.broadcast_to(np.asarray(t, dtype=np.uint64), env_ids.shape)
+    agent = np.broadcast_to(np.asarray(agent, dtype=np.uint64), env_ids.shape)
+    h = np.full(env_ids.shape, H0, dtype=np.uint64)
+    h = mix32_np(h ^ np.uint64(seed & M32))
+    h = mix32_np(h ^ np.uint64((seed >> 32) & M32))
+    h = mix32_np(h ^ (env_ids & M32))
+    h = mix32_np(h ^ (episodes & M32))
+    pk = mix32_np(mix32_np(h ^ (t & M32)) ^ np.uint64(S_POLICY))
+    d1 = mix32_np(pk ^ agent)
+    d2 = mix32_np(pk ^ (agent + np.uint64(16)))
+    return d1.astype(np.uint32), d2.astype(np.uint32)
+
+
+def ws_uniforms(d1, d2):
+    """(u, u1, u2) float32 of the draws above: u = (d1 >> 8) * 2^-24 in [0, 1) for the categorical pick; u1 = ((d1 >> 8) + 1) *
+    2^-24 in (0, 1] and u2 = (d2 >> 8) * 2^-24 for the normal deviate (include/ssd.h)."""
+    k1 = np.asarray(d1, np.uint32) >> np.uint32(8)
+    k2 = np.asarray(d2, np.uint32) >> np.uint32(8)
+    s = np.float32(2.0 ** -24)
+    return ((k1.astype(np.float32) * s).astype(np.float32), ((k1 + np.uint32(1)).astype(np.float32) * s).astype(np.float32),
+            (k2.astype(np.float32) * s).astype(np.float32))

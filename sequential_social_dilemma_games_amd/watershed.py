@@ -57,6 +57,7 @@ class WatershedVecEngine(object):
         obs, agent, rew, done = eng.step(actions)           actions f32 [E]; rew f64 [E]; done u8 [E] (SSD_WS_* bits)
         eng.rollout_actions(actions [R,E], n_steps, obs [ring,E,12], agent, rew, done)   n_steps phases in one launch
         eng.info()                                          viol, true_end, running_rew, temp, other_agent_actions
+        eng.sample(policy, n_steps)                         a closed-loop rollout with a WatershedLSTMPolicy (policy.py) on the device
     """
 
     def __init__(self, variant=SEQ, num_envs=1, seed=0, local_obs=False, local_rew=False, env_index_base=0, device=0):
@@ -73,6 +74,8 @@ class WatershedVecEngine(object):
         self._h = C.c_void_p()
         _capi.ws_check(self._L.ssd_ws_create(C.byref(c), C.byref(self._h)))
         self._dev = torch.device("cuda", self.device)
+        self._last_obs = self._last_agent = None                 # the current observation and its agent, for sample()
+        self._pol_scratch = self._pol_key = self._pol_state = None   # rollout_policy's action scratch; sample()'s policy state
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -125,6 +128,11 @@ class WatershedVecEngine(object):
             m = torch.as_tensor(mask, device=self._dev).to(torch.uint8).contiguous()
             self._check_tensor(m, (self.E,), torch.uint8, "mask")
         self._check(self._L.ssd_ws_reset(self._h, _p(m), _p(obs), _p(agent), _stream(self._dev)))
+        if mask is None:
+            self._last_obs, self._last_agent = obs, agent        # where sample() starts
+        elif self._last_obs is not None:                         # the reset rows replace those of the kept observation
+            self._last_obs = torch.where(m.bool()[:, None], obs, self._last_obs)
+            self._last_agent = torch.where(m.bool(), agent, self._last_agent)
         return obs, agent
 
     def step(self, actions, auto_reset=False, out=None):
@@ -136,6 +144,7 @@ class WatershedVecEngine(object):
         self._check_outputs((), obs, agent, rew, done)
         flags = _capi.SSD_AUTO_RESET if auto_reset else 0
         self._check(self._L.ssd_ws_step(self._h, _p(a), _p(obs), _p(agent), _p(rew), _p(done), flags, _stream(self._dev)))
+        self._last_obs, self._last_agent = obs, agent
         return obs, agent, rew, done
 
     def rollout_actions(self, actions, n_steps, obs=None, agent=None, rew=None, done=None, step0=0, auto_reset=False):
@@ -156,6 +165,103 @@ class WatershedVecEngine(object):
         flags = _capi.SSD_AUTO_RESET if auto_reset else 0
         self._check(self._L.ssd_ws_rollout_actions(self._h, _p(a), a.shape[0], int(n_steps), int(step0), _p(obs), _p(agent), _p(rew),
                                                    _p(done), ring, flags, _stream(self._dev)))
+        if int(n_steps) > 0:
+            last = (int(step0) + int(n_steps) - 1) % ring
+            self._last_obs, self._last_agent = (obs[last], agent[last]) if obs is not None and agent is not None else (None, None)
+
+    # ---------------------------------------------------------------- policy rollouts (include/ssd.h, WATERSHED POLICY ROLLOUTS)
+    def _check_policy(self, policy):
+        from .policy import WatershedLSTMPolicy
+        if not isinstance(policy, WatershedLSTMPolicy):
+            raise ValueError("policy must be a WatershedLSTMPolicy")
+        if policy.variant != self.variant:
+            raise ValueError("the policy is of variant %d, the engine of variant %d" % (policy.variant, self.variant))
+        w = policy.packed()
+        if w.device != self._dev:
+            raise ValueError("the policy's parameters must be on %s" % (self._dev,))
+        return w
+
+    def policy_forward(self, policy, obs, agent, state, starts=None):
+        """The policy's forward pass on the device: obs f32 [B,12], agent i8 [B] (the acting agent of each row), state f32
+        [B,2,C] (each row's own), starts u8 / bool [B] or None -> (dist f32 [B,5], value f32 [B], new state f32 [B,2,C])."""
+        import torch
+        w = self._check_policy(policy)
+        B, Cc = int(agent.shape[0]) if agent.dim() == 1 else -1, policy.cell_size
+        if B < 1:
+            raise ValueError("agent must be i8 [B] with B >= 1")
+        self._check_tensor(obs, (B, OBS_WIDTH), torch.float32, "policy obs")
+        self._check_tensor(agent, (B,), torch.int8, "agent")
+        self._check_tensor(state, (B, 2, Cc), torch.float32, "state")
+        s = None
+        if starts is not None:
+            s = torch.as_tensor(starts, device=self._dev).to(torch.uint8).contiguous()
+            self._check_tensor(s, (B,), torch.uint8, "starts")
+        dist = torch.empty((B, 5), dtype=torch.float32, device=self._dev)
+        value = torch.empty((B,), dtype=torch.float32, device=self._dev)
+        out = torch.empty_like(state)
+        _capi.policy_check(self._L.ssd_ws_policy_forward(_p(w), policy.num_sets, Cc, self.variant, _p(obs), _p(agent), _p(state), _p(s),
+                                                         B, _p(out), _p(dist), _p(value), self.device, 0, _stream(self._dev)))
+        return dist, value, out
+
+    def rollout_policy(self, policy, obs_in, agent_in, n_steps, obs, agent, rew=None, done=None, actor=None, actions=None, logp=None,
+                       value=None, dist=None, state=None, state_ring=None, last_value=None, step0=0, greedy=False):
+        """n_steps phases of the closed loop in one call (no host round trip): step k runs the policy on the current observation
+        (obs_in f32 [E,12] / agent_in i8 [E] for k = 0, then the previous ring slot), advances row [e, agent] of state f32
+        [E,num_sets,2,C] in place, writes actor i8, actions f32 (unclipped), logp f32, value f32 ([ring,E]), dist f32 [ring,E,5]
+        and state_ring f32 [ring,E,2,C] (the state it used) into ring slot (step0 + k) % ring, then steps the env (auto-reset)
+        with the clipped action into obs / agent / rew / done of the same slot.  obs, agent, actions and state are required;
+        last_value f32 [E] receives the value of the final observation."""
+        import torch
+        w = self._check_policy(policy)
+        E, Cc = self.E, policy.cell_size
+        if obs is None or agent is None or actions is None or state is None:
+            raise ValueError("obs, agent, actions and state are required")
+        ring = int(obs.shape[0]) if obs.dim() == 3 else 0
+        if ring < 1:
+            raise ValueError("obs must be f32 [ring, E, 12] with ring >= 1")
+        if int(n_steps) < 1 or int(step0) < 0:
+            raise ValueError("n_steps must be >= 1 and step0 >= 0")
+        self._check_tensor(obs_in, (E, OBS_WIDTH), torch.float32, "obs")
+        self._check_tensor(agent_in, (E,), torch.int8, "agent_in")
+        self._check_outputs((ring,), obs, agent, rew, done)
+        self._check_tensor(state, (E, policy.num_sets, 2, Cc), torch.float32, "state")
+        for t, shape, dtype, name in ((actor, (ring, E), torch.int8, "actor"), (actions, (ring, E), torch.float32, "actions"),
+                                      (logp, (ring, E), torch.float32, "logp"), (value, (ring, E), torch.float32, "value"),
+                                      (dist, (ring, E, 5), torch.float32, "dist"), (state_ring, (ring, E, 2, Cc), torch.float32, "state_ring"),
+                                      (last_value, (E,), torch.float32, "last_value")):
+            if t is not None:
+                self._check_tensor(t, shape, dtype, name)
+        if self._pol_scratch is None:
+            self._pol_scratch = torch.zeros((E,), dtype=torch.float32, device=self._dev)
+        flags = _capi.SSD_POLICY_GREEDY if greedy else 0
+        self._check(self._L.ssd_ws_rollout_policy(self._h, _p(w), policy.num_sets, Cc, _p(obs_in), _p(agent_in), int(n_steps), int(step0),
+                                                  _p(state), _p(state_ring), _p(self._pol_scratch), _p(obs), _p(agent), _p(rew), _p(done),
+                                                  _p(actor), _p(actions), _p(logp), _p(value), _p(dist), ring, _p(last_value), flags,
+                                                  _stream(self._dev)))
+        last = (int(step0) + int(n_steps) - 1) % ring
+        self._last_obs, self._last_agent = obs[last], agent[last]
+
+    def sample(self, policy, n_steps, greedy=False):
+        """A closed-loop rollout of n_steps phases from where the last sample() (or reset()) left the envs.  Keeps the last
+        observation, its agent and the policy state between calls (it zeroes nothing itself: the start rule does), so two calls
+        give what one call of twice the length gives.  Returns a dict of device tensors [K,E,...]: obs, agent (after each step),
+        actor, actions, logp, value, dist, rew, done, and state_in [K,E,2,C] (the state each step used), last_value [E]."""
+        import torch
+        K, E, d = int(n_steps), self.E, self._dev
+        key = (id(policy), policy.cell_size)
+        if self._pol_key != key:
+            self._pol_key = key
+            self._pol_state = policy.initial_state((E, policy.num_sets), device=d).to(torch.float32)
+        if self._last_obs is None:
+            raise RuntimeError("sample() needs the current observation: call reset() (or step()) first")
+        obs, agent, rew, done = self._outputs((K,))
+        f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=d)   # noqa: E731
+        out = dict(obs=obs, agent=agent, rew=rew, done=done, actor=torch.empty((K, E), dtype=torch.int8, device=d), actions=f(K, E),
+                   logp=f(K, E), value=f(K, E), dist=f(K, E, 5), state_in=f(K, E, 2, policy.cell_size), last_value=f(E))
+        self.rollout_policy(policy, self._last_obs, self._last_agent, K, obs, agent, rew=rew, done=done, actor=out["actor"],
+                            actions=out["actions"], logp=out["logp"], value=out["value"], dist=out["dist"], state=self._pol_state,
+                            state_ring=out["state_in"], last_value=out["last_value"], greedy=greedy)
+        return out
 
     def info(self):
         """The info fields of the current state, as device tensors."""
