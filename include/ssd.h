@@ -689,6 +689,44 @@ int ssd_ws_rollout_policy(ssd_ws_env *env, const float *weights, int32_t num_set
                           float *obs, int8_t *agent, double *rew, uint8_t *done, int8_t *actor, float *actions, float *logp,
                           float *value, float *dist, int32_t ring, float *last_value, uint32_t flags, void *stream);
 
+/* ======================================================================================================================
+ * ADVANTAGES AND VALUE TARGETS -- what every trainer does between sampling and its loss (RLlib's compute_advantages:
+ * generalised advantage estimation for PPO, discounted returns for A3C), computed on the device from the [ring, ...] rings
+ * of the policy rollouts above (csrc/ssd_gae.hip).  Added after ABI 6 without a version bump: the
+ * call is additive.
+ *
+ * Lanes are trajectories: L = lanes (E * N for the rollouts' rings), lane l is column l of the [ring, L] rings.  Row k of a
+ * call is slot (step0 + k) % ring.  Every operation is one IEEE float64 operation in the order written here (no fused
+ * multiply-add); the two results are rounded to float32 once, when they are stored.  gl = gamma * lambda, formed once.
+ * Walking k = n_steps - 1 ... 0, per lane:
+ *   r      = (double)rew[k], or (double)rew[k] + bonus_weight * (double)bonus[k] with a bonus (multiply, then add)
+ *   v_next = 0.0 if done[k] != 0; else (double)last_value for k = n_steps - 1 and (double)value[k + 1] otherwise
+ *   carry  = 0.0 if done[k] != 0 or k = n_steps - 1; else the running A of row k + 1
+ * SSD_ADV_GAE | SSD_ADV_CRITIC:   delta = (r + gamma * v_next) - (double)value[k];  A = delta + gl * carry;
+ *                                 advantages[k] = (float)A;  value_targets[k] = (float)(A + (double)value[k])
+ * SSD_ADV_CRITIC:                 G = r + gamma * G_next, where G_next is v_next where the carry is cut (a done row or the
+ *                                 last row) and the running G of row k + 1 otherwise;
+ *                                 advantages[k] = (float)(G - (double)value[k]);  value_targets[k] = (float)G
+ * 0:                              the same G;  advantages[k] = (float)G;  value_targets[k] = 0;  value may be NULL
+ * done[k] != 0 says that the episode ended with step k and row k + 1 belongs to the next one (what the rollouts record at
+ * the horizon); a fragment that ends without one is bootstrapped with last_value.  NULL done: no episode ends.  NULL
+ * last_value: 0.  NULL bonus: none (bonus_weight is not read).  Inputs are assumed finite.
+ *
+ * rew i32, bonus f32, value f32, done u8, advantages f32 and value_targets f32 are [ring, L]; last_value f32 is [L]; device
+ * pointers on device_id.  One launch on `stream`, no allocation, no synchronisation.  SSD_E_INVALID before any device call
+ * (ssd_advantages_last_error says why) for lanes < 1, ring < 1, n_steps < 1 or > ring, step0 < 0, an unknown flag, the first
+ * flag without the second, a missing rew, output or (with the critic) value pointer, a gamma, lambda or (with a bonus)
+ * bonus_weight that is not finite; SSD_E_DEVICE without a usable HIP device.
+ * ====================================================================================================================== */
+enum {
+    SSD_ADV_GAE = 1u << 0,      /* generalised advantage estimation (needs SSD_ADV_CRITIC); else discounted returns */
+    SSD_ADV_CRITIC = 1u << 1    /* value is the critic's prediction: a baseline for the returns, the target of value_targets */
+};
+int ssd_advantages(const int32_t *rew, const float *bonus, double bonus_weight, const float *value, const uint8_t *done,
+                   const float *last_value, int32_t lanes, int32_t ring, int32_t step0, int32_t n_steps, double gamma,
+                   double lambda, uint32_t flags, float *advantages, float *value_targets, int32_t device_id, void *stream);
+const char *ssd_advantages_last_error(void);   /* the calling thread's last ssd_advantages error */
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@
     from sequential_social_dilemma_games_amd import ConvLSTMPolicy              # the same trunk under the baseline's LSTM
     from sequential_social_dilemma_games_amd import ConvMOAPolicy               # the causal-influence (MOA) policy
     from sequential_social_dilemma_games_amd import WatershedLSTMPolicy         # the Watershed baselines' LSTM-FC policy
+    from sequential_social_dilemma_games_amd import compute_advantages          # GAE / discounted returns of a rollout batch
 
 Everything that steps an env goes through libssd_hip.so (include/ssd.h); importing this package does
 not load it, constructing an env does -- and fails loudly if it is missing.
@@ -34,6 +35,9 @@ def __getattr__(name):
     if name in ("ConvFCPolicy", "ConvLSTMPolicy", "ConvMOAPolicy", "WatershedLSTMPolicy"):
         from . import policy
         return getattr(policy, name)
+    if name == "compute_advantages":
+        from .postprocessing import compute_advantages
+        return compute_advantages
     if name == "MapEnv":
         from .map_env import MapEnv
         return MapEnv

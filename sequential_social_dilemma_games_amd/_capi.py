@@ -22,6 +22,7 @@ SSD_WS_DONE_AGENT, SSD_WS_DONE_ALL, SSD_WS_END, SSD_WS_REW_INT, SSD_WS_REW_F64 =
 SSD_ST_NOT_RESET = 16
 SSD_WS_OBS_WIDTH = 12
 SSD_STATS_KEEP = 1
+SSD_ADV_GAE, SSD_ADV_CRITIC = 1, 2
 # the policy network's weight layout (include/ssd.h, SSD_POL_*): float offsets within one weight set
 SSD_S_POLICY = 9
 SSD_POL_VIEW, SSD_POL_CONV_OUT, SSD_POL_FILTERS, SSD_POL_HIDDEN, SSD_POL_FLAT, SSD_POL_MAX_ACTIONS = 15, 13, 6, 32, 1014, 15
@@ -179,11 +180,12 @@ SYMBOLS = ("ssd_create", "ssd_destroy", "ssd_reset", "ssd_step", "ssd_step_rando
            "ssd_stats_create", "ssd_stats_destroy", "ssd_stats_fold", "ssd_stats_set_chunk", "ssd_stats_discard", "ssd_stats_drain",
            "ssd_stats_last_error", "ssd_policy_forward", "ssd_policy_last_error", "ssd_rollout_policy",
            "ssd_policy_lstm_forward", "ssd_rollout_policy_lstm", "ssd_policy_moa_forward", "ssd_rollout_policy_moa",
-           "ssd_ws_policy_forward", "ssd_ws_rollout_policy")
+           "ssd_ws_policy_forward", "ssd_ws_rollout_policy", "ssd_advantages", "ssd_advantages_last_error")
 # added after ABI 6 without a version bump (the calls are additive): a library built before them lacks them
 LSTM_SYMBOLS = ("ssd_policy_lstm_forward", "ssd_rollout_policy_lstm")
 MOA_SYMBOLS = ("ssd_policy_moa_forward", "ssd_rollout_policy_moa")
 WS_POLICY_SYMBOLS = ("ssd_ws_policy_forward", "ssd_ws_rollout_policy")
+ADVANTAGES_SYMBOLS = ("ssd_advantages", "ssd_advantages_last_error")
 
 
 class SsdConfig(C.Structure):
@@ -296,9 +298,9 @@ def lib():
         L.ssd_policy_last_error.argtypes = []
         L.ssd_policy_last_error.restype = C.c_char_p
         L.ssd_rollout_policy.argtypes = [vp, vp, i32, vp, i32, i32] + [vp] * 7 + [i32, vp, u32, vp]
-        missing = [name for name in LSTM_SYMBOLS + MOA_SYMBOLS + WS_POLICY_SYMBOLS if not hasattr(L, name)]
+        missing = [name for name in LSTM_SYMBOLS + MOA_SYMBOLS + WS_POLICY_SYMBOLS + ADVANTAGES_SYMBOLS if not hasattr(L, name)]
         if missing:
-            raise SsdError("%s lacks %s (built before the recurrent, MOA or Watershed policy calls): rebuild it with `python -c 'import "
+            raise SsdError("%s lacks %s (built before the recurrent, MOA or Watershed policy calls or the advantages call): rebuild it with `python -c 'import "
                            "__graft_entry__ as g; g.build()'`" % (LIB_PATH, ", ".join(missing)))
         L.ssd_policy_lstm_forward.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, u32, vp]
         L.ssd_rollout_policy_lstm.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, vp, i32, i32] + [vp] * 8 + [i32, vp, u32, vp]
@@ -307,6 +309,9 @@ def lib():
                                              + [i32, vp, u32, vp])
         L.ssd_ws_policy_forward.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, u32, vp]
         L.ssd_ws_rollout_policy.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32] + [vp] * 12 + [i32, vp, u32, vp]
+        L.ssd_advantages.argtypes = [vp, vp, C.c_double, vp, vp, vp, i32, i32, i32, i32, C.c_double, C.c_double, u32, vp, vp, i32, vp]
+        L.ssd_advantages_last_error.argtypes = []
+        L.ssd_advantages_last_error.restype = C.c_char_p
         for name in SYMBOLS:
             getattr(L, name)
         if L.ssd_abi_version() != ABI_VERSION:
@@ -331,6 +336,12 @@ def policy_check(rc):
     if rc != SSD_OK:
         msg = lib().ssd_policy_last_error()
         raise SsdError("libssd_hip policy call failed (%d): %s" % (rc, msg.decode() if msg else "?"))
+
+
+def advantages_check(rc):
+    if rc != SSD_OK:
+        msg = lib().ssd_advantages_last_error()
+        raise SsdError("libssd_hip advantages call failed (%d): %s" % (rc, msg.decode() if msg else "?"))
 
 
 def check(rc, handle=None):

@@ -152,7 +152,8 @@ class SSDVectorEnv(object):
         self._advance()
         return self._wrap(obs, self._act_buf, done if self.horizon > 0 else None), rew, done
 
-    def sample(self, policy, n_steps, greedy=False, state_every=None, influence_weight=1.0):
+    def sample(self, policy, n_steps, greedy=False, state_every=None, influence_weight=1.0, gamma=None, lambda_=1.0, use_gae=True,
+               use_critic=True):
         """n_steps closed-loop steps of a ConvFCPolicy or a ConvLSTMPolicy on the device in one call (VecEngine.rollout_policy): returns a dict of
         device tensors obs u8 [K,E,N,15,15,3], actions i32, logp f32, value f32, rew i32, done u8 (all [K,E,N], step k in row
         k) and last_value f32 [E,N] (the value of the final observation).  Episodes end at the horizon as in step(): a finished
@@ -166,7 +167,10 @@ class SSDVectorEnv(object):
         A ConvMOAPolicy's state [E,N,4,C] and previous joint action [E,N] are kept the same way (both zero after reset() and
         at every episode start), and the dict gains "state_in", "state" (with state_every), "influence" f32 [K,E,N],
         "prev_actions" i32 [K,E,N] (what each step's MOA read) and "rewards" f32 [K,E,N] = rew + influence_weight *
-        influence."""
+        influence.
+        With a gamma the dict gains "advantages" and "value_targets" f32 [K,E,N]: postprocessing.compute_advantages of rew,
+        value, done and last_value (for a ConvMOAPolicy of rew + influence_weight * influence, formed in float64), enqueued
+        behind the rollout on the same stream."""
         import torch
         if self.float32_obs:
             raise ValueError("sample() records uint8 observations: construct with float32_obs=False")
@@ -177,6 +181,13 @@ class SSDVectorEnv(object):
             raise ValueError("n_steps must be >= 1")
         eng = self.engine
         eng._policy_weights(policy)                  # (every check before anything is enqueued)
+        if gamma is not None:
+            import math
+            gamma, lambda_ = float(gamma), float(lambda_)
+            if not (math.isfinite(gamma) and math.isfinite(lambda_)):
+                raise ValueError("gamma and lambda_ must be finite")
+            if use_gae and not use_critic:
+                raise ValueError("use_gae needs use_critic: generalised advantage estimation uses the value function")
         moa = eng._is_moa(policy)
         recurrent = eng._is_recurrent(policy) or moa
         if not recurrent and state_every is not None:
@@ -229,6 +240,12 @@ class SSDVectorEnv(object):
         self._out[0].copy_(out["obs"][n_steps - 1])  # the current observation, as step() would have left it
         if moa:
             out["rewards"] = out["rew"].to(torch.float32) + float(influence_weight) * out["influence"]
+        if gamma is not None:
+            from .postprocessing import compute_advantages
+            bonus = dict(bonus=out["influence"], bonus_weight=float(influence_weight)) if moa else {}
+            out["advantages"], out["value_targets"] = compute_advantages(
+                out["rew"], out["value"], out["last_value"], out["done"], gamma=gamma, lambda_=lambda_, use_gae=use_gae,
+                use_critic=use_critic, **bonus)
         return out
 
     @staticmethod
