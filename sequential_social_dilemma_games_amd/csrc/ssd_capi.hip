@@ -1469,55 +1469,107 @@ int ssd_set_horizon(ssd_env *env, int32_t horizon) {
     return SSD_OK;
 }
 
-// A closed-loop rollout: per step one launch of the policy kernel (ssd_policy.hip: forward + action into the ring slot), then the
-// step launch of ssd_step(..., SSD_AUTO_RESET) reading those actions.  Both through hipLaunchKernel on `stream`: the library's
-// AQL chains (ssd_rollout_actions) are not used here.
+}  // extern "C"
+
+// A closed-loop rollout: per step the policy's launches (ssd_policy*.hip: forward + action into the ring slot), then the step
+// launch of ssd_step(..., SSD_AUTO_RESET) reading those actions.  All through hipLaunchKernel on `stream`: the library's AQL
+// chains (ssd_rollout_actions) are not used here.  The three policies share the argument rules and the
+// loop below; each adds its own rules, its argument blocks and its launches.
+namespace {
+
+constexpr size_t kPolObs = (size_t)SSD_POL_VIEW * SSD_POL_VIEW * 3;    // observation bytes per agent
+
+int policy_actions(const ssd_env *env) { return env->game == SSD_GAME_HARVEST ? 8 : 9; }   // harvest.py:44, cleanup.py:70
+
+// the rules of the step counts and the optional state ring (null: none); null = fine
+const char *check_rollout_steps(int32_t n_steps, int32_t step0, int32_t ring, const float *state_ring, int32_t state_ring_len,
+                                int32_t state_every) {
+    if (n_steps < 1) return "n_steps must be >= 1";
+    if (ring < 1) return "ring must be >= 1";
+    if (step0 < 0) return "step0 must be >= 0";
+    if (state_ring) {
+        if (state_every < 1) return "state_every must be >= 1";
+        if ((int64_t)state_ring_len * state_every < n_steps) return "the state ring needs ceil(n_steps / state_every) slots";
+    }
+    return nullptr;
+}
+
+// the rules of the flags and the observation ring; null = fine
+const char *check_rollout_obs(const ssd_env *env, uint32_t flags, const uint8_t *obs, int32_t ring) {
+    if (flags & ~(uint32_t)SSD_POLICY_GREEDY) return "flags: only the greedy-policy bit is defined";
+    if (reinterpret_cast<uintptr_t>(obs) & 3u) return "obs must be 4-byte aligned";
+    if (ring > 1 && (((size_t)env->E * env->N * kPolObs) & 3u))
+        return "an observation ring of more than one slot needs E * N to be a multiple of 4 (4-byte aligned slots)";
+    return nullptr;
+}
+
+// The loop: step k acts on obs_in (k = 0) or the previous slot's observations and writes ring slot (step0 + k) % ring.
+// policy(k, obs_k, slot) launches the policy, leaving the actions in actions[slot]; last(obs) what follows the loop (the
+// last_value pass on the final observations).  Both return SSD_OK or an error code with env->err set (SSD_HIP).
+template <class Policy, class Last>
+int rollout_policy_steps(ssd_env *env, const uint8_t *obs_in, int32_t n_steps, int32_t step0, int32_t ring, uint8_t *obs,
+                         int32_t *actions, int32_t *rew, uint8_t *done, void *stream, Policy policy, Last last) {
+    if (const hipError_t e = ssd::select_device(env->device)) {
+        env->err = std::string("hipSetDevice(env->device): ") + hipGetErrorString(e);
+        return SSD_E_DEVICE;
+    }
+    const size_t en = (size_t)env->E * env->N, ob = en * kPolObs;
+    size_t slot = 0;
+    for (int32_t k = 0; k < n_steps; ++k) {
+        const size_t prev = slot;
+        slot = (size_t)(((int64_t)step0 + k) % ring);
+        int rc = policy(k, k == 0 ? obs_in : obs + prev * ob, slot);
+        if (rc) return rc;
+        rc = run(env, ssd::kModeStepAuto, actions + slot * en, nullptr, nullptr, 0, nullptr, obs + slot * ob,
+                           rew ? rew + slot * en : nullptr, done ? done + slot * en : nullptr, 1, 0, stream);
+        if (rc) return rc;
+    }
+    return last(obs + slot * ob);
+}
+
+// slot `slot` of an optional ring of n elements per slot
+template <class T>
+T *ring_slot(T *p, size_t slot, size_t n) { return p ? p + slot * n : nullptr; }
+
+}  // namespace
+
+extern "C" {
+
 int ssd_rollout_policy(ssd_env *env, const float *weights, int32_t num_sets, const uint8_t *obs_in, int32_t n_steps, int32_t step0,
                        uint8_t *obs, int32_t *actions, float *logp, float *value, float *logits, int32_t *rew, uint8_t *done,
                        int32_t ring, float *last_value, uint32_t flags, void *stream) {
     if (!env) return SSD_E_INVALID;
     auto bad = [&](const char *msg) { env->err = msg; return SSD_E_INVALID; };
-    const int A = env->game == SSD_GAME_HARVEST ? 8 : 9;        // harvest.py:44, cleanup.py:70
+    const int A = policy_actions(env);
     if (env->view_len != 7 || env->V != SSD_POL_VIEW) return bad("policy rollouts need view_len 7 (15 x 15 observations)");
     if (env->N < 1) return bad("policy rollouts need at least one agent");
     if (!weights || !obs_in || !obs || !actions) return bad("weights, obs_in, obs and actions are required");
-    if (reinterpret_cast<uintptr_t>(weights) & 3u) return bad("weights must be 4-byte aligned");
-    if (num_sets != 1 && num_sets != env->N) return bad("num_sets must be 1 or num_agents");
-    if (n_steps < 1) return bad("n_steps must be >= 1");
-    if (ring < 1) return bad("ring must be >= 1");
-    if (step0 < 0) return bad("step0 must be >= 0");
-    if (flags & ~(uint32_t)SSD_POLICY_GREEDY) return bad("flags: only the greedy-policy bit is defined");
-    const size_t en = (size_t)env->E * env->N, ob = en * SSD_POL_VIEW * SSD_POL_VIEW * 3;
-    if (reinterpret_cast<uintptr_t>(obs) & 3u) return bad("obs must be 4-byte aligned");
-    if (ring > 1 && (ob & 3u)) return bad("an observation ring of more than one slot needs E * N to be a multiple of 4 (4-byte aligned slots)");
-    {
-        int cur = -1;
-        if (hipGetDevice(&cur) != hipSuccess || cur != env->device) SSD_HIP(env, hipSetDevice(env->device));
-    }
+    if (const char *why = ssd::check_policy_net(ssd::kNetConvFc, weights, num_sets, env->N, A)) return bad(why);
+    if (const char *why = check_rollout_steps(n_steps, step0, ring, nullptr, 0, 0)) return bad(why);
+    if (const char *why = check_rollout_obs(env, flags, obs, ring)) return bad(why);
+    const size_t en = (size_t)env->E * env->N;
     ssd::PolicyArgs pa{};
     pa.w = weights; pa.P = num_sets; pa.A = A; pa.B = env->E; pa.N = env->N; pa.set_floats = SSD_POL_SET_FLOATS(A);
     pa.hdr = env->p.hdr; pa.seed_lo = env->p.seed_lo; pa.seed_hi = env->p.seed_hi; pa.env_base = env->p.env_base;
     pa.greedy = (flags & SSD_POLICY_GREEDY) ? 1 : 0;
-    size_t slot = 0;
-    for (int32_t k = 0; k < n_steps; ++k) {
-        const size_t prev = slot;
-        slot = (size_t)(((int64_t)step0 + k) % ring);
-        pa.obs = k == 0 ? obs_in : obs + prev * ob;
-        pa.actions = actions + slot * en;
-        pa.logp = logp ? logp + slot * en : nullptr;
-        pa.value = value ? value + slot * en : nullptr;
-        pa.logits = logits ? logits + slot * en * A : nullptr;
-        SSD_HIP(env, ssd::launch_policy(pa, stream));
-        const int rc = run(env, ssd::kModeStepAuto, pa.actions, nullptr, nullptr, 0, nullptr, obs + slot * ob, rew ? rew + slot * en : nullptr,
-                           done ? done + slot * en : nullptr, 1, 0, stream);
-        if (rc) return rc;
-    }
-    if (last_value) {
-        pa.obs = obs + slot * ob;
-        pa.actions = nullptr; pa.logp = nullptr; pa.logits = nullptr; pa.value = last_value;
-        SSD_HIP(env, ssd::launch_policy(pa, stream));
-    }
-    return SSD_OK;
+    return rollout_policy_steps(
+        env, obs_in, n_steps, step0, ring, obs, actions, rew, done, stream,
+        [&](int32_t, const uint8_t *o, size_t slot) -> int {
+            pa.obs = o;
+            pa.actions = actions + slot * en;
+            pa.logp = ring_slot(logp, slot, en);
+            pa.value = ring_slot(value, slot, en);
+            pa.logits = ring_slot(logits, slot, en * A);
+            SSD_HIP(env, ssd::launch_policy(pa, stream));
+            return SSD_OK;
+        },
+        [&](const uint8_t *o) -> int {
+            if (!last_value) return SSD_OK;
+            pa.obs = o;
+            pa.actions = nullptr; pa.logp = nullptr; pa.logits = nullptr; pa.value = last_value;
+            SSD_HIP(env, ssd::launch_policy(pa, stream));
+            return SSD_OK;
+        });
 }
 
 int ssd_rollout_policy_lstm(ssd_env *env, const float *weights, int32_t num_sets, int32_t cell_size, const uint8_t *obs_in,
@@ -1527,29 +1579,15 @@ int ssd_rollout_policy_lstm(ssd_env *env, const float *weights, int32_t num_sets
                             void *stream) {
     if (!env) return SSD_E_INVALID;
     auto bad = [&](const char *msg) { env->err = msg; return SSD_E_INVALID; };
-    const int A = env->game == SSD_GAME_HARVEST ? 8 : 9;        // harvest.py:44, cleanup.py:70
+    const int A = policy_actions(env);
     if (env->view_len != 7 || env->V != SSD_POL_VIEW) return bad("policy rollouts need view_len 7 (15 x 15 observations)");
     if (env->N < 1) return bad("policy rollouts need at least one agent");
     if (!weights || !obs_in || !obs || !actions || !state || !features)
         return bad("weights, obs_in, obs, actions, state and features are required");
-    if (reinterpret_cast<uintptr_t>(weights) & 3u) return bad("weights must be 4-byte aligned");
-    if (cell_size != 64 && cell_size != 128 && cell_size != 256) return bad("cell_size must be 64, 128 or 256");
-    if (num_sets != 1 && num_sets != env->N) return bad("num_sets must be 1 or num_agents");
-    if (n_steps < 1) return bad("n_steps must be >= 1");
-    if (ring < 1) return bad("ring must be >= 1");
-    if (step0 < 0) return bad("step0 must be >= 0");
-    if (state_ring) {
-        if (state_every < 1) return bad("state_every must be >= 1");
-        if ((int64_t)state_ring_len * state_every < n_steps) return bad("the state ring needs ceil(n_steps / state_every) slots");
-    }
-    if (flags & ~(uint32_t)SSD_POLICY_GREEDY) return bad("flags: only the greedy-policy bit is defined");
-    const size_t en = (size_t)env->E * env->N, ob = en * SSD_POL_VIEW * SSD_POL_VIEW * 3, sn = en * 2 * cell_size;
-    if (reinterpret_cast<uintptr_t>(obs) & 3u) return bad("obs must be 4-byte aligned");
-    if (ring > 1 && (ob & 3u)) return bad("an observation ring of more than one slot needs E * N to be a multiple of 4 (4-byte aligned slots)");
-    {
-        int cur = -1;
-        if (hipGetDevice(&cur) != hipSuccess || cur != env->device) SSD_HIP(env, hipSetDevice(env->device));
-    }
+    if (const char *why = ssd::check_policy_net(ssd::kNetLstm, weights, num_sets, env->N, A, cell_size)) return bad(why);
+    if (const char *why = check_rollout_steps(n_steps, step0, ring, state_ring, state_ring_len, state_every)) return bad(why);
+    if (const char *why = check_rollout_obs(env, flags, obs, ring)) return bad(why);
+    const size_t en = (size_t)env->E * env->N, sn = en * 2 * cell_size;
     ssd::PolicyArgs tr{};                       // the trunk, features mode
     tr.w = weights; tr.P = num_sets; tr.A = A; tr.B = env->E; tr.N = env->N; tr.set_floats = SSD_LSTM_SET_FLOATS(cell_size, A);
     tr.feat = features;
@@ -1558,30 +1596,28 @@ int ssd_rollout_policy_lstm(ssd_env *env, const float *weights, int32_t num_sets
     la.feat = features; la.state_in = state; la.state_out = state;
     la.hdr = env->p.hdr; la.seed_lo = env->p.seed_lo; la.seed_hi = env->p.seed_hi; la.env_base = env->p.env_base;
     la.greedy = (flags & SSD_POLICY_GREEDY) ? 1 : 0;
-    size_t slot = 0;
-    for (int32_t k = 0; k < n_steps; ++k) {
-        const size_t prev = slot;
-        slot = (size_t)(((int64_t)step0 + k) % ring);
-        tr.obs = k == 0 ? obs_in : obs + prev * ob;
+    const auto both = [&](const uint8_t *o) -> int {
+        tr.obs = o;
         SSD_HIP(env, ssd::launch_policy_features(tr, stream));
-        la.state_used = state_ring && k % state_every == 0 ? state_ring + (size_t)(k / state_every) * sn : nullptr;
-        la.actions = actions + slot * en;
-        la.logp = logp ? logp + slot * en : nullptr;
-        la.value = value ? value + slot * en : nullptr;
-        la.logits = logits ? logits + slot * en * A : nullptr;
         SSD_HIP(env, ssd::launch_policy_lstm(la, stream));
-        const int rc = run(env, ssd::kModeStepAuto, la.actions, nullptr, nullptr, 0, nullptr, obs + slot * ob, rew ? rew + slot * en : nullptr,
-                           done ? done + slot * en : nullptr, 1, 0, stream);
-        if (rc) return rc;
-    }
-    if (last_value) {                           // the final observation under the final state; the state stays as it is
-        tr.obs = obs + slot * ob;
-        SSD_HIP(env, ssd::launch_policy_features(tr, stream));
-        la.state_out = nullptr; la.state_used = nullptr;
-        la.actions = nullptr; la.logp = nullptr; la.logits = nullptr; la.value = last_value;
-        SSD_HIP(env, ssd::launch_policy_lstm(la, stream));
-    }
-    return SSD_OK;
+        return SSD_OK;
+    };
+    return rollout_policy_steps(
+        env, obs_in, n_steps, step0, ring, obs, actions, rew, done, stream,
+        [&](int32_t k, const uint8_t *o, size_t slot) -> int {
+            la.state_used = state_ring && k % state_every == 0 ? state_ring + (size_t)(k / state_every) * sn : nullptr;
+            la.actions = actions + slot * en;
+            la.logp = ring_slot(logp, slot, en);
+            la.value = ring_slot(value, slot, en);
+            la.logits = ring_slot(logits, slot, en * A);
+            return both(o);
+        },
+        [&](const uint8_t *o) -> int {          // the final observation under the final state; the state stays as it is
+            if (!last_value) return SSD_OK;
+            la.state_out = nullptr; la.state_used = nullptr;
+            la.actions = nullptr; la.logp = nullptr; la.logits = nullptr; la.value = last_value;
+            return both(o);
+        });
 }
 
 int ssd_rollout_policy_moa(ssd_env *env, const float *weights, int32_t num_sets, int32_t cell_size, const uint8_t *obs_in,
@@ -1592,31 +1628,16 @@ int ssd_rollout_policy_moa(ssd_env *env, const float *weights, int32_t num_sets,
                            void *stream) {
     if (!env) return SSD_E_INVALID;
     auto bad = [&](const char *msg) { env->err = msg; return SSD_E_INVALID; };
-    const int A = env->game == SSD_GAME_HARVEST ? 8 : 9;        // harvest.py:44, cleanup.py:70
+    const int A = policy_actions(env);
     if (env->view_len != 7 || env->V != SSD_POL_VIEW) return bad("policy rollouts need view_len 7 (15 x 15 observations)");
     if (env->N < 2 || env->N > SSD_MOA_MAX_AGENTS) return bad("the MOA policy needs 2..16 agents");
     if (!weights || !obs_in || !obs || !actions || !state || !prev_actions || !scratch)
         return bad("weights, obs_in, obs, actions, state, prev_actions and scratch are required");
-    if (reinterpret_cast<uintptr_t>(weights) & 3u) return bad("weights must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(scratch) & 3u) return bad("scratch must be 4-byte aligned");
-    if (cell_size != 64 && cell_size != 128 && cell_size != 256) return bad("cell_size must be 64, 128 or 256");
-    if (num_sets != 1 && num_sets != env->N) return bad("num_sets must be 1 or num_agents");
-    if (n_steps < 1) return bad("n_steps must be >= 1");
-    if (ring < 1) return bad("ring must be >= 1");
-    if (step0 < 0) return bad("step0 must be >= 0");
-    if (state_ring) {
-        if (state_every < 1) return bad("state_every must be >= 1");
-        if ((int64_t)state_ring_len * state_every < n_steps) return bad("the state ring needs ceil(n_steps / state_every) slots");
-    }
+    if (const char *why = ssd::check_policy_net(ssd::kNetMoa, weights, num_sets, env->N, A, cell_size, scratch)) return bad(why);
+    if (const char *why = check_rollout_steps(n_steps, step0, ring, state_ring, state_ring_len, state_every)) return bad(why);
     if (influence && !(influence_clip >= 0.f && influence_clip <= 3.0e38f)) return bad("influence_clip must be finite and >= 0");
-    if (flags & ~(uint32_t)SSD_POLICY_GREEDY) return bad("flags: only the greedy-policy bit is defined");
-    const size_t en = (size_t)env->E * env->N, ob = en * SSD_POL_VIEW * SSD_POL_VIEW * 3, sn = en * 4 * cell_size;
-    if (reinterpret_cast<uintptr_t>(obs) & 3u) return bad("obs must be 4-byte aligned");
-    if (ring > 1 && (ob & 3u)) return bad("an observation ring of more than one slot needs E * N to be a multiple of 4 (4-byte aligned slots)");
-    {
-        int cur = -1;
-        if (hipGetDevice(&cur) != hipSuccess || cur != env->device) SSD_HIP(env, hipSetDevice(env->device));
-    }
+    if (const char *why = check_rollout_obs(env, flags, obs, ring)) return bad(why);
+    const size_t en = (size_t)env->E * env->N, sn = en * 4 * cell_size;
     // scratch (include/ssd.h): features [en][2][32], logits [en][16], the joint-action ping-pong i32 [2][en]
     int32_t *pp[2] = {reinterpret_cast<int32_t *>(scratch + 80 * en), reinterpret_cast<int32_t *>(scratch + 81 * en)};
     ssd::PolicyArgs tr{};                       // the trunk, MOA mode
@@ -1628,38 +1649,38 @@ int ssd_rollout_policy_moa(ssd_env *env, const float *weights, int32_t num_sets,
     ma.hdr = env->p.hdr; ma.seed_lo = env->p.seed_lo; ma.seed_hi = env->p.seed_hi; ma.env_base = env->p.env_base;
     ma.greedy = (flags & SSD_POLICY_GREEDY) ? 1 : 0;
     ma.pi_logits = ma.logits_scratch; ma.pi_stride = 16; ma.clip = influence_clip;
-    size_t slot = 0;
-    for (int32_t k = 0; k < n_steps; ++k) {
-        const size_t prev = slot;
-        slot = (size_t)(((int64_t)step0 + k) % ring);
-        tr.obs = k == 0 ? obs_in : obs + prev * ob;
+    const auto trunk_actions = [&](const uint8_t *o) -> int {
+        tr.obs = o;
         SSD_HIP(env, ssd::launch_policy_moa_features(tr, stream));
-        ma.state_used = state_ring && k % state_every == 0 ? state_ring + (size_t)(k / state_every) * sn : nullptr;
-        ma.actions = actions + slot * en;
-        ma.actions_copy = pp[(k + 1) & 1];      // the next step's previous joint action: never the buffer this step reads
-        ma.logp = logp ? logp + slot * en : nullptr;
-        ma.value = value ? value + slot * en : nullptr;
-        ma.logits = logits ? logits + slot * en * A : nullptr;
         SSD_HIP(env, ssd::launch_policy_moa_actions(ma, stream));
-        ma.prev = k == 0 ? prev_actions : pp[k & 1];
-        ma.prev_used = prev_actions_ring ? prev_actions_ring + slot * en : nullptr;
-        ma.taken = influence ? ma.actions : nullptr;
-        ma.influence = influence ? influence + slot * en : nullptr;
-        SSD_HIP(env, ssd::launch_policy_moa_cell(ma, stream));
-        const int rc = run(env, ssd::kModeStepAuto, ma.actions, nullptr, nullptr, 0, nullptr, obs + slot * ob, rew ? rew + slot * en : nullptr,
-                           done ? done + slot * en : nullptr, 1, 0, stream);
-        if (rc) return rc;
-    }
-    SSD_HIP(env, hipMemcpyAsync(prev_actions, pp[n_steps & 1], en * sizeof(int32_t), hipMemcpyDeviceToDevice,
-                                static_cast<hipStream_t>(stream)));
-    if (last_value) {                           // the final observation under the final state; the state stays as it is
-        tr.obs = obs + slot * ob;
-        SSD_HIP(env, ssd::launch_policy_moa_features(tr, stream));
-        ma.state_out = nullptr; ma.state_used = nullptr; ma.actions = nullptr; ma.actions_copy = nullptr; ma.logp = nullptr;
-        ma.logits = nullptr; ma.logits_scratch = nullptr; ma.value = last_value;
-        SSD_HIP(env, ssd::launch_policy_moa_actions(ma, stream));
-    }
-    return SSD_OK;
+        return SSD_OK;
+    };
+    return rollout_policy_steps(
+        env, obs_in, n_steps, step0, ring, obs, actions, rew, done, stream,
+        [&](int32_t k, const uint8_t *o, size_t slot) -> int {
+            ma.state_used = state_ring && k % state_every == 0 ? state_ring + (size_t)(k / state_every) * sn : nullptr;
+            ma.actions = actions + slot * en;
+            ma.actions_copy = pp[(k + 1) & 1];  // the next step's previous joint action: never the buffer this step reads
+            ma.logp = ring_slot(logp, slot, en);
+            ma.value = ring_slot(value, slot, en);
+            ma.logits = ring_slot(logits, slot, en * A);
+            if (const int rc = trunk_actions(o)) return rc;
+            ma.prev = k == 0 ? prev_actions : pp[k & 1];
+            ma.prev_used = ring_slot(prev_actions_ring, slot, en);
+            ma.taken = influence ? ma.actions : nullptr;
+            ma.influence = ring_slot(influence, slot, en);
+            SSD_HIP(env, ssd::launch_policy_moa_cell(ma, stream));
+            return SSD_OK;
+        },
+        [&](const uint8_t *o) -> int {
+            SSD_HIP(env, hipMemcpyAsync(prev_actions, pp[n_steps & 1], en * sizeof(int32_t), hipMemcpyDeviceToDevice,
+                                        static_cast<hipStream_t>(stream)));
+            if (!last_value) return SSD_OK;
+            // the final observation under the final state; the state stays as it is
+            ma.state_out = nullptr; ma.state_used = nullptr; ma.actions = nullptr; ma.actions_copy = nullptr; ma.logp = nullptr;
+            ma.logits = nullptr; ma.logits_scratch = nullptr; ma.value = last_value;
+            return trunk_actions(o);
+        });
 }
 
 int ssd_rollout_path(const ssd_env *env) { return env ? env->last_path : SSD_E_INVALID; }

@@ -11,9 +11,12 @@
 //      are added through LDS.  fc1's weights stream from L2 (130 KB per set, shared by every workgroup of the set);
 //   4. fc2, the logits and the value on the VALU (1.3 kMAC per env);
 //   5. rollouts: one thread per env picks the action (greedy or the S_POLICY draw) and its log-probability.
-// Every sum is in a fixed order, so two calls on the same input agree bit for bit.  kModeFeatures stops after fc2 and writes its
-// output instead: the trunk of the recurrent policy (ssd_policy_lstm.hip).  kModeMoa runs steps 3 and 4 (to fc2) once per FC
-// stack of the MOA policy, with tanh for ReLU, on the same conv output and writes both outputs (ssd_policy_moa.hip).
+// Steps 3 and 4 to fc2 are fc_stack below; the heads and the action are ssd_policy_device.hpp's (heads, pick_actions), shared
+// with the recurrent kernels.  Every sum is in a fixed order, so two calls on the same input agree bit for bit.  kModeFeatures
+// stops after fc2 and writes its output instead: the trunk of the recurrent policy (ssd_policy_lstm.hip).  kModeMoa runs
+// fc_stack once per FC stack of the MOA policy, with tanh for ReLU, on the same conv output and writes both outputs
+// (ssd_policy_moa.hip).  This file also holds the argument checks every policy entry point shares (check_policy_net,
+// check_state_out, select_device; declared in ssd_policy.hpp).
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -21,7 +24,7 @@
 #include <string>
 
 #include "../../include/ssd.h"
-#include "ssd_policy.hpp"
+#include "ssd_policy_device.hpp"
 
 namespace {
 
@@ -40,20 +43,24 @@ static_assert(SSD_POL_FC1_B == SSD_POL_FC1_W + kFlat * 32 && SSD_POL_FC2_W == SS
               SSD_POL_VALUE_W == SSD_POL_FC2_B + 32 && SSD_POL_VALUE_B == SSD_POL_VALUE_W + 32 && SSD_POL_LOGITS_W >= SSD_POL_VALUE_B + 1,
               "weight layout of include/ssd.h");
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using ssd::f32x4;
 
 constexpr int kModeHeads = 0, kModeFeatures = 1, kModeMoa = 2;
 
-// The MOA policy's FC stack s on the conv output of s_conv (steps 3 and 4 of ssd_policy_kernel with tanh, stack s's weights at
-// SSD_MOA_FC1_W(s), the trunk's relative offsets): writes feat [B][N][2][32] at stack s.
-__device__ __forceinline__ void moa_stack(const ssd::PolicyArgs &a, const float *__restrict__ w, int s, const float *s_conv,
-                                          float *s_part, float *s_h1, int tid, int i, int b0) {
-    const float *ws = w + (SSD_MOA_FC1_W(s) - SSD_POL_FC1_W);
+// Steps 3 and 4 up to fc2 on the conv output in s_conv: fc1 on the matrix cores, its two K halves added through LDS, fc2 on the
+// VALU; ReLU after both layers, or tanh (the MOA policy's stacks).  ws: a weight set's base, moved so that SSD_POL_FC1_W ..
+// SSD_POL_FC2_B address the stack's layers.  fc2's output of tile row m < rows goes to out[m * stride + 0..31].
+template <bool kTanh>
+__device__ __forceinline__ void fc_stack(const float *__restrict__ ws, const float *s_conv, float *s_part, float *s_h1, int tid,
+                                         float *out, size_t stride, int rows) {
+    const auto act = [](float x) { return kTanh ? tanhf(x) : fmaxf(x, 0.f); };
+    // fc1: A[m][k] = conv row m, B[k][n] = fc1_w[k][n] (the lane layout: ssd_policy_device.hpp)
     const int wave = tid >> 6, lane = tid & 63, nt = wave & 1, kh = wave >> 1;
     const int l15 = lane & 15, l4 = lane >> 4;
     const float *a_row = s_conv + l15 * kPitch + l4;
     const float *w1 = ws + SSD_POL_FC1_W + l4 * 32 + nt * 16 + l15;
     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
+    // (wave half 0: k-steps 0..126; half 1: 127..253, whose last step is peeled -- its rows 1014, 1015 are padding)
     const int kb = kh * kHalf;
 #pragma unroll 4
     for (int p = 0; p < (kHalf - 1) / 2; ++p) {
@@ -78,27 +85,27 @@ __device__ __forceinline__ void moa_stack(const ssd::PolicyArgs &a, const float 
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int m = l4 * 4 + r;
-            s_h1[m * kHP + n] = tanhf(acc[r] + s_part[(nt * 16 + m) * 16 + l15] + bias);
+            s_h1[m * kHP + n] = act(acc[r] + s_part[(nt * 16 + m) * 16 + l15] + bias);
         }
     }
     __syncthreads();
+    // fc2: thread (m, n) takes columns n and n + 16 of row m
     const int m = tid >> 4, n = tid & 15;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         const int nn = n + 16 * h;
-        float acc2 = 0.f;
+        float s = 0.f;
 #pragma unroll 8
-        for (int k = 0; k < 32; ++k) acc2 = fmaf(s_h1[m * kHP + k], ws[SSD_POL_FC2_W + k * 32 + nn], acc2);
-        if (b0 + m < a.B) a.feat[(((size_t)(b0 + m) * a.N + i) * 2 + s) * 32 + nn] = tanhf(acc2 + ws[SSD_POL_FC2_B + nn]);
+        for (int k = 0; k < 32; ++k) s = fmaf(s_h1[m * kHP + k], ws[SSD_POL_FC2_W + k * 32 + nn], s);
+        if (m < rows) out[m * stride + nn] = act(s + ws[SSD_POL_FC2_B + nn]);
     }
-    __syncthreads();                                    // s_part and s_h1 are the next stack's
 }
 
 // kModeFeatures: stop after fc2 and write its output to a.feat (the trunk of the recurrent policy, ssd_policy_lstm.hip).
-// kModeMoa: both FC stacks of the MOA policy after the conv (moa_stack).
+// kModeMoa: both FC stacks of the MOA policy after the conv (stack s's weights at SSD_MOA_FC1_W(s), the trunk's relative
+// offsets), to a.feat [B][N][2][32].
 template <int kMode>
 __global__ void __launch_bounds__(kThreads) ssd_policy_kernel(ssd::PolicyArgs a) {
-    constexpr bool kFeatures = kMode != kModeHeads;
     __shared__ float s_norm[256];
     __shared__ float s_conv[kTile * kPitch];
     __shared__ float s_buf[(kTile * kObs + 3) / 4];   // the observation bytes; after the conv, the small buffers below
@@ -110,7 +117,7 @@ __global__ void __launch_bounds__(kThreads) ssd_policy_kernel(ssd::PolicyArgs a)
     static_assert(512 + 2 * kTile * kHP + kTile * 16 <= (kTile * kObs + 3) / 4, "small buffers fit the observation area");
 
     const int tid = threadIdx.x, i = blockIdx.y, b0 = blockIdx.x * kTile;
-    const int N = a.N, B = a.B, A = a.A;
+    const int N = a.N, B = a.B;
     const float *__restrict__ w = a.w + (size_t)(a.P == 1 ? 0 : i) * (size_t)a.set_floats;
 
     // ---- 1. inputs ----
@@ -151,102 +158,28 @@ __global__ void __launch_bounds__(kThreads) ssd_policy_kernel(ssd::PolicyArgs a)
         for (int f = 0; f < 6; ++f) dst[f] = fmaxf(acc[f] + w[SSD_POL_CONV_B + f], 0.f);
     }
     __syncthreads();
+
+    // ---- 3, 4. fc1, fc2 (fc_stack) ----
+    const size_t row0 = (size_t)b0 * N + i;                 // the tile's first row of a [B][N] array; its rows are N apart
     if constexpr (kMode == kModeMoa) {
-        moa_stack(a, w, 0, s_conv, s_part, s_h1, tid, i, b0);
-        moa_stack(a, w, 1, s_conv, s_part, s_h1, tid, i, b0);
-        return;
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            fc_stack<true>(w + (SSD_MOA_FC1_W(s) - SSD_POL_FC1_W), s_conv, s_part, s_h1, tid, a.feat + (row0 * 2 + s) * 32,
+                           (size_t)N * 64, B - b0);
+            __syncthreads();                                // s_part and s_h1 are the next stack's
+        }
+    } else if constexpr (kMode == kModeFeatures) {
+        fc_stack<false>(w, s_conv, s_part, s_h1, tid, a.feat + row0 * 32, (size_t)N * 32, B - b0);
     } else {
-
-    // ---- 3. fc1 on the matrix cores: A[m][k] = conv row m, B[k][n] = fc1_w[k][n] ----
-    // v_mfma_f32_16x16x4_f32: lane l holds A[l & 15][k = l >> 4] and B[k = l >> 4][l & 15]; D: col l & 15, row 4 (l >> 4) + r
-    const int wave = tid >> 6, lane = tid & 63, nt = wave & 1, kh = wave >> 1;
-    const int l15 = lane & 15, l4 = lane >> 4;
-    const float *a_row = s_conv + l15 * kPitch + l4;
-    const float *w1 = w + SSD_POL_FC1_W + l4 * 32 + nt * 16 + l15;
-    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
-    // (wave half 0: k-steps 0..126; half 1: 127..253, whose last step is peeled -- its rows 1014, 1015 are padding)
-    const int kb = kh * kHalf;
-#pragma unroll 4
-    for (int p = 0; p < (kHalf - 1) / 2; ++p) {
-        const int kk = kb + 2 * p;
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a_row[4 * kk], w1[(size_t)kk * 128], acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a_row[4 * kk + 4], w1[(size_t)kk * 128 + 128], acc1, 0, 0, 0);
+        fc_stack<false>(w, s_conv, s_part, s_h1, tid, s_h2, kHP, kTile);
+        __syncthreads();
+        // ---- 4. the heads, 5. the action: argmax, or the first a with u < cumulative softmax (include/ssd.h) ----
+        ssd::heads<32, kTile, kThreads>(a, s_h2, kHP, w + SSD_POL_LOGITS_W, w + SSD_POL_VALUE_W, w + SSD_POL_LOGITS_W + 32 * a.A,
+                                        w + SSD_POL_VALUE_B, s_out, nullptr, tid, b0, i);
+        if (!a.actions) return;
+        __syncthreads();
+        ssd::pick_actions<kTile>(a, s_out, nullptr, tid, b0, i);
     }
-    {
-        const int kl = kb + kHalf - 1;
-        const float bv = 4 * kl + l4 < kFlat ? w1[(size_t)kl * 128] : 0.f;
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a_row[4 * kl], bv, acc0, 0, 0, 0);
-    }
-    const f32x4 acc = acc0 + acc1;
-    if (kh) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) s_part[(nt * 16 + l4 * 4 + r) * 16 + l15] = acc[r];
-    }
-    __syncthreads();
-    if (!kh) {
-        const int n = nt * 16 + l15;
-        const float bias = w[SSD_POL_FC1_B + n];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int m = l4 * 4 + r;
-            s_h1[m * kHP + n] = fmaxf(acc[r] + s_part[(nt * 16 + m) * 16 + l15] + bias, 0.f);
-        }
-    }
-    __syncthreads();
-
-    // ---- 4. fc2 + ReLU, then the heads ----
-    {
-        const int m = tid >> 4, n = tid & 15;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int nn = n + 16 * h;
-            float s = 0.f;
-#pragma unroll 8
-            for (int k = 0; k < 32; ++k) s = fmaf(s_h1[m * kHP + k], w[SSD_POL_FC2_W + k * 32 + nn], s);
-            const float hv = fmaxf(s + w[SSD_POL_FC2_B + nn], 0.f);
-            if (kFeatures) {
-                if (b0 + m < B) a.feat[((size_t)(b0 + m) * N + i) * 32 + nn] = hv;
-            } else {
-                s_h2[m * kHP + nn] = hv;
-            }
-        }
-    }
-    if (kFeatures) return;
-    __syncthreads();
-    {
-        const int m = tid >> 4, j = tid & 15, b = b0 + m;
-        if (j <= A) {                                       // j < A: logit j; j == A: the value
-            const float *hw = j < A ? w + SSD_POL_LOGITS_W + j : w + SSD_POL_VALUE_W;
-            const int stride = j < A ? A : 1;
-            float s = 0.f;
-#pragma unroll 8
-            for (int k = 0; k < 32; ++k) s = fmaf(s_h2[m * kHP + k], hw[k * stride], s);
-            s += j < A ? w[SSD_POL_LOGITS_W + 32 * A + j] : w[SSD_POL_VALUE_B];
-            s_out[m * 16 + j] = s;
-            if (b < B) {
-                const size_t row = (size_t)b * N + i;
-                if (j < A) {
-                    if (a.logits) a.logits[row * A + j] = s;
-                } else if (a.value) {
-                    a.value[row] = s;
-                }
-            }
-        }
-    }
-    if (!a.actions) return;
-    __syncthreads();
-
-    // ---- 5. the action: argmax, or the first a with u < cumulative softmax (include/ssd.h) ----
-    if (tid < kTile && b0 + tid < B) {
-        const int b = b0 + tid;
-        float lp;
-        const int act = ssd::policy_pick(s_out + tid * 16, A, a.greedy, a.greedy ? uint4{} : a.hdr[b], a.seed_lo, a.seed_hi,
-                                         a.env_base + (uint32_t)b, (uint32_t)i, &lp);
-        const size_t row = (size_t)b * N + i;
-        a.actions[row] = act;
-        if (a.logp) a.logp[row] = lp;
-    }
-    }  // (kMode != kModeMoa)
 }
 
 thread_local std::string g_policy_error;
@@ -279,7 +212,46 @@ hipError_t launch_policy_moa_features(const PolicyArgs &a, void *stream) {
 }
 
 int policy_fail(const char *msg) { return fail(msg); }
-void policy_set_error(const char *msg) { g_policy_error = msg; }
+
+const char *check_policy_net(PolicyNet net, const float *weights, int32_t num_sets, int32_t num_agents, int32_t num_actions,
+                             int32_t cell_size, const float *moa_scratch) {
+    if (reinterpret_cast<uintptr_t>(weights) & 3u) return "weights must be 4-byte aligned";
+    if (net == kNetMoa && (reinterpret_cast<uintptr_t>(moa_scratch) & 3u)) return "scratch must be 4-byte aligned";
+    if (net != kNetConvFc && cell_size != 64 && cell_size != 128 && cell_size != 256) return "cell_size must be 64, 128 or 256";
+    if (net == kNetMoa) {
+        if (num_agents < 2 || num_agents > SSD_MOA_MAX_AGENTS) return "the MOA policy needs 2..16 agents";
+    } else if (num_agents < 1 || num_agents > 64) {
+        return "num_agents must be 1..64";
+    }
+    if (num_sets != 1 && num_sets != num_agents) return "num_sets must be 1 or num_agents";
+    if (num_actions < 1 || num_actions > SSD_POL_MAX_ACTIONS) return "num_actions must be 1..15";
+    return nullptr;
+}
+
+const char *check_state_out(const float *state_in, const float *state_out, size_t bytes) {
+    if (!state_out || state_out == state_in) return nullptr;
+    const char *p = reinterpret_cast<const char *>(state_in), *q = reinterpret_cast<const char *>(state_out);
+    return q < p + bytes && p < q + bytes ? "state_out must be state_in or not overlap it" : nullptr;
+}
+
+hipError_t select_device(int device_id) {
+    int cur = -1;
+    if (hipGetDevice(&cur) == hipSuccess && cur == device_id) return hipSuccess;
+    return hipSetDevice(device_id);
+}
+
+int policy_use_device(int device_id) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || device_id < 0 || device_id >= count) return fail("no such HIP device");
+    if (select_device(device_id) != hipSuccess) { g_policy_error = "hipSetDevice failed"; return SSD_E_DEVICE; }
+    return SSD_OK;
+}
+
+int policy_launched(hipError_t e) {
+    if (e == hipSuccess) return SSD_OK;
+    g_policy_error = std::string("policy launch: ") + hipGetErrorString(e);
+    return SSD_E_DEVICE;
+}
 
 }  // namespace ssd
 
@@ -290,24 +262,14 @@ const char *ssd_policy_last_error(void) { return g_policy_error.c_str(); }
 int ssd_policy_forward(const float *weights, int32_t num_sets, int32_t num_actions, const uint8_t *obs, int32_t batch,
                        int32_t num_agents, float *logits, float *value, int32_t device_id, uint32_t flags, void *stream) {
     if (!weights || !obs) return fail("weights and obs are required");
-    if (reinterpret_cast<uintptr_t>(weights) & 3u) return fail("weights must be 4-byte aligned");
-    if (num_agents < 1 || num_agents > 64) return fail("num_agents must be 1..64");
-    if (num_sets != 1 && num_sets != num_agents) return fail("num_sets must be 1 or num_agents");
-    if (num_actions < 1 || num_actions > SSD_POL_MAX_ACTIONS) return fail("num_actions must be 1..15");
+    if (const char *why = ssd::check_policy_net(ssd::kNetConvFc, weights, num_sets, num_agents, num_actions)) return fail(why);
     if (batch < 1) return fail("batch must be >= 1");
     if (flags) return fail("flags must be 0");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device_id < 0 || device_id >= count) return fail("no such HIP device");
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != device_id) {
-        if (hipSetDevice(device_id) != hipSuccess) { g_policy_error = "hipSetDevice failed"; return SSD_E_DEVICE; }
-    }
+    if (const int rc = ssd::policy_use_device(device_id)) return rc;
     ssd::PolicyArgs a{};
     a.w = weights; a.P = num_sets; a.A = num_actions; a.B = batch; a.N = num_agents; a.set_floats = SSD_POL_SET_FLOATS(num_actions);
     a.obs = obs; a.logits = logits; a.value = value;
-    const hipError_t e = ssd::launch_policy(a, stream);
-    if (e != hipSuccess) { g_policy_error = std::string("policy launch: ") + hipGetErrorString(e); return SSD_E_DEVICE; }
-    return SSD_OK;
+    return ssd::policy_launched(ssd::launch_policy(a, stream));
 }
 
 }  // extern "C"

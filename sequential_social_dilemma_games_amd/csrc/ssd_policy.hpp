@@ -1,6 +1,7 @@
-// csrc/ssd_policy.hpp -- the policy kernels' argument blocks and the action selection they share, used by ssd_policy.hip (trunk
-// kernel, ssd_policy_forward), ssd_policy_lstm.hip (recurrent cell, ssd_policy_lstm_forward) and ssd_capi.hip (the rollouts, which
-// interleave them with the step kernel).
+// csrc/ssd_policy.hpp -- the policy kernels' argument blocks, their launchers and the argument checks every policy entry point
+// shares (host-readable; the device pieces the kernels share are in ssd_policy_device.hpp).  Used by ssd_policy.hip (trunk kernel,
+// ssd_policy_forward), ssd_policy_lstm.hip, ssd_policy_moa.hip, ssd_ws_policy.hip and ssd_capi.hip (the rollouts, which interleave
+// the launches with the step kernel).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -87,45 +88,19 @@ hipError_t launch_policy_moa_actions(const MoaArgs &a, void *stream);
 hipError_t launch_policy_moa_cell(const MoaArgs &a, void *stream);
 // The calling thread's ssd_policy_last_error text; returns SSD_E_INVALID.
 int policy_fail(const char *msg);
-void policy_set_error(const char *msg);
 
-// shared PRNG (prng.py): the triple32 chain of ssd_kernels.hip
-__device__ __forceinline__ uint32_t pol_mix32(uint32_t x) {
-    x ^= x >> 17; x *= 0xED5AD4BBu;
-    x ^= x >> 11; x *= 0xAC4C1B51u;
-    x ^= x >> 15; x *= 0x31848BABu;
-    x ^= x >> 14;
-    return x;
-}
-
-// The action of agent i of env b from its logits l[0..A-1]: argmax (greedy), or the first a with u < cumulative softmax, u from
-// the S_POLICY draw of the env's (episode, t) in h = hdr[b] (include/ssd.h); *logp its log-probability.
-__device__ __forceinline__ int policy_pick(const float *l, int A, int greedy, uint4 h, uint32_t seed_lo, uint32_t seed_hi,
-                                           uint32_t env, uint32_t i, float *logp) {
-    float mx = l[0];
-    int arg = 0;
-    for (int k = 1; k < A; ++k)
-        if (l[k] > mx) { mx = l[k]; arg = k; }
-    float s = 0.f;
-    for (int k = 0; k < A; ++k) s += expf(l[k] - mx);
-    int act = arg;
-    if (!greedy) {
-        uint32_t key = 0x243F6A88u;
-        key = pol_mix32(key ^ seed_lo);
-        key = pol_mix32(key ^ seed_hi);
-        key = pol_mix32(key ^ env);
-        key = pol_mix32(key ^ h.z);
-        const uint32_t pk = pol_mix32(pol_mix32(key ^ h.y) ^ (uint32_t)SSD_S_POLICY);
-        const float u = (float)(pol_mix32(pk ^ i) >> 8) * 0x1p-24f;
-        act = A - 1;
-        float c = 0.f;
-        for (int k = 0; k < A; ++k) {
-            c += expf(l[k] - mx) / s;
-            if (u < c) { act = k; break; }
-        }
-    }
-    *logp = l[act] - (mx + logf(s));
-    return act;
-}
+// The rules every policy net's arguments follow, in the order callers have always seen them reported: null = fine, else the
+// error text.  kNetConvFc has no cell (cell_size is not looked at); kNetMoa also has a float scratch and 2..16 agents.  The
+// rollouts pass the engine's own agent and action counts, which always pass.
+enum PolicyNet { kNetConvFc, kNetLstm, kNetMoa };
+const char *check_policy_net(PolicyNet net, const float *weights, int32_t num_sets, int32_t num_agents, int32_t num_actions,
+                             int32_t cell_size = 0, const float *moa_scratch = nullptr);
+// state_out may be state_in itself (in place) or a buffer that does not overlap its `bytes` bytes: null = fine
+const char *check_state_out(const float *state_in, const float *state_out, size_t bytes);
+// Makes device_id the calling thread's device unless it is already: hipSuccess, or hipSetDevice's error.
+hipError_t select_device(int device_id);
+// The forward calls' device rule (device_id must exist) and their launch result: SSD_OK, or the code with the error text set.
+int policy_use_device(int device_id);
+int policy_launched(hipError_t e);
 
 }  // namespace ssd

@@ -10,21 +10,21 @@
 //   then one pass per distinct agent id in the tile (envs reset together stay in lock step, so normally one pass; masked
 //   resets mix ids, and a pass keeps its results for the rows of its id only):
 //   2. dense0, dense1 on the VALU into the x columns of the [x, h] tile;
-//   3. z = [x, h] @ lstm_w on the matrix cores, v_mfma_f32_16x16x4_f32 (exact f32: a k-ordered fmaf chain per accumulator):
-//      wave w takes cells 16w .. 16w + 15 of all four gates, so a lane holds the four gates of its (env, cell);
-//   4. the cell update in registers: h' and c' to the actor's row of the state (in place), h' to LDS;
-//   5. dist and value on the VALU (fmaf chains over the C cells of h');
-//   6. rollouts: one thread per env draws the action (policy_pick for the comm agents, the Gaussian rule for the action
-//      agents) and writes the clipped action where the env's step launch reads it.
+//   3. z = [x, h] @ lstm_w on the matrix cores (lstm_gates): a lane ends up with the four gates of its (env, cell);
+//   4. the cell update in registers (cell_update, the Keras cell): h' and c' to the actor's row of the state (in place), h' to
+//      LDS;
+//   5. dist and value on the VALU (head: fmaf chains over the C cells of h');
+//   6. rollouts: one thread per env draws the action (policy_pick for the comm agents, the Gaussian rule on policy_key's draws
+//      for the action agents) and writes the clipped action where the env's step launch reads it.
+// load_h (step 1), lstm_gates, cell_update and head are ssd_policy_device.hpp's, shared with the other policy kernels.
 // The state may be updated in place: a workgroup reads only rows it owns, and the h rows are in LDS before any is written.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
 #include <stdint.h>
-#include <string>
 
 #include "../../include/ssd.h"
-#include "ssd_policy.hpp"
+#include "ssd_policy_device.hpp"
 #include "ssd_ws_policy.hpp"
 
 namespace {
@@ -34,7 +34,8 @@ constexpr int kObs = SSD_WS_OBS_WIDTH;
 constexpr int kOut = SSD_WSP_OUT;
 constexpr int kM = 16;                  // envs per workgroup
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using ssd::f32x4;
+using Cell = ssd::KerasCell;             // gates i, f, c~, o, no forget bias; a state is (h, c)
 
 struct WspArgs {
     const float *w;                // num_sets weight sets of set_floats floats each
@@ -59,14 +60,12 @@ struct WspArgs {
     int32_t greedy;
 };
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
-
 template <int C>
 __global__ void __launch_bounds__(4 * C) ssd_ws_policy_kernel(WspArgs a) {
     constexpr int kThreads = 4 * C;     // C / 16 waves; >= 256
     constexpr int kK = kX + C;          // rows of lstm_w: the MFMA's K
-    constexpr int kPitch = kK + 52;     // LDS row pitch, = 4 (mod 64): lane (l15, l4) of an A load hits bank 4 l15 + l4
-    static_assert(kK % 4 == 0 && kPitch % 64 == 4 && kThreads >= kM * kX, "tile");
+    constexpr int kPitch = kK + 52;     // LDS row pitch, = 4 (mod 64)
+    static_assert(kThreads >= kM * kX, "tile");
     __shared__ float s_in[kM * kPitch];  // rows [x (16), h (C)]; h' after the gates
     __shared__ float s_obs[kM * kObs];
     __shared__ float s_d0[kM * kX];
@@ -95,7 +94,7 @@ __global__ void __launch_bounds__(4 * C) ssd_ws_policy_kernel(WspArgs a) {
                 st = a.starts ? a.starts[b] != 0 : 0;
             }
         }
-        s_agent[tid] = ag; s_start[tid] = st; s_ep[tid] = ep; s_t[tid] = t;
+        s_agent[tid] = ag; s_start[tid] = ag < 0 ? 1 : st; s_ep[tid] = ep; s_t[tid] = t;   // (nobody acts: nothing read)
     }
     __syncthreads();
     uint32_t present = 0u;                                       // the agent ids of this tile (workgroup-uniform)
@@ -107,21 +106,12 @@ __global__ void __launch_bounds__(4 * C) ssd_ws_policy_kernel(WspArgs a) {
         const int m = q / kObs;
         s_obs[q] = s_agent[m] >= 0 ? a.obs[(size_t)(b0 + m) * kObs + (q - m * kObs)] : 0.f;
     }
-    for (int q = tid; q < kM * C; q += kThreads) {
-        const int m = q / C, u = q - m * C, b = b0 + m, ag = s_agent[m];
-        const bool live = ag >= 0 && !s_start[m];
-        const size_t r = ((size_t)b * NA + (NA > 1 ? ag : 0)) * 2 * C;
-        const float h = live ? a.state_in[r + u] : 0.f;
-        s_in[m * kPitch + kX + u] = h;
-        if (a.state_used && b < B) {
-            a.state_used[(size_t)b * 2 * C + u] = h;
-            a.state_used[(size_t)b * 2 * C + C + u] = live ? a.state_in[r + C + u] : 0.f;
-        }
-    }
+    ssd::load_h<Cell, C, kM>(
+        s_in + kX, kPitch, s_start, a.state_in, a.state_used, tid,
+        [=](int m) { return ssd::StateRow{true, ((size_t)(b0 + m) * NA + (NA > 1 ? s_agent[m] : 0)) * 2 * C}; },
+        [=](int m) { return ssd::StateRow{b0 + m < B, (size_t)(b0 + m) * 2 * C}; });
     if (tid < kM * 8) s_out[tid] = 0.f;                          // rows nobody acts in report zeros
 
-    const int wave = tid >> 6, lane = tid & 63, l15 = lane & 15, l4 = lane >> 4;
-    const int u = 16 * wave + l15;                               // this lane's cell
     while (present) {
         const int g = __ffs(present) - 1;
         present &= present - 1u;
@@ -145,60 +135,21 @@ __global__ void __launch_bounds__(4 * C) ssd_ws_policy_kernel(WspArgs a) {
         }
         __syncthreads();
 
-        // ---- 3. the gates on the matrix cores: A[m][k] = s_in row m, B[k][n] = lstm_w[k][gate C + 16 wave + n] ----
-        // v_mfma_f32_16x16x4_f32: lane l holds A[l & 15][k = l >> 4] and B[k = l >> 4][l & 15]; D: col l & 15, row 4 (l >> 4) + r
-        const float *a_row = s_in + l15 * kPitch + l4;
-        const float *wg = w + SSD_WSP_LSTM_W + (size_t)l4 * 4 * C + u;
-        f32x4 acc[4];
-#pragma unroll
-        for (int gt = 0; gt < 4; ++gt) acc[gt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 2
-        for (int kk = 0; kk < kK / 4; ++kk) {
-            const float *wk = wg + (size_t)kk * 16 * C;
-            float bv[4];
-#pragma unroll
-            for (int gt = 0; gt < 4; ++gt) bv[gt] = wk[gt * C];
-            const float av = a_row[4 * kk];
-#pragma unroll
-            for (int gt = 0; gt < 4; ++gt) acc[gt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[gt], acc[gt], 0, 0, 0);
-        }
+        // ---- 3. the gates on the matrix cores, 4. the cell update in registers, for the rows of agent g ----
+        f32x4 acc[4][1];
+        ssd::lstm_gates<C, kK, kPitch, 1>(s_in, w + SSD_WSP_LSTM_W, tid, acc);
         __syncthreads();                                         // every wave is done with the h rows of s_in
-
-        // ---- 4. the cell update: lane (l15, l4) holds the four gates of cell u for envs 4 l4 + r ----
-        {
-            const float bi = w[SSD_WSP_LSTM_B(C) + u], bf = w[SSD_WSP_LSTM_B(C) + C + u];
-            const float bg = w[SSD_WSP_LSTM_B(C) + 2 * C + u], bo = w[SSD_WSP_LSTM_B(C) + 3 * C + u];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int m = 4 * l4 + r, b = b0 + m;
-                if (s_agent[m] != g) continue;
-                const size_t row = ((size_t)b * NA + (NA > 1 ? g : 0)) * 2 * C;
-                const float c = s_start[m] ? 0.f : a.state_in[row + C + u];
-                const float zi = acc[0][r] + bi, zf = acc[1][r] + bf, zg = acc[2][r] + bg, zo = acc[3][r] + bo;
-                const float c2 = sigmoidf_(zf) * c + sigmoidf_(zi) * tanhf(zg);
-                const float h2 = sigmoidf_(zo) * tanhf(c2);
-                s_in[m * kPitch + kX + u] = h2;
-                if (a.state_out) {
-                    a.state_out[row + u] = h2;
-                    a.state_out[row + C + u] = c2;
-                }
-            }
-        }
+        ssd::cell_update<Cell, C, 1>(acc, w + SSD_WSP_LSTM_B(C), s_start, a.state_in, a.state_out, s_in + kX, kPitch, tid, [=](int m) {
+            return ssd::StateRow{s_agent[m] == g, ((size_t)(b0 + m) * NA + (NA > 1 ? g : 0)) * 2 * C};
+        });
         __syncthreads();
 
         // ---- 5. the heads on h': thread (m, j), j < 5 dist, j == 5 the value ----
         if (tid < kM * 8) {
             const int m = tid >> 3, j = tid & 7;
-            if (j <= kOut && s_agent[m] == g) {
-                const float *hw = j < kOut ? w + SSD_WSP_OUT_W(C) + j : w + SSD_WSP_VALUE_W(C);
-                const int stride = j < kOut ? kOut : 1;
-                const float *hr = s_in + m * kPitch + kX;
-                float s = 0.f;
-#pragma unroll 8
-                for (int k = 0; k < C; ++k) s = fmaf(hr[k], hw[k * stride], s);
-                s += j < kOut ? w[SSD_WSP_OUT_B(C) + j] : w[SSD_WSP_VALUE_B(C)];
-                s_out[m * 8 + j] = s;
-            }
+            if (j <= kOut && s_agent[m] == g)
+                s_out[m * 8 + j] = ssd::head<C>(s_in + m * kPitch + kX, w + SSD_WSP_OUT_W(C), w + SSD_WSP_VALUE_W(C), w + SSD_WSP_OUT_B(C),
+                                                w + SSD_WSP_VALUE_B(C), kOut, j);
         }
     }
     __syncthreads();
@@ -232,12 +183,7 @@ __global__ void __launch_bounds__(4 * C) ssd_ws_policy_kernel(WspArgs a) {
                 const float sd = expf(log_std);
                 float n = 0.f;
                 if (!a.greedy) {
-                    uint32_t key = 0x243F6A88u;
-                    key = ssd::pol_mix32(key ^ a.seed_lo);
-                    key = ssd::pol_mix32(key ^ a.seed_hi);
-                    key = ssd::pol_mix32(key ^ env);
-                    key = ssd::pol_mix32(key ^ s_ep[tid]);
-                    const uint32_t pk = ssd::pol_mix32(ssd::pol_mix32(key ^ s_t[tid]) ^ (uint32_t)SSD_S_POLICY);
+                    const uint32_t pk = ssd::policy_key(a.seed_lo, a.seed_hi, env, s_ep[tid], s_t[tid]);
                     const uint32_t d1 = ssd::pol_mix32(pk ^ (uint32_t)ag), d2 = ssd::pol_mix32(pk ^ (uint32_t)(ag + 16));
                     const float u1 = (float)((d1 >> 8) + 1u) * 0x1p-24f, u2 = (float)(d2 >> 8) * 0x1p-24f;
                     n = sqrtf(-2.f * logf(u1)) * cosf(6.2831855f * u2);
@@ -267,11 +213,11 @@ hipError_t launch(const WspArgs &a, void *stream) {
     return hipGetLastError();
 }
 
-// the argument rules both calls share; null = fine
+// the argument rules both calls share; null = fine.  (One acting agent per env and 5 outputs: check_policy_net's rules for the
+// weights and the cell; the sets follow the variant.)
 const char *check_net(const float *weights, int32_t num_sets, int32_t cell_size, int32_t variant) {
     if (!weights) return "weights are required";
-    if (reinterpret_cast<uintptr_t>(weights) & 3u) return "weights must be 4-byte aligned";
-    if (cell_size != 64 && cell_size != 128 && cell_size != 256) return "cell_size must be 64, 128 or 256";
+    if (const char *why = ssd::check_policy_net(ssd::kNetLstm, weights, 1, 1, kOut, cell_size)) return why;
     if (variant != SSD_WS_SEQ && variant != SSD_WS_SEQ_COMM) return "unknown variant";
     if (num_sets != (variant == SSD_WS_SEQ ? 4 : 8)) return "num_sets must be 4 (Seq) or 8 (SeqComm): one set per agent id";
     return nullptr;
@@ -293,27 +239,13 @@ int ssd_ws_policy_forward(const float *weights, int32_t num_sets, int32_t cell_s
         return policy_fail("float buffers must be 4-byte aligned");
     if (batch < 1) return policy_fail("batch must be >= 1");
     if (flags) return policy_fail("flags must be 0");
-    const size_t sb = (size_t)batch * 2 * cell_size * sizeof(float);
-    if (state_out && state_out != state_in) {
-        const char *p = reinterpret_cast<const char *>(state_in), *q = reinterpret_cast<const char *>(state_out);
-        if (q < p + sb && p < q + sb) return policy_fail("state_out must be state_in or not overlap it");
-    }
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device_id < 0 || device_id >= count) return policy_fail("no such HIP device");
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != device_id) {
-        if (hipSetDevice(device_id) != hipSuccess) { ssd::policy_set_error("hipSetDevice failed"); return SSD_E_DEVICE; }
-    }
+    if (const char *why = ssd::check_state_out(state_in, state_out, (size_t)batch * 2 * cell_size * sizeof(float))) return policy_fail(why);
+    if (const int rc = ssd::policy_use_device(device_id)) return rc;
     WspArgs a{};
     a.w = weights; a.num_sets = num_sets; a.B = batch; a.C = cell_size; a.set_floats = SSD_WSP_SET_FLOATS(cell_size);
     a.variant = variant; a.NA = 1; a.obs = obs; a.agent = agent; a.state_in = state_in; a.state_out = state_out; a.starts = starts;
     a.dist = dist; a.value = value;
-    const hipError_t e = launch(a, stream);
-    if (e != hipSuccess) {
-        ssd::policy_set_error((std::string("policy launch: ") + hipGetErrorString(e)).c_str());
-        return SSD_E_DEVICE;
-    }
-    return SSD_OK;
+    return ssd::policy_launched(launch(a, stream));
 }
 
 int ssd_ws_rollout_policy(ssd_ws_env *env, const float *weights, int32_t num_sets, int32_t cell_size, const float *obs_in,
