@@ -61,6 +61,7 @@ class VecEngine(object):
         # horizon.
         self.steps_since_full_reset = None
         self._torch_dev = None
+        self._scratch_bufs = {}                      # _scratch(): key -> (the buffer, its view of the shape last asked for)
         if L.ssd_potential_waste_area(self._h) != self.potential_waste_area:
             raise _capi.SsdError("potential_waste_area mismatch between host and library")
 
@@ -305,6 +306,9 @@ class VecEngine(object):
         return _capi.SSD_ROLLOUT_FUSED if fused else 0
 
     # ------------------------------------------------------------------ policy in the loop (include/ssd.h, POLICY ROLLOUTS)
+    # What differs between the policies is read from the policy's class attributes (policy.PolicyBase): STATE_ROWS (0: no
+    # state), TAKES_PREV_ACTIONS (the MOA's previous joint action, influence and clip), C_FORWARD / C_ROLLOUT (the library's
+    # entry points) and scratch_shape().
     def _policy_weights(self, policy):
         """Checks a ConvFCPolicy, ConvLSTMPolicy or ConvMOAPolicy against this engine (everything before anything is enqueued);
         returns its weight-set count."""
@@ -312,7 +316,7 @@ class VecEngine(object):
         torch, dev = self._torch()
         if not isinstance(policy, (ConvFCPolicy, ConvLSTMPolicy, ConvMOAPolicy)):
             raise ValueError("policy must be a ConvFCPolicy, a ConvLSTMPolicy or a ConvMOAPolicy")
-        if isinstance(policy, ConvMOAPolicy) and policy.num_agents != self.N:
+        if policy.TAKES_PREV_ACTIONS and policy.num_agents != self.N:
             raise ValueError("the MOA policy is built for %d agents, the engine has %d" % (policy.num_agents, self.N))
         if self.V != _capi.SSD_POL_VIEW:
             raise ValueError("the policy network takes 15 x 15 views (view_len 7); this engine has V = %d" % self.V)
@@ -326,25 +330,18 @@ class VecEngine(object):
             raise ValueError("a policy needs at least one agent")
         return policy.num_sets
 
-    @staticmethod
-    def _is_recurrent(policy):
-        from .policy import ConvLSTMPolicy
-        return isinstance(policy, ConvLSTMPolicy)
-
-    @staticmethod
-    def _is_moa(policy):
-        from .policy import ConvMOAPolicy
-        return isinstance(policy, ConvMOAPolicy)
-
-    def _moa_scratch(self, rows):
-        """The engine's scratch of the MOA policy's calls: SSD_MOA_SCRATCH_FLOATS(rows) floats, reused between calls."""
-        torch, dev = self._torch()
-        n = _capi.SSD_MOA_SCRATCH_FLOATS(rows)
-        buf = getattr(self, "_moa_buf", None)
-        if buf is None or buf.numel() < n:
-            buf = torch.empty(n, dtype=torch.float32, device=dev)
-            self._moa_buf = buf
-        return buf
+    def _scratch(self, key, shape, dtype):
+        """The engine's buffer `key` as a tensor of `shape`: kept between calls, allocated anew only to grow.  "policy" is the
+        scratch of a recurrent policy's calls (policy.scratch_shape), "actions" the action ring a rollout was not given."""
+        flat, t = self._scratch_bufs.get(key, (None, None))
+        if t is None or tuple(t.shape) != shape:
+            torch, dev = self._torch()
+            n = int(np.prod(shape))
+            if flat is None or flat.numel() < n:
+                flat = torch.empty(n, dtype=dtype, device=dev)
+            t = flat[:n].view(shape)
+            self._scratch_bufs[key] = (flat, t)
+        return t
 
     def _check_actions_like(self, t, shape, name):
         torch, dev = self._torch()
@@ -352,42 +349,29 @@ class VecEngine(object):
             raise ValueError("%s must be an int32 tensor of shape %s" % (name, tuple(shape)))
         self._check_tensor(t, tuple(shape), torch.int32, name)
 
-    def _policy_forward_moa(self, policy, obs, lead, B, state, starts, prev_actions, actions, influence_clip):
+    def _check_state(self, state, shape, who, shown):
+        """The state a call of a policy with one needs: a float32 tensor of `shape` on the engine's device."""
         torch, dev = self._torch()
-        N, A, C = self.N, self.num_actions, policy.cell_size
         if not isinstance(state, torch.Tensor):
-            raise ValueError("a ConvMOAPolicy needs state: a float32 tensor %s" % ((lead + (4, C)),))
-        self._check_tensor(state, lead + (4, C), torch.float32, "state")
-        self._check_actions_like(prev_actions, lead, "prev_actions")
-        if actions is not None:
-            self._check_actions_like(actions, lead, "actions")
-        if starts is not None:
-            if not isinstance(starts, torch.Tensor) or starts.dtype not in (torch.bool, torch.uint8):
-                raise ValueError("starts must be a bool or uint8 tensor of shape %s" % (lead,))
-            self._check_tensor(starts, lead, starts.dtype, "starts")
-            starts = starts.view(torch.uint8)
+            raise ValueError("%s needs state: a float32 tensor %s" % (who, shown))
+        self._check_tensor(state, shape, torch.float32, "state")
+
+    def _check_starts(self, starts, lead):
+        """starts bool / uint8 of shape lead, or None -> the uint8 tensor the library reads, or None."""
+        torch, dev = self._torch()
+        if starts is None:
+            return None
+        if not isinstance(starts, torch.Tensor) or starts.dtype not in (torch.bool, torch.uint8):
+            raise ValueError("starts must be a bool or uint8 tensor of shape %s" % (lead,))
+        self._check_tensor(starts, lead, starts.dtype, "starts")
+        return starts.view(torch.uint8)
+
+    @staticmethod
+    def _check_clip(influence_clip):
         clip = float(influence_clip)
         if not (0.0 <= clip < float("inf")):
             raise ValueError("influence_clip must be finite and >= 0")
-        e = lambda shape: torch.empty(lead + shape, dtype=torch.float32, device=dev)   # noqa: E731
-        logits, value, moa, cf, new_state = e((A,)), e(()), e((N - 1, A)), e((A, N - 1, A)), torch.empty_like(state)
-        infl = e(()) if actions is not None else None
-        w = policy.packed()
-        dp = self._dp
-        _capi.policy_check(self._L.ssd_policy_moa_forward(dp(w), policy.num_sets, A, C, dp(obs), dp(prev_actions), dp(state),
-                                                          dp(starts), B, N, dp(self._moa_scratch(B * N)), dp(new_state),
-                                                          dp(logits), dp(value), dp(moa), dp(cf), dp(actions), dp(infl), clip,
-                                                          self.device, 0, self._stream()))
-        return logits, value, moa, cf, new_state, infl
-
-    def _features(self, rows):
-        """The engine's trunk-feature scratch of the recurrent policy: f32 [rows, 32], reused between calls."""
-        torch, dev = self._torch()
-        buf = getattr(self, "_feat_buf", None)
-        if buf is None or buf.shape[0] < rows:
-            buf = torch.empty((rows, _capi.SSD_LSTM_X), dtype=torch.float32, device=dev)
-            self._feat_buf = buf
-        return buf
+        return clip
 
     def policy_forward(self, policy, obs, state=None, starts=None, prev_actions=None, actions=None, influence_clip=10.0):
         """The policy's forward pass on the device (ssd_policy_forward): obs uint8 [..., N, 15, 15, 3] -> (logits float32
@@ -407,37 +391,41 @@ class VecEngine(object):
         if B < 1:
             raise ValueError("obs holds no observation")
         lead = tuple(obs.shape[:-3])
-        if self._is_moa(policy):
-            return self._policy_forward_moa(policy, obs, lead, B, state, starts, prev_actions, actions, influence_clip)
-        if prev_actions is not None or actions is not None:
+        rows, moa = policy.STATE_ROWS, policy.TAKES_PREV_ACTIONS
+        if not moa and (prev_actions is not None or actions is not None):
             raise ValueError("prev_actions and actions belong to a ConvMOAPolicy")
-        recurrent = self._is_recurrent(policy)
-        if not recurrent:
+        if not rows:
             if state is not None or starts is not None:
                 raise ValueError("state and starts belong to a ConvLSTMPolicy; a ConvFCPolicy has no state")
         else:
             C = policy.cell_size
-            if not isinstance(state, torch.Tensor):
-                raise ValueError("a ConvLSTMPolicy needs state: a float32 tensor %s" % ((lead + (2, C)),))
-            self._check_tensor(state, lead + (2, C), torch.float32, "state")
-            if starts is not None:
-                if not isinstance(starts, torch.Tensor) or starts.dtype not in (torch.bool, torch.uint8):
-                    raise ValueError("starts must be a bool or uint8 tensor of shape %s" % (lead,))
-                self._check_tensor(starts, lead, starts.dtype, "starts")
-                starts = starts.view(torch.uint8)
-        logits = torch.empty(lead + (A,), dtype=torch.float32, device=dev)
-        value = torch.empty(lead, dtype=torch.float32, device=dev)
+            self._check_state(state, lead + (rows, C), "a " + type(policy).__name__, lead + (rows, C))
+        if moa:
+            self._check_actions_like(prev_actions, lead, "prev_actions")
+            if actions is not None:
+                self._check_actions_like(actions, lead, "actions")
+        starts = self._check_starts(starts, lead)
+        clip = self._check_clip(influence_clip) if moa else None
+        e = lambda shape: torch.empty(lead + shape, dtype=torch.float32, device=dev)   # noqa: E731
+        dp = self._dp
+        logits, value = e((A,)), e(())
+        # the entry points take (weights, P, A[, C], obs[, prev_actions][, state, starts], B, N[, scratch, new state], logits,
+        # value[, moa_logits, cf_logits, actions, influence, clip], device, flags, stream)
+        out, net, inp, res, extra = (logits, value), [], [], [], []
+        if rows:
+            new_state = torch.empty_like(state)
+            scratch = self._scratch("policy", policy.scratch_shape(B * N), torch.float32)
+            net, inp, res = [C], [dp(state), dp(starts)], [dp(scratch), dp(new_state)]
+            out += (new_state,)
+        if moa:
+            pred, cf, infl = e((N - 1, A)), e((A, N - 1, A)), e(()) if actions is not None else None
+            inp.insert(0, dp(prev_actions))
+            extra = [dp(pred), dp(cf), dp(actions), dp(infl), clip]
+            out = (logits, value, pred, cf, new_state, infl)
         w = policy.packed()
-        if not recurrent:
-            _capi.policy_check(self._L.ssd_policy_forward(self._dp(w), P, A, self._dp(obs), B, N, self._dp(logits), self._dp(value),
-                                                          self.device, 0, self._stream()))
-            return logits, value
-        new_state = torch.empty_like(state)
-        feat = self._features(B * N)
-        _capi.policy_check(self._L.ssd_policy_lstm_forward(self._dp(w), P, A, C, self._dp(obs), self._dp(state), self._dp(starts), B, N,
-                                                           self._dp(feat), self._dp(new_state), self._dp(logits), self._dp(value),
-                                                           self.device, 0, self._stream()))
-        return logits, value, new_state
+        _capi.policy_check(getattr(self._L, policy.C_FORWARD)(dp(w), P, A, *net, dp(obs), *inp, B, N, *res, dp(logits), dp(value),
+                                                               *extra, self.device, 0, self._stream()))
+        return out
 
     def rollout_policy(self, policy, obs_in, n_steps, obs, actions=None, logp=None, value=None, logits=None, rew=None, done=None,
                        last_value=None, step0=0, greedy=False, stats=None, state=None, state_ring=None, state_every=1,
@@ -459,9 +447,7 @@ class VecEngine(object):
         clipped to influence_clip)."""
         torch, dev = self._torch()
         P = self._policy_weights(policy)
-        moa = self._is_moa(policy)
-        recurrent = self._is_recurrent(policy) or moa
-        SR = 4 if moa else 2
+        SR, moa = policy.STATE_ROWS, policy.TAKES_PREV_ACTIONS
         n_steps, step0 = int(n_steps), int(step0)
         if n_steps < 1:
             raise ValueError("n_steps must be >= 1")
@@ -491,14 +477,12 @@ class VecEngine(object):
             self._check_stats(stats, rew, n_steps)
             if done is None:
                 raise ValueError("stats need the call's done flags: pass done")
-        if not recurrent:
+        if not SR:
             if state is not None or state_ring is not None:
                 raise ValueError("state and state_ring belong to a ConvLSTMPolicy; a ConvFCPolicy has no state")
         else:
             C = policy.cell_size
-            if not isinstance(state, torch.Tensor):
-                raise ValueError("a recurrent policy needs state: a float32 tensor [%d,%d,%d,%d]" % (E, N, SR, C))
-            self._check_tensor(state, (E, N, SR, C), torch.float32, "state")
+            self._check_state(state, (E, N, SR, C), "a recurrent policy", "[%d,%d,%d,%d]" % (E, N, SR, C))
             state_every = int(state_every)
             S = 0
             if state_ring is not None:
@@ -520,34 +504,24 @@ class VecEngine(object):
                 if not isinstance(influence, torch.Tensor):
                     raise ValueError("influence must be a float32 ring [R,%d,%d]" % (E, N))
                 self._check_tensor(influence, (R, E, N), torch.float32, "influence")
-            clip = float(influence_clip)
-            if not (0.0 <= clip < float("inf")):
-                raise ValueError("influence_clip must be finite and >= 0")
+            clip = self._check_clip(influence_clip)
         elif prev_actions is not None or prev_actions_ring is not None or influence is not None:
             raise ValueError("prev_actions, prev_actions_ring and influence belong to a ConvMOAPolicy")
         if actions is None:
-            buf = getattr(self, "_policy_actions", None)
-            if buf is None or tuple(buf.shape) != (R, E, N):
-                buf = torch.empty((R, E, N), dtype=torch.int32, device=dev)
-                self._policy_actions = buf
-            actions = buf
+            actions = self._scratch("actions", (R, E, N), torch.int32)
         w = policy.packed()
         dp = self._dp
-        if moa:
-            rc = self._L.ssd_rollout_policy_moa(self._h, dp(w), P, C, dp(obs_in), n_steps, step0, dp(state), dp(state_ring), S,
-                                                state_every, dp(prev_actions), dp(prev_actions_ring), dp(influence), clip,
-                                                dp(self._moa_scratch(E * N)), dp(obs), dp(actions), dp(logp), dp(value),
-                                                dp(logits), dp(rew), dp(done), R, dp(last_value),
-                                                _capi.SSD_POLICY_GREEDY if greedy else 0, self._stream())
-        elif recurrent:
-            rc = self._L.ssd_rollout_policy_lstm(self._h, dp(w), P, C, dp(obs_in), n_steps, step0, dp(state), dp(state_ring), S,
-                                                 state_every, dp(self._features(E * N)), dp(obs), dp(actions), dp(logp), dp(value),
-                                                 dp(logits), dp(rew), dp(done), R, dp(last_value),
-                                                 _capi.SSD_POLICY_GREEDY if greedy else 0, self._stream())
-        else:
-            rc = self._L.ssd_rollout_policy(self._h, dp(w), P, dp(obs_in), n_steps, step0, dp(obs), dp(actions), dp(logp), dp(value),
-                                            dp(logits), dp(rew), dp(done), R, dp(last_value),
-                                            _capi.SSD_POLICY_GREEDY if greedy else 0, self._stream())
+        # (handle, weights, P[, C], obs_in, n_steps, step0[, the state's arguments][, the MOA's][, scratch]), then what every
+        # policy's rollout ends in
+        head = [self._h, dp(w), P, dp(obs_in), n_steps, step0]
+        if SR:
+            head.insert(3, C)
+            head += [dp(state), dp(state_ring), S, state_every]
+            if moa:
+                head += [dp(prev_actions), dp(prev_actions_ring), dp(influence), clip]
+            head.append(dp(self._scratch("policy", policy.scratch_shape(E * N), torch.float32)))
+        rc = getattr(self._L, policy.C_ROLLOUT)(*head, dp(obs), dp(actions), dp(logp), dp(value), dp(logits), dp(rew), dp(done), R,
+                                                dp(last_value), _capi.SSD_POLICY_GREEDY if greedy else 0, self._stream())
         if rc:
             _capi.check(rc, self._h)
         self._count_auto_steps(n_steps)

@@ -2,7 +2,9 @@
 as a torch module whose weights the device kernels read (include/ssd.h, SSD_POL_*; csrc/ssd_policy.hip), ConvLSTMPolicy, the
 same trunk under RLlib's LSTM (SSD_LSTM_*; csrc/ssd_policy_lstm.hip), and ConvMOAPolicy, the causal-influence policy of
 train_moa.py with its social-influence reward, influence() (SSD_MOA_*; csrc/ssd_policy_moa.hip).  WatershedLSTMPolicy, at the
-end of the file, is the LSTM-FC network of the Watershed launchers (SSD_WSP_*; csrc/ssd_ws_policy.hip).
+end of the file, is the LSTM-FC network of the Watershed launchers (SSD_WSP_*; csrc/ssd_ws_policy.hip).  All four are built on
+PolicyBase (parameters from layout(), load_arrays(), packed(), initial_state(), and what an engine asks of a policy) and on
+the forward pieces that follow it.
 
     policy = ConvFCPolicy(num_actions=8, num_sets=5).cuda()       # one weight set per agent, as train_baseline.py:87-96
     logits, value = policy(obs_u8)                                # [..., N, 15, 15, 3] -> [..., N, A], [..., N]
@@ -37,36 +39,57 @@ def normc(shape, std, generator):
     return out * (std / out.square().sum(dim=-2, keepdim=True).sqrt())
 
 
-class ConvFCPolicy(torch.nn.Module):
-    """num_sets P independent weight sets: P = 1 is one policy shared by every agent, P = N one per agent (agent i uses
-    set i).  Input: uint8 observations [..., 15, 15, 3] (P = 1) or [..., P, 15, 15, 3], normalised as float((u8 - 128) / 255)
-    (the reference observation, map_env.py:199).  Output: (logits [..., A], value [...])."""
+def _glorot(shape, fan_in, fan_out, generator):
+    """Glorot uniform: the default kernel initializer of slim.conv2d, of TF's LSTMCell and of Keras' layers."""
+    limit = float(np.sqrt(6.0 / (fan_in + fan_out)))
+    return (torch.rand(shape, generator=generator, dtype=torch.float64) * 2 - 1) * limit
 
-    def __init__(self, num_actions, num_sets=1, seed=0):
-        super().__init__()
-        A, P = int(num_actions), int(num_sets)
-        if not 1 <= A <= _capi.SSD_POL_MAX_ACTIONS:
+
+def _orthogonal(P, rows, cols, generator):
+    """Keras' Orthogonal initializer for [rows, cols] kernels (rows <= cols), one per weight set."""
+    out = torch.empty((P, rows, cols), dtype=torch.float64)
+    for p in range(P):
+        q, r = torch.linalg.qr(torch.randn((cols, rows), generator=generator, dtype=torch.float64))
+        out[p] = (q * torch.sign(torch.diagonal(r))).T
+    return out
+
+
+class PolicyBase(torch.nn.Module):
+    """What the four policy modules share.  A subclass sets num_sets (and cell_size, if it has a state), defines layout() and
+    set_floats, and registers its parameters with _register().  The class attributes are what an engine asks of a policy to
+    run it on the device."""
+    STATE_ROWS = 0                  # a state is [..., STATE_ROWS, cell_size]; 0: the policy has none
+    TAKES_PREV_ACTIONS = False      # the network reads the previous joint action (and gives the influence reward)
+    REF_PARAM = "conv_w"            # the parameter whose dtype and device stand for the module's
+    C_FORWARD = C_ROLLOUT = None    # the library's forward and rollout entry points of this network (include/ssd.h)
+
+    @staticmethod
+    def _check_ranges(num_actions=None, num_sets=None, cell_size=None):
+        if num_actions is not None and not 1 <= num_actions <= _capi.SSD_POL_MAX_ACTIONS:
             raise ValueError("num_actions must be 1..%d" % _capi.SSD_POL_MAX_ACTIONS)
-        if not 1 <= P <= 64:
+        if num_sets is not None and not 1 <= num_sets <= 64:
             raise ValueError("num_sets must be 1..64")
-        self.num_actions, self.num_sets = A, P
-        g = torch.Generator().manual_seed(int(seed))
-        limit = float(np.sqrt(6.0 / (27 + 9 * FILTERS)))        # slim.conv2d's default initializer: Glorot uniform
-        init = {"conv_w": (torch.rand((P, 3, 3, 3, FILTERS), generator=g, dtype=torch.float64) * 2 - 1) * limit,
-                "fc1_w": normc((P, FLAT, HIDDEN), 1.0, g), "fc2_w": normc((P, HIDDEN, HIDDEN), 1.0, g),
-                "value_w": normc((P, HIDDEN, 1), 1.0, g), "logits_w": normc((P, HIDDEN, A), 0.01, g)}
+        if cell_size is not None and cell_size not in _capi.LSTM_CELL_SIZES:
+            raise ValueError("cell_size must be one of %s" % (_capi.LSTM_CELL_SIZES,))
+
+    def _register(self, init):
+        """Registers every parameter of layout(), in its order, from init {name: float64 [entries, *shape of one set]}; one
+        that init does not name (a bias) starts at zero."""
         for name, shape, _ in self.layout():
             t = init.get(name)
             if t is None:
-                t = torch.zeros((P,) + shape, dtype=torch.float64)       # biases start at zero
+                t = torch.zeros((self._entries(name),) + shape, dtype=torch.float64)
             self.register_parameter(name, torch.nn.Parameter(t.to(torch.float32)))
         self._packed = None
         self._tables = {}
 
-    def layout(self):
-        """(name, shape of one set, float offset within a packed set) of every parameter, in packed order."""
-        A = self.num_actions
-        return _FIXED + (("logits_w", (HIDDEN, A), _capi.SSD_POL_LOGITS_W), ("logits_b", (A,), _capi.SSD_POL_LOGITS_B(A)))
+    def _entries(self, name):
+        """The length of parameter `name`'s leading axis: num_sets, or fewer where several sets share one layer."""
+        return self.num_sets
+
+    def scratch_shape(self, rows):
+        """The float32 scratch the library's calls need for `rows` (env, agent) rows, or None."""
+        return None
 
     def load_arrays(self, weights):
         """Set the parameters from a dict of arrays {name: [P, *shape of one set]} in the layouts above (a TF checkpoint's
@@ -80,31 +103,75 @@ class ConvFCPolicy(torch.nn.Module):
                 dst.copy_(src.to(dst.dtype))
         return self
 
-    @property
-    def set_floats(self):
-        return _capi.SSD_POL_SET_FLOATS(self.num_actions)
-
     def packed(self):
         """All weight sets as ONE contiguous float32 tensor on the parameters' device, in the layout of include/ssd.h: set p
-        at p * SSD_POL_SET_FLOATS(A).  Rebuilt from the parameters on every call by device copies on the current stream (no
-        host synchronisation), so an optimiser's update takes effect on the next call.  The buffer is reused between calls."""
+        at p * set_floats.  A parameter with fewer entries than sets is repeated into them (entry k serves sets k, k +
+        entries, ...).  Rebuilt from the parameters on every call by device copies on the current stream (no host
+        synchronisation), so an optimiser's update takes effect on the next call.  The buffer is reused between calls."""
         P, S = self.num_sets, self.set_floats
-        dev = self.conv_w.device
+        dev = getattr(self, self.REF_PARAM).device
         if self._packed is None or self._packed.device != dev:
             self._packed = torch.zeros(P * S, dtype=torch.float32, device=dev)
         v = self._packed.view(P, S)
         with torch.no_grad():
             for name, shape, off in self.layout():
                 n = int(np.prod(shape))
-                v[:, off:off + n].copy_(getattr(self, name).reshape(P, n))
+                t = getattr(self, name).reshape(-1, n)
+                if t.shape[0] != P:
+                    t = t.repeat(P // t.shape[0], 1)
+                v[:, off:off + n].copy_(t)
         return self._packed
 
-    def forward(self, obs):
-        P, A = self.num_sets, self.num_actions
-        h, lead = _trunk(self, obs)
-        logits = torch.einsum("mpk,pkj->mpj", h, self.logits_w) + self.logits_b
-        value = (torch.einsum("mpk,pkj->mpj", h, self.value_w) + self.value_b)[..., 0]
-        return logits.reshape(lead + (A,)), value.reshape(lead)
+    def initial_state(self, lead, device=None):
+        """A zero state [*lead, STATE_ROWS, C] (the parameters' dtype, on their device unless given)."""
+        lead = (int(lead),) if isinstance(lead, int) else tuple(int(n) for n in lead)
+        ref = getattr(self, self.REF_PARAM)
+        return torch.zeros(lead + (self.STATE_ROWS, self.cell_size), dtype=ref.dtype, device=ref.device if device is None else device)
+
+
+# ---- the forward pieces the policies share ----
+
+def _dense(h, w, b):
+    """Per weight set p: h [M, P, K] @ w [P, K, J] + b [P, J]."""
+    return torch.einsum("mpk,pkj->mpj", h, w) + b
+
+
+def _heads(h, logits_w, logits_b, value_w, value_b):
+    """(logits [M, P, A], value [M, P]) on h [M, P, K]."""
+    return _dense(h, logits_w, logits_b), _dense(h, value_w, value_b)[..., 0]
+
+
+def _conv_flat(module, obs, G, conv_w, conv_b):
+    """uint8 observations [..., G, 15, 15, 3] (any leading shape of M x G rows) -> the conv layer's output [M, G, 1014]:
+    float((u8 - 128) / 255) from a table, the G weight sets conv_w [G, 3, 3, 3, 6] / conv_b [G, 6] as conv groups, ReLU, and
+    TF's flatten of NHWC."""
+    dt = module.conv_w.dtype
+    key = (obs.device, dt)
+    if key not in module._tables:                                # float((u8 - 128) / 255), from the float64 values
+        module._tables[key] = torch.from_numpy(_NORMALISE).to(dt).to(obs.device)
+    x = module._tables[key][obs.long()].reshape(-1, G, VIEW, VIEW, 3)
+    M = x.shape[0]
+    x = x.permute(0, 1, 4, 2, 3).reshape(M, G * 3, VIEW, VIEW)    # NHWC -> NCHW, the sets as conv groups
+    wc = conv_w.permute(0, 4, 3, 1, 2).reshape(G * FILTERS, 3, 3, 3)
+    h = torch.relu(torch.nn.functional.conv2d(x, wc, conv_b.reshape(G * FILTERS), groups=G))
+    return h.reshape(M, G, FILTERS, 13, 13).permute(0, 1, 3, 4, 2).reshape(M, G, FLAT)   # flatten (row, col, channel)
+
+
+def _zero_where(starts, t, tail):
+    """The start rule: t with the rows where starts (t's shape less its last `tail` axes) is true replaced by zero --
+    selected, not multiplied: whatever t holds there is never used."""
+    m = starts.to(torch.bool).reshape(t.shape[:t.dim() - tail] + (1,) * tail).to(t.device)
+    return torch.where(m, torch.zeros((), dtype=t.dtype, device=t.device), t)
+
+
+def _unroll(step, T, state, resets):
+    """step(t, state, resets[t] or None) -> (outputs..., new state) for t = 0 .. T - 1; returns the outputs stacked over t and
+    the final state."""
+    rows = []
+    for t in range(T):
+        *out, state = step(t, state, None if resets is None else resets[t])
+        rows.append(out)
+    return tuple(torch.stack(col) for col in zip(*rows)) + (state,)
 
 
 def _trunk(module, obs):
@@ -115,24 +182,43 @@ def _trunk(module, obs):
         raise ValueError("observations must end in (15, 15, 3), got %s" % (tuple(obs.shape),))
     if P > 1 and (obs.dim() < 4 or obs.shape[-4] != P):
         raise ValueError("with %d weight sets the observations need an agent axis of %d: [..., %d, 15, 15, 3]" % (P, P, P))
-    lead = obs.shape[:-3]
-    dt = module.conv_w.dtype
-    key = (obs.device, dt)
-    if key not in module._tables:                                # float((u8 - 128) / 255), from the float64 values
-        module._tables[key] = torch.from_numpy(_NORMALISE).to(dt).to(obs.device)
-    x = module._tables[key][obs.long()]
-    x = x.reshape(-1, P, VIEW, VIEW, 3)
-    M = x.shape[0]
-    x = x.permute(0, 1, 4, 2, 3).reshape(M, P * 3, VIEW, VIEW)    # NHWC -> NCHW, the sets as conv groups
-    wc = module.conv_w.permute(0, 4, 3, 1, 2).reshape(P * FILTERS, 3, 3, 3)
-    h = torch.relu(torch.nn.functional.conv2d(x, wc, module.conv_b.reshape(P * FILTERS), groups=P))
-    h = h.reshape(M, P, FILTERS, 13, 13).permute(0, 1, 3, 4, 2).reshape(M, P, FLAT)   # flatten (row, col, channel)
-    h = torch.relu(torch.einsum("mpk,pkj->mpj", h, module.fc1_w) + module.fc1_b)
-    h = torch.relu(torch.einsum("mpk,pkj->mpj", h, module.fc2_w) + module.fc2_b)
-    return h, lead
+    h = _conv_flat(module, obs, P, module.conv_w, module.conv_b)
+    h = torch.relu(_dense(h, module.fc1_w, module.fc1_b))
+    return torch.relu(_dense(h, module.fc2_w, module.fc2_b)), obs.shape[:-3]
 
 
-class ConvLSTMPolicy(torch.nn.Module):
+class ConvFCPolicy(PolicyBase):
+    """num_sets P independent weight sets: P = 1 is one policy shared by every agent, P = N one per agent (agent i uses
+    set i).  Input: uint8 observations [..., 15, 15, 3] (P = 1) or [..., P, 15, 15, 3], normalised as float((u8 - 128) / 255)
+    (the reference observation, map_env.py:199).  Output: (logits [..., A], value [...])."""
+    C_FORWARD, C_ROLLOUT = "ssd_policy_forward", "ssd_rollout_policy"
+
+    def __init__(self, num_actions, num_sets=1, seed=0):
+        super().__init__()
+        A, P = int(num_actions), int(num_sets)
+        self._check_ranges(A, P)
+        self.num_actions, self.num_sets = A, P
+        g = torch.Generator().manual_seed(int(seed))
+        self._register({"conv_w": _glorot((P, 3, 3, 3, FILTERS), 27, 9 * FILTERS, g),
+                        "fc1_w": normc((P, FLAT, HIDDEN), 1.0, g), "fc2_w": normc((P, HIDDEN, HIDDEN), 1.0, g),
+                        "value_w": normc((P, HIDDEN, 1), 1.0, g), "logits_w": normc((P, HIDDEN, A), 0.01, g)})
+
+    def layout(self):
+        """(name, shape of one set, float offset within a packed set) of every parameter, in packed order."""
+        A = self.num_actions
+        return _FIXED + (("logits_w", (HIDDEN, A), _capi.SSD_POL_LOGITS_W), ("logits_b", (A,), _capi.SSD_POL_LOGITS_B(A)))
+
+    @property
+    def set_floats(self):
+        return _capi.SSD_POL_SET_FLOATS(self.num_actions)
+
+    def forward(self, obs):
+        h, lead = _trunk(self, obs)
+        logits, value = _heads(h, self.logits_w, self.logits_b, self.value_w, self.value_b)
+        return logits.reshape(lead + (self.num_actions,)), value.reshape(lead)
+
+
+class ConvLSTMPolicy(PolicyBase):
     """The baseline's recurrent policy (run_scripts/train_baseline.py:146-147, "use_lstm": True): the trunk of ConvFCPolicy
     (conv, fc1, fc2) and RLlib 0.7.6's LSTM of cell_size C cells on fc2's output, with the logits and the value on the LSTM's
     output h' (include/ssd.h, RECURRENT POLICY ROLLOUTS).  The cell is TF's LSTMCell: z = [x, h] @ lstm_w + lstm_b split into
@@ -145,31 +231,19 @@ class ConvLSTMPolicy(torch.nn.Module):
 
     Parameters in TF's layouts with a leading weight-set axis: the trunk's, lstm_w [P, 32 + C, 4C], lstm_b [P, 4C], logits_w
     [P, C, A], logits_b [P, A], value_w [P, C, 1], value_b [P, 1]."""
+    STATE_ROWS = 2
+    C_FORWARD, C_ROLLOUT = "ssd_policy_lstm_forward", "ssd_rollout_policy_lstm"
 
     def __init__(self, num_actions, num_sets=1, cell_size=128, seed=0):
         super().__init__()
         A, P, C = int(num_actions), int(num_sets), int(cell_size)
-        if not 1 <= A <= _capi.SSD_POL_MAX_ACTIONS:
-            raise ValueError("num_actions must be 1..%d" % _capi.SSD_POL_MAX_ACTIONS)
-        if not 1 <= P <= 64:
-            raise ValueError("num_sets must be 1..64")
-        if C not in _capi.LSTM_CELL_SIZES:
-            raise ValueError("cell_size must be one of %s" % (_capi.LSTM_CELL_SIZES,))
+        self._check_ranges(A, P, C)
         self.num_actions, self.num_sets, self.cell_size = A, P, C
         g = torch.Generator().manual_seed(int(seed))
-        limit = float(np.sqrt(6.0 / (27 + 9 * FILTERS)))        # slim.conv2d's default initializer: Glorot uniform
-        lstm_limit = float(np.sqrt(6.0 / ((HIDDEN + C) + 4 * C)))   # TF's default kernel initializer: Glorot uniform
-        init = {"conv_w": (torch.rand((P, 3, 3, 3, FILTERS), generator=g, dtype=torch.float64) * 2 - 1) * limit,
-                "fc1_w": normc((P, FLAT, HIDDEN), 1.0, g), "fc2_w": normc((P, HIDDEN, HIDDEN), 1.0, g),
-                "lstm_w": (torch.rand((P, HIDDEN + C, 4 * C), generator=g, dtype=torch.float64) * 2 - 1) * lstm_limit,
-                "value_w": normc((P, C, 1), 1.0, g), "logits_w": normc((P, C, A), 0.01, g)}
-        for name, shape, _ in self.layout():
-            t = init.get(name)
-            if t is None:
-                t = torch.zeros((P,) + shape, dtype=torch.float64)       # biases start at zero
-            self.register_parameter(name, torch.nn.Parameter(t.to(torch.float32)))
-        self._packed = None
-        self._tables = {}
+        self._register({"conv_w": _glorot((P, 3, 3, 3, FILTERS), 27, 9 * FILTERS, g),
+                        "fc1_w": normc((P, FLAT, HIDDEN), 1.0, g), "fc2_w": normc((P, HIDDEN, HIDDEN), 1.0, g),
+                        "lstm_w": _glorot((P, HIDDEN + C, 4 * C), HIDDEN + C, 4 * C, g),
+                        "value_w": normc((P, C, 1), 1.0, g), "logits_w": normc((P, C, A), 0.01, g)})
 
     def layout(self):
         """(name, shape of one set, float offset within a packed set) of every parameter, in packed order."""
@@ -178,18 +252,13 @@ class ConvLSTMPolicy(torch.nn.Module):
                              ("value_w", (C, 1), _capi.SSD_LSTM_VALUE_W(C)), ("value_b", (1,), _capi.SSD_LSTM_VALUE_B(C)),
                              ("logits_w", (C, A), _capi.SSD_LSTM_LOGITS_W(C)), ("logits_b", (A,), _capi.SSD_LSTM_LOGITS_B(C, A)))
 
-    load_arrays = ConvFCPolicy.load_arrays
-    packed = ConvFCPolicy.packed
-
     @property
     def set_floats(self):
         return _capi.SSD_LSTM_SET_FLOATS(self.cell_size, self.num_actions)
 
-    def initial_state(self, lead, device=None):
-        """A zero state [*lead, 2, C] (float32, on the parameters' device unless given)."""
-        lead = (int(lead),) if isinstance(lead, int) else tuple(int(n) for n in lead)
-        return torch.zeros(lead + (2, self.cell_size), dtype=self.lstm_w.dtype,
-                           device=self.lstm_w.device if device is None else device)
+    def scratch_shape(self, rows):
+        """The trunk's features: f32 [rows, 32]."""
+        return (rows, _capi.SSD_LSTM_X)
 
     def forward(self, obs, state, starts=None):
         """obs u8 [..., (P,) 15, 15, 3], state [..., 2, C] (the same leading shape), starts bool [...] or None: rows whose state
@@ -204,14 +273,13 @@ class ConvLSTMPolicy(torch.nn.Module):
         if starts is not None:
             if tuple(starts.shape) != tuple(lead):
                 raise ValueError("starts must have shape %s, got %s" % (tuple(lead), tuple(starts.shape)))
-            st = torch.where(starts.to(torch.bool).reshape(M, P, 1, 1).to(st.device), torch.zeros((), dtype=st.dtype, device=st.device), st)
+            st = _zero_where(starts, st, 2)
         c, h = st[:, :, 0], st[:, :, 1]
-        z = torch.einsum("mpk,pkj->mpj", torch.cat([x, h], dim=-1), self.lstm_w) + self.lstm_b
+        z = _dense(torch.cat([x, h], dim=-1), self.lstm_w, self.lstm_b)
         zi, zj, zf, zo = z[..., :C], z[..., C:2 * C], z[..., 2 * C:3 * C], z[..., 3 * C:]
         c2 = torch.sigmoid(zf + 1.0) * c + torch.sigmoid(zi) * torch.tanh(zj)
         h2 = torch.sigmoid(zo) * torch.tanh(c2)
-        logits = torch.einsum("mpk,pkj->mpj", h2, self.logits_w) + self.logits_b
-        value = (torch.einsum("mpk,pkj->mpj", h2, self.value_w) + self.value_b)[..., 0]
+        logits, value = _heads(h2, self.logits_w, self.logits_b, self.value_w, self.value_b)
         new_state = torch.stack([c2, h2], dim=2)
         return logits.reshape(tuple(lead) + (A,)), value.reshape(lead), new_state.reshape(tuple(lead) + (2, C))
 
@@ -222,35 +290,40 @@ class ConvLSTMPolicy(torch.nn.Module):
         T = int(obs.shape[0])
         if resets is not None and int(resets.shape[0]) != T:
             raise ValueError("resets must have T = %d rows" % T)
-        logits, values = [], []
-        for t in range(T):
-            lg, v, state = self.forward(obs[t], state, None if resets is None else resets[t])
-            logits.append(lg)
-            values.append(v)
-        return torch.stack(logits), torch.stack(values), state
+        return _unroll(lambda t, st, reset: self.forward(obs[t], st, reset), T, state, resets)
+
+
+def _softmax_cdf(logits):
+    """The float32 cumulative softmax as the device accumulates it (include/ssd.h): logits [..., A] -> (logits as float32, their
+    maximum mx [...], the sum s [...] of exp(logits - mx), the cumulative probabilities cdf [..., A])."""
+    lg = np.asarray(logits, dtype=np.float32)
+    mx = lg.max(axis=-1)
+    e = np.exp(lg - mx[..., None]).astype(np.float32)
+    s = np.zeros(mx.shape, np.float32)
+    for a in range(lg.shape[-1]):
+        s = (s + e[..., a]).astype(np.float32)
+    c = np.zeros(mx.shape, np.float32)
+    cdf = np.empty(lg.shape, np.float32)
+    for a in range(lg.shape[-1]):
+        c = (c + (e[..., a] / s).astype(np.float32)).astype(np.float32)
+        cdf[..., a] = c
+    return lg, mx, s, cdf
 
 
 def sample_host(logits, u, greedy=False):
     """The rollout's action selection in NumPy float32 (include/ssd.h): logits [..., A] float32, u [...] float32 from
     prng.policy_uniforms.  Returns (actions int32, logp float32).  The device uses expf / logf, so an action may differ where
     u lies within an ulp or so of a boundary of the cumulative softmax."""
-    lg = np.asarray(logits, dtype=np.float32)
+    lg, mx, s, cdf = _softmax_cdf(logits)
     A = lg.shape[-1]
-    mx = lg.max(axis=-1)
-    e = np.exp(lg - mx[..., None]).astype(np.float32)
-    s = np.zeros(mx.shape, np.float32)
-    for a in range(A):
-        s = (s + e[..., a]).astype(np.float32)
     if greedy:
         act = lg.argmax(axis=-1).astype(np.int32)                    # the first of equal maxima
     else:
         u = np.asarray(u, dtype=np.float32)
         act = np.full(mx.shape, A - 1, np.int32)
         found = np.zeros(mx.shape, bool)
-        c = np.zeros(mx.shape, np.float32)
         for a in range(A):
-            c = (c + (e[..., a] / s).astype(np.float32)).astype(np.float32)
-            hit = ~found & (u < c)
+            hit = ~found & (u < cdf[..., a])
             act[hit] = a
             found |= hit
     la = np.take_along_axis(lg, act[..., None].astype(np.int64), axis=-1)[..., 0]
@@ -261,32 +334,11 @@ def sample_host(logits, u, greedy=False):
 def cdf_margin(logits, u):
     """Distance of u from the nearest boundary of the float32 cumulative softmax of logits (for deciding which sampled actions
     a host mirror may legitimately get differently)."""
-    lg = np.asarray(logits, dtype=np.float32)
-    mx = lg.max(axis=-1)
-    e = np.exp(lg - mx[..., None]).astype(np.float32)
-    s = np.zeros(mx.shape, np.float32)
-    for a in range(lg.shape[-1]):
-        s = (s + e[..., a]).astype(np.float32)
-    c = np.zeros(mx.shape, np.float32)
+    lg, mx, _, cdf = _softmax_cdf(logits)
     margin = np.full(mx.shape, np.inf)
     for a in range(lg.shape[-1]):
-        c = (c + (e[..., a] / s).astype(np.float32)).astype(np.float32)
-        margin = np.minimum(margin, np.abs(np.asarray(u, np.float64) - c.astype(np.float64)))
+        margin = np.minimum(margin, np.abs(np.asarray(u, np.float64) - cdf[..., a].astype(np.float64)))
     return margin
-
-
-def _glorot(shape, fan_in, fan_out, generator):
-    limit = float(np.sqrt(6.0 / (fan_in + fan_out)))
-    return (torch.rand(shape, generator=generator, dtype=torch.float64) * 2 - 1) * limit
-
-
-def _orthogonal(P, rows, cols, generator):
-    """Keras' Orthogonal initializer for [rows, cols] kernels (rows <= cols), one per weight set."""
-    out = torch.empty((P, rows, cols), dtype=torch.float64)
-    for p in range(P):
-        q, r = torch.linalg.qr(torch.randn((cols, rows), generator=generator, dtype=torch.float64))
-        out[p] = (q * torch.sign(torch.diagonal(r))).T
-    return out
 
 
 def agent_order(num_agents):
@@ -309,7 +361,7 @@ def keras_lstm(x, h, c, kernel, recurrent, bias):
     return torch.sigmoid(zo) * torch.tanh(c2), c2
 
 
-class ConvMOAPolicy(torch.nn.Module):
+class ConvMOAPolicy(PolicyBase):
     """The causal-influence policy of run_scripts/train_moa.py (MOA_LSTM, models/moa_model.py:121-311): the trunk's conv, two
     tanh FC stacks (32, 32), a Keras LSTM of cell_size C cells for the actions (logits and value on its output) and one for the
     model of other agents (MOA), whose input is the MOA stack's output and the N previous actions, own first and the others in
@@ -324,18 +376,19 @@ class ConvMOAPolicy(torch.nn.Module):
     Parameters in Keras' layouts with a leading weight-set axis: conv_w, conv_b; a_fc1_w [1014, 32] ... a_fc2_b (actions stack),
     m_fc1_w ... m_fc2_b (MOA stack); lstm_kernel [32, 4C], lstm_recurrent [C, 4C], lstm_bias [4C], logits_w [C, A], logits_b,
     value_w [C, 1], value_b; moa_kernel [32 + N, 4C], moa_recurrent [C, 4C], moa_bias [4C], pred_w [C, (N-1) A], pred_b."""
+    STATE_ROWS = 4
+    TAKES_PREV_ACTIONS = True
+    C_FORWARD, C_ROLLOUT = "ssd_policy_moa_forward", "ssd_rollout_policy_moa"
 
     def __init__(self, num_actions, num_agents, num_sets=1, cell_size=128, seed=0):
         super().__init__()
         A, N, P, C = int(num_actions), int(num_agents), int(num_sets), int(cell_size)
-        if not 1 <= A <= _capi.SSD_POL_MAX_ACTIONS:
-            raise ValueError("num_actions must be 1..%d" % _capi.SSD_POL_MAX_ACTIONS)
+        self._check_ranges(num_actions=A)
         if not 2 <= N <= _capi.SSD_MOA_MAX_AGENTS:
             raise ValueError("the MOA policy needs 2..%d agents" % _capi.SSD_MOA_MAX_AGENTS)
         if P not in (1, N):
             raise ValueError("num_sets must be 1 or num_agents")
-        if C not in _capi.LSTM_CELL_SIZES:
-            raise ValueError("cell_size must be one of %s" % (_capi.LSTM_CELL_SIZES,))
+        self._check_ranges(cell_size=C)
         self.num_actions, self.num_agents, self.num_sets, self.cell_size = A, N, P, C
         g = torch.Generator().manual_seed(int(seed))
         init = {"conv_w": _glorot((P, 3, 3, 3, FILTERS), 27, 9 * FILTERS, g),
@@ -350,17 +403,12 @@ class ConvMOAPolicy(torch.nn.Module):
             b = torch.zeros((P, 4 * C), dtype=torch.float64)
             b[:, C:2 * C] = 1.0
             init[name] = b
-        for name, shape, _ in self.layout():
-            t = init.get(name)
-            if t is None:
-                t = torch.zeros((P,) + shape, dtype=torch.float64)       # the other biases start at zero
-            self.register_parameter(name, torch.nn.Parameter(t.to(torch.float32)))
-        self._packed = None
-        self._tables = {}
+        self._register(init)
         self.register_buffer("_others", torch.from_numpy(other_agents(N)), persistent=False)
 
     def layout(self):
-        """(name, shape of one set, float offset within a packed set) of every parameter, in packed order."""
+        """(name, shape of one set, float offset within a packed set) of every parameter, in packed order.  (The MOA input's
+        zero rows 32 + N .. 47 belong to no parameter: packed() never writes them.)"""
         A, N, C = self.num_actions, self.num_agents, self.cell_size
         out = list(_FIXED[:2])
         for s, p in ((0, "a"), (1, "m")):
@@ -376,18 +424,12 @@ class ConvMOAPolicy(torch.nn.Module):
                 ("pred_w", (C, (N - 1) * A), _capi.SSD_MOA_PRED_W(C, A)), ("pred_b", ((N - 1) * A,), _capi.SSD_MOA_PRED_B(C, A, N))]
         return tuple(out)
 
-    load_arrays = ConvFCPolicy.load_arrays
-    packed = ConvFCPolicy.packed                                 # (the MOA input's zero rows 32 + N .. 47 are never written)
-
     @property
     def set_floats(self):
         return _capi.SSD_MOA_SET_FLOATS(self.cell_size, self.num_actions, self.num_agents)
 
-    def initial_state(self, lead, device=None):
-        """A zero state [*lead, 4, C] (float32, on the parameters' device unless given)."""
-        lead = (int(lead),) if isinstance(lead, int) else tuple(int(n) for n in lead)
-        return torch.zeros(lead + (4, self.cell_size), dtype=self.lstm_kernel.dtype,
-                           device=self.lstm_kernel.device if device is None else device)
+    def scratch_shape(self, rows):
+        return (_capi.SSD_MOA_SCRATCH_FLOATS(rows),)
 
     def _per_agent(self, name):
         """Parameter `name` with one entry per agent [N, ...] (set i, or set 0 for all when shared)."""
@@ -396,25 +438,15 @@ class ConvMOAPolicy(torch.nn.Module):
 
     def _stacks(self, obs):
         """u8 [..., N, 15, 15, 3] -> (actions-stack output [M, N, 32], MOA-stack output [M, N, 32], leading shape [..., N])."""
-        N = self.num_agents
+        N, w = self.num_agents, self._per_agent
         if obs.shape[-3:] != (VIEW, VIEW, 3) or obs.dim() < 4 or obs.shape[-4] != N:
             raise ValueError("observations must be [..., %d, 15, 15, 3], got %s" % (N, tuple(obs.shape)))
-        lead = tuple(obs.shape[:-3])
-        dt = self.conv_w.dtype
-        key = (obs.device, dt)
-        if key not in self._tables:
-            self._tables[key] = torch.from_numpy(_NORMALISE).to(dt).to(obs.device)
-        x = self._tables[key][obs.long()].reshape(-1, N, VIEW, VIEW, 3)
-        M = x.shape[0]
-        x = x.permute(0, 1, 4, 2, 3).reshape(M, N * 3, VIEW, VIEW)
-        wc = self._per_agent("conv_w").permute(0, 4, 3, 1, 2).reshape(N * FILTERS, 3, 3, 3)
-        h = torch.relu(torch.nn.functional.conv2d(x, wc, self._per_agent("conv_b").reshape(N * FILTERS), groups=N))
-        h = h.reshape(M, N, FILTERS, 13, 13).permute(0, 1, 3, 4, 2).reshape(M, N, FLAT)
+        h = _conv_flat(self, obs, N, w("conv_w"), w("conv_b"))
         out = []
         for p in ("a", "m"):
-            y = torch.tanh(torch.einsum("mnk,nkj->mnj", h, self._per_agent(p + "_fc1_w")) + self._per_agent(p + "_fc1_b"))
-            out.append(torch.tanh(torch.einsum("mnk,nkj->mnj", y, self._per_agent(p + "_fc2_w")) + self._per_agent(p + "_fc2_b")))
-        return out[0], out[1], lead
+            y = torch.tanh(_dense(h, w(p + "_fc1_w"), w(p + "_fc1_b")))
+            out.append(torch.tanh(_dense(y, w(p + "_fc2_w"), w(p + "_fc2_b"))))
+        return out[0], out[1], tuple(obs.shape[:-3])
 
     def _step(self, obs, prev_actions, state, starts, counterfactuals):
         N, A, C = self.num_agents, self.num_actions, self.cell_size
@@ -426,22 +458,20 @@ class ConvMOAPolicy(torch.nn.Module):
             raise ValueError("prev_actions must have shape %s, got %s" % (lead, tuple(prev_actions.shape)))
         st = state.to(ya.dtype).reshape(M, N, 4, C)
         prev = prev_actions.reshape(M, N).to(ya.device)
-        s = None
         if starts is not None:
             if tuple(starts.shape) != lead:
                 raise ValueError("starts must have shape %s, got %s" % (lead, tuple(starts.shape)))
-            s = starts.to(torch.bool).reshape(M, N).to(st.device)
-            st = torch.where(s[..., None, None], torch.zeros((), dtype=st.dtype, device=st.device), st)
+            st = _zero_where(starts, st, 2)
         h1, c1 = keras_lstm(ya[:, :, None, :], st[:, :, 0, None], st[:, :, 1, None], self._per_agent("lstm_kernel"),
                             self._per_agent("lstm_recurrent"), self._per_agent("lstm_bias")[:, None])
         h1, c1 = h1[:, :, 0], c1[:, :, 0]
-        logits = torch.einsum("mnk,nkj->mnj", h1, self._per_agent("logits_w")) + self._per_agent("logits_b")
-        value = (torch.einsum("mnk,nkj->mnj", h1, self._per_agent("value_w")) + self._per_agent("value_b"))[..., 0]
+        logits, value = _heads(h1, self._per_agent("logits_w"), self._per_agent("logits_b"), self._per_agent("value_w"),
+                               self._per_agent("value_b"))
         # the MOA input of row (m, i): own previous action, then the others' in string order (zero at a start)
         others = prev[:, self._others.to(prev.device)]                           # [M, N, N-1]
         acts = torch.cat([prev[..., None], others], dim=-1)                      # [M, N, N]
-        if s is not None:                                       # a starting row's whole vector is zero (selected)
-            acts = torch.where(s[..., None], torch.zeros_like(acts), acts)
+        if starts is not None:                                  # a starting row's whole vector is zero (selected)
+            acts = _zero_where(starts, acts, 1)
         acts = acts.to(ya.dtype)
         mk, mr, mb = self._per_agent("moa_kernel"), self._per_agent("moa_recurrent"), self._per_agent("moa_bias")[:, None]
         h2s, c2s = st[:, :, 2, None], st[:, :, 3, None]
@@ -457,7 +487,7 @@ class ConvMOAPolicy(torch.nn.Module):
         h2, c2 = keras_lstm(torch.cat([ym, acts], dim=-1)[:, :, None, :], h2s, c2s, mk, mr, mb)
         h2, c2 = h2[:, :, 0], c2[:, :, 0]
         if not counterfactuals:
-            moa = (torch.einsum("mnk,nkj->mnj", h2, self._per_agent("pred_w")) + self._per_agent("pred_b")).reshape(M, N, N - 1, A)
+            moa = _dense(h2, self._per_agent("pred_w"), self._per_agent("pred_b")).reshape(M, N, N - 1, A)
             cf = None
         new_state = torch.stack([h1, c1, h2, c2], dim=2)
         out = (logits.reshape(lead + (A,)), value.reshape(lead), moa.reshape(lead + (N - 1, A)),
@@ -479,13 +509,11 @@ class ConvMOAPolicy(torch.nn.Module):
         T = int(obs.shape[0])
         if int(prev_actions.shape[0]) != T or (resets is not None and int(resets.shape[0]) != T):
             raise ValueError("prev_actions and resets must have T = %d rows" % T)
-        logits, values, moas = [], [], []
-        for t in range(T):
-            lg, v, moa, _, state = self._step(obs[t], prev_actions[t], state, None if resets is None else resets[t], False)
-            logits.append(lg)
-            values.append(v)
-            moas.append(moa)
-        return torch.stack(logits), torch.stack(values), torch.stack(moas), state
+
+        def step(t, st, reset):
+            lg, v, moa, _, st = self._step(obs[t], prev_actions[t], st, reset, False)
+            return lg, v, moa, st
+        return _unroll(step, T, state, resets)
 
     def moa_loss(self, moa_logits, actions, weight=1.0):
         """MOALoss (algorithms/common_funcs.py:70-95): the mean over rows and other agents of the cross-entropy of moa_logits
@@ -563,7 +591,7 @@ def sample_gaussian_host(mean, log_std, u1, u2, greedy=False, dtype=np.float32):
     return a, logp, np.fmin(np.fmax(a, f(0.0)), f(1.0)).astype(dtype)
 
 
-class WatershedLSTMPolicy(torch.nn.Module):
+class WatershedLSTMPolicy(PolicyBase):
     """LSTMFCNet of the reference's Watershed launchers (models/watershed_nets.py:94-177): per agent id its own weight set of
     dense0 (obs -> 16, ReLU), dense1 (16 -> 16, ReLU), a Keras LSTM of cell_size C cells and, on its output, a 5-wide
     distribution head and a value head.  One agent acts per env and phase; a row uses the set of its acting agent.
@@ -574,11 +602,15 @@ class WatershedLSTMPolicy(torch.nn.Module):
         dist, value, final = policy.forward_sequence(5, obs_seq, state_in)   # BPTT over agent 5's own steps
 
     dist is the input of the action distribution: the five logits of a comm agent's Categorical, or (mean, log_std, 3 unused) of
-    an action agent's DiagGaussian.  A state is [..., 2, C]: (h, c).  Parameters in Keras' layouts with a leading weight-set
-    axis: dense0_w [S, 12, 16] (the rows beyond an agent's observation length meet the zero padding of the engine's rows),
-    dense0_b, dense1_w [S, 16, 16], dense1_b, lstm_kernel [S, 16, 4C], lstm_recurrent [S, C, 4C], lstm_bias [S, 4C], out_w
-    [S, C, 5], out_b, value_w [S, C, 1], value_b.  share_comm_layer: dense1 of agents k and k + 4 is ONE layer (the
-    reference's shared_layers[id % 4]): dense1_w / dense1_b have 4 entries, and packed() writes each into both sets."""
+    an action agent's DiagGaussian.  A state is [..., 2, C]: (h, c); a rollout's carried state is initial_state((E, num_sets)).
+    Parameters in Keras' layouts with a leading weight-set axis: dense0_w [S, 12, 16] (the rows beyond an agent's observation
+    length meet the zero padding of the engine's rows), dense0_b, dense1_w [S, 16, 16], dense1_b, lstm_kernel [S, 16, 4C],
+    lstm_recurrent [S, C, 4C], lstm_bias [S, 4C], out_w [S, C, 5], out_b, value_w [S, C, 1], value_b.  share_comm_layer: dense1
+    of agents k and k + 4 is ONE layer (the reference's shared_layers[id % 4]): dense1_w / dense1_b have 4 entries, and packed()
+    writes each into both sets."""
+    STATE_ROWS = 2
+    REF_PARAM = "dense0_w"
+    C_FORWARD, C_ROLLOUT = "ssd_ws_policy_forward", "ssd_ws_rollout_policy"
 
     def __init__(self, variant, local_obs=False, cell_size=128, share_comm_layer=False, seed=0):
         super().__init__()
@@ -586,8 +618,7 @@ class WatershedLSTMPolicy(torch.nn.Module):
         V, C = int(variant), int(cell_size)
         if V not in (_capi.SSD_WS_SEQ, _capi.SSD_WS_SEQ_COMM):
             raise ValueError("variant must be SEQ or SEQ_COMM")
-        if C not in _capi.LSTM_CELL_SIZES:
-            raise ValueError("cell_size must be one of %s" % (_capi.LSTM_CELL_SIZES,))
+        self._check_ranges(cell_size=C)
         S = 4 if V == _capi.SSD_WS_SEQ else 8
         self.variant, self.local_obs, self.cell_size, self.num_sets = V, bool(local_obs), C, S
         self.share_comm_layer = bool(share_comm_layer)
@@ -597,16 +628,12 @@ class WatershedLSTMPolicy(torch.nn.Module):
         d0 = torch.zeros((S, WS_OBS, WS_X), dtype=torch.float64)
         for i, n in enumerate(self.obs_lens):                    # Keras' Glorot uniform on the [n, 16] kernel the agent has
             d0[i, :n] = _glorot((n, WS_X), n, WS_X, g)
-        init = {"dense0_w": d0, "dense1_w": normc((self.num_dense1, WS_X, WS_X), 1.0, g),
-                "lstm_kernel": _glorot((S, WS_X, 4 * C), WS_X, 4 * C, g), "lstm_recurrent": _orthogonal(S, C, 4 * C, g),
-                "out_w": _glorot((S, C, WS_OUT), C, WS_OUT, g), "value_w": _glorot((S, C, 1), C, 1, g)}
-        for name, shape, _ in self.layout():
-            t = init.get(name)
-            n = self.num_dense1 if name.startswith("dense1") else S
-            if t is None:
-                t = torch.zeros((n,) + shape, dtype=torch.float64)       # Keras' bias_initializer "zeros"
-            self.register_parameter(name, torch.nn.Parameter(t.to(torch.float32)))
-        self._packed = None
+        self._register({"dense0_w": d0, "dense1_w": normc((self.num_dense1, WS_X, WS_X), 1.0, g),
+                        "lstm_kernel": _glorot((S, WS_X, 4 * C), WS_X, 4 * C, g), "lstm_recurrent": _orthogonal(S, C, 4 * C, g),
+                        "out_w": _glorot((S, C, WS_OUT), C, WS_OUT, g), "value_w": _glorot((S, C, 1), C, 1, g)})
+
+    def _entries(self, name):
+        return self.num_dense1 if name.startswith("dense1") else self.num_sets
 
     def layout(self):
         """(name, shape of one set, float offset within a packed set) of every parameter, in packed order."""
@@ -619,8 +646,6 @@ class WatershedLSTMPolicy(torch.nn.Module):
                 ("out_w", (C, WS_OUT), _capi.SSD_WSP_OUT_W(C)), ("out_b", (WS_OUT,), _capi.SSD_WSP_OUT_B(C)),
                 ("value_w", (C, 1), _capi.SSD_WSP_VALUE_W(C)), ("value_b", (1,), _capi.SSD_WSP_VALUE_B(C)))
 
-    load_arrays = ConvFCPolicy.load_arrays
-
     @property
     def set_floats(self):
         return _capi.SSD_WSP_SET_FLOATS(self.cell_size)
@@ -629,31 +654,6 @@ class WatershedLSTMPolicy(torch.nn.Module):
         """Parameter `name` of agent id i (a shared dense1 is entry i % 4)."""
         t = getattr(self, name)
         return t[i % t.shape[0]]
-
-    def packed(self):
-        """All weight sets as ONE contiguous float32 tensor on the parameters' device, in the layout of include/ssd.h: set p
-        at p * SSD_WSP_SET_FLOATS(C).  Rebuilt from the parameters on every call by device copies on the current stream (no
-        host synchronisation), so an optimiser's update takes effect on the next call.  The buffer is reused between calls."""
-        S, F = self.num_sets, self.set_floats
-        dev = self.dense0_w.device
-        if self._packed is None or self._packed.device != dev:
-            self._packed = torch.zeros(S * F, dtype=torch.float32, device=dev)
-        v = self._packed.view(S, F)
-        with torch.no_grad():
-            for name, shape, off in self.layout():
-                n = int(np.prod(shape))
-                t = getattr(self, name).reshape(-1, n)
-                if t.shape[0] != S:                              # the shared dense1: entry k serves sets k and k + 4
-                    t = t.repeat(S // t.shape[0], 1)
-                v[:, off:off + n].copy_(t)
-        return self._packed
-
-    def initial_state(self, lead, device=None):
-        """A zero state [*lead, 2, C] (the parameters' dtype, on their device unless given); a rollout's carried state is
-        initial_state((E, num_sets))."""
-        lead = (int(lead),) if isinstance(lead, int) else tuple(int(n) for n in lead)
-        return torch.zeros(lead + (2, self.cell_size), dtype=self.dense0_w.dtype,
-                           device=self.dense0_w.device if device is None else device)
 
     def _cell(self, i, x, h, c):
         """Set i on rows x [M, 12], (h, c) [M, C] -> (dist [M, 5], value [M], h', c')."""
@@ -678,7 +678,7 @@ class WatershedLSTMPolicy(torch.nn.Module):
         if starts is not None:
             if tuple(starts.shape) != lead:
                 raise ValueError("starts must have shape %s, got %s" % (lead, tuple(starts.shape)))
-            st = torch.where(starts.to(torch.bool).reshape(-1, 1, 1).to(st.device), torch.zeros((), dtype=dt, device=st.device), st)
+            st = _zero_where(starts, st, 2)
         M = x.shape[0]
         dist = torch.zeros((M, WS_OUT), dtype=dt, device=x.device)
         value = torch.zeros((M,), dtype=dt, device=x.device)
@@ -704,14 +704,10 @@ class WatershedLSTMPolicy(torch.nn.Module):
         lead = tuple(obs.shape[1:-1])
         dt = self.dense0_w.dtype
         st = state.to(dt).reshape(-1, 2, C)
-        h, c = st[:, 0], st[:, 1]
-        dists, values = [], []
-        for t in range(T):
-            if resets is not None:
-                keep = ~resets[t].to(torch.bool).reshape(-1, 1).to(h.device)
-                zero = torch.zeros((), dtype=dt, device=h.device)
-                h, c = torch.where(keep, h, zero), torch.where(keep, c, zero)
+
+        def step(t, hc, reset):
+            h, c = hc if reset is None else (_zero_where(reset, hc[0], 1), _zero_where(reset, hc[1], 1))
             d, v, h, c = self._cell(i, obs[t].to(dt).reshape(-1, WS_OBS), h, c)
-            dists.append(d.reshape(lead + (WS_OUT,)))
-            values.append(v.reshape(lead))
-        return torch.stack(dists), torch.stack(values), torch.stack([h, c], dim=1).reshape(lead + (2, C))
+            return d.reshape(lead + (WS_OUT,)), v.reshape(lead), (h, c)
+        dists, values, hc = _unroll(step, T, (st[:, 0], st[:, 1]), resets)
+        return dists, values, torch.stack(hc, dim=1).reshape(lead + (2, C))

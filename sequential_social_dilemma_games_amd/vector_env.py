@@ -42,9 +42,9 @@ class SSDVectorEnv(object):
         self._extras = None
         self._act_buf = None
         self._pending = None
-        self._lstm_state = None                  # the recurrent policy's state [E,N,2,C] carried across sample() calls
-        self._moa_state = None                   # the MOA policy's state [E,N,4,C] and previous joint action [E,N], likewise
-        self._moa_prev = None
+        # what sample() carries across calls, per kind of policy (its C_ROLLOUT): {"state": [E,N,rows,C]} and, for the MOA policy,
+        # "prev_actions" [E,N], the previous joint action
+        self._carried = {}
         # track_episodes: step k writes rew / done into slot k % track_ring of a ring that the episode statistics fold
         self.stats = None
         if track_episodes:
@@ -107,8 +107,7 @@ class SSDVectorEnv(object):
             self._fold()
             self.stats.discard()                 # the episodes still open are cut short
         self._alloc()
-        self._lstm_state = None
-        self._moa_state = self._moa_prev = None
+        self._carried = {}
         self.engine.reset(obs=self._out[0])
         return self._wrap(self._out[0], None, None)
 
@@ -188,15 +187,14 @@ class SSDVectorEnv(object):
                 raise ValueError("gamma and lambda_ must be finite")
             if use_gae and not use_critic:
                 raise ValueError("use_gae needs use_critic: generalised advantage estimation uses the value function")
-        moa = eng._is_moa(policy)
-        recurrent = eng._is_recurrent(policy) or moa
-        if not recurrent and state_every is not None:
+        rows, moa = policy.STATE_ROWS, policy.TAKES_PREV_ACTIONS
+        if not rows and state_every is not None:
             raise ValueError("state_every belongs to a ConvLSTMPolicy")
-        if recurrent:
-            held = self._moa_state if moa else self._lstm_state
-            if held is not None and held.shape[-1] != policy.cell_size:
+        if rows:
+            held = self._carried.get(policy.C_ROLLOUT)       # what this kind of policy left here: its state (and previous actions)
+            if held is not None and held["state"].shape[-1] != policy.cell_size:
                 raise ValueError("the adapter holds the state of a %d-cell policy, this one has %d cells: reset() first"
-                                 % (held.shape[-1], policy.cell_size))
+                                 % (held["state"].shape[-1], policy.cell_size))
             every = n_steps if state_every is None else int(state_every)
             if every < 1:
                 raise ValueError("state_every must be >= 1")
@@ -204,7 +202,7 @@ class SSDVectorEnv(object):
         if n_steps > 1 and (E * N) % 4:
             raise ValueError("an observation ring of more than one slot needs num_envs * num_agents to be a multiple of 4")
         if self._out is None:
-            self.reset()
+            self.reset()                             # (an adapter that never sampled: nothing is carried, held is None)
         dev = self._out[1].device
         out = {"obs": torch.empty((n_steps, E, N, V, V, 3), dtype=torch.uint8, device=dev),
                "actions": torch.empty((n_steps, E, N), dtype=torch.int32, device=dev),
@@ -214,23 +212,17 @@ class SSDVectorEnv(object):
                "done": torch.empty((n_steps, E, N), dtype=torch.uint8, device=dev),
                "last_value": torch.empty((E, N), dtype=torch.float32, device=dev)}
         kw = {}
-        if moa:
-            if self._moa_state is None:
-                self._moa_state = torch.zeros((E, N, 4, policy.cell_size), dtype=torch.float32, device=dev)
-                self._moa_prev = torch.zeros((E, N), dtype=torch.int32, device=dev)
-            ring = torch.empty((-(-n_steps // every), E, N, 4, policy.cell_size), dtype=torch.float32, device=dev)
-            out["influence"] = torch.empty((n_steps, E, N), dtype=torch.float32, device=dev)
-            out["prev_actions"] = torch.empty((n_steps, E, N), dtype=torch.int32, device=dev)
-            kw = dict(state=self._moa_state, state_ring=ring, state_every=every, prev_actions=self._moa_prev,
-                      prev_actions_ring=out["prev_actions"], influence=out["influence"])
-            out["state_in"] = ring[0]
-            if state_every is not None:
-                out["state"] = ring
-        elif recurrent:
-            if self._lstm_state is None:
-                self._lstm_state = torch.zeros((E, N, 2, policy.cell_size), dtype=torch.float32, device=dev)
-            ring = torch.empty((-(-n_steps // every), E, N, 2, policy.cell_size), dtype=torch.float32, device=dev)
-            kw = dict(state=self._lstm_state, state_ring=ring, state_every=every)
+        if rows:
+            if held is None:
+                held = self._carried[policy.C_ROLLOUT] = {"state": torch.zeros((E, N, rows, policy.cell_size), dtype=torch.float32, device=dev)}
+                if moa:
+                    held["prev_actions"] = torch.zeros((E, N), dtype=torch.int32, device=dev)
+            ring = torch.empty((-(-n_steps // every), E, N, rows, policy.cell_size), dtype=torch.float32, device=dev)
+            if moa:
+                out["influence"] = torch.empty((n_steps, E, N), dtype=torch.float32, device=dev)
+                out["prev_actions"] = torch.empty((n_steps, E, N), dtype=torch.int32, device=dev)
+                kw = dict(prev_actions_ring=out["prev_actions"], influence=out["influence"])
+            kw.update(held, state_ring=ring, state_every=every)
             out["state_in"] = ring[0]
             if state_every is not None:
                 out["state"] = ring

@@ -170,6 +170,7 @@ class WatershedVecEngine(object):
             self._last_obs, self._last_agent = (obs[last], agent[last]) if obs is not None and agent is not None else (None, None)
 
     # ---------------------------------------------------------------- policy rollouts (include/ssd.h, WATERSHED POLICY ROLLOUTS)
+    # (the network's state rows and the library's entry points are the policy's class attributes, policy.PolicyBase)
     def _check_policy(self, policy):
         from .policy import WatershedLSTMPolicy
         if not isinstance(policy, WatershedLSTMPolicy):
@@ -191,7 +192,7 @@ class WatershedVecEngine(object):
             raise ValueError("agent must be i8 [B] with B >= 1")
         self._check_tensor(obs, (B, OBS_WIDTH), torch.float32, "policy obs")
         self._check_tensor(agent, (B,), torch.int8, "agent")
-        self._check_tensor(state, (B, 2, Cc), torch.float32, "state")
+        self._check_tensor(state, (B, policy.STATE_ROWS, Cc), torch.float32, "state")
         s = None
         if starts is not None:
             s = torch.as_tensor(starts, device=self._dev).to(torch.uint8).contiguous()
@@ -199,8 +200,8 @@ class WatershedVecEngine(object):
         dist = torch.empty((B, 5), dtype=torch.float32, device=self._dev)
         value = torch.empty((B,), dtype=torch.float32, device=self._dev)
         out = torch.empty_like(state)
-        _capi.policy_check(self._L.ssd_ws_policy_forward(_p(w), policy.num_sets, Cc, self.variant, _p(obs), _p(agent), _p(state), _p(s),
-                                                         B, _p(out), _p(dist), _p(value), self.device, 0, _stream(self._dev)))
+        _capi.policy_check(getattr(self._L, policy.C_FORWARD)(_p(w), policy.num_sets, Cc, self.variant, _p(obs), _p(agent), _p(state), _p(s),
+                                                              B, _p(out), _p(dist), _p(value), self.device, 0, _stream(self._dev)))
         return dist, value, out
 
     def rollout_policy(self, policy, obs_in, agent_in, n_steps, obs, agent, rew=None, done=None, actor=None, actions=None, logp=None,
@@ -224,20 +225,21 @@ class WatershedVecEngine(object):
         self._check_tensor(obs_in, (E, OBS_WIDTH), torch.float32, "obs")
         self._check_tensor(agent_in, (E,), torch.int8, "agent_in")
         self._check_outputs((ring,), obs, agent, rew, done)
-        self._check_tensor(state, (E, policy.num_sets, 2, Cc), torch.float32, "state")
+        SR = policy.STATE_ROWS
+        self._check_tensor(state, (E, policy.num_sets, SR, Cc), torch.float32, "state")
         for t, shape, dtype, name in ((actor, (ring, E), torch.int8, "actor"), (actions, (ring, E), torch.float32, "actions"),
                                       (logp, (ring, E), torch.float32, "logp"), (value, (ring, E), torch.float32, "value"),
-                                      (dist, (ring, E, 5), torch.float32, "dist"), (state_ring, (ring, E, 2, Cc), torch.float32, "state_ring"),
+                                      (dist, (ring, E, 5), torch.float32, "dist"), (state_ring, (ring, E, SR, Cc), torch.float32, "state_ring"),
                                       (last_value, (E,), torch.float32, "last_value")):
             if t is not None:
                 self._check_tensor(t, shape, dtype, name)
         if self._pol_scratch is None:
             self._pol_scratch = torch.zeros((E,), dtype=torch.float32, device=self._dev)
         flags = _capi.SSD_POLICY_GREEDY if greedy else 0
-        self._check(self._L.ssd_ws_rollout_policy(self._h, _p(w), policy.num_sets, Cc, _p(obs_in), _p(agent_in), int(n_steps), int(step0),
-                                                  _p(state), _p(state_ring), _p(self._pol_scratch), _p(obs), _p(agent), _p(rew), _p(done),
-                                                  _p(actor), _p(actions), _p(logp), _p(value), _p(dist), ring, _p(last_value), flags,
-                                                  _stream(self._dev)))
+        self._check(getattr(self._L, policy.C_ROLLOUT)(self._h, _p(w), policy.num_sets, Cc, _p(obs_in), _p(agent_in), int(n_steps), int(step0),
+                                                       _p(state), _p(state_ring), _p(self._pol_scratch), _p(obs), _p(agent), _p(rew), _p(done),
+                                                       _p(actor), _p(actions), _p(logp), _p(value), _p(dist), ring, _p(last_value), flags,
+                                                       _stream(self._dev)))
         last = (int(step0) + int(n_steps) - 1) % ring
         self._last_obs, self._last_agent = obs[last], agent[last]
 
@@ -257,7 +259,7 @@ class WatershedVecEngine(object):
         obs, agent, rew, done = self._outputs((K,))
         f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=d)   # noqa: E731
         out = dict(obs=obs, agent=agent, rew=rew, done=done, actor=torch.empty((K, E), dtype=torch.int8, device=d), actions=f(K, E),
-                   logp=f(K, E), value=f(K, E), dist=f(K, E, 5), state_in=f(K, E, 2, policy.cell_size), last_value=f(E))
+                   logp=f(K, E), value=f(K, E), dist=f(K, E, 5), state_in=f(K, E, policy.STATE_ROWS, policy.cell_size), last_value=f(E))
         self.rollout_policy(policy, self._last_obs, self._last_agent, K, obs, agent, rew=rew, done=done, actor=out["actor"],
                             actions=out["actions"], logp=out["logp"], value=out["value"], dist=out["dist"], state=self._pol_state,
                             state_ring=out["state_in"], last_value=out["last_value"], greedy=greedy)
