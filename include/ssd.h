@@ -727,6 +727,73 @@ int ssd_advantages(const int32_t *rew, const float *bonus, double bonus_weight, 
                    double lambda, uint32_t flags, float *advantages, float *value_targets, int32_t device_id, void *stream);
 const char *ssd_advantages_last_error(void);   /* the calling thread's last ssd_advantages error */
 
+/* ======================================================================================================================
+ * PPO LOSS AND GRADIENTS -- the learner's half of the loop for the conv-FC policy: RLlib 0.7.6's PPOLoss with use_gae=True
+ * (what algorithms/ppo_causal.py:53-72 builds) on a sampled fragment, its statistics and the gradient of every parameter, in
+ * one call (csrc/ssd_policy_grad.hip).  Added after ABI 6 without a version bump: the call is additive.
+ *
+ * Network: that of ssd_policy_forward above, the same packed weight layout, P = 1 or P = N sets, A <= 15, view 15.
+ *
+ * Rows.  A fragment is K x E x N rows (n_steps, num_envs, num_agents); every per-row array below is [K,E,N] (behaviour_logits
+ * [K,E,N,A]).  Row (k, e, i) uses weight set i when P = N and set 0 when P = 1.  A set's rows are all the rows that use it:
+ * K E of them for P = N, K E N for P = 1, in (k, e, i) order.
+ *
+ * Observation shift.  With obs_first u8 [E,N,15,15,3], row k reads obs_first for k = 0 and obs[k - 1] otherwise: what the
+ * rollouts record (slot k of their obs ring is the observation AFTER step k, and step k acted on the one before it).  The
+ * shift is address arithmetic; nothing is copied, and obs[K - 1] is not read (obs may be NULL when K = 1).  Without obs_first
+ * (NULL), row k reads obs[k].  obs is u8 [K,E,N,15,15,3]; a leading-axis slice of a ring is such an array, so the minibatch of
+ * steps k0 .. k1 - 1 of a fragment is obs_first = ring[k0 - 1] (the fragment's own obs_first for k0 = 0), obs = ring + k0.
+ *
+ * Loss.  Per row, with (logits, value) the network's outputs, a = actions[row] (0 <= a < A; the caller's duty):
+ *   logp  = log_softmax(logits)[a]                    ratio = exp(logp - logp_old)
+ *   surr  = min(adv * ratio, adv * clip(ratio, 1 - c, 1 + c))                               c = clip_param
+ *   kl    = KL(softmax(behaviour_logits) || softmax(logits))   (0 without behaviour_logits)
+ *   ent   = the entropy of softmax(logits)
+ *   vf1   = (value - vt)^2      vf2 = (vf_pred + clip(value - vf_pred, -vc, vc) - vt)^2     vc = vf_clip_param
+ *   vf    = max(vf1, vf2)
+ *   row_loss = -surr + kl_coeff * kl + vf_loss_coeff * vf - entropy_coeff * ent
+ * loss_p is the mean of row_loss over set p's rows, and the call's scalar is the sum of loss_p over the sets: the sets share
+ * no parameter, so each set's gradient is its own policy's (train_baseline.py:87-96).  behaviour_logits must be NULL if and
+ * only if kl_coeff == 0.
+ *
+ * Derivatives at the kinks:
+ *   d surr / d ratio = adv when 1 - c <= ratio <= 1 + c, or when adv * ratio < adv * clip(ratio) strictly; else 0
+ *   d vf / d value   = 2 (value - vt) when |value - vf_pred| <= vc or vf1 >= vf2; else 0
+ *   ReLU's derivative at 0 is 0.
+ * So the first epoch, where ratio = 1 and value = vf_pred up to rounding and both branches tie, gives the unclipped gradient.
+ * This equals torch autograd everywhere except on exact clip boundaries (at a tie torch's half-and-half split of minimum /
+ * maximum sums to the same number).
+ *
+ * Arithmetic and order.  Exact float32, as the forward (the hyper-parameters are rounded to float32 once); the per-row loss
+ * terms are float32 and enter float64 sums.  Every sum over rows has a fixed order that is a function of (K, E, N, P) alone:
+ * a set's rows are cut into tiles of SSD_PPO_TILE rows, workgroup g of the G = SSD_PPO_GROUPS(set rows, P) of a set sums
+ * tiles g, g + G, ... in that order in float32 (float64 for the statistics), and the G partial sums are added in order in
+ * float64, scaled by 1 / rows and rounded to float32 once.  No atomics: the same inputs give the same bits on every call and
+ * on every device.
+ *
+ * Outputs.  grads f32 [P, SSD_POL_SET_FLOATS(A)]: d loss / d weights in the packed layout, padding floats zero.  stats f64
+ * [P, 5]: the set means of row_loss, -surr (policy loss), vf, kl and ent (RLlib's kl_and_loss_stats less the explained
+ * variance).  scratch: SSD_PPO_SCRATCH_FLOATS(set rows, P, A) floats the call overwrites, 8-byte aligned as stats is.
+ *
+ * Device pointers on device_id; two launches on `stream`, no allocation, no host synchronisation.  SSD_E_INVALID before
+ * anything is launched (ssd_policy_last_error says why) for the network rules of ssd_policy_forward, n_steps or num_envs
+ * < 1, more than 2^31 - 17 rows, a missing pointer, a misaligned scratch, grads or stats, a hyper-parameter that is not finite, a
+ * negative clip_param or vf_clip_param, behaviour_logits without kl_coeff or the reverse, flags other than 0.
+ * ====================================================================================================================== */
+enum { SSD_PPO_TILE = 16, SSD_PPO_STAT_FLOATS = 16, SSD_PPO_MAX_GROUPS = 1024 };
+/* workgroups (partial sums) per set: one per tile up to SSD_PPO_MAX_GROUPS / P */
+#define SSD_PPO_TILES(set_rows) ((set_rows) / SSD_PPO_TILE + ((set_rows) % SSD_PPO_TILE != 0))
+#define SSD_PPO_GROUPS(set_rows, P) \
+    (SSD_PPO_TILES(set_rows) < SSD_PPO_MAX_GROUPS / (P) ? SSD_PPO_TILES(set_rows) : SSD_PPO_MAX_GROUPS / (P))
+#define SSD_PPO_SCRATCH_FLOATS(set_rows, P, A) \
+    ((size_t)(P) * (size_t)SSD_PPO_GROUPS(set_rows, P) * (size_t)(SSD_POL_SET_FLOATS(A) + SSD_PPO_STAT_FLOATS))
+int ssd_policy_ppo_grad(const float *weights, int32_t num_sets, int32_t num_actions, const uint8_t *obs_first, const uint8_t *obs,
+                        const int32_t *actions, const float *logp_old, const float *advantages, const float *value_targets,
+                        const float *vf_preds, const float *behaviour_logits, int32_t n_steps, int32_t num_envs,
+                        int32_t num_agents, double clip_param, double vf_clip_param, double vf_loss_coeff, double entropy_coeff,
+                        double kl_coeff, float *scratch, float *grads, double *stats, int32_t device_id, uint32_t flags,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,18 @@ def SSD_POL_SET_FLOATS(num_actions):
     return (SSD_POL_LOGITS_W + 33 * int(num_actions) + 63) // 64 * 64
 
 
+# the PPO loss-and-gradient call's partial sums (include/ssd.h, SSD_PPO_*)
+SSD_PPO_TILE, SSD_PPO_STAT_FLOATS, SSD_PPO_MAX_GROUPS = 16, 16, 1024
+
+
+def SSD_PPO_GROUPS(set_rows, num_sets):
+    return min((int(set_rows) + SSD_PPO_TILE - 1) // SSD_PPO_TILE, SSD_PPO_MAX_GROUPS // int(num_sets))
+
+
+def SSD_PPO_SCRATCH_FLOATS(set_rows, num_sets, num_actions):
+    return int(num_sets) * SSD_PPO_GROUPS(set_rows, num_sets) * (SSD_POL_SET_FLOATS(num_actions) + SSD_PPO_STAT_FLOATS)
+
+
 # the recurrent policy's weight layout (include/ssd.h, SSD_LSTM_*): the trunk at the SSD_POL_* offsets, then these blocks
 SSD_LSTM_W, SSD_LSTM_X, SSD_LSTM_MAX_CELLS = 33728, 32, 256
 LSTM_CELL_SIZES = (64, 128, 256)
@@ -180,12 +192,14 @@ SYMBOLS = ("ssd_create", "ssd_destroy", "ssd_reset", "ssd_step", "ssd_step_rando
            "ssd_stats_create", "ssd_stats_destroy", "ssd_stats_fold", "ssd_stats_set_chunk", "ssd_stats_discard", "ssd_stats_drain",
            "ssd_stats_last_error", "ssd_policy_forward", "ssd_policy_last_error", "ssd_rollout_policy",
            "ssd_policy_lstm_forward", "ssd_rollout_policy_lstm", "ssd_policy_moa_forward", "ssd_rollout_policy_moa",
-           "ssd_ws_policy_forward", "ssd_ws_rollout_policy", "ssd_advantages", "ssd_advantages_last_error")
+           "ssd_ws_policy_forward", "ssd_ws_rollout_policy", "ssd_advantages", "ssd_advantages_last_error",
+           "ssd_policy_ppo_grad")
 # added after ABI 6 without a version bump (the calls are additive): a library built before them lacks them
 LSTM_SYMBOLS = ("ssd_policy_lstm_forward", "ssd_rollout_policy_lstm")
 MOA_SYMBOLS = ("ssd_policy_moa_forward", "ssd_rollout_policy_moa")
 WS_POLICY_SYMBOLS = ("ssd_ws_policy_forward", "ssd_ws_rollout_policy")
 ADVANTAGES_SYMBOLS = ("ssd_advantages", "ssd_advantages_last_error")
+PPO_SYMBOLS = ("ssd_policy_ppo_grad",)
 
 
 class SsdConfig(C.Structure):
@@ -298,9 +312,9 @@ def lib():
         L.ssd_policy_last_error.argtypes = []
         L.ssd_policy_last_error.restype = C.c_char_p
         L.ssd_rollout_policy.argtypes = [vp, vp, i32, vp, i32, i32] + [vp] * 7 + [i32, vp, u32, vp]
-        missing = [name for name in LSTM_SYMBOLS + MOA_SYMBOLS + WS_POLICY_SYMBOLS + ADVANTAGES_SYMBOLS if not hasattr(L, name)]
+        missing = [name for name in LSTM_SYMBOLS + MOA_SYMBOLS + WS_POLICY_SYMBOLS + ADVANTAGES_SYMBOLS + PPO_SYMBOLS if not hasattr(L, name)]
         if missing:
-            raise SsdError("%s lacks %s (built before the recurrent, MOA or Watershed policy calls or the advantages call): rebuild it with `python -c 'import "
+            raise SsdError("%s lacks %s (built before the recurrent, MOA or Watershed policy calls, the advantages call or the PPO gradient call): rebuild it with `python -c 'import "
                            "__graft_entry__ as g; g.build()'`" % (LIB_PATH, ", ".join(missing)))
         L.ssd_policy_lstm_forward.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, u32, vp]
         L.ssd_rollout_policy_lstm.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, vp, i32, i32] + [vp] * 8 + [i32, vp, u32, vp]
@@ -312,6 +326,7 @@ def lib():
         L.ssd_advantages.argtypes = [vp, vp, C.c_double, vp, vp, vp, i32, i32, i32, i32, C.c_double, C.c_double, u32, vp, vp, i32, vp]
         L.ssd_advantages_last_error.argtypes = []
         L.ssd_advantages_last_error.restype = C.c_char_p
+        L.ssd_policy_ppo_grad.argtypes = [vp, i32, i32] + [vp] * 8 + [i32, i32, i32] + [C.c_double] * 5 + [vp, vp, vp, i32, u32, vp]
         for name in SYMBOLS:
             getattr(L, name)
         if L.ssd_abi_version() != ABI_VERSION:

@@ -11,12 +11,13 @@
 //      are added through LDS.  fc1's weights stream from L2 (130 KB per set, shared by every workgroup of the set);
 //   4. fc2, the logits and the value on the VALU (1.3 kMAC per env);
 //   5. rollouts: one thread per env picks the action (greedy or the S_POLICY draw) and its log-probability.
-// Steps 3 and 4 to fc2 are fc_stack below; the heads and the action are ssd_policy_device.hpp's (heads, pick_actions), shared
-// with the recurrent kernels.  Every sum is in a fixed order, so two calls on the same input agree bit for bit.  kModeFeatures
-// stops after fc2 and writes its output instead: the trunk of the recurrent policy (ssd_policy_lstm.hip).  kModeMoa runs
-// fc_stack once per FC stack of the MOA policy, with tanh for ReLU, on the same conv output and writes both outputs
-// (ssd_policy_moa.hip).  This file also holds the argument checks every policy entry point shares (check_policy_net,
-// check_state_out, select_device; declared in ssd_policy.hpp).
+// Step 2 is conv_tile and steps 3 and 4 to fc2 are fc_stack, both ssd_policy_device.hpp's (shared with the PPO gradient kernel,
+// ssd_policy_grad.hip), as are the heads and the action (heads, pick_actions), shared with the recurrent kernels.  Every sum
+// is in a fixed order, so two calls on the same input agree bit for bit.  kModeFeatures stops after fc2 and writes its output
+// instead: the trunk of the recurrent policy (ssd_policy_lstm.hip).  kModeMoa runs fc_stack once per FC stack of the MOA
+// policy, with tanh for ReLU, on the same conv output and writes both outputs (ssd_policy_moa.hip).  This file also holds the
+// argument checks every policy entry point shares (check_policy_net, check_state_out, select_device; declared in
+// ssd_policy.hpp).
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -28,78 +29,11 @@
 
 namespace {
 
-constexpr int kTile = 16;          // envs per workgroup: M of the fc1 tile
-constexpr int kThreads = 256;      // 4 waves
-constexpr int kObs = 675;          // 15 * 15 * 3 bytes
-constexpr int kPos = 169;          // 13 * 13 conv outputs per filter
-constexpr int kFlat = 1014;        // 13 * 13 * 6
-constexpr int kPitch = 1017;       // LDS pitch (floats) of a row of conv outputs: 1014 + zero padding, odd against bank conflicts
-constexpr int kKSteps = 254;       // fc1: K = 1014 padded to 1016 = 254 MFMA k-steps of 4
-constexpr int kHalf = kKSteps / 2; // k-steps per wave (odd: 63 pairs and one more)
-constexpr int kHP = 33;            // LDS pitch of the hidden layers
-
-static_assert(kThreads == 256, "one thread per entry of the normalisation table");
-static_assert(SSD_POL_FC1_B == SSD_POL_FC1_W + kFlat * 32 && SSD_POL_FC2_W == SSD_POL_FC1_B + 32 && SSD_POL_FC2_B == SSD_POL_FC2_W + 1024 &&
-              SSD_POL_VALUE_W == SSD_POL_FC2_B + 32 && SSD_POL_VALUE_B == SSD_POL_VALUE_W + 32 && SSD_POL_LOGITS_W >= SSD_POL_VALUE_B + 1,
-              "weight layout of include/ssd.h");
+using namespace ssd::trunk;      // the tile constants, conv_tile and fc_stack (ssd_policy_device.hpp)
 
 using ssd::f32x4;
 
 constexpr int kModeHeads = 0, kModeFeatures = 1, kModeMoa = 2;
-
-// Steps 3 and 4 up to fc2 on the conv output in s_conv: fc1 on the matrix cores, its two K halves added through LDS, fc2 on the
-// VALU; ReLU after both layers, or tanh (the MOA policy's stacks).  ws: a weight set's base, moved so that SSD_POL_FC1_W ..
-// SSD_POL_FC2_B address the stack's layers.  fc2's output of tile row m < rows goes to out[m * stride + 0..31].
-template <bool kTanh>
-__device__ __forceinline__ void fc_stack(const float *__restrict__ ws, const float *s_conv, float *s_part, float *s_h1, int tid,
-                                         float *out, size_t stride, int rows) {
-    const auto act = [](float x) { return kTanh ? tanhf(x) : fmaxf(x, 0.f); };
-    // fc1: A[m][k] = conv row m, B[k][n] = fc1_w[k][n] (the lane layout: ssd_policy_device.hpp)
-    const int wave = tid >> 6, lane = tid & 63, nt = wave & 1, kh = wave >> 1;
-    const int l15 = lane & 15, l4 = lane >> 4;
-    const float *a_row = s_conv + l15 * kPitch + l4;
-    const float *w1 = ws + SSD_POL_FC1_W + l4 * 32 + nt * 16 + l15;
-    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
-    // (wave half 0: k-steps 0..126; half 1: 127..253, whose last step is peeled -- its rows 1014, 1015 are padding)
-    const int kb = kh * kHalf;
-#pragma unroll 4
-    for (int p = 0; p < (kHalf - 1) / 2; ++p) {
-        const int kk = kb + 2 * p;
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a_row[4 * kk], w1[(size_t)kk * 128], acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a_row[4 * kk + 4], w1[(size_t)kk * 128 + 128], acc1, 0, 0, 0);
-    }
-    {
-        const int kl = kb + kHalf - 1;
-        const float bv = 4 * kl + l4 < kFlat ? w1[(size_t)kl * 128] : 0.f;
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a_row[4 * kl], bv, acc0, 0, 0, 0);
-    }
-    const f32x4 acc = acc0 + acc1;
-    if (kh) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) s_part[(nt * 16 + l4 * 4 + r) * 16 + l15] = acc[r];
-    }
-    __syncthreads();
-    if (!kh) {
-        const int n = nt * 16 + l15;
-        const float bias = ws[SSD_POL_FC1_B + n];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int m = l4 * 4 + r;
-            s_h1[m * kHP + n] = act(acc[r] + s_part[(nt * 16 + m) * 16 + l15] + bias);
-        }
-    }
-    __syncthreads();
-    // fc2: thread (m, n) takes columns n and n + 16 of row m
-    const int m = tid >> 4, n = tid & 15;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int nn = n + 16 * h;
-        float s = 0.f;
-#pragma unroll 8
-        for (int k = 0; k < 32; ++k) s = fmaf(s_h1[m * kHP + k], ws[SSD_POL_FC2_W + k * 32 + nn], s);
-        if (m < rows) out[m * stride + nn] = act(s + ws[SSD_POL_FC2_B + nn]);
-    }
-}
 
 // kModeFeatures: stop after fc2 and write its output to a.feat (the trunk of the recurrent policy, ssd_policy_lstm.hip).
 // kModeMoa: both FC stacks of the MOA policy after the conv (stack s's weights at SSD_MOA_FC1_W(s), the trunk's relative
@@ -138,25 +72,7 @@ __global__ void __launch_bounds__(kThreads) ssd_policy_kernel(ssd::PolicyArgs a)
     __syncthreads();
 
     // ---- 2. conv 3x3, 6 filters, ReLU; output (row, col, channel) ----
-    for (int q = tid; q < kTile * kPos; q += kThreads) {
-        const int r = q / kPos, pos = q - r * kPos, y = pos / 13, x = pos - y * 13;
-        const uint8_t *src = s_obs + r * kObs + (y * 15 + x) * 3;
-        float acc[6];
-#pragma unroll
-        for (int f = 0; f < 6; ++f) acc[f] = 0.f;
-#pragma unroll
-        for (int dy = 0; dy < 3; ++dy) {
-#pragma unroll
-            for (int j = 0; j < 9; ++j) {                   // (dx, c) = (j / 3, j % 3): 9 contiguous bytes of view row y + dy
-                const float v = s_norm[src[dy * 45 + j]];
-#pragma unroll
-                for (int f = 0; f < 6; ++f) acc[f] = fmaf(v, w[SSD_POL_CONV_W + (dy * 9 + j) * 6 + f], acc[f]);
-            }
-        }
-        float *dst = s_conv + r * kPitch + pos * 6;
-#pragma unroll
-        for (int f = 0; f < 6; ++f) dst[f] = fmaxf(acc[f] + w[SSD_POL_CONV_B + f], 0.f);
-    }
+    conv_tile(w, s_obs, s_norm, s_conv, tid);
     __syncthreads();
 
     // ---- 3, 4. fc1, fc2 (fc_stack) ----

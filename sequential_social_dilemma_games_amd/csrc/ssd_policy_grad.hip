@@ -1,0 +1,412 @@
+// ssd_policy_grad.hip -- RLlib's PPO loss of the conv-FC policy network on a sampled fragment, its statistics and the gradient of
+// every parameter: ssd_policy_ppo_grad.  include/ssd.h states the contract (rows, the observation shift, the loss, the derivatives
+// at the kinks, the order of the sums); DESIGN.md section 16 the shape and the measurements.
+//
+// Workgroups are persistent: workgroup (g, p) of a (G, P) grid takes the 16-row tiles g, g + G, ... of weight set p, so what a
+// workgroup sums, and in which order, is a function of (K, E, N, P) alone.  Per tile:
+//   1. the forward of ssd_policy.hip from the shared pieces (conv_tile and fc_stack, head): conv output, h1, h2, the logits and
+//      the value stay in LDS;
+//   2. one thread per row: the loss terms, the statistics (float64 sums) and d row_loss / d (logits, value);
+//   3. the backward through the heads, fc2 and fc1 on the VALU (a few kMAC per row), each thread keeping the sums of the
+//      gradient entries it owns in registers across tiles;
+//   4. dW1 += conv^T dh1 (1014 x 16 . 16 x 32) on the matrix cores, v_mfma_f32_16x16x4_f32: wave w owns rows 256 w .. 256 w + 255
+//      of dW1, 32 accumulator tiles = 128 registers a lane, kept across tiles;
+//   5. dconv = dh1 W1^T (16 x 32 . 32 x 1014) on the matrix cores, masked by the conv's ReLU and written over the conv output in
+//      LDS (wave w writes the 256 columns only it read in 4);
+//   6. the conv's weight gradient: thread (tap, slice) sums x[tap] * dconv[f] over every ninth (row, position) for the six
+//      filters; the slices are added in order when the workgroup is done.
+// At the end a workgroup writes its partial gradient set and statistics to the caller's scratch; a second kernel adds the G
+// partials of a set in order (float64), scales by 1 / rows and rounds once.  No atomics anywhere: the same inputs give the same
+// bits.
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/ssd.h"
+#include "ssd_policy_device.hpp"
+
+namespace {
+
+using namespace ssd::trunk;      // the tile constants, conv_tile and fc_stack (ssd_policy_device.hpp)
+using ssd::f32x4;
+
+constexpr int kSlices = 9;                  // step 6: 27 taps x 9 slices = 243 threads
+constexpr int kStatFloats = SSD_PPO_STAT_FLOATS;
+
+struct GradArgs {
+    const float *w;                // P weight sets
+    int32_t P, A, N, set_floats;
+    int32_t G;                     // workgroups per set
+    int32_t set_rows;              // rows of one set
+    int32_t step_rows;             // E * N: rows of one step
+    const uint8_t *obs_first;      // u8 [E][N][675] or null
+    const uint8_t *obs;            // u8 [K][E][N][675]
+    const int32_t *actions;        // [K][E][N]
+    const float *logp_old, *adv, *vt, *vf_pred;   // [K][E][N]
+    const float *beh;              // [K][E][N][A] or null
+    float clip, vf_clip, vf_coeff, ent_coeff, kl_coeff;
+    float *scratch;                // [P][G][set_floats + kStatFloats]
+    float *grads;                  // [P][set_floats]
+    double *stats;                 // [P][5]
+};
+
+__global__ void __launch_bounds__(kThreads) ssd_ppo_grad_kernel(GradArgs a) {
+    __shared__ float s_norm[256];
+    __shared__ float s_conv[kTile * kPitch + 8];       // the conv output; after step 5, d loss / d conv.  (+ 8: step 4's last A rows)
+    __shared__ float s_obsf[(kTile * kObs + 3) / 4];   // the observation bytes
+    __shared__ float s_part[512];                      // [2][16][16] fc1 partial sums of the second K half
+    __shared__ float s_h1[kTile * kHP], s_h2[kTile * kHP], s_dh1[kTile * kHP], s_dh2[kTile * kHP];
+    __shared__ float s_out[kTile * 16];                // logits 0..A-1, value at A
+    __shared__ float s_dout[kTile * 16];               // d row_loss / d (logits, value); zero beyond A and for rows past the set
+    __shared__ double s_stat[kTile * 5];
+    uint8_t *s_obs = reinterpret_cast<uint8_t *>(s_obsf);
+
+    const int tid = threadIdx.x, g = blockIdx.x, p = blockIdx.y;
+    const int A = a.A, R = a.set_rows;
+    const int stride = a.P == 1 ? 1 : a.N;             // a set's row r is row r * stride + p of the [K][E][N] arrays
+    const float *w_set = a.w + (size_t)p * (size_t)a.set_floats;
+    const int wave = tid >> 6, lane = tid & 63, l15 = lane & 15, l4 = lane >> 4;
+
+    s_norm[tid] = (float)(((double)tid - 128.0) / 255.0);
+    if (tid < kTile * (kPitch - kFlat)) s_conv[(tid / 3) * kPitch + kFlat + tid % 3] = 0.f;
+    if (tid < 8) s_conv[kTile * kPitch + tid] = 0.f;
+
+    // the sums this thread owns, kept across tiles
+    f32x4 acc_w1[16][2];                               // step 4: dW1 rows 16 (16 wave + t) + 4 l4 + r, column 16 c + l15
+#pragma unroll
+    for (int t = 0; t < 16; ++t) acc_w1[t][0] = acc_w1[t][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float acc_hd[2] = {0.f, 0.f};                      // heads' kernels: entry q = tid + 256 u is (k, j) = (q >> 4, q & 15); j == A: the value
+    float acc_w2[4] = {0.f, 0.f, 0.f, 0.f};            // fc2_w entry q = tid + 256 u is (k, n) = (q >> 5, q & 31)
+    float acc_b1 = 0.f, acc_b2 = 0.f, acc_bh = 0.f;    // tid < 32: fc1_b, fc2_b; tid < 16: the heads' biases
+    float acc_cw[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // step 6: conv_w [tap][f] of this thread's slice
+    float acc_cb[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // ... and conv_b [f] (tap 0's threads)
+    double st[5] = {0.0, 0.0, 0.0, 0.0, 0.0};          // tid < 16: total, policy, vf, kl, entropy of tile row tid
+
+    const int tiles = R / kTile + (R % kTile != 0);
+    for (int tile = g; tile < tiles; tile += a.G) {
+        const int r0 = tile * kTile;
+        // (the weights' address passes through an empty asm each tile: without it every weight load of the body is loop
+        // invariant, the compiler hoists some hundreds of them out of the tile loop and spills them)
+        asm volatile("" : "+s"(w_set));
+        const float *__restrict__ w = w_set;
+        __syncthreads();                               // the previous tile's step 6 has read s_obs and s_conv
+        // ---- 1. the forward ----
+        {   // 16 threads a row, byte c + 16 u of it each (every load of the thread issued before the first store)
+            constexpr int kLoads = (kObs + 15) / 16;
+            const int m = tid >> 4, c = tid & 15, r = r0 + m;
+            const uint8_t *src = nullptr;
+            if (r < R) {
+                const size_t row = (size_t)r * stride + p;
+                if (!a.obs_first) src = a.obs + row * kObs + c;
+                else if (row < (size_t)a.step_rows) src = a.obs_first + row * kObs + c;     // k = 0
+                else src = a.obs + (row - a.step_rows) * kObs + c;                          // row k reads obs[k - 1]
+            }
+            uint8_t v[kLoads];
+#pragma unroll
+            for (int u = 0; u < kLoads; ++u) v[u] = src && c + 16 * u < kObs ? src[16 * u] : (uint8_t)128;
+#pragma unroll
+            for (int u = 0; u < kLoads; ++u)
+                if (c + 16 * u < kObs) s_obs[m * kObs + c + 16 * u] = v[u];
+        }
+        __syncthreads();
+        conv_tile(w, s_obs, s_norm, s_conv, tid);
+        __syncthreads();
+        fc_stack<false>(w, s_conv, s_part, s_h1, tid, s_h2, kHP, kTile);
+        __syncthreads();
+        {
+            const int m = tid >> 4, j = tid & 15;
+            if (j <= A)
+                s_out[tid] = ssd::head<32>(s_h2 + m * kHP, w + SSD_POL_LOGITS_W, w + SSD_POL_VALUE_W, w + SSD_POL_LOGITS_W + 32 * A,
+                                           w + SSD_POL_VALUE_B, A, j);
+            s_dout[tid] = 0.f;
+        }
+        __syncthreads();
+
+        // ---- 2. the loss terms of row tid and their derivatives ----
+        if (tid < kTile && r0 + tid < R) {
+            const size_t row = (size_t)(r0 + tid) * stride + p;
+            const float *l = s_out + tid * 16;
+            float *d = s_dout + tid * 16;
+            const float value = l[A];
+            int act = a.actions[row];
+            act = act < 0 ? 0 : (act >= A ? A - 1 : act);
+            const float adv = a.adv[row], vt = a.vt[row], vfp = a.vf_pred[row], lpo = a.logp_old[row];
+            float mx = l[0];
+            for (int k = 1; k < A; ++k) mx = fmaxf(mx, l[k]);
+            float s = 0.f;
+            for (int k = 0; k < A; ++k) s += expf(l[k] - mx);
+            const float lse = mx + logf(s);
+            float ent = 0.f;
+            for (int k = 0; k < A; ++k) {
+                const float lp = l[k] - lse;
+                ent -= expf(lp) * lp;
+            }
+            float kl = 0.f;
+            float bl_lse = 0.f;
+            const float *bl = a.beh ? a.beh + row * A : nullptr;
+            if (bl) {
+                float bm = bl[0];
+                for (int k = 1; k < A; ++k) bm = fmaxf(bm, bl[k]);
+                float bs = 0.f;
+                for (int k = 0; k < A; ++k) bs += expf(bl[k] - bm);
+                bl_lse = bm + logf(bs);
+                for (int k = 0; k < A; ++k) {
+                    const float blp = bl[k] - bl_lse;
+                    kl += expf(blp) * (blp - (l[k] - lse));
+                }
+            }
+            const float logp = l[act] - lse;
+            const float ratio = expf(logp - lpo);
+            const float lo = 1.f - a.clip, hi = 1.f + a.clip;
+            const float s1 = adv * ratio, s2 = adv * fminf(fmaxf(ratio, lo), hi);
+            const float surr = fminf(s1, s2);
+            const float dsurr = ((ratio >= lo && ratio <= hi) || s1 < s2) ? adv : 0.f;     // d surr / d ratio
+            const float d1 = value - vt, dv = value - vfp;
+            const float d2 = (vfp + fminf(fmaxf(dv, -a.vf_clip), a.vf_clip)) - vt;
+            const float vf1 = d1 * d1, vf2 = d2 * d2;
+            const float vf = fmaxf(vf1, vf2);
+            const float dvf = (fabsf(dv) <= a.vf_clip || vf1 >= vf2) ? 2.f * d1 : 0.f;     // d vf / d value
+            const float row_loss = ((-surr + a.kl_coeff * kl) + a.vf_coeff * vf) - a.ent_coeff * ent;
+            st[0] += (double)row_loss; st[1] += (double)(-surr); st[2] += (double)vf; st[3] += (double)kl; st[4] += (double)ent;
+            const float gl = -dsurr * ratio;           // d row_loss / d logp
+            for (int k = 0; k < A; ++k) {
+                const float lp = l[k] - lse, pk = expf(lp);
+                float dk = gl * ((k == act ? 1.f : 0.f) - pk) + a.ent_coeff * (pk * (lp + ent));
+                if (bl) dk += a.kl_coeff * (pk - expf(bl[k] - bl_lse));
+                d[k] = dk;
+            }
+            d[A] = a.vf_coeff * dvf;
+        }
+        __syncthreads();
+
+        // ---- 3. the backward through the heads, fc2 and fc1's activation ----
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {                  // the heads' kernels, and dh2 through h2's ReLU
+            const int q = tid + u * kThreads, k = q >> 4, j = q & 15;
+            float sum = 0.f;
+#pragma unroll
+            for (int m = 0; m < kTile; ++m) sum = fmaf(s_h2[m * kHP + k], s_dout[m * 16 + j], sum);
+            acc_hd[u] += sum;
+            const int m = q >> 5, n = q & 31;          // dh2[m][n] = sum_j dout[m][j] * W[n][j]
+            float dh = 0.f;
+            for (int jj = 0; jj < A; ++jj) dh = fmaf(s_dout[m * 16 + jj], w[SSD_POL_LOGITS_W + n * A + jj], dh);
+            dh = fmaf(s_dout[m * 16 + A], w[SSD_POL_VALUE_W + n], dh);
+            s_dh2[m * kHP + n] = s_h2[m * kHP + n] > 0.f ? dh : 0.f;
+        }
+        if (tid < 16) {
+            float sum = 0.f;
+#pragma unroll
+            for (int m = 0; m < kTile; ++m) sum += s_dout[m * 16 + tid];
+            acc_bh += sum;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {                  // fc2's kernel
+            const int q = tid + u * kThreads, k = q >> 5, n = q & 31;
+            float sum = 0.f;
+#pragma unroll
+            for (int m = 0; m < kTile; ++m) sum = fmaf(s_h1[m * kHP + k], s_dh2[m * kHP + n], sum);
+            acc_w2[u] += sum;
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {                  // dh1[m][k] = sum_n dh2[m][n] * fc2_w[k][n], through h1's ReLU
+            const int q = tid + u * kThreads, m = q >> 5, k = q & 31;
+            float dh = 0.f;
+#pragma unroll 8
+            for (int n = 0; n < 32; ++n) dh = fmaf(s_dh2[m * kHP + n], w[SSD_POL_FC2_W + k * 32 + n], dh);
+            s_dh1[m * kHP + k] = s_h1[m * kHP + k] > 0.f ? dh : 0.f;
+        }
+        if (tid < 32) {
+            float sum = 0.f;
+#pragma unroll
+            for (int m = 0; m < kTile; ++m) sum += s_dh2[m * kHP + tid];
+            acc_b2 += sum;
+        }
+        __syncthreads();
+        if (tid < 32) {
+            float sum = 0.f;
+#pragma unroll
+            for (int m = 0; m < kTile; ++m) sum += s_dh1[m * kHP + tid];
+            acc_b1 += sum;
+        }
+
+        // ---- 4. dW1 += conv^T dh1: A[c][m] = conv[m][c], B[m][n] = dh1[m][n] (the lane layout: ssd_policy_device.hpp) ----
+        {
+            const float *a_base = s_conv + l4 * kPitch + 256 * wave + l15;
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                const float b0 = s_dh1[(4 * ks + l4) * kHP + l15], b1 = s_dh1[(4 * ks + l4) * kHP + 16 + l15];
+#pragma unroll
+                for (int t = 0; t < 16; ++t) {
+                    const float av = a_base[4 * ks * kPitch + 16 * t];
+                    acc_w1[t][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b0, acc_w1[t][0], 0, 0, 0);
+                    acc_w1[t][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b1, acc_w1[t][1], 0, 0, 0);
+                }
+            }
+        }
+        __syncthreads();
+
+        // ---- 5. dconv = dh1 W1^T through the conv's ReLU, over the conv output: A[m][k] = dh1[m][k], B[k][c] = fc1_w[c][k] ----
+        {
+            float av[8];
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) av[ks] = s_dh1[l15 * kHP + 4 * ks + l4];
+#pragma unroll 2
+            for (int t = 0; t < 16; ++t) {
+                const int c = 256 * wave + 16 * t + l15;
+                const float *wc = w + SSD_POL_FC1_W + (size_t)c * 32 + l4;
+                float bv[8];
+#pragma unroll
+                for (int ks = 0; ks < 8; ++ks) bv[ks] = c < kFlat ? wc[4 * ks] : 0.f;
+                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int ks = 0; ks < 8; ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[ks], bv[ks], acc, 0, 0, 0);
+                if (c < kFlat) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        float *dst = s_conv + (4 * l4 + r) * kPitch + c;
+                        *dst = *dst > 0.f ? acc[r] : 0.f;
+                    }
+                }
+            }
+        }
+        __syncthreads();
+
+        // ---- 6. the conv's weight gradient: thread (tap, slice) over (row, position) slice, slice + 9, ... ----
+        if (tid < 27 * kSlices) {
+            const int tap = tid / kSlices, sl = tid - tap * kSlices;     // tap = dy * 9 + j: byte dy * 45 + j of the window
+            const int off = (tap / 9) * 45 + tap % 9;
+            for (int q = sl; q < kTile * kPos; q += kSlices) {
+                const int m = q / kPos, pos = q - m * kPos, y = pos / 13, x = pos - y * 13;
+                const float v = s_norm[s_obs[m * kObs + (y * 15 + x) * 3 + off]];
+                const float *dc = s_conv + m * kPitch + pos * 6;
+#pragma unroll
+                for (int f = 0; f < 6; ++f) acc_cw[f] = fmaf(v, dc[f], acc_cw[f]);
+                if (tap == 0) {                            // conv_b: tap 0's nine threads, the same slices
+#pragma unroll
+                    for (int f = 0; f < 6; ++f) acc_cb[f] += dc[f];
+                }
+            }
+        }
+    }
+
+    // ---- the workgroup's partial set and statistics ----
+    float *part = a.scratch + ((size_t)p * a.G + g) * (size_t)(a.set_floats + kStatFloats);
+    __syncthreads();
+    float *s_red = s_conv;                             // [27][kSlices][6] conv_w slices, then [kSlices][6] conv_b slices
+    if (tid < 27 * kSlices) {
+#pragma unroll
+        for (int f = 0; f < 6; ++f) s_red[tid * 6 + f] = acc_cw[f];
+        if (tid < kSlices) {
+#pragma unroll
+            for (int f = 0; f < 6; ++f) s_red[27 * kSlices * 6 + tid * 6 + f] = acc_cb[f];
+        }
+    }
+    if (tid < kTile) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k) s_stat[tid * 5 + k] = st[k];
+    }
+    __syncthreads();
+    if (tid < 168) {                                   // conv_w [27][6], then conv_b [6]: the slices in order
+        const float *src = tid < 162 ? s_red + (tid / 6) * kSlices * 6 + tid % 6 : s_red + 27 * kSlices * 6 + (tid - 162);
+        float sum = 0.f;
+#pragma unroll
+        for (int sl = 0; sl < kSlices; ++sl) sum += src[sl * 6];
+        part[SSD_POL_CONV_W + tid] = sum;
+    }
+    if (tid < 5) {
+        double sum = 0.0;
+        for (int m = 0; m < kTile; ++m) sum += s_stat[m * 5 + tid];
+        reinterpret_cast<double *>(part + a.set_floats)[tid] = sum;
+    }
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = 256 * wave + 16 * t + 4 * l4 + r;
+                if (row < kFlat) part[SSD_POL_FC1_W + row * 32 + 16 * c + l15] = acc_w1[t][c][r];
+            }
+        }
+    }
+    if (tid < 32) {
+        part[SSD_POL_FC1_B + tid] = acc_b1;
+        part[SSD_POL_FC2_B + tid] = acc_b2;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) part[SSD_POL_FC2_W + tid + u * kThreads] = acc_w2[u];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int q = tid + u * kThreads, k = q >> 4, j = q & 15;
+        if (j < A) part[SSD_POL_LOGITS_W + k * A + j] = acc_hd[u];
+        else if (j == A) part[SSD_POL_VALUE_W + k] = acc_hd[u];
+    }
+    if (tid < A) part[SSD_POL_LOGITS_W + 32 * A + tid] = acc_bh;
+    else if (tid == A) part[SSD_POL_VALUE_B] = acc_bh;
+}
+
+// The G partials of a set added in order g = 0 .. G - 1 in float64, times 1 / rows, rounded once; the padding floats are zero.
+__global__ void __launch_bounds__(256) ssd_ppo_reduce_kernel(GradArgs a) {
+    const int idx = blockIdx.x * 256 + threadIdx.x, p = blockIdx.y, S = a.set_floats;
+    const size_t pitch = (size_t)S + kStatFloats;
+    const float *part = a.scratch + (size_t)p * a.G * pitch;
+    if (idx < S) {
+        const bool pad = (idx > SSD_POL_VALUE_B && idx < SSD_POL_LOGITS_W) || idx >= SSD_POL_LOGITS_W + 33 * a.A;
+        double sum = 0.0;
+        if (!pad)
+            for (int g = 0; g < a.G; ++g) sum += (double)part[g * pitch + idx];
+        a.grads[(size_t)p * S + idx] = (float)(sum / (double)a.set_rows);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 5) {
+        double sum = 0.0;
+        for (int g = 0; g < a.G; ++g) sum += reinterpret_cast<const double *>(part + g * pitch + S)[threadIdx.x];
+        a.stats[p * 5 + threadIdx.x] = sum / (double)a.set_rows;
+    }
+}
+
+}  // namespace
+
+extern "C" int ssd_policy_ppo_grad(const float *weights, int32_t num_sets, int32_t num_actions, const uint8_t *obs_first,
+                                   const uint8_t *obs, const int32_t *actions, const float *logp_old, const float *advantages,
+                                   const float *value_targets, const float *vf_preds, const float *behaviour_logits, int32_t n_steps,
+                                   int32_t num_envs, int32_t num_agents, double clip_param, double vf_clip_param,
+                                   double vf_loss_coeff, double entropy_coeff, double kl_coeff, float *scratch, float *grads,
+                                   double *stats, int32_t device_id, uint32_t flags, void *stream) {
+    using ssd::policy_fail;
+    if (!weights) return policy_fail("weights are required");
+    if (const char *why = ssd::check_policy_net(ssd::kNetConvFc, weights, num_sets, num_agents, num_actions)) return policy_fail(why);
+    if (n_steps < 1 || num_envs < 1) return policy_fail("n_steps and num_envs must be >= 1");
+    const int64_t rows = (int64_t)n_steps * num_envs * num_agents;
+    if (rows > INT32_MAX - 16) return policy_fail("n_steps * num_envs * num_agents must be at most 2^31 - 17");   // (row + 15 is an int)
+    if (!obs && !(obs_first && n_steps == 1)) return policy_fail("obs is required (it may be null only with obs_first and n_steps 1)");
+    if (!actions || !logp_old || !advantages || !value_targets || !vf_preds)
+        return policy_fail("actions, logp_old, advantages, value_targets and vf_preds are required");
+    if (!scratch || !grads || !stats) return policy_fail("scratch, grads and stats are required");
+    if ((reinterpret_cast<uintptr_t>(scratch) & 7u) || (reinterpret_cast<uintptr_t>(stats) & 7u))
+        return policy_fail("scratch and stats must be 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(grads) & 3u) return policy_fail("grads must be 4-byte aligned");
+    if (!(isfinite(clip_param) && isfinite(vf_clip_param) && isfinite(vf_loss_coeff) && isfinite(entropy_coeff) && isfinite(kl_coeff)))
+        return policy_fail("the hyper-parameters must be finite");
+    if (clip_param < 0.0 || vf_clip_param < 0.0) return policy_fail("clip_param and vf_clip_param must be >= 0");
+    if ((kl_coeff != 0.0) != (behaviour_logits != nullptr))
+        return policy_fail("behaviour_logits must be given if and only if kl_coeff is not 0");
+    if (flags) return policy_fail("flags must be 0");
+    if (const int rc = ssd::policy_use_device(device_id)) return rc;
+    GradArgs a{};
+    a.w = weights; a.P = num_sets; a.A = num_actions; a.N = num_agents; a.set_floats = SSD_POL_SET_FLOATS(num_actions);
+    a.set_rows = (int32_t)(rows / num_sets);
+    a.G = SSD_PPO_GROUPS(a.set_rows, num_sets);
+    a.step_rows = num_envs * num_agents;
+    a.obs_first = obs_first; a.obs = obs; a.actions = actions; a.logp_old = logp_old; a.adv = advantages; a.vt = value_targets;
+    a.vf_pred = vf_preds; a.beh = behaviour_logits;
+    a.clip = (float)clip_param; a.vf_clip = (float)vf_clip_param; a.vf_coeff = (float)vf_loss_coeff;
+    a.ent_coeff = (float)entropy_coeff; a.kl_coeff = (float)kl_coeff;
+    a.scratch = scratch; a.grads = grads; a.stats = stats;
+    hipLaunchKernelGGL(ssd_ppo_grad_kernel, dim3((unsigned)a.G, (unsigned)a.P), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+    if (const hipError_t e = hipGetLastError()) return ssd::policy_launched(e);
+    hipLaunchKernelGGL(ssd_ppo_reduce_kernel, dim3((unsigned)((a.set_floats + 255) / 256), (unsigned)a.P), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), a);
+    return ssd::policy_launched(hipGetLastError());
+}

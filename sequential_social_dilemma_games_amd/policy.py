@@ -212,6 +212,11 @@ class ConvFCPolicy(PolicyBase):
     def set_floats(self):
         return _capi.SSD_POL_SET_FLOATS(self.num_actions)
 
+    def ppo_scratch_shape(self, set_rows):
+        """The float32 scratch ssd_policy_ppo_grad needs for a fragment with `set_rows` rows per weight set (K E for num_sets =
+        N, K E N for num_sets = 1): the workgroups' partial gradient sets and statistics."""
+        return (_capi.SSD_PPO_SCRATCH_FLOATS(set_rows, self.num_sets, self.num_actions),)
+
     def forward(self, obs):
         h, lead = _trunk(self, obs)
         logits, value = _heads(h, self.logits_w, self.logits_b, self.value_w, self.value_b)
@@ -540,6 +545,195 @@ def influence(logits, cf_logits, actions, clip=10.0):
     kl = torch.where(p != 0, p * (lp - lq), torch.zeros((), dtype=p.dtype, device=p.device)).sum(-1).sum(-1)
     kl = torch.where(torch.isfinite(kl), kl, torch.zeros((), dtype=kl.dtype, device=kl.device))
     return kl.clamp(-float(clip), float(clip))
+
+
+# ---- the PPO loss and its gradients for the conv-FC policy (include/ssd.h, PPO LOSS AND GRADIENTS; csrc/ssd_policy_grad.hip) ----
+
+PPO_STATS = ("total_loss", "policy_loss", "vf_loss", "kl", "entropy")      # the columns of the library's stats, in order
+_PPO_KEYS = (("obs", ("obs",)), ("actions", ("actions",)), ("logp_old", ("logp_old", "logp")),
+             ("advantages", ("advantages",)), ("value_targets", ("value_targets",)), ("vf_pred", ("vf_pred", "value")),
+             ("behaviour_logits", ("behaviour_logits", "logits")))
+
+
+def _ppo_tensors(policy, batch, obs_first, kl_coeff):
+    """The loss's inputs by their contract names from the dict sample() returns (logp as logp_old, value as vf_pred, logits
+    as behaviour_logits) or a tuple in _PPO_KEYS' order, checked against each other: K from actions [K, E, N]."""
+    if isinstance(batch, dict):
+        t = {name: next((batch[k] for k in keys if k in batch), None) for name, keys in _PPO_KEYS}
+    else:
+        vals = tuple(batch)
+        if not 6 <= len(vals) <= 7:
+            raise ValueError("the tensors are (obs, actions, logp_old, advantages, value_targets, vf_pred[, behaviour_logits])")
+        t = dict(zip((name for name, _ in _PPO_KEYS), vals + (None,) * (7 - len(vals))))
+    for name in ("actions", "logp_old", "advantages", "value_targets", "vf_pred"):
+        if not isinstance(t[name], torch.Tensor):
+            raise ValueError("%s is required" % name)
+    acts = t["actions"]
+    if acts.dim() != 3 or acts.numel() == 0:
+        raise ValueError("actions must be [K, E, N], got %s" % (tuple(acts.shape),))
+    K, E, N = (int(n) for n in acts.shape)
+    A, P, dev = policy.num_actions, policy.num_sets, acts.device
+    if P not in (1, N):
+        raise ValueError("the policy must have 1 or N = %d weight sets, not %d" % (N, P))
+    if K * E * N > 2 ** 31 - 17:
+        raise ValueError("the fragment must have at most 2^31 - 17 rows")
+    if float(kl_coeff) == 0.0:
+        t["behaviour_logits"] = None                        # not part of the loss
+    elif t["behaviour_logits"] is None:
+        raise ValueError("kl_coeff != 0 needs behaviour_logits (the logits the actions were sampled from)")
+
+    def check(x, dtype, shape, name):
+        if not isinstance(x, torch.Tensor) or x.dtype != dtype or tuple(x.shape) != shape or x.device != dev or not x.is_contiguous():
+            raise ValueError("%s must be a contiguous %s tensor of shape %s on %s" % (name, dtype, shape, dev))
+    check(acts, torch.int32, (K, E, N), "actions")
+    for name in ("logp_old", "advantages", "value_targets", "vf_pred"):
+        check(t[name], torch.float32, (K, E, N), name)
+    if t["behaviour_logits"] is not None:
+        check(t["behaviour_logits"], torch.float32, (K, E, N, A), "behaviour_logits")
+    obs = t["obs"]
+    need = K if obs_first is None else K - 1                # with obs_first the last row of obs is never read
+    if need or obs is not None:
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 6 or obs.shape[0] < need:
+            raise ValueError("obs must be a uint8 tensor [K, E, N, 15, 15, 3] of at least %d steps" % need)
+        check(obs, torch.uint8, (int(obs.shape[0]), E, N, VIEW, VIEW, 3), "obs")
+    if obs_first is not None:
+        check(obs_first, torch.uint8, (E, N, VIEW, VIEW, 3), "obs_first")
+    t["obs_first"] = obs_first
+    return t, (K, E, N)
+
+
+def ppo_terms(logits, value, t, clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff):
+    """RLlib 0.7.6's PPOLoss (use_gae=True) per row in plain torch, in the dtype of logits: (row_loss, -surr, vf, kl, ent),
+    each of actions' shape.  t: the inputs by their contract names (include/ssd.h)."""
+    dt = logits.dtype
+    logp_all = torch.log_softmax(logits, dim=-1)
+    p_all = logp_all.exp()
+    logp = logp_all.gather(-1, t["actions"].long().unsqueeze(-1)).squeeze(-1)
+    adv, vt, vfp = t["advantages"].to(dt), t["value_targets"].to(dt), t["vf_pred"].to(dt)
+    ratio = torch.exp(logp - t["logp_old"].to(dt))
+    surr = torch.minimum(adv * ratio, adv * ratio.clamp(1.0 - clip_param, 1.0 + clip_param))
+    ent = -(p_all * logp_all).sum(-1)
+    if t.get("behaviour_logits") is not None:
+        blp = torch.log_softmax(t["behaviour_logits"].to(dt), dim=-1)
+        kl = (blp.exp() * (blp - logp_all)).sum(-1)
+    else:
+        kl = torch.zeros_like(ent)
+    vf1 = (value - vt).square()
+    vf2 = (vfp + (value - vfp).clamp(-vf_clip_param, vf_clip_param) - vt).square()
+    vf = torch.maximum(vf1, vf2)
+    return -surr + kl_coeff * kl + vf_loss_coeff * vf - entropy_coeff * ent, -surr, vf, kl, ent
+
+
+def _set_means(x, P):
+    """The means of x [K, E, N] over each weight set's rows: [P]."""
+    return x.mean().reshape(1) if P == 1 else x.reshape(-1, P).mean(0)
+
+
+def _ppo_obs(t, K):
+    """The observation each row acted on, by an explicit copy (the torch path): obs_first, then obs[:K - 1]."""
+    if t["obs_first"] is None:
+        return t["obs"][:K]
+    return t["obs_first"].unsqueeze(0) if K == 1 else torch.cat([t["obs_first"].unsqueeze(0), t["obs"][:K - 1]])
+
+
+def unpack_gradient(policy, grads, scale=None):
+    """A packed gradient [P, set_floats] (the layout packed() writes) as one tensor per parameter of policy.layout(), in its
+    order and the parameter's shape, times scale where given.  For a parameter with fewer entries than sets -- packed() wrote
+    entry k into sets k, k + entries, ... -- the sets' gradients are summed (no ConvFCPolicy parameter is shared this way; a
+    WatershedLSTMPolicy's dense1 with share_comm_layer is)."""
+    P = policy.num_sets
+    out = []
+    for name, shape, off in policy.layout():
+        n = int(np.prod(shape))
+        g = grads[:, off:off + n]
+        entries = getattr(policy, name).shape[0]
+        if entries != P:
+            g = g.reshape(P // entries, entries, n).sum(0)
+        if scale is not None:
+            g = g * scale
+        out.append(g.reshape((entries,) + tuple(shape)))
+    return out
+
+
+class _PPOLossFunction(torch.autograd.Function):
+    """ssd_policy_ppo_grad as a torch function of the policy's parameters: forward enqueues the library's two launches on the
+    current stream and keeps the packed gradient, backward scatters it into the parameters' shapes by layout()."""
+
+    @staticmethod
+    def forward(ctx, policy, t, dims, hyper, *params):
+        import ctypes as C
+        K, E, N = dims
+        P, A = policy.num_sets, policy.num_actions
+        dev = t["actions"].device
+        weights = policy.packed()
+        set_rows = K * E * N // P
+        need = policy.ppo_scratch_shape(set_rows)[0]
+        scratch = getattr(policy, "_ppo_scratch", None)          # kept between calls, as packed()'s buffer is
+        if scratch is None or scratch.device != dev or scratch.numel() < need:
+            scratch = policy._ppo_scratch = torch.empty(need, dtype=torch.float32, device=dev)
+        grads = torch.empty((P, policy.set_floats), dtype=torch.float32, device=dev)
+        stats = torch.empty((P, len(PPO_STATS)), dtype=torch.float64, device=dev)
+        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())   # noqa: E731
+        index = dev.index if dev.index is not None else torch.cuda.current_device()
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _capi.policy_check(_capi.lib().ssd_policy_ppo_grad(
+            ptr(weights), P, A, ptr(t["obs_first"]), ptr(t["obs"]), ptr(t["actions"]), ptr(t["logp_old"]), ptr(t["advantages"]),
+            ptr(t["value_targets"]), ptr(t["vf_pred"]), ptr(t["behaviour_logits"]), K, E, N, *hyper, ptr(scratch), ptr(grads),
+            ptr(stats), index, 0, stream))
+        ctx.policy = policy
+        ctx.save_for_backward(grads)
+        ctx.mark_non_differentiable(stats)
+        return stats[:, 0].sum().to(torch.float32), stats
+
+    @staticmethod
+    def backward(ctx, g_loss, g_stats):
+        (grads,) = ctx.saved_tensors
+        out = unpack_gradient(ctx.policy, grads, g_loss)
+        return (None, None, None, None) + tuple(g if needs else None for g, needs in zip(out, ctx.needs_input_grad[4:]))
+
+
+def ppo_loss(policy, batch, *, clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff, obs_first=None):
+    """RLlib 0.7.6's PPO loss (PPOLoss with use_gae=True) of a ConvFCPolicy on a sampled fragment -> (loss, stats): loss a
+    scalar tensor that backpropagates into the policy's parameters, stats a dict of [P] tensors (PPO_STATS: the set means of
+    the total, policy, value-function, KL and entropy terms).  include/ssd.h (PPO LOSS AND GRADIENTS) states the loss, the
+    rows of a weight set, the derivatives at the clip boundaries and the order of the sums; loss is the sum over the weight
+    sets of each set's mean row loss.
+
+        first = env.reset().clone()
+        batch = env.sample(policy, 128, gamma=0.99, lambda_=0.95)
+        loss, stats = ppo_loss(policy, batch, clip_param=0.3, vf_clip_param=10.0, vf_loss_coeff=1e-4, entropy_coeff=1e-3,
+                               kl_coeff=0.0, obs_first=first)
+        loss.backward(); optimiser.step()
+
+    batch: the dict sample() returns (obs, actions, logp as logp_old, value as vf_pred, advantages, value_targets and, where
+    present, logits as behaviour_logits; the contract names are accepted too), or the tensors as a tuple in that order:
+    obs u8 [K,E,N,15,15,3], actions i32, the rest f32 [K,E,N], behaviour_logits f32 [K,E,N,A] (needed if and only if kl_coeff
+    != 0).  obs_first u8 [E,N,15,15,3]: row k acted on obs_first for k = 0 and on obs[k - 1] otherwise, as sample() records
+    them; None: on obs[k].  A minibatch of steps k0 .. k1 - 1 is the leading-axis slices [k0:k1] of every tensor with
+    obs_first = obs[k0 - 1].
+    CUDA tensors go to the library (ssd_policy_ppo_grad: two launches on torch's current stream, no synchronisation, no
+    activation kept); CPU tensors run the same loss in plain torch under autograd."""
+    if not isinstance(policy, ConvFCPolicy):
+        raise ValueError("ppo_loss is for a ConvFCPolicy (the recurrent policies need backpropagation through time)")
+    hyper = tuple(float(x) for x in (clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff))
+    if not all(np.isfinite(hyper)) or hyper[0] < 0 or hyper[1] < 0:
+        raise ValueError("the hyper-parameters must be finite, clip_param and vf_clip_param >= 0")
+    t, (K, E, N) = _ppo_tensors(policy, batch, obs_first, hyper[4])
+    dev, P = t["actions"].device, policy.num_sets
+    if policy.conv_w.device != dev:
+        raise ValueError("the policy is on %s, the batch on %s" % (policy.conv_w.device, dev))
+    if dev.type == "cuda":
+        if policy.conv_w.dtype != torch.float32:
+            raise ValueError("the device path needs a float32 policy")
+        params = tuple(getattr(policy, name) for name, _, _ in policy.layout())
+        loss, stats = _PPOLossFunction.apply(policy, t, (K, E, N), hyper, *params)
+        return loss, {name: stats[:, k] for k, name in enumerate(PPO_STATS)}
+    if dev.type != "cpu":
+        raise ValueError("the tensors must be on the CPU or on a GPU, not on %s" % (dev,))
+    logits, value = policy(_ppo_obs(t, K))
+    terms = ppo_terms(logits, value, t, *hyper)
+    means = [_set_means(x, P) for x in terms]
+    return means[0].sum(), {name: m.detach() for name, m in zip(PPO_STATS, means)}
 
 
 # ---- the Watershed baselines' policy (include/ssd.h, WATERSHED POLICY ROLLOUTS; csrc/ssd_ws_policy.hip) ----
