@@ -767,8 +767,10 @@ const char *ssd_advantages_last_error(void);   /* the calling thread's last ssd_
  * Arithmetic and order.  Exact float32, as the forward (the hyper-parameters are rounded to float32 once); the per-row loss
  * terms are float32 and enter float64 sums.  Every sum over rows has a fixed order that is a function of (K, E, N, P) alone:
  * a set's rows are cut into tiles of SSD_PPO_TILE rows, workgroup g of the G = SSD_PPO_GROUPS(set rows, P) of a set sums
- * tiles g, g + G, ... in that order in float32 (float64 for the statistics), and the G partial sums are added in order in
- * float64, scaled by 1 / rows and rounded to float32 once.  No atomics: the same inputs give the same bits on every call and
+ * tiles g, g + G, ... in that order in float32 (float64 for the statistics) -- the dense layers' biases, fc2's kernel and the
+ * heads' kernels as a sum per tile added to the sum carried so far, fc1's and the conv's kernel and the conv's bias as one
+ * accumulator continued through the tiles --, and the G partial sums are added in order in float64, scaled by 1 / rows and
+ * rounded to float32 once.  No atomics: the same inputs give the same bits on every call and
  * on every device.
  *
  * Outputs.  grads f32 [P, SSD_POL_SET_FLOATS(A)]: d loss / d weights in the packed layout, padding floats zero.  stats f64

@@ -175,3 +175,101 @@ def max_err(a, b):
 def as_numpy_u32(x):
     return x.detach().cpu().contiguous().view(torch.int32).numpy().view(np.uint32) if x.dtype == torch.float32 else \
         x.detach().cpu().contiguous().view(torch.int64).numpy().view(np.uint64)
+
+
+# ---- builders for the edge, row-accounting and discrimination tests ----
+
+def zero_policy(A, P):
+    """A ConvFCPolicy with every parameter zero: value = 0 and logits = 0 exactly, whatever the observation."""
+    pol = ConvFCPolicy(A, num_sets=P, seed=0)
+    with torch.no_grad():
+        for name, _, _ in pol.layout():
+            getattr(pol, name).zero_()
+    return pol
+
+
+def counting_inputs(A, K, E, N, seed, obs_first=True):
+    """The fragment of the row-accounting test for zero_policy: adv = 0, vf_pred = 0, logp_old = -log A, random observations and
+    actions, value_targets[flat row] = 1 + flat row mod 4093.  With vf_loss_coeff = 0.5 each row's d loss / d value is -vt and
+    its vf is vt^2 <= 4093^2 < 2^24: every sum the kernel forms is an exact integer in float32 or float64."""
+    g = torch.Generator().manual_seed(seed)
+    rows = (K, E, N)
+    t = {"obs": torch.randint(0, 256, rows + (15, 15, 3), dtype=torch.uint8, generator=g),
+         "actions": torch.randint(0, A, rows, dtype=torch.int32, generator=g),
+         "logp_old": torch.full(rows, -float(np.log(float(A))), dtype=torch.float32),
+         "advantages": torch.zeros(rows), "vf_pred": torch.zeros(rows),
+         "value_targets": (1 + torch.arange(K * E * N, dtype=torch.int64) % 4093).reshape(rows).float()}
+    first = torch.randint(0, 256, (E, N, 15, 15, 3), dtype=torch.uint8, generator=g) if obs_first else None
+    return t, first
+
+
+COUNTING_HYPER = dict(clip_param=0.3, vf_clip_param=1.0, vf_loss_coeff=0.5, entropy_coeff=0.0, kl_coeff=0.0)
+
+
+def clipped_fragment(policy, K, E, N, seed, live=False, obs_first=True):
+    """A fragment whose every row is clipped, built from the float64 forward: ratio 1.5 with adv = 1 (the clipped branch is the
+    minimum: nothing through the ratio), value - vf_pred = -2 (clipped to -1) and vt = value + 0.2 (vf2 = 0.64 > vf1 = 0.04:
+    dead, nothing through the value) or, live, vt = value + 3 (vf1 = 9 > vf2 = 4).  For entropy_coeff = kl_coeff = 0."""
+    t, first = make_inputs(policy, K, E, N, seed=seed, obs_first=obs_first, behaviour=False)
+    return dict(t, **clipped_rows(policy, t, first, live)), first
+
+
+def clipped_rows(policy, t, first, live=False):
+    """logp_old, advantages, vf_pred and value_targets of clipped_fragment for the observations and actions of t."""
+    with torch.no_grad():
+        logits, value = copy.deepcopy(policy).double()(shifted_obs(t["obs"], first, t["actions"].shape[0]))
+        logp = torch.log_softmax(logits, -1).gather(-1, t["actions"].long().unsqueeze(-1)).squeeze(-1)
+    return {"advantages": torch.ones(t["actions"].shape), "logp_old": (logp - float(np.log(1.5))).float().contiguous(),
+            "vf_pred": (value + 2.0).float().contiguous(), "value_targets": (value + (3.0 if live else 0.2)).float().contiguous()}
+
+
+def set_policy(policy, p):
+    """Weight set p of `policy` as a ConvFCPolicy of its own with one set."""
+    one = ConvFCPolicy(policy.num_actions, num_sets=1, seed=0)
+    with torch.no_grad():
+        for name, _, _ in policy.layout():
+            getattr(one, name).copy_(getattr(policy, name)[p:p + 1])
+    return one
+
+
+def set_fragment(t, first, p):
+    """Agent p's rows of a [K, E, N] fragment gathered into a [K, E, 1] fragment, the shifted observations passed explicitly
+    (no obs_first)."""
+    K = t["actions"].shape[0]
+    out = {k: v[:, :, p:p + 1].contiguous() for k, v in t.items() if k != "obs"}
+    out["obs"] = shifted_obs(t["obs"], first, K)[:, :, p:p + 1].contiguous()
+    return out
+
+
+def take_set_rows(policy, t, first, idx):
+    """Rows idx (indices into a weight set's rows; the same rows of every set for P = N) as a fragment [len(idx), 1, N or 1]
+    with explicit shifted observations."""
+    K, E, N = t["actions"].shape
+    lead = (K * E, N) if policy.num_sets == N and N > 1 else (K * E * N, 1)
+    out = {k: v.reshape(lead + tuple(v.shape[3:]))[idx].unsqueeze(1).contiguous() for k, v in t.items() if k != "obs"}
+    obs = shifted_obs(t["obs"], first, K)
+    out["obs"] = obs.reshape(lead + tuple(obs.shape[3:]))[idx].unsqueeze(1).contiguous()
+    return out
+
+
+def skipped_rows_error(policy, t, h, first, idx):
+    """What a kernel that skipped rows idx of every set (and still divided by the set's rows) would be off by, per parameter:
+    the loss is a mean over rows, so the truth less that kernel's gradient is grad(rows idx alone) * len(idx) / set rows."""
+    rows = t["actions"].numel() // policy.num_sets
+    _, _, g = autograd_loss(policy, take_set_rows(policy, t, first, idx), h)
+    return {name: x * (len(idx) / rows) for name, x in g.items()}
+
+
+def saturate(policy, t_builder, floor=-80.0):
+    """Doubles logits_w until the float64 reference's smallest chosen-action log-probability of t_builder(policy)'s fragment is
+    below `floor` (float32 probabilities of such actions underflow to zero) -> (t, first, that smallest log-probability)."""
+    for _ in range(20):
+        t, first = t_builder(policy)
+        with torch.no_grad():
+            logits, _ = copy.deepcopy(policy).double()(shifted_obs(t["obs"], first, t["actions"].shape[0]))
+            low = float(torch.log_softmax(logits, -1).gather(-1, t["actions"].long().unsqueeze(-1)).min())
+        if low < floor:
+            return t, first, low
+        with torch.no_grad():
+            policy.logits_w.mul_(2.0)
+    raise AssertionError("the logits did not saturate")

@@ -1,13 +1,15 @@
 """ppo_loss without a device: the CPU path against the float64 restatement (ppo_ref.py), the restatement's autograd against the
 contract's explicit derivatives, a case worked by hand, every clip branch, the first-epoch tie, the observation shift and
-minibatch slices against an explicit torch.cat, both weight-set modes, and the C ABI's argument checks."""
+minibatch slices against an explicit torch.cat, both weight-set modes, the C ABI's argument checks, and that the GPU tests'
+acceptance bound tells the right gradient from one that lost a row or a tile."""
 import ctypes as C
 import math
 
 import pytest
 import torch
 
-from ppo_ref import HYPER, MARGIN, autograd_loss, branch_report, kink_loss, make_inputs, make_policy, max_err, row_terms
+from ppo_ref import (HYPER, MARGIN, autograd_loss, branch_report, kink_loss, make_inputs, make_policy, max_err, row_terms,
+                     skipped_rows_error)
 from sequential_social_dilemma_games_amd import _capi, ppo_loss
 from sequential_social_dilemma_games_amd.policy import PPO_STATS, ConvLSTMPolicy
 
@@ -260,3 +262,42 @@ def test_scratch_query_and_gradient_unpacking():
         (rebuilt * packed).sum().backward()
         for leaf, got in zip(leaves, unpack_gradient(policy, packed)):
             assert torch.allclose(leaf.grad, got, rtol=0, atol=1e-6)
+
+
+# (A, P, K, E, N, behaviour_logits, seed): multi-iteration cases of tests/test_ppo_loss_gpu.py's CASES (same seeds, so the same
+# inputs), P = 1 and P = N
+NEAR_MISS_CASES = [(9, 1, 7, 601, 4, False, 16), (9, 1, 3, 1825, 3, True, 20), (8, 5, 8, 513, 5, True, 15), (8, 64, 257, 1, 64, True, 18)]
+
+
+@pytest.mark.parametrize("A,P,K_,E,N,beh,seed", NEAR_MISS_CASES)
+def test_bound_separates_the_gradient_from_a_near_miss(A, P, K_, E, N, beh, seed):
+    """The GPU tests accept ek <= 4 et + 1e-6 max(1, max |ref|), and with gradients of 1e-2 the 1e-6 floor is most of it.
+    Would that bound notice a kernel whose persistent loop lost rows in its second iteration?  The loss is a mean over a
+    set's rows, so such a kernel's gradient is off by exactly grad(the lost rows alone) * lost / rows: one float64 autograd.
+    With et from torch's float32 autograd on the CPU (a stand-in for the device's), max |difference| / bound must be
+      >= 10 for some tensor when the one row 16 G is lost (the first row of the second iteration),
+      >= 5 for every tensor when the ragged last tile is lost,
+      >= 10 for every tensor when every tile >= G is lost (the whole second iteration).
+    For P = N the rows are lost in every set, as an error in the tiling would lose them (the sets share one tiling), and ek
+    is the largest difference over the whole [P, ...] tensor, as the GPU tests form it.  These are conditions on the inputs (a
+    seed that misses one is replaced, the ratios stay)."""
+    h = dict(HYPER, kl_coeff=HYPER["kl_coeff"] if beh else 0.0)
+    pol = make_policy(A, P, seed=seed)
+    t, first = make_inputs(pol, K_, E, N, seed=100 + seed, behaviour=beh)
+    R = K_ * E * N // P
+    G = _capi.SSD_PPO_GROUPS(R, P)
+    tiles = (R + 15) // 16
+    assert G < tiles <= 2 * G and R > 16 * G                      # the loop runs a second time and no third
+    _, _, g64 = autograd_loss(pol, t, h, first)
+    _, _, g32 = autograd_loss(pol, t, h, first, dtype=torch.float32)
+    bound = {name: 4.0 * max_err(g32[name], g64[name]) + 1e-6 * max(1.0, float(g64[name].abs().max())) for name in g64}
+    lost = {"row 16 G": torch.tensor([16 * G]), "ragged last tile": torch.arange(16 * (tiles - 1), R),
+            "second iteration": torch.arange(16 * G, R)}
+    ratios = {}
+    for what, idx in lost.items():
+        diff = skipped_rows_error(pol, t, h, first, idx)
+        ratios[what] = {name: float(d.abs().max()) / bound[name] for name, d in diff.items()}
+        print(what, len(idx), "rows of", R, {name: round(r, 1) for name, r in ratios[what].items()})
+    assert max(ratios["row 16 G"].values()) >= 10.0, ratios["row 16 G"]
+    assert min(ratios["ragged last tile"].values()) >= 5.0, ratios["ragged last tile"]
+    assert min(ratios["second iteration"].values()) >= 10.0, ratios["second iteration"]

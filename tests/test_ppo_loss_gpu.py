@@ -29,7 +29,11 @@ CASES = [(8, 5, 1, 1, 5, True, True, False, 1), (8, 5, 3, 5, 5, False, True, Fal
          # more tiles than workgroups, so that the persistent loop runs more than once, with a ragged last tile: 4104 rows per set =
          # 257 tiles over 204 workgroups (53 take two tiles, 151 one); 16 828 rows = 1052 tiles over 1024; 1500 rows per set = 94
          # tiles over 32 workgroups (two or three tiles each)
-         (8, 5, 8, 513, 5, True, True, False, 15), (9, 1, 7, 601, 4, False, True, False, 16), (8, 32, 3, 500, 32, True, False, True, 17)]
+         (8, 5, 8, 513, 5, True, True, False, 15), (9, 1, 7, 601, 4, False, True, False, 16), (8, 32, 3, 500, 32, True, False, True, 17),
+         # just past the point where the loop starts a second iteration, 1025 tiles or so in all: N = P = 64, the largest allowed
+         # and so the smallest G (16), with 257 rows per set = 17 tiles, workgroup 0's second tile holding one live row (K = 257:
+         # a row per step; E = 257: every row in step 0); 16 425 rows = 1027 tiles over 1024, the last tile with 9 rows
+         (8, 64, 257, 1, 64, True, True, False, 18), (9, 64, 1, 257, 64, False, False, False, 19), (9, 1, 3, 1825, 3, True, True, False, 20)]
 
 
 def _to_dev(t):
@@ -56,17 +60,11 @@ def _check_against_reference(got, tor, ref, what):
     assert not bad, (what, bad)
 
 
-@pytest.mark.parametrize("A,P,K_,E,N,beh,use_first,own_stream,seed", CASES)
-def test_gradients_and_stats_against_float64(A, P, K_, E, N, beh, use_first, own_stream, seed):
-    h = dict(HYPER, kl_coeff=HYPER["kl_coeff"] if beh else 0.0)
-    pol = make_policy(A, P, seed=seed)
-    t, first = make_inputs(pol, K_, E, N, seed=100 + seed, obs_first=use_first, behaviour=beh)
-    rep = branch_report(pol, t, h, first)
-    print("case", (A, P, K_, E, N, beh, use_first, own_stream), rep)
-    assert rep["margin"] > MARGIN, rep                     # conditions on the inputs: no float32 branch can flip ...
-    if K_ * E * N // P >= 1000:                            # ... and every branch holds a real share of the rows
-        for k in ("clipped_pos", "clipped_neg", "open_pos", "open_neg", "vf_dead", "vf_live", "vf_clipped_live"):
-            assert rep[k] > 0.1, rep
+def compare_with_float64(pol, t, first, h, own_stream=False, only=None):
+    """The kernel on (pol, t, first, h) against the float64 restatement with torch's float32 autograd on the device as the
+    yardstick -- gradients (the tensors named in `only`, or all), statistics and loss under the bound --, all outputs finite,
+    and a second call `uint32`-equal to the first.  Returns (loss, stats, grads, float64 grads) of the kernel's first call."""
+    P = pol.num_sets
     loss64, stats64, g64 = autograd_loss(pol, t, h, first)
     loss32, stats32, g32 = autograd_loss(pol, t, h, first, dtype=torch.float32, device=DEV)      # torch's own float32, same device
     dpol, dt, dfirst = copy.deepcopy(pol).to(DEV), _to_dev(t), None if first is None else first.to(DEV)
@@ -80,7 +78,9 @@ def test_gradients_and_stats_against_float64(A, P, K_, E, N, beh, use_first, own
         loss, stats, g = _run(dpol, dt, dfirst, h)
     torch.cuda.synchronize()
     assert all(tuple(stats[k].shape) == (P,) and stats[k].dtype == torch.float64 for k in PPO_STATS)
-    _check_against_reference(g, g32, g64, "grad")
+    assert all(bool(torch.isfinite(x).all()) for x in list(g.values()) + list(stats.values()) + [loss])
+    keep = (lambda d: d) if only is None else (lambda d: {k: d[k] for k in only})   # noqa: E731
+    _check_against_reference(keep(g), keep(g32), keep(g64), "grad")
     _check_against_reference(stats, stats32, stats64, "stat")
     _check_against_reference({"loss": loss}, {"loss": loss32}, {"loss": loss64}, "loss")
     # the same inputs give the same bits, on the default stream too
@@ -91,6 +91,21 @@ def test_gradients_and_stats_against_float64(A, P, K_, E, N, beh, use_first, own
         assert np.array_equal(as_numpy_u32(stats[k]), as_numpy_u32(stats2[k])), k
     for name in g:
         assert np.array_equal(as_numpy_u32(g[name]), as_numpy_u32(g2[name])), name
+    return loss, stats, g, g64
+
+
+@pytest.mark.parametrize("A,P,K_,E,N,beh,use_first,own_stream,seed", CASES)
+def test_gradients_and_stats_against_float64(A, P, K_, E, N, beh, use_first, own_stream, seed):
+    h = dict(HYPER, kl_coeff=HYPER["kl_coeff"] if beh else 0.0)
+    pol = make_policy(A, P, seed=seed)
+    t, first = make_inputs(pol, K_, E, N, seed=100 + seed, obs_first=use_first, behaviour=beh)
+    rep = branch_report(pol, t, h, first)
+    print("case", (A, P, K_, E, N, beh, use_first, own_stream), rep)
+    assert rep["margin"] > MARGIN, rep                     # conditions on the inputs: no float32 branch can flip ...
+    if K_ * E * N >= 1000:                                 # ... and every branch holds a real share of the rows
+        for k in ("clipped_pos", "clipped_neg", "open_pos", "open_neg", "vf_dead", "vf_live", "vf_clipped_live"):
+            assert rep[k] > 0.1, rep
+    compare_with_float64(pol, t, first, h, own_stream)
 
 
 def test_packed_gradient_padding_and_scaling():
