@@ -632,8 +632,6 @@ uint64_t read_index(const Queue *Q) { return g_api.hsa_queue_load_read_index_sca
 // device address); the packet's system-scope release makes the rollout's results visible to everybody.  (The caller's stream
 // waits for the counter with ssd_wait_counter_kernel.)
 void join(Queue *Q, const void *flag_kernarg) {
-    // (measured: the packet without fences where the chain's stores were all write-through -- the waiting kernel's own end-of-kernel
-    // release would do -- saves nothing: 6.63 against 6.56 us per step of the driver's 20-step call)
     dispatch(Q, Q->flag_kernel, 1, 64, 0, flag_kernarg, /*barrier=*/true, HSA_FENCE_SCOPE_AGENT, HSA_FENCE_SCOPE_SYSTEM);
     ring(Q);
 }

@@ -224,11 +224,7 @@ int fail_create(const std::string &msg, int code) {
     return code;
 }
 
-#ifdef SSD_EXP_OBS768   // (experiment builds only: see ssd_kernels.hip)
-size_t obs_bytes(const ssd_env *env, bool f32 = false) { return f32 ? (size_t)env->E * env->N * env->V * env->V * 3 * 4 : (size_t)env->E * env->N * SSD_EXP_OBS768; }
-#else
 size_t obs_bytes(const ssd_env *env, bool f32 = false) { return (size_t)env->E * env->N * env->V * env->V * 3 * (f32 ? 4 : 1); }
-#endif
 
 int ensure_staging(ssd_env *env) {
     if (env->st_obs) return SSD_OK;
@@ -284,10 +280,6 @@ int run(ssd_env *env, int mode, const int32_t *actions, const uint8_t *order, co
         env->last_stream = s; env->last_stream_set = true;
         p.actions = actions; p.order = order; p.mask = mask; p.actions_out = actions_out;
         p.obs = obs; p.rew = rew; p.done = done;
-        // (measured, round 2: the per-call step with the coherent kernel variant -- nothing left dirty for the launch's release -- 7.9
-        // against 8.0 us per Python call.  Round 4: twenty such steps captured into a HIP graph replay at the pace of twenty calls,
-        // 7.15 against 7.13 us per 4096-env step (bench.py, policy_step): back-to-back per-call steps are bound by the kernel --
-        // one launch whose waves step AND render, each launch waiting for the one before -- not by the host's 5 us per launch)
         ssd::launch(p, env->game, stream);
         SSD_HIP(env, hipGetLastError());
         return SSD_OK;
@@ -967,9 +959,6 @@ static int rollout_aql(ssd_env *env, int chains, const ChainJob *jobs, hipStream
     // Sync mode: the call itself waits -- for the stream before, for the chains after -- and no kernel waits for another queue's
     // kernel.  Chosen automatically when a profiling tool is attached (aql_sync_mode), or with SSD_AQL_SYNC=1.
     const bool sync_mode = ssd::aql::sync_mode();
-    // (measured: an empty barrier packet + doorbell on every chain's queue HERE, so that an idle queue wakes while the host still
-    // looks at the stream and writes the first step's packets: 6.65 against 6.62 us per step of the driver's 20-step call, and no
-    // better as a rank under torch.distributed.run, where that call follows an RCCL barrier and takes 7.1 - 7.2)
     if (sync_mode) { SSD_HIP(env, hipStreamSynchronize(s)); env->last_path |= SSD_PATH_SYNC; }
     bool stream_idle = sync_mode || (!always_fork && hipStreamQuery(s) == hipSuccess);
     if (!stream_idle && !always_fork) {
@@ -1054,9 +1043,6 @@ static int rollout_aql(ssd_env *env, int chains, const ChainJob *jobs, hipStream
             const int rel = (obs_wb && (step0 + k) % j0.ring == 0) ? 1 : kRel;
             put(c, i, o * KO + base, true, reset ? kAcq : acq, rel);
             if (split && k == j0.n_steps - 1) put(c, i, (1 - o) * KO + AqlState::kB, true, kAcq, kRel);   // (renders the buffer this step wrote)
-            // (tried: the call's last step rendering itself, its renderer waves in the env's own workgroup behind a barrier -- with
-            // a one-slot ring both write the same bytes -- instead of the renderer-only launch: 6.60 against 6.62 us per step of
-            // a 20-step call, no gain)
             // (the doorbell -- an uncached write across the bus, 0.3 - 0.5 us -- after the first two steps, so that the device starts
             // at once, and then after every fourth: the device needs 5 us per step, the host under 1, it never runs dry; the join
             // rings for the rest)

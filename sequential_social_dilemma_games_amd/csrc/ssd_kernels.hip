@@ -31,17 +31,7 @@
 #include "ssd_internal.hpp"
 #include <type_traits>
 
-#ifndef SSD_PIN_EARLY          // (experiment switch: 0 = the prologue's kernel arguments requested where they always were)
-#define SSD_PIN_EARLY 1
-#endif
-#ifndef SSD_WB_UNROLL          // (experiment switch: 0 = the write-back of a known map's grid as a loop)
-#define SSD_WB_UNROLL 1
-#endif
-#ifdef SSD_EXP_OBS768
-#define SSD_OBS_STRIDE SSD_EXP_OBS768
-#else
 #define SSD_OBS_STRIDE 675
-#endif
 
 namespace ssd {
 
@@ -74,11 +64,7 @@ __device__ __forceinline__ uint32_t phase_key(uint32_t key, uint32_t t, uint32_t
 }
 // (the two halves of phase_key: the first is the same for every stream of a step -- computed once per pass, on the scalar unit)
 __device__ __forceinline__ uint32_t step_key(uint32_t key, uint32_t t) { return mix32(key ^ t); }
-#ifdef SSD_EXP_NOSTREAMKEY   // (experiment switch, wrong results: the upper bound of what cheaper stream keys could give)
-__device__ __forceinline__ uint32_t stream_key(uint32_t skey, uint32_t stream) { return skey ^ (stream * 0x9E3779B9u); }
-#else
 __device__ __forceinline__ uint32_t stream_key(uint32_t skey, uint32_t stream) { return mix32(skey ^ stream); }
-#endif
 __device__ __forceinline__ uint32_t draw(uint32_t pkey, uint32_t index) { return mix32(pkey ^ index); }
 __device__ __forceinline__ uint32_t randint(uint32_t u, uint32_t n) { return __umulhi(u, n); }
 
@@ -168,15 +154,10 @@ typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 // output ring that does not fit in it (32 slots: 442 MB) thrashes it: 8.07 us per step with plain write-through stores.  So the host
 // asks for `nt` when the ring's observation bytes exceed what the cache can hold (ssd_capi.hip: obs_nt).
 // What then bounds WRITE-THROUGH stores is that the two ends of every agent block (675 bytes: any alignment) are 64-byte sectors
-// written partly by one store instruction and partly by another: with the blocks padded to 704 / 768 bytes (NOT the output layout)
-// a ring of 32 slots takes 5.95 / 5.74 us per step against 6.96; dword alignment alone (676) 6.81.
+// written partly by one store instruction and partly by another (padded blocks, and merging inside the wave, were measured:
+// EXPERIMENTS.md, "observation stores: padded blocks, merging inside the wave").
 // wt = 3: `nt` alone -- write-BACK and non-temporal: the partial sectors meet in L2 and leave it as whole lines: 5.79 us per step in
-// the real layout; what uint8 observations use for such a ring (select() below).  Before that was found, merging inside the wave
-// was built and measured (commit ae4b8b6: the env's N x 675 bytes written as ONE stream of 16-byte pieces aligned in memory, eight
-// whole lines per instruction, the block's two partial ends as 8 / 4 / 2 / 1-byte pieces; bit-exact): the memory system is relieved
-// as hoped -- env waves 15 % shorter, stores land in 950 cycles instead of 2 700 -- but a piece's 16 bytes are 5 1/3 view cells of
-// up to two agents, so cell coordinates become per-lane arithmetic where the 12-byte form has per-lane CONSTANTS: the renderer's
-// render phase grows from 3 100 to 5 400 cycles and the renderer wave becomes the launch's critical path: 7.6 against 7.03 us.
+// the real layout; what uint8 observations use for such a ring (select() below).
 __device__ __forceinline__ void store12_wt(rsrc_t r, uint32_t soff, uint32_t off, u32x3_t d, int wt) {
     // (the usual policy first: in the fused kernel's step loop every test in front of it showed, 3.75 -> 3.91 us per step)
     if (wt == 1) __builtin_amdgcn_raw_buffer_store_b96(d, r, (int)off, (int)soff, kAuxSc1);
@@ -271,9 +252,7 @@ __device__ __forceinline__ void render_views_std(const int lane, const int WP, c
                 d[u].y = __builtin_amdgcn_perm(px[u][2], px[u][1], 0x05040201u);   // g1 b1 r2 g2
                 d[u].z = __builtin_amdgcn_perm(px[u][3], px[u][2], 0x06050402u);   // b2 r3 g3 b3
             }
-            // (measured with agent blocks 768 bytes apart instead -- every store then covers whole 128-byte lines: 5.30 against
-            // 5.33 us per step; the partly written lines at the blocks' ends are not what bounds write-through stores in the
-            // memory-side cache.)  The store policy is wave-uniform: ONE branch per pass of five agents, the five stores of a
+            // The store policy is wave-uniform: ONE branch per pass of five agents, the five stores of a
             // policy behind each other (a test per store showed in the fused kernel's step loop: 3.75 -> 3.91 us per step).
             auto stores = [&](auto policy) {
 #pragma unroll
@@ -287,9 +266,6 @@ __device__ __forceinline__ void render_views_std(const int lane, const int WP, c
     }
 }
 
-#ifndef SSD_ROLL_VKEYS      // (1: the rollout kernel hashes its phase keys on the vector unit, all streams at once)
-#define SSD_ROLL_VKEYS 1
-#endif
 // Per-phase cycle stamps for tools/phase_profile.py: compiled only into the diagnostic library
 // (make stamps); the product build contains no stamp code.
 #ifdef SSD_STAMPS
@@ -370,8 +346,7 @@ constexpr FastMap kFastMap[2][3] = {
 // COH ("coherent"): the env's state, rewards, dones and observations move with agent-scope (sc1) accesses only: nothing of a
 // launch stays dirty in an XCD's L2 and nothing is read through a CU's L1, so consecutive launches of a chain need no cache
 // write-back / invalidate between them -- the library's own dispatch queues (ssd_aql.hip) then order them with the packet's
-// barrier bit alone (release fence NONE: -0.85 us per step).  (Round 2 also had a variant whose waves waited env by env on pass
-// counters, "pipelined launches": 4.44 against 4.50 us per step at 2048 envs, nothing at 4096 -- removed in round 3.)
+// barrier bit alone (release fence NONE: -0.85 us per step).
 template <int GAME, int MODE, bool F32, int NA, bool STD, int FAST, bool COH = false, bool ACTS = false>
 // The leading arguments repeat the Params fields the first global loads need (14 dwords).  Built with
 // -mllvm -amdgpu-kernarg-preload-count=14 the command processor delivers them in SGPRs when the wave starts, so the
@@ -426,9 +401,7 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
     //      env waves of the launch read the same lines and write elsewhere), overlaid with the agents' glyphs and the previous
     //      step's beam marks (p.beam_list_in); or, for the rare step that left one, the overlay snapshot (p.snap_in) ----
     if constexpr (MODE == kModeStep && COH && STD && NA > 0 && NA % 5 == 0 && !F32 && FAST != 0) {
-        // (measured: the renderer workgroups FIRST in the grid: 6.44 against 5.33 us per step; renderer waves that start their work
-        // out of phase, by up to 0.3 / 0.7 us: 5.56 / 5.53 against 5.35 -- neither role of a launch has slack; the renderer waves
-        // of an env in the env's own workgroup, behind its env waves: 5.65 against 5.30, with 2 envs per workgroup 5.40 against 5.33)
+        // (where the renderer workgroups sit in the grid and when their waves start is measured: EXPERIMENTS.md, "renderer placement")
         if ((p.snap_mode & 2) && blk >= p.blocks_a) {
             const int eb = a_e_begin + (blk - p.blocks_a) * a_epb + wv;
 #ifdef SSD_STAMPS   // renderer waves stamp into the second half of the buffer: [E_total + env][16]
@@ -477,10 +450,6 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
                 }
 #pragma unroll
                 for (int j = 0; j < kGridLoads; ++j) {
-#ifdef SSD_EXP_RENDER_BLANK     // (experiment switch, wrong pictures: the grid is fetched as ever and then shown blank -- what of the no-fetch bound is the CONTENT's)
-                    asm volatile("" : "+v"(g0[j]));
-                    g0[j] = u32x4_t{0x20202020u, 0x20202020u, 0x20202020u, 0x20202020u};
-#endif
                     if (lane * 16 + j * 1024 < S) *reinterpret_cast<uint4 *>(s_world + lane * 16 + j * 1024) = make_uint4(g0[j].x, g0[j].y, g0[j].z, g0[j].w);
                 }
                 wave_sync();
@@ -508,8 +477,6 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
                 SSD_BSTAMP(2, __builtin_readcyclecounter());                // stores issued
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 SSD_BSTAMP(3, __builtin_readcyclecounter());                // stores landed
-                // (a renderer wave that takes TWO envs -- 3 waves per env pair instead of 4 -- made the renderer the launch's
-                // critical path: 5.63 against 5.23 us per step)
             }
             SSD_BSTAMP(11, __builtin_amdgcn_s_memrealtime());
             return;
@@ -531,56 +498,35 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
         //      the ones that need further kernel arguments (actions, order, waste list).
         // (COH: the env's state may have been written a moment ago by a wave on another XCD, i.e. behind another L2: agent-
         // scope loads and stores, dword by dword, instead of cache write-backs / invalidations around ordinary ones.
-        // Measured once more in round 3: ORDINARY loads of header, agents and grid -- through this XCD's L2, every packet
-        // invalidating the CUs' L1s -- give bit-exact results over 1000 steps of 4096 envs (in practice an env's workgroup lands on
-        // the same XCD launch after launch) and are no faster, 5.57 against 5.43 us per step: the write-through stores of the launch
-        // before do not leave the lines in L2 to be hit, and the invalidate costs its 0.14 us.  Nothing to gain by speculating on it.
-        // And the grid's loads as `sc1 nt`: 6.10 against 5.48 -- the state is served by the memory-side cache, which `nt` goes past.)
+        // Ordinary loads through this XCD's L2, and `sc1 nt` loads, were measured and are no faster: EXPERIMENTS.md, "state loads".)
         auto cload = [](const uint32_t *ptr) -> uint32_t {
             return kCoh ? __hip_atomic_load(ptr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *ptr;
         };
         // (coherent variants: lanes 0..3 fetch the header's four words.  The v_readlanes right behind the load make the wave
-        // wait for it before it issues the others -- two round trips to memory in a row.  Measured, not reasoned: reading the
-        // lanes out after the common wait shortens the wave by 0.2 us (diagnostic build: load phase 1605 -> 1138 cycles) and
-        // makes the 4096-env step SLOWER, 5.35 -> 5.53 us (Cleanup 5.79 -> 5.95; no difference at 1024 or 16 384 envs):
-        // with two chains of launches in flight the step is not the wave's latency alone, and the staggered loads suit it.
-        // Measured again at the end of round 3, on that round's kernels: 5.51 -> 5.66 us, Harvest 25 x 38 6.00 -> 6.18 -- a launch's
-        // loads are a burst the memory side serves at its own rate, and a wave that asks for everything at once lengthens it.
-        // And a third time on round 4's kernels, now behind a switch (-DSSD_EXP_HDR_LATE): Harvest 5.16 -> 5.40, Cleanup 5.48 -> 5.72,
-        // Harvest 25 x 38 5.81 -> 5.88, Cleanup 48 x 36 6.60 -> 6.58: profiles/r04_ab/hdr_late_r04.txt)
+        // wait for it before it issues the others -- two round trips to memory in a row.  That order is measured, three times over,
+        // to give the faster STEP: EXPERIMENTS.md, "late header read")
         // kPre (Cleanup, the map-specific coherent step kernels).  Cleanup's spawn pass starts with a DEPENDENT fetch: the two
         // thresholds of the current waste count (cleanup.py:156-171 through the host's tables), a scalar load that can only go
         // out once the beams have said how many cells they cleaned -- a round trip to L2 in the middle of the wave, with nothing
         // to overlap it.  Here a window of both tables is requested in the prologue instead, lane l taking the entries of
         // (count in the header - l): the spawn pass then reads its pair out of lane `cells cleaned this step` (almost always
-        // < 64; else the fetch as before).  (The compiler sinks the window's loads into the spawn pass -- they are vector loads
-        // there instead of two scalar loads behind a wait -- and pinning them into the prologue changes nothing: 7.68 against 7.70.)
+        // < 64; else the fetch as before).
         // Measured (Cleanup 48 x 36, 10 agents, 2048 envs, alternating fresh processes): 8.18 -> 7.90 us per step; 25 x 18 x 4096:
-        // 5.97 -> 5.90.  Tried on top of it and dropped: the respawn's keyed draws (up to 23 per lane on the 48 x 36 map) computed
-        // in the prologue too, in the shadow of the grid's loads -- lists and window requested ahead of the grid as inline-asm
-        // loads, s_waitcnt vmcnt(<grid pieces>) -- 8.30 us: the load phase grows by more than the spawn pass shrinks (every wave
-        // of the launch multiplies at the same moment); the lists requested before the header has arrived: 8.72.  (And a lesson
-        // kept: a load the compiler cannot see must not sit under a divergent branch, nor have much code between it and its
-        // wait -- the compiler is free to copy or reuse its destination register before the data lands.)
+        // 5.97 -> 5.90.  (What was tried on top of it and dropped: EXPERIMENTS.md, "kPre: orders of loads".)
+        // A lesson kept: a load the compiler cannot see must not sit under a divergent branch, nor have much code between it and its
+        // wait -- the compiler is free to copy or reuse its destination register before the data lands.
         constexpr bool kPre = GAME == 1 && MODE == kModeStep && COH && FAST != 0;
         uint4 hdr;
-        uint32_t hdr_lanes = 0;
         if (kCoh) {
             const uint32_t hv = cload(reinterpret_cast<const uint32_t *>(a_hdr + e) + (lane & 3));
             // (these kernel arguments are fetched while the header is on its way)
             if constexpr (kPre) asm volatile("" ::"s"(p.waste_cells), "s"(p.thr_ca), "s"(p.thr_cw), "s"(p.n_thr));
-#if SSD_PIN_EARLY
             // ... and so are the ones the rest of the prologue and the respawn need (the pins further down): requested only after
             // the header had arrived they were two scalar-cache round trips in a row, each holding up the vector loads behind it
             asm volatile("" ::"s"(p.actions), "s"(p.order), "s"(p.num_actions_random), "s"(p.obs));
             if (GAME == 1) asm volatile("" ::"s"(p.waste_cells), "s"(n_waste), "s"(p.thr_ca), "s"(p.thr_cw), "s"(p.n_thr), "s"(p.rew), "s"(p.done), "s"(p.horizon));
             else asm volatile("" ::"s"(p.thr_h32[0]), "s"(p.thr_h32[1]), "s"(p.thr_h32[2]), "s"(p.thr_h32[3]), "s"(p.thr_h_always));
-#endif
-#ifndef SSD_EXP_HDR_LATE    // (experiment switch: the header's lanes read out after ALL the prologue's loads have been issued -- one round trip)
             hdr = make_uint4(rl(hv, 0), rl(hv, 1), rl(hv, 2), rl(hv, 3));
-#else
-            hdr_lanes = hv;
-#endif
         } else {
             hdr = a_hdr[e];
         }
@@ -634,7 +580,7 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
         // The other kernel arguments are fetched lazily by default, one scalar-cache round trip per basic block that needs
         // one.  Pin what the rest of the prologue and the respawn need into SGPRs here -- the loads above are in flight --
         // so that those fetches go out as one batch.
-        // (which ones is measured, not reasoned: pinning rew / done / horizon too gains 1 % in Cleanup and costs 3 % in Harvest)
+        // (which arguments are pinned is measured: EXPERIMENTS.md, "pinned kernel arguments")
         asm volatile("" ::"s"(p.actions), "s"(p.order), "s"(p.num_actions_random), "s"(p.obs));
         if (GAME == 1) asm volatile("" ::"s"(p.waste_cells), "s"(n_waste), "s"(p.thr_ca), "s"(p.thr_cw), "s"(p.n_thr), "s"(p.rew), "s"(p.done), "s"(p.horizon));
         else asm volatile("" ::"s"(p.thr_h32[0]), "s"(p.thr_h32[1]), "s"(p.thr_h32[2]), "s"(p.thr_h32[3]), "s"(p.thr_h_always));
@@ -650,9 +596,6 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
             wlist[j] = 0u;
             if (GAME == 1 && 64 * j < n_waste) wlist[j] = (mode != kModeObserve && idx < n_waste) ? p.waste_cells[idx] : 0u;
         }
-#ifdef SSD_EXP_HDR_LATE
-        if (kCoh) hdr = make_uint4(rl(hdr_lanes, 0), rl(hdr_lanes, 1), rl(hdr_lanes, 2), rl(hdr_lanes, 3));
-#endif
         // kPre: thresholds by waste count, lane l holding those of (count in the header - l): the spawn pass will see the count
         // less what this step's CLEAN beams clean (cleanup.py:115 after :94-111), almost always within the window
         uint64_t thr_pa = 0, thr_pw = 0;
@@ -707,10 +650,6 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
         // while its occupant was still there, map_env.py:480-483; never after a reset; ssd_set_state computes it).  Exact after
         // every step's consume phase; lets the move phase of a step that finds its agents apart skip the pair-by-pair look.
         bool share = (rfl(hdr.w) >> 31) != 0u;
-        // (measured and dropped, round 3: the grid written back right after the beams -- its stores then overlap the spawn pass --
-        // and only the 16-byte pieces the spawn pass changed written again at the end: Harvest 4096 envs 5.50 against 5.50 us per
-        // step (a first pair of runs said 5.43 against 5.54: box noise), 2048 envs 4.68 against 4.61, 8192 envs 10.56 against
-        // 10.37, Cleanup 25 x 18 5.96 against 5.87, 48 x 36 8.14 against 7.73: the stores are not what the wave's end waits for)
         // (`top_bit`, per lane: bit 19 of the agent's word = "the highest index on its cell" -- what shows on the cell,
         // map_env.py:289-297 -- for the renderer workgroups of the next launch: they then need not compare the agents' cells pair by
         // pair again)
@@ -724,7 +663,7 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
                 // word: a list of beam marks / an overlay snapshot; readers of the word take bits 0..17)
                 auto cstore = [](uint32_t *ptr, uint32_t v) { __hip_atomic_store(ptr, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
                 const rsrc_t out_r = make_rsrc(gw, (uint32_t)S);         // (16-byte write-through stores; past the grid's end: dropped)
-                if constexpr (FAST != 0 && SSD_WB_UNROLL) {
+                if constexpr (FAST != 0) {
                     // a known map's grid is kGridLoads pieces of 1 KiB: all of them are read out of LDS first, into registers of their
                     // own, and the stores then follow each other -- as a loop (LDS read, wait, store, next piece into the same
                     // registers) every piece waited for the one before
@@ -856,16 +795,14 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
             // (every keyed draw of this pass -- actions, move shuffle, apples, waste coins and order -- hashes (key, t) first: once,
             // here, instead of once per stream inside whatever branch needs one: 12 scalar instructions per further stream)
             const uint32_t skey = step_key(key, t);
-            // (measured and dropped, round 4: the second half for ALL streams at once on the vector unit -- lane s hashing stream s, a
-            // needed stream reading its lane: 12 vector instructions instead of 12 scalar ones per stream.  A hash is three 32-bit
-            // multiplies, quarter rate on the vector unit: with the pairwise test below on DPP as well, Harvest 5.13 -> 5.33 us per
-            // step; the scalar form stays)
-            // (... and kept for the ROLLOUT kernel alone, like the pairwise test on DPP below: that kernel is bound by issue slots, the
-            // scalar unit's first -- 24 scalar instructions per Harvest step become 12 vector ones and two v_readlane)
+            // (the ROLLOUT kernel alone hashes the second half for all streams at once on the vector unit -- lane s hashing stream s, a
+            // needed stream reading its lane: that kernel is bound by issue slots, the scalar unit's first, and 24 scalar instructions per
+            // Harvest step become 12 vector ones and two v_readlane.  The per-step kernels keep the scalar form, which is measured:
+            // EXPERIMENTS.md, "stream keys on the vector unit")
             uint32_t vkeys = 0;
-            if constexpr (roll && SSD_ROLL_VKEYS) vkeys = stream_key(skey, (uint32_t)lane);       // lane s: the key of stream s
+            if constexpr (roll) vkeys = stream_key(skey, (uint32_t)lane);       // lane s: the key of stream s
             auto stream_key_of = [&](uint32_t stream) -> uint32_t {
-                if constexpr (roll && SSD_ROLL_VKEYS) return rl(vkeys, stream);
+                if constexpr (roll) return rl(vkeys, stream);
                 else return stream_key(skey, stream);
             };
             if (is_step) {
@@ -930,18 +867,12 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
                 // reference algorithm in full.
                 const uint64_t agents_m = N >= 64 ? ~0ull : bit((uint32_t)N) - 1;
                 uint64_t clashm = 0, dupm = 0;                   // lanes (!= j) whose target is agent j's cell or mover j's target
-#ifndef SSD_EXP_NOCLASH   // (experiment switch, wrong results: the upper bound of what a cheaper clash test could give)
                 // The pairwise comparison.  Up to 16 agents sit in one row of 16 lanes, so lane i can look at lane (i + k) mod 16's
                 // cell and target with DPP row rotations, k = 1 .. 15 (never at itself; lanes that hold no agent / no mover carry
                 // values no target can equal): its clash bit is "some xor came out zero", one min per partner, all on the vector
-                // unit.  As a loop over the agents with v_readlane + scalar mask arithmetic the same test was 13 instructions per
-                // agent, 9 of them scalar -- on the unit the CU's four SIMDs share; its upper bound (no test at all, no slow path)
-                // measured 5.19 -> 5.00 us per step for Harvest and 7.05 -> 6.22 for Cleanup 48 x 36 with ten agents.  The exact masks
-                // the slow path wants (who shares WHICH target) are still made by the loop, there.
-                // In the ROLLOUT kernel only: there it pays (fused 3.39 -> 3.29 us per step: that kernel is bound by issue slots, the
-                // scalar unit's first); in the per-step kernels of the chains the same change costs (Harvest 5.13 -> 5.32, Cleanup
-                // 48 x 36 7.08 -> 7.21, alternating fresh processes): their env waves are a chain of dependent operations, and
-                // 24 - 45 dependent vector instructions with DPP hazards are a longer one than the loop's scalar arithmetic.
+                // unit.  The exact masks the slow path wants (who shares WHICH target) are still made by the loop, there.
+                // In the ROLLOUT kernel only: that kernel is bound by issue slots, the scalar unit's first; the env waves of the per-step
+                // kernels are a chain of dependent operations and keep the loop (both measured: EXPERIMENTS.md, "clash test").
                 bool exact_loop = !roll || (NA == 0 && N > 16);
                 if (!exact_loop) {
                     const uint32_t cellx = is_agent ? cell : 0xFFFFFFFEu, tcellm = mover ? tcell : 0xFFFFFFFFu;
@@ -987,16 +918,7 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
                         clashm |= (ballot(tcell == cj) | ballot(tcell == tj)) & ~bit(j);
                     }
                 }
-#endif
-                // (1.75 % of the envs of a random-action Harvest step; upper bound of what a faster slow path could give -- every env
-                // taking the fast path, wrong results --: 5.13 against 5.35 us per 4096-env step; Cleanup: no difference)
-#ifdef SSD_EXP_NOSLOW       // (experiment switch, wrong results: every env takes the fast path; the pairwise test stays)
-                const bool slow = false;
-#elif defined(SSD_EXP_NOSLOW_KEEPCODE)   // (... and the same with the slow path's code still in the kernel, never entered)
-                const bool slow = (clashm & M) != 0 && p.n_spawn < 0;
-#else
                 const bool slow = (clashm & M) != 0;
-#endif
                 SSD_NOTE(12, slow ? 1 : 0);
                 // (likelihood hints: the rare arms -- contested moves, beams that land one after the other, long lists -- go out of line,
                 // the common path falls through)
@@ -1036,15 +958,8 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
                 if (__builtin_expect(!slow, 1)) {
                     if (mover) cell = tcell;
                     all_apart = (clashm & agents_m) == 0;        // nobody's target is anybody else's target or cell
-#ifdef SSD_EXP_ALLAPART     // (experiment switch, wrong results: the consume phase never compares the agents' cells)
-                    all_apart = true;
-#endif
                 } else if (chains_only) {
-#if defined(SSD_EXP_MUT_CHAINS) && SSD_EXP_MUT_CHAINS == 1   // (mutation switch, wrong results: proves that the tests reach this path)
-                    if (mover) cell = tcell;
-#else
                     if (resolve_chains(mover & (tcell != cell), occ_fold)) cell = tcell;
-#endif
                     all_apart = true;
                 } else {                                         // :415 (M != 0 here)
                     __builtin_amdgcn_s_setprio(3);               // the slowest waves of a launch come through here (1-2 % of the envs)
@@ -1052,13 +967,6 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
                     // :424-491 cells wanted by several agents, in lexicographic order (np.unique, axis=0): visited in
                     // ascending cell order (scalar min over the few lanes involved).  The shuffle of :421-423 only
                     // decides who wins such a cell, so it is only computed when there is one (draws are counter-keyed).
-                    // These waves are the tail of their launch: forced onto the fast path (wrong results; the code still in the
-                    // kernel) Cleanup 48 x 36 with ten agents steps in 6.47 instead of 6.98 us, Harvest in 5.12 instead of 5.15.
-                    // (Measured and dropped, round 4: what the two loops below ask -- do two movers share a target, who stands on
-                    // each agent's target, do two agents share a cell -- asked through LDS instead, every agent marking its cell
-                    // and every mover its target in the two still-empty layers: ~12 instructions and ONE round trip instead of
-                    // N x 15 instructions, bit-exact -- and slower: 7.00 -> 7.12 / 5.11 -> 5.24 us per step.  Under this load a
-                    // dependent trip through LDS costs a wave more than a hundred scalar instructions do.)
                     if constexpr (!kFold)
                     for (int j = 0; j < N; ++j)                  // lanes (!= j) whose target is mover j's target
                         if ((M >> j) & 1) dupm |= ballot(tcell == rl(tcell, j)) & ~bit(j);
@@ -1130,9 +1038,6 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
                                 if constexpr (kFold) {           // (the list's first entry that is a contender)
                                     const uint64_t firstm = ballot(lane < nm && ((Cm >> (perm & 63u)) & 1ull) != 0);
                                     w = rl(perm, __builtin_ctzll(firstm));
-#if defined(SSD_EXP_MUT_CHAINS) && SSD_EXP_MUT_CHAINS == 2   // (mutation switch, wrong results: the lowest contender wins, not the shuffle's first)
-                                    w = (uint32_t)__builtin_ctzll(Cm);
-#endif
                                     // the agent that waited for the winner's cell finds it empty
                                     occ_fold = occ_fold == (int)w ? -1 : occ_fold;
                                     entered_taken |= Pm != 0;
@@ -1305,8 +1210,6 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
                         const bool covered = inray & (kk < len);
                         bool landed = false;                                            // marks and cleaning already applied
                         bool top_clean = clean;                                         // kind of the mark that survives on this lane's cell
-                        // (upper bound of what skipping this block could give -- no claims at all, wrong results: Cleanup 25 x 18
-                        // 5.68 -> 5.53 us per 4096-env step, 48 x 36 with 10 agents 7.98 -> 7.62 per 2048-env step)
                         if (GAME == 1 && (all_shooters & (all_shooters - 1))) {         // two or more shooters
                             // Which slots cover each cell: one LDS atomic OR per covered lane into the cell's byte of the (still
                             // empty) beam layer.  Sharing a cell matters in two ways.  (1) Beams of different kind: the mark of
@@ -1464,9 +1367,6 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
                     const uint32_t t0 = p.thr_h32[0], d1 = p.thr_h32[1] - t0, d2 = p.thr_h32[2] - p.thr_h32[1],
                                    d3 = p.thr_h32[3] - p.thr_h32[2];
                     // 3x3 apple count, threshold and keyed draw of one candidate cell (:90-103)
-                    // (measured and dropped, round 4: the three cells of a row as ONE unaligned 4-byte LDS read and the apples among them by
-                    // byte arithmetic -- 3 reads + 13 vector instructions instead of 8 + ~30; the compiler emits ds_read_b32 for it, and
-                    // the hardware serves it slowly: 5.14 -> 5.35 us per 4096-env step, the fused kernel 3.39 -> 3.86)
                     auto wins = [&](uint32_t ce) -> bool {
                         const int c = (int)(ce & 0xFFFFu);
                         uint32_t n = 0;
@@ -1495,11 +1395,7 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
                             total += __builtin_popcountll(em[j]);
                         }
                     }
-#ifdef SSD_EXP_NOCOMPACT    // (experiment switch: every lane evaluates its own list entries -- no compaction, one LDS round trip fewer)
-                    if (false) {
-#else
                     if (__builtin_expect(a_iters <= kLR && total <= 64, 1)) {
-#endif
                         // Usual case: at most 64 candidates among the (up to 512) apple points.  Compact them through
                         // 128 B of LDS scratch so that ONE pass of lanes does the stencil + draw instead of three.
                         if (total) {
@@ -1578,13 +1474,8 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
                         auto waste = [&](uint32_t ce, bool valid) {
                             ce = valid ? ce : safe;
                             const uint32_t c = ce & 0xFFFFu;                             // ties break on the cell: grid and dense order agree
-#ifdef SSD_EXP_WASTE_ONE_DRAW   // (experiment switch, results differ from the oracle's: one keyed draw per waste point instead of two)
-                            const uint32_t kh = draw(pk_ord, ce >> 16);
-                            const bool cand = valid & (s_world[c] != 'H') & ((uint64_t)kh < thr_w);
-#else
                             const bool cand = valid & (s_world[c] != 'H') & ((uint64_t)draw(pk_coin, ce >> 16) < thr_w);
                             const uint32_t kh = draw(pk_ord, ce >> 16);
-#endif
                             const bool better = cand & (!has | (kh < bh) | ((kh == bh) & (c < bl)));
                             bh = better ? kh : bh; bl = better ? c : bl; has = has | cand;
                         };
@@ -1891,9 +1782,7 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
         // Measured alternative: the state left dirty in L2 and written back by an agent-scope release on the packet instead --
         // no wait here -- 5.48 against 5.45 us per step.  Without that release the results are wrong even while every env
         // stays on its XCD: an sc1 load does not return what an earlier launch left dirty in the same L2.)
-#ifndef SSD_EXP_NO_END_WAIT
         if constexpr (COH) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
     }
     SSD_STAMP(9);       // observations issued
     SSD_STAMP_RT(11);
@@ -2001,19 +1890,12 @@ bool select(const Params &p_in, int game, Launch *out) {
     // of the ring (ssd_capi.hip; HIP-launched plain kernels release after every launch anyway).  float32 observations are whole
     // aligned lines per instruction already: write-through + non-temporal (2) as before.
     if (p.obs_nt) p.obs_wt = p.obs_f32 ? (p.obs_wt == 1 ? 2 : p.obs_wt) : 3;
-#ifdef SSD_EXP_OBS_WB                               // (experiment: such a ring with another store policy)
-    if (p.obs_nt) p.obs_wt = SSD_EXP_OBS_WB;
-#endif
-#ifdef SSD_EXP_OBS_WT_ALL                           // (experiment, unsafe: EVERY coherent launch's observation stores with this policy)
-    if (p.coherent) p.obs_wt = SSD_EXP_OBS_WT_ALL;
-#endif
     static const int forced_epb = SSD_KNOB("SSD_ENVS_PER_BLOCK", 0);
     const bool f32 = p.obs && p.obs_f32;            // the float32-observation variant is a separate instantiation
     int epb = envs_per_block(p, f32);
     static const int split_epb = SSD_HOOK("SSD_SPLIT_EPB", 4);   // (test-hook build: tuning override)
     // split rollouts run twice the waves per launch: smaller workgroups (measured: 4 envs per workgroup 5.23, 8: 5.78 us per step)
     if (p.snap_mode && forced_epb_early() <= 0 && epb > split_epb && split_epb >= 1) epb = split_epb;
-    // (raising the issue priority of the env waves over the renderer waves changes nothing: 5.23 - 5.36 us)
     // test knob of the coherent chains (ssd_capi.hip, SSD_AQL_ALTERNATE): half the envs per workgroup, i.e. another env ->
     // workgroup -> XCD mapping than the launches before and after
     if (p.coherent == 2 && epb > 1 && forced_epb <= 0) epb /= 2;

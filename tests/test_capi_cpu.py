@@ -21,6 +21,24 @@ def test_library_exports_every_declared_symbol():
     assert L.ssd_abi_version() == _capi.ABI_VERSION
 
 
+def test_libraries_export_nothing_but_the_declared_symbols():
+    """The defined, unmangled ssd_* names of the product's and the test-hook library's dynamic symbol tables are the header's:
+    what a library keeps for itself -- the embedded code object's two labels (ssd_codeobj.S) -- is hidden."""
+    import subprocess
+    header = open(os.path.join(REPO, "include", "ssd.h")).read()
+    declared = set(re.findall(r"\b(ssd_[a-z_]+)\s*\(", header))
+    for name in ("libssd_hip.so", "libssd_hip_testhooks.so"):
+        lib = os.path.join(REPO, "sequential_social_dilemma_games_amd", name)
+        assert os.path.exists(lib), "make all"
+        out = subprocess.run(["readelf", "--dyn-syms", "-W", lib], stdout=subprocess.PIPE, check=True).stdout.decode()
+        exported = set()
+        for line in out.splitlines():                            # Num: Value Size Type Bind Vis Ndx Name
+            f = line.split()
+            if len(f) >= 8 and f[0].rstrip(":").isdigit() and f[6] != "UND" and f[7].startswith("ssd_"):
+                exported.add(f[7].split("@")[0])
+        assert exported == declared, (name, exported ^ declared)
+
+
 def test_create_rejects_bad_configs_and_needs_a_gpu():
     import torch
     L = _capi.lib()
