@@ -796,6 +796,76 @@ int ssd_policy_ppo_grad(const float *weights, int32_t num_sets, int32_t num_acti
                         double kl_coeff, float *scratch, float *grads, double *stats, int32_t device_id, uint32_t flags,
                         void *stream);
 
+/* ======================================================================================================================
+ * RECURRENT PPO LOSS AND GRADIENTS -- the learner's half of the loop for the recurrent policy the baseline trains: the loss of
+ * PPO LOSS AND GRADIENTS above with truncated backpropagation through time (BPTT), its statistics and the gradient of every
+ * parameter, in one call (csrc/ssd_policy_lstm_grad.hip).  Added after ABI 6 without a version bump: the
+ * call is additive.
+ *
+ * Network: that of ssd_policy_lstm_forward above, the same packed weight layout (SSD_LSTM_*), P = 1 or P = N sets, A <= 15,
+ * C = cell_size = 64, 128 or 256.
+ *
+ * Rows, observation shift, loss, statistics and derivatives at the kinks: exactly those of PPO LOSS AND GRADIENTS above (the
+ * same device code forms a row's terms); loss = the sum over the sets of the set's mean row loss.  A sequence is one (e, i):
+ * the K rows (k, e, i), k = 0 .. K - 1.
+ *
+ * State rule.  With T = seq_len (RLlib's max_seq_len) and state f32 [S, E, N, 2, C], S = ceil(K / T), the ring
+ * ssd_rollout_policy_lstm records with state_every = T ((c, h) order), the state step k of sequence (e, i) uses is
+ *   state[k / T] as stored, when k % T == 0: data, no gradient flows into it -- the truncation;
+ *   zero, when k % T != 0 and done[k - 1, e, i] != 0 (selected, never loaded, as the forward's start rule): neither values nor
+ *     gradient cross an episode end;
+ *   the (c', h') this call computed for step k - 1 with the current weights, otherwise.
+ * done is u8 [K, E, N] or NULL (no episode ends inside the fragment); done[K - 1] is not read.  The ring holds zero at a window
+ * start that is an episode start, so a minibatch of steps k0 .. k1 - 1 with k0 % T == 0 is the slices [k0:k1] of the per-row
+ * arrays and of done, obs_first = obs ring[k0 - 1] and state = ring + k0 / T.  Every row is a valid row: no padding, no mask;
+ * a window cut short by K is a shorter window.
+ *
+ * Arithmetic and order.  The forward is exact float32 from the device pieces of the rollout (trunk, gates, cell, heads), the
+ * per-row loss terms are float32 and enter float64 sums.  Every sum has a fixed order that is a function of (K, E, N, P, A, C,
+ * T) alone; the call walks the windows w = 0, 1, ... in order and every partial sum below is continued from window to window:
+ *   heads' kernels and biases, statistics: the sequences of a set ((e) for P = N, (e, i) for P = 1, in that order) are cut into
+ *     tiles of SSD_RPPO_TILE; workgroup g of the Gs = SSD_RPPO_GROUPS(sequences of a set, P) takes tiles g, g + Gs, ...;
+ *     per tile it walks the window's steps backwards (forwards for the statistics) and adds each step's sum over the tile
+ *     to the sum carried so far (float32; float64 for the statistics);
+ *   lstm_w, lstm_b: a set's rows of the window, in (k, e, i) order, are cut into chunks of SSD_RPPO_CHUNK rows; split s of
+ *     the SSD_RPPO_SPLITS(a whole window's set rows) takes chunks s, s + S, ... as one accumulator in row order (lstm_b: four
+ *     accumulators of every fourth row, added in order at the end of a window);
+ *   the trunk: as PPO LOSS AND GRADIENTS orders it, over the window's rows, with G = SSD_PPO_GROUPS(a whole window's set rows, P).
+ * A whole window has min(T, K) steps.  The partial sums of an entry are then added in order in float64, scaled by 1 / (the
+ * set's rows, K E or K E N) and rounded to float32 once.  No atomics: the same inputs give the same bits.
+ *
+ * Outputs.  grads f32 [P, SSD_LSTM_SET_FLOATS(C, A)] in the packed layout, padding floats zero.  stats f64 [P, 5] as above.
+ * scratch: SSD_RPPO_SCRATCH_FLOATS(K, E, N, P, A, C, T) floats the call overwrites, 8-byte aligned; it grows with the rows
+ * of one window and the numbers of partial sums, not with K beyond min(T, K).
+ *
+ * Device pointers on device_id; everything is enqueued on `stream`, no allocation, no host synchronisation.  SSD_E_INVALID
+ * before anything is launched (ssd_policy_last_error says why) for everything ssd_policy_ppo_grad refuses, a cell_size other
+ * than 64, 128 or 256, seq_len < 1, a missing or misaligned state.
+ * ====================================================================================================================== */
+enum { SSD_RPPO_TILE = 16, SSD_RPPO_CHUNK = 64, SSD_RPPO_MAX_SPLITS = 32 };
+#define SSD_RPPO_MIN(a, b) ((a) < (b) ? (a) : (b))
+/* sequences of one weight set; workgroups (partial sums) per set of the sequence kernel; splits per set of lstm_w's */
+#define SSD_RPPO_SEQS(E, N, P) ((E) * (N) / (P))
+#define SSD_RPPO_GROUPS(seqs, P) \
+    SSD_RPPO_MIN(((seqs) + SSD_RPPO_TILE - 1) / SSD_RPPO_TILE, SSD_PPO_MAX_GROUPS / (P))
+#define SSD_RPPO_SPLITS(window_set_rows) \
+    ((int)SSD_RPPO_MIN(((window_set_rows) + SSD_RPPO_CHUNK - 1) / SSD_RPPO_CHUNK, SSD_RPPO_MAX_SPLITS))
+/* per row of a whole window: features 32, d (logits, value) / dx 32, (c', h') 2C, gates / dz 4C */
+#define SSD_RPPO_ROW_FLOATS(C) (64 + 6 * (C))
+#define SSD_RPPO_WINDOW_SET_ROWS(K, E, N, P, T) ((int64_t)SSD_RPPO_MIN(T, K) * SSD_RPPO_SEQS(E, N, P))
+#define SSD_RPPO_SCRATCH_FLOATS(K, E, N, P, A, C, T)                                                                          \
+    ((size_t)(P) * (32 + (C)) * 4 * (C) + (size_t)SSD_RPPO_MIN(T, K) * (E) * (N) * SSD_RPPO_ROW_FLOATS(C) +               \
+     (size_t)(P) * SSD_PPO_GROUPS((int32_t)SSD_RPPO_WINDOW_SET_ROWS(K, E, N, P, T), P) * (SSD_LSTM_W + SSD_PPO_STAT_FLOATS) + \
+     (size_t)(P) * SSD_RPPO_GROUPS(SSD_RPPO_SEQS(E, N, P), P) * (16 * (C) + 16 + SSD_PPO_STAT_FLOATS) +                  \
+     (size_t)(P) * SSD_RPPO_SPLITS(SSD_RPPO_WINDOW_SET_ROWS(K, E, N, P, T)) * ((32 + (C)) * 4 * (C) + 4 * (C)))
+int ssd_policy_lstm_ppo_grad(const float *weights, int32_t num_sets, int32_t num_actions, int32_t cell_size, int32_t seq_len,
+                             const uint8_t *obs_first, const uint8_t *obs, const float *state, const uint8_t *done,
+                             const int32_t *actions, const float *logp_old, const float *advantages, const float *value_targets,
+                             const float *vf_preds, const float *behaviour_logits, int32_t n_steps, int32_t num_envs,
+                             int32_t num_agents, double clip_param, double vf_clip_param, double vf_loss_coeff,
+                             double entropy_coeff, double kl_coeff, float *scratch, float *grads, double *stats,
+                             int32_t device_id, uint32_t flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

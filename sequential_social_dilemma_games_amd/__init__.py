@@ -10,6 +10,7 @@
     from sequential_social_dilemma_games_amd import WatershedLSTMPolicy         # the Watershed baselines' LSTM-FC policy
     from sequential_social_dilemma_games_amd import compute_advantages          # GAE / discounted returns of a rollout batch
     from sequential_social_dilemma_games_amd import ppo_loss                    # the PPO loss and its gradients, on the device
+    from sequential_social_dilemma_games_amd import ppo_loss_recurrent          # the same for the recurrent policy, with BPTT
 
 Everything that steps an env goes through libssd_hip.so (include/ssd.h); importing this package does
 not load it, constructing an env does -- and fails loudly if it is missing.
@@ -33,7 +34,7 @@ def __getattr__(name):
     if name == "EpisodeStats":
         from .episode_stats import EpisodeStats
         return EpisodeStats
-    if name in ("ConvFCPolicy", "ConvLSTMPolicy", "ConvMOAPolicy", "WatershedLSTMPolicy", "ppo_loss"):
+    if name in ("ConvFCPolicy", "ConvLSTMPolicy", "ConvMOAPolicy", "WatershedLSTMPolicy", "ppo_loss", "ppo_loss_recurrent"):
         from . import policy
         return getattr(policy, name)
     if name == "compute_advantages":

@@ -86,6 +86,30 @@ struct MoaArgs {
 hipError_t launch_policy_moa_actions(const MoaArgs &a, void *stream);
 // The MOA cell: gates, the A counterfactual updates and predictions, moa_logits and the influence (ssd_policy_moa.hip).
 hipError_t launch_policy_moa_cell(const MoaArgs &a, void *stream);
+// The PPO gradient kernel's arguments (ssd_policy_grad.hip).
+struct PpoGradArgs {
+    const float *w;                // P weight sets
+    int32_t P, A, N, set_floats;
+    int32_t G;                     // workgroups per set
+    int32_t set_rows;              // rows of one set
+    int32_t step_rows;             // E * N: rows of one step
+    const uint8_t *obs_first;      // u8 [E][N][675] or null
+    const uint8_t *obs;            // u8 [K][E][N][675]
+    const int32_t *actions;        // [K][E][N]
+    const float *logp_old, *adv, *vt, *vf_pred;   // [K][E][N]
+    const float *beh;              // [K][E][N][A] or null
+    float clip, vf_clip, vf_coeff, ent_coeff, kl_coeff;
+    float *scratch;                // [P][G][set_floats + SSD_PPO_STAT_FLOATS]
+    float *grads;                  // [P][set_floats]
+    double *stats;                 // [P][5]
+    // launch_ppo_trunk_grad only
+    const float *dx;               // [K][E][N][32] d loss / d fc2's output (after its ReLU), not yet divided by the rows
+    int32_t accumulate;            // add the partial sets to what scratch holds
+    int32_t w_pitch;               // floats between the weight sets of w (set_floats is the partial sets' pitch alone)
+};
+// The same kernel as the trunk's backward alone (the recurrent policy's, ssd_policy_lstm_grad.hip): set_floats floats of a
+// partial set are the trunk's (SSD_POL_CONV_W .. SSD_POL_FC2_B); a (G, P) grid whatever set_rows is.
+hipError_t launch_ppo_trunk_grad(const PpoGradArgs &a, void *stream);
 // The calling thread's ssd_policy_last_error text; returns SSD_E_INVALID.
 int policy_fail(const char *msg);
 

@@ -1,7 +1,7 @@
 // csrc/ssd_policy_device.hpp -- the device pieces the policy kernels are built from, each defined once: the LSTM gate GEMM, the
-// two cell rules and the cell update, the start rule and the loader of the h rows, the heads, the action draw, and the conv-FC
-// trunk (conv, fc1, fc2) on a tile.  Used by ssd_policy.hip (conv-FC), ssd_policy_grad.hip, ssd_policy_lstm.hip,
-// ssd_policy_moa.hip and ssd_ws_policy.hip; the argument blocks stay in
+// two cell rules and the cell update, the start rule and the loader of the h rows, the heads, the PPO loss terms of a row, the
+// action draw, and the conv-FC trunk (conv, fc1, fc2) on a tile.  Used by ssd_policy.hip (conv-FC), ssd_policy_grad.hip,
+// ssd_policy_lstm.hip, ssd_policy_lstm_grad.hip, ssd_policy_moa.hip and ssd_ws_policy.hip; the argument blocks stay in
 // ssd_policy.hpp, which host code reads too.  Every sum below is one chain in a fixed order, so a change here changes the
 // bits of every kernel that uses the piece, and the tests that compare kernels and paths bit for bit see it.
 //
@@ -160,6 +160,64 @@ __device__ __forceinline__ void heads(const Args &a, const float *s_h, int pitch
             }
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------------------ the PPO loss
+// The loss terms of one row (include/ssd.h, PPO LOSS AND GRADIENTS), one thread per row: l = the row's logits 0..A-1 and its
+// value at A, act its action (already within 0 .. A-1), bl its behaviour logits or null.  The five terms are float32 and are
+// added to st (total, policy, vf, kl, entropy); d[0..A] receives d row_loss / d (logits, value) with the contract's derivatives
+// at the kinks.  Used by the PPO gradient kernels of both policies (ssd_policy_grad.hip, ssd_policy_lstm_grad.hip).
+struct PpoHyper {
+    float clip, vf_clip, vf_coeff, ent_coeff, kl_coeff;
+};
+
+__device__ __forceinline__ void ppo_row(const float *l, float *d, int A, int act, float adv, float vt, float vfp, float lpo,
+                                        const float *bl, const PpoHyper &a, double (&st)[5]) {
+    const float value = l[A];
+    float mx = l[0];
+    for (int k = 1; k < A; ++k) mx = fmaxf(mx, l[k]);
+    float s = 0.f;
+    for (int k = 0; k < A; ++k) s += expf(l[k] - mx);
+    const float lse = mx + logf(s);
+    float ent = 0.f;
+    for (int k = 0; k < A; ++k) {
+        const float lp = l[k] - lse;
+        ent -= expf(lp) * lp;
+    }
+    float kl = 0.f;
+    float bl_lse = 0.f;
+    if (bl) {
+        float bm = bl[0];
+        for (int k = 1; k < A; ++k) bm = fmaxf(bm, bl[k]);
+        float bs = 0.f;
+        for (int k = 0; k < A; ++k) bs += expf(bl[k] - bm);
+        bl_lse = bm + logf(bs);
+        for (int k = 0; k < A; ++k) {
+            const float blp = bl[k] - bl_lse;
+            kl += expf(blp) * (blp - (l[k] - lse));
+        }
+    }
+    const float logp = l[act] - lse;
+    const float ratio = expf(logp - lpo);
+    const float lo = 1.f - a.clip, hi = 1.f + a.clip;
+    const float s1 = adv * ratio, s2 = adv * fminf(fmaxf(ratio, lo), hi);
+    const float surr = fminf(s1, s2);
+    const float dsurr = ((ratio >= lo && ratio <= hi) || s1 < s2) ? adv : 0.f;     // d surr / d ratio
+    const float d1 = value - vt, dv = value - vfp;
+    const float d2 = (vfp + fminf(fmaxf(dv, -a.vf_clip), a.vf_clip)) - vt;
+    const float vf1 = d1 * d1, vf2 = d2 * d2;
+    const float vf = fmaxf(vf1, vf2);
+    const float dvf = (fabsf(dv) <= a.vf_clip || vf1 >= vf2) ? 2.f * d1 : 0.f;     // d vf / d value
+    const float row_loss = ((-surr + a.kl_coeff * kl) + a.vf_coeff * vf) - a.ent_coeff * ent;
+    st[0] += (double)row_loss; st[1] += (double)(-surr); st[2] += (double)vf; st[3] += (double)kl; st[4] += (double)ent;
+    const float gl = -dsurr * ratio;           // d row_loss / d logp
+    for (int k = 0; k < A; ++k) {
+        const float lp = l[k] - lse, pk = expf(lp);
+        float dk = gl * ((k == act ? 1.f : 0.f) - pk) + a.ent_coeff * (pk * (lp + ent));
+        if (bl) dk += a.kl_coeff * (pk - expf(bl[k] - bl_lse));
+        d[k] = dk;
+    }
+    d[A] = a.vf_coeff * dvf;
 }
 
 // -------------------------------------------------------------------------------------------------------------- the action

@@ -17,7 +17,8 @@
 //      filters; the slices are added in order when the workgroup is done.
 // At the end a workgroup writes its partial gradient set and statistics to the caller's scratch; a second kernel adds the G
 // partials of a set in order (float64), scales by 1 / rows and rounds once.  No atomics anywhere: the same inputs give the same
-// bits.
+// bits.  The kernel's second instantiation is the trunk's backward alone, from a given d loss / d fc2's output: what the
+// recurrent policy's call (ssd_policy_lstm_grad.hip) runs below its cell.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -34,23 +35,12 @@ using ssd::f32x4;
 constexpr int kSlices = 9;                  // step 6: 27 taps x 9 slices = 243 threads
 constexpr int kStatFloats = SSD_PPO_STAT_FLOATS;
 
-struct GradArgs {
-    const float *w;                // P weight sets
-    int32_t P, A, N, set_floats;
-    int32_t G;                     // workgroups per set
-    int32_t set_rows;              // rows of one set
-    int32_t step_rows;             // E * N: rows of one step
-    const uint8_t *obs_first;      // u8 [E][N][675] or null
-    const uint8_t *obs;            // u8 [K][E][N][675]
-    const int32_t *actions;        // [K][E][N]
-    const float *logp_old, *adv, *vt, *vf_pred;   // [K][E][N]
-    const float *beh;              // [K][E][N][A] or null
-    float clip, vf_clip, vf_coeff, ent_coeff, kl_coeff;
-    float *scratch;                // [P][G][set_floats + kStatFloats]
-    float *grads;                  // [P][set_floats]
-    double *stats;                 // [P][5]
-};
+using GradArgs = ssd::PpoGradArgs;
 
+// kFromDx: the trunk's backward alone, for the recurrent policy (ssd_policy_lstm_grad.hip): steps 1 (to fc2) and 3 (from fc2
+// down) to 6, with d loss / d fc2's output read from a.dx instead of formed from the heads; nothing of the heads or the
+// statistics is summed or written, and with a.accumulate the partial set is added to what scratch holds (the windows before).
+template <bool kFromDx>
 __global__ void __launch_bounds__(kThreads) ssd_ppo_grad_kernel(GradArgs a) {
     __shared__ float s_norm[256];
     __shared__ float s_conv[kTile * kPitch + 8];       // the conv output; after step 5, d loss / d conv.  (+ 8: step 4's last A rows)
@@ -65,7 +55,7 @@ __global__ void __launch_bounds__(kThreads) ssd_ppo_grad_kernel(GradArgs a) {
     const int tid = threadIdx.x, g = blockIdx.x, p = blockIdx.y;
     const int A = a.A, R = a.set_rows;
     const int stride = a.P == 1 ? 1 : a.N;             // a set's row r is row r * stride + p of the [K][E][N] arrays
-    const float *w_set = a.w + (size_t)p * (size_t)a.set_floats;
+    const float *w_set = a.w + (size_t)p * (size_t)(kFromDx ? a.w_pitch : a.set_floats);
     const int wave = tid >> 6, lane = tid & 63, l15 = lane & 15, l4 = lane >> 4;
 
     s_norm[tid] = (float)(((double)tid - 128.0) / 255.0);
@@ -114,7 +104,7 @@ __global__ void __launch_bounds__(kThreads) ssd_ppo_grad_kernel(GradArgs a) {
         __syncthreads();
         fc_stack<false>(w, s_conv, s_part, s_h1, tid, s_h2, kHP, kTile);
         __syncthreads();
-        {
+        if constexpr (!kFromDx) {
             const int m = tid >> 4, j = tid & 15;
             if (j <= A)
                 s_out[tid] = ssd::head<32>(s_h2 + m * kHP, w + SSD_POL_LOGITS_W, w + SSD_POL_VALUE_W, w + SSD_POL_LOGITS_W + 32 * A,
@@ -124,81 +114,43 @@ __global__ void __launch_bounds__(kThreads) ssd_ppo_grad_kernel(GradArgs a) {
         __syncthreads();
 
         // ---- 2. the loss terms of row tid and their derivatives ----
-        if (tid < kTile && r0 + tid < R) {
+        if (!kFromDx && tid < kTile && r0 + tid < R) {
             const size_t row = (size_t)(r0 + tid) * stride + p;
-            const float *l = s_out + tid * 16;
-            float *d = s_dout + tid * 16;
-            const float value = l[A];
             int act = a.actions[row];
             act = act < 0 ? 0 : (act >= A ? A - 1 : act);
-            const float adv = a.adv[row], vt = a.vt[row], vfp = a.vf_pred[row], lpo = a.logp_old[row];
-            float mx = l[0];
-            for (int k = 1; k < A; ++k) mx = fmaxf(mx, l[k]);
-            float s = 0.f;
-            for (int k = 0; k < A; ++k) s += expf(l[k] - mx);
-            const float lse = mx + logf(s);
-            float ent = 0.f;
-            for (int k = 0; k < A; ++k) {
-                const float lp = l[k] - lse;
-                ent -= expf(lp) * lp;
-            }
-            float kl = 0.f;
-            float bl_lse = 0.f;
-            const float *bl = a.beh ? a.beh + row * A : nullptr;
-            if (bl) {
-                float bm = bl[0];
-                for (int k = 1; k < A; ++k) bm = fmaxf(bm, bl[k]);
-                float bs = 0.f;
-                for (int k = 0; k < A; ++k) bs += expf(bl[k] - bm);
-                bl_lse = bm + logf(bs);
-                for (int k = 0; k < A; ++k) {
-                    const float blp = bl[k] - bl_lse;
-                    kl += expf(blp) * (blp - (l[k] - lse));
-                }
-            }
-            const float logp = l[act] - lse;
-            const float ratio = expf(logp - lpo);
-            const float lo = 1.f - a.clip, hi = 1.f + a.clip;
-            const float s1 = adv * ratio, s2 = adv * fminf(fmaxf(ratio, lo), hi);
-            const float surr = fminf(s1, s2);
-            const float dsurr = ((ratio >= lo && ratio <= hi) || s1 < s2) ? adv : 0.f;     // d surr / d ratio
-            const float d1 = value - vt, dv = value - vfp;
-            const float d2 = (vfp + fminf(fmaxf(dv, -a.vf_clip), a.vf_clip)) - vt;
-            const float vf1 = d1 * d1, vf2 = d2 * d2;
-            const float vf = fmaxf(vf1, vf2);
-            const float dvf = (fabsf(dv) <= a.vf_clip || vf1 >= vf2) ? 2.f * d1 : 0.f;     // d vf / d value
-            const float row_loss = ((-surr + a.kl_coeff * kl) + a.vf_coeff * vf) - a.ent_coeff * ent;
-            st[0] += (double)row_loss; st[1] += (double)(-surr); st[2] += (double)vf; st[3] += (double)kl; st[4] += (double)ent;
-            const float gl = -dsurr * ratio;           // d row_loss / d logp
-            for (int k = 0; k < A; ++k) {
-                const float lp = l[k] - lse, pk = expf(lp);
-                float dk = gl * ((k == act ? 1.f : 0.f) - pk) + a.ent_coeff * (pk * (lp + ent));
-                if (bl) dk += a.kl_coeff * (pk - expf(bl[k] - bl_lse));
-                d[k] = dk;
-            }
-            d[A] = a.vf_coeff * dvf;
+            ssd::ppo_row(s_out + tid * 16, s_dout + tid * 16, A, act, a.adv[row], a.vt[row], a.vf_pred[row], a.logp_old[row],
+                         a.beh ? a.beh + row * A : nullptr, ssd::PpoHyper{a.clip, a.vf_clip, a.vf_coeff, a.ent_coeff, a.kl_coeff}, st);
         }
         __syncthreads();
 
         // ---- 3. the backward through the heads, fc2 and fc1's activation ----
+        if constexpr (kFromDx) {                       // dh2 from the caller's rows, through h2's ReLU
 #pragma unroll
-        for (int u = 0; u < 2; ++u) {                  // the heads' kernels, and dh2 through h2's ReLU
-            const int q = tid + u * kThreads, k = q >> 4, j = q & 15;
-            float sum = 0.f;
+            for (int u = 0; u < 2; ++u) {
+                const int q = tid + u * kThreads, m = q >> 5, n = q & 31;
+                const float dh = r0 + m < R ? a.dx[((size_t)(r0 + m) * stride + p) * 32 + n] : 0.f;
+                s_dh2[m * kHP + n] = s_h2[m * kHP + n] > 0.f ? dh : 0.f;
+            }
+        } else {
 #pragma unroll
-            for (int m = 0; m < kTile; ++m) sum = fmaf(s_h2[m * kHP + k], s_dout[m * 16 + j], sum);
-            acc_hd[u] += sum;
-            const int m = q >> 5, n = q & 31;          // dh2[m][n] = sum_j dout[m][j] * W[n][j]
-            float dh = 0.f;
-            for (int jj = 0; jj < A; ++jj) dh = fmaf(s_dout[m * 16 + jj], w[SSD_POL_LOGITS_W + n * A + jj], dh);
-            dh = fmaf(s_dout[m * 16 + A], w[SSD_POL_VALUE_W + n], dh);
-            s_dh2[m * kHP + n] = s_h2[m * kHP + n] > 0.f ? dh : 0.f;
-        }
-        if (tid < 16) {
-            float sum = 0.f;
+            for (int u = 0; u < 2; ++u) {                  // the heads' kernels, and dh2 through h2's ReLU
+                const int q = tid + u * kThreads, k = q >> 4, j = q & 15;
+                float sum = 0.f;
 #pragma unroll
-            for (int m = 0; m < kTile; ++m) sum += s_dout[m * 16 + tid];
-            acc_bh += sum;
+                for (int m = 0; m < kTile; ++m) sum = fmaf(s_h2[m * kHP + k], s_dout[m * 16 + j], sum);
+                acc_hd[u] += sum;
+                const int m = q >> 5, n = q & 31;          // dh2[m][n] = sum_j dout[m][j] * W[n][j]
+                float dh = 0.f;
+                for (int jj = 0; jj < A; ++jj) dh = fmaf(s_dout[m * 16 + jj], w[SSD_POL_LOGITS_W + n * A + jj], dh);
+                dh = fmaf(s_dout[m * 16 + A], w[SSD_POL_VALUE_W + n], dh);
+                s_dh2[m * kHP + n] = s_h2[m * kHP + n] > 0.f ? dh : 0.f;
+            }
+            if (tid < 16) {
+                float sum = 0.f;
+#pragma unroll
+                for (int m = 0; m < kTile; ++m) sum += s_dout[m * 16 + tid];
+                acc_bh += sum;
+            }
         }
         __syncthreads();
 #pragma unroll
@@ -293,6 +245,10 @@ __global__ void __launch_bounds__(kThreads) ssd_ppo_grad_kernel(GradArgs a) {
 
     // ---- the workgroup's partial set and statistics ----
     float *part = a.scratch + ((size_t)p * a.G + g) * (size_t)(a.set_floats + kStatFloats);
+    const auto put = [=](int at, float v) {            // kFromDx: onto the sums so far, carried in scratch from window to window
+        if constexpr (kFromDx) part[at] = a.accumulate ? part[at] + v : v;
+        else part[at] = v;
+    };
     __syncthreads();
     float *s_red = s_conv;                             // [27][kSlices][6] conv_w slices, then [kSlices][6] conv_b slices
     if (tid < 27 * kSlices) {
@@ -313,9 +269,9 @@ __global__ void __launch_bounds__(kThreads) ssd_ppo_grad_kernel(GradArgs a) {
         float sum = 0.f;
 #pragma unroll
         for (int sl = 0; sl < kSlices; ++sl) sum += src[sl * 6];
-        part[SSD_POL_CONV_W + tid] = sum;
+        put(SSD_POL_CONV_W + tid, sum);
     }
-    if (tid < 5) {
+    if (!kFromDx && tid < 5) {
         double sum = 0.0;
         for (int m = 0; m < kTile; ++m) sum += s_stat[m * 5 + tid];
         reinterpret_cast<double *>(part + a.set_floats)[tid] = sum;
@@ -327,16 +283,17 @@ __global__ void __launch_bounds__(kThreads) ssd_ppo_grad_kernel(GradArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = 256 * wave + 16 * t + 4 * l4 + r;
-                if (row < kFlat) part[SSD_POL_FC1_W + row * 32 + 16 * c + l15] = acc_w1[t][c][r];
+                if (row < kFlat) put(SSD_POL_FC1_W + row * 32 + 16 * c + l15, acc_w1[t][c][r]);
             }
         }
     }
     if (tid < 32) {
-        part[SSD_POL_FC1_B + tid] = acc_b1;
-        part[SSD_POL_FC2_B + tid] = acc_b2;
+        put(SSD_POL_FC1_B + tid, acc_b1);
+        put(SSD_POL_FC2_B + tid, acc_b2);
     }
 #pragma unroll
-    for (int u = 0; u < 4; ++u) part[SSD_POL_FC2_W + tid + u * kThreads] = acc_w2[u];
+    for (int u = 0; u < 4; ++u) put(SSD_POL_FC2_W + tid + u * kThreads, acc_w2[u]);
+    if constexpr (kFromDx) return;
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         const int q = tid + u * kThreads, k = q >> 4, j = q & 15;
@@ -367,6 +324,15 @@ __global__ void __launch_bounds__(256) ssd_ppo_reduce_kernel(GradArgs a) {
 }
 
 }  // namespace
+
+namespace ssd {
+
+hipError_t launch_ppo_trunk_grad(const PpoGradArgs &a, void *stream) {
+    hipLaunchKernelGGL(ssd_ppo_grad_kernel<true>, dim3((unsigned)a.G, (unsigned)a.P), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+    return hipGetLastError();
+}
+
+}  // namespace ssd
 
 extern "C" int ssd_policy_ppo_grad(const float *weights, int32_t num_sets, int32_t num_actions, const uint8_t *obs_first,
                                    const uint8_t *obs, const int32_t *actions, const float *logp_old, const float *advantages,
@@ -404,7 +370,7 @@ extern "C" int ssd_policy_ppo_grad(const float *weights, int32_t num_sets, int32
     a.clip = (float)clip_param; a.vf_clip = (float)vf_clip_param; a.vf_coeff = (float)vf_loss_coeff;
     a.ent_coeff = (float)entropy_coeff; a.kl_coeff = (float)kl_coeff;
     a.scratch = scratch; a.grads = grads; a.stats = stats;
-    hipLaunchKernelGGL(ssd_ppo_grad_kernel, dim3((unsigned)a.G, (unsigned)a.P), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(ssd_ppo_grad_kernel<false>, dim3((unsigned)a.G, (unsigned)a.P), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
     if (const hipError_t e = hipGetLastError()) return ssd::policy_launched(e);
     hipLaunchKernelGGL(ssd_ppo_reduce_kernel, dim3((unsigned)((a.set_floats + 255) / 256), (unsigned)a.P), dim3(256), 0,
                        static_cast<hipStream_t>(stream), a);

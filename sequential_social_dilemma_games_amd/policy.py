@@ -265,6 +265,12 @@ class ConvLSTMPolicy(PolicyBase):
         """The trunk's features: f32 [rows, 32]."""
         return (rows, _capi.SSD_LSTM_X)
 
+    def ppo_scratch_shape(self, n_steps, num_envs, num_agents, seq_len):
+        """The float32 scratch ssd_policy_lstm_ppo_grad needs for a [n_steps, num_envs, num_agents] fragment walked in windows
+        of seq_len steps: what is kept of one window's rows for the backward, and the partial gradient sums."""
+        return (_capi.SSD_RPPO_SCRATCH_FLOATS(n_steps, num_envs, num_agents, self.num_sets, self.num_actions, self.cell_size,
+                                                  seq_len),)
+
     def forward(self, obs, state, starts=None):
         """obs u8 [..., (P,) 15, 15, 3], state [..., 2, C] (the same leading shape), starts bool [...] or None: rows whose state
         is replaced by zero (selected, not multiplied: whatever the state holds there is never used).  Returns (logits [..., A],
@@ -731,6 +737,132 @@ def ppo_loss(policy, batch, *, clip_param, vf_clip_param, vf_loss_coeff, entropy
     if dev.type != "cpu":
         raise ValueError("the tensors must be on the CPU or on a GPU, not on %s" % (dev,))
     logits, value = policy(_ppo_obs(t, K))
+    terms = ppo_terms(logits, value, t, *hyper)
+    means = [_set_means(x, P) for x in terms]
+    return means[0].sum(), {name: m.detach() for name, m in zip(PPO_STATS, means)}
+
+
+# ---- the same loss for the recurrent policy, with truncated BPTT (include/ssd.h, RECURRENT PPO LOSS AND GRADIENTS) ----
+
+def _recurrent_tensors(policy, batch, K, E, N, seq_len, dev):
+    """The state ring [S, E, N, 2, C] and done [K, E, N] (or None) of a recurrent fragment, checked."""
+    C, T = policy.cell_size, int(seq_len)
+    S = -(-K // T)
+    state = batch.get("state")
+    if state is None and T >= K and batch.get("state_in") is not None:
+        state = batch["state_in"].unsqueeze(0)                    # one window: the state step 0 used
+    if not isinstance(state, torch.Tensor):
+        raise ValueError("state is required: the ring sample(..., state_every=seq_len) records (state_in serves when seq_len >= K)")
+    if state.dim() != 5 or tuple(state.shape[1:4]) != (E, N, 2) or state.shape[0] < S:
+        raise ValueError("state must be [S, %d, %d, 2, C] with S >= ceil(K / seq_len) = %d, got %s" % (E, N, S, tuple(state.shape)))
+    if state.shape[-1] != C:
+        raise ValueError("state has %d cells, the policy %d" % (state.shape[-1], C))
+    if state.dtype != torch.float32 or state.device != dev or not state.is_contiguous():
+        raise ValueError("state must be a contiguous torch.float32 tensor on %s" % (dev,))
+    done = batch.get("done")
+    if done is not None:
+        if (not isinstance(done, torch.Tensor) or done.dtype != torch.uint8 or tuple(done.shape) != (K, E, N) or done.device != dev
+                or not done.is_contiguous()):
+            raise ValueError("done must be a contiguous torch.uint8 tensor of shape %s on %s" % ((K, E, N), dev))
+    return state, done
+
+
+class _RecurrentPPOLossFunction(torch.autograd.Function):
+    """ssd_policy_lstm_ppo_grad as a torch function of the policy's parameters, as _PPOLossFunction."""
+
+    @staticmethod
+    def forward(ctx, policy, t, dims, seq_len, hyper, *params):
+        import ctypes as C
+        K, E, N = dims
+        P, A = policy.num_sets, policy.num_actions
+        dev = t["actions"].device
+        weights = policy.packed()
+        need = policy.ppo_scratch_shape(K, E, N, seq_len)[0]
+        scratch = getattr(policy, "_ppo_scratch", None)          # kept between calls, as packed()'s buffer is
+        if scratch is None or scratch.device != dev or scratch.numel() < need:
+            scratch = policy._ppo_scratch = torch.empty(need, dtype=torch.float32, device=dev)
+        grads = torch.empty((P, policy.set_floats), dtype=torch.float32, device=dev)
+        stats = torch.empty((P, len(PPO_STATS)), dtype=torch.float64, device=dev)
+        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())   # noqa: E731
+        index = dev.index if dev.index is not None else torch.cuda.current_device()
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _capi.policy_check(_capi.lib().ssd_policy_lstm_ppo_grad(
+            ptr(weights), P, A, policy.cell_size, seq_len, ptr(t["obs_first"]), ptr(t["obs"]), ptr(t["state"]), ptr(t["done"]),
+            ptr(t["actions"]), ptr(t["logp_old"]), ptr(t["advantages"]), ptr(t["value_targets"]), ptr(t["vf_pred"]),
+            ptr(t["behaviour_logits"]), K, E, N, *hyper, ptr(scratch), ptr(grads), ptr(stats), index, 0, stream))
+        ctx.policy = policy
+        ctx.save_for_backward(grads)
+        ctx.mark_non_differentiable(stats)
+        return stats[:, 0].sum().to(torch.float32), stats
+
+    @staticmethod
+    def backward(ctx, g_loss, g_stats):
+        (grads,) = ctx.saved_tensors
+        out = unpack_gradient(ctx.policy, grads, g_loss)
+        return (None, None, None, None, None) + tuple(g if needs else None for g, needs in zip(out, ctx.needs_input_grad[5:]))
+
+
+def recurrent_forward(policy, obs, state, done, seq_len):
+    """The learner's forward of a ConvLSTMPolicy over a fragment, in plain torch under autograd, by the state rule of
+    include/ssd.h: obs u8 [K, E, N, 15, 15, 3] (the observation each row acted on), the ring state [S, E, N, 2, C] (detached:
+    data), done u8 [K, E, N] or None -> (logits [K, E, N, A], value [K, E, N]).  Window by window through forward_sequence;
+    step k of a window resets where done[k - 1] is set."""
+    K, T = int(obs.shape[0]), int(seq_len)
+    dt = policy.conv_w.dtype
+    logits, value = [], []
+    for w, k0 in enumerate(range(0, K, T)):
+        k1 = min(k0 + T, K)
+        resets = None
+        if done is not None and k1 - k0 > 1:
+            resets = torch.cat([torch.zeros_like(done[:1]), done[k0:k1 - 1]]).to(torch.bool)
+        lg, v, _ = policy.forward_sequence(obs[k0:k1], state[w].detach().to(dt), resets)
+        logits.append(lg)
+        value.append(v)
+    return torch.cat(logits), torch.cat(value)
+
+
+def ppo_loss_recurrent(policy, batch, *, seq_len, clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff, obs_first=None):
+    """ppo_loss for a ConvLSTMPolicy: the same loss, rows, observation shift and statistics, with truncated backpropagation
+    through time over windows of seq_len steps (RLlib's max_seq_len) -> (loss, stats).  include/ssd.h (RECURRENT PPO LOSS AND
+    GRADIENTS) states the state rule: a window starts from the recorded state (no gradient into it), a step after a done row
+    starts from zero, every other step from the state the step before it computed with the current weights.
+
+        first = env.reset().clone()
+        batch = env.sample(policy, 128, state_every=16, gamma=0.99, lambda_=0.95)
+        loss, stats = ppo_loss_recurrent(policy, batch, seq_len=16, clip_param=0.3, vf_clip_param=10.0, vf_loss_coeff=1e-4,
+                                         entropy_coeff=1e-3, kl_coeff=0.0, obs_first=first)
+        loss.backward(); optimiser.step()
+
+    batch: the dict sample(policy, K, state_every=seq_len, gamma=...) returns -- ppo_loss's keys and besides "state" f32
+    [S,E,N,2,C], S = ceil(K / seq_len) ("state_in" serves when seq_len >= K) and "done" u8 [K,E,N] (absent or None: no episode
+    ends inside the fragment).  A minibatch of steps k0 .. k1 - 1 with k0 a multiple of seq_len is the slices [k0:k1] of the
+    per-row tensors, state[k0 // seq_len:] and obs_first = obs[k0 - 1].
+    CUDA tensors go to the library (ssd_policy_lstm_ppo_grad on torch's current stream, no synchronisation; the scratch is
+    kept on the policy); CPU tensors run forward_sequence per window and ppo_terms under autograd."""
+    if not isinstance(policy, ConvLSTMPolicy):
+        raise ValueError("ppo_loss_recurrent is for a ConvLSTMPolicy (ppo_loss is the ConvFCPolicy's)")
+    if not isinstance(batch, dict):
+        raise ValueError("batch must be the dict sample() returns")
+    if isinstance(seq_len, bool) or int(seq_len) != seq_len or int(seq_len) < 1:
+        raise ValueError("seq_len must be an integer >= 1")
+    seq_len = int(seq_len)
+    hyper = tuple(float(x) for x in (clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff))
+    if not all(np.isfinite(hyper)) or hyper[0] < 0 or hyper[1] < 0:
+        raise ValueError("the hyper-parameters must be finite, clip_param and vf_clip_param >= 0")
+    t, (K, E, N) = _ppo_tensors(policy, batch, obs_first, hyper[4])
+    dev, P = t["actions"].device, policy.num_sets
+    if policy.conv_w.device != dev:
+        raise ValueError("the policy is on %s, the batch on %s" % (policy.conv_w.device, dev))
+    t["state"], t["done"] = _recurrent_tensors(policy, batch, K, E, N, seq_len, dev)
+    if dev.type == "cuda":
+        if policy.conv_w.dtype != torch.float32:
+            raise ValueError("the device path needs a float32 policy")
+        params = tuple(getattr(policy, name) for name, _, _ in policy.layout())
+        loss, stats = _RecurrentPPOLossFunction.apply(policy, t, (K, E, N), seq_len, hyper, *params)
+        return loss, {name: stats[:, k] for k, name in enumerate(PPO_STATS)}
+    if dev.type != "cpu":
+        raise ValueError("the tensors must be on the CPU or on a GPU, not on %s" % (dev,))
+    logits, value = recurrent_forward(policy, _ppo_obs(t, K), t["state"], t["done"], seq_len)
     terms = ppo_terms(logits, value, t, *hyper)
     means = [_set_means(x, P) for x in terms]
     return means[0].sum(), {name: m.detach() for name, m in zip(PPO_STATS, means)}
