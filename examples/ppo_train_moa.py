@@ -1,0 +1,59 @@
+#!/usr/bin/env python3
+"""A few PPO iterations on Harvest with the causal-influence (MOA) policy of run_scripts/train_moa.py, sampler and learner both
+on the device: sample a fragment with the influence reward inside the advantages and the state every window started from
+(SSDVectorEnv.sample(..., state_every=seq_len, influence_weight=, gamma=, lambda_=)), then a few epochs of window-aligned
+step-range minibatches through ppo_loss_moa -- PPOLoss + moa_weight * MOALoss with truncated backpropagation through time
+through both LSTMs, its statistics and every gradient from one library call -- and Adam.  The MOA twin of
+examples/ppo_train_lstm.py: an example of how the pieces fit, not a trainer (no influence-weight schedule).
+
+    python examples/ppo_train_moa.py [envs] [steps] [iterations]
+"""
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from sequential_social_dilemma_games_amd import ConvMOAPolicy, ppo_loss_moa  # noqa: E402
+from sequential_social_dilemma_games_amd import constants as K  # noqa: E402
+from sequential_social_dilemma_games_amd.vector_env import SSDVectorEnv  # noqa: E402
+
+
+def main():
+    E = int(sys.argv[1]) if len(sys.argv) > 1 else 256
+    steps = int(sys.argv[2]) if len(sys.argv) > 2 else 32
+    iterations = int(sys.argv[3]) if len(sys.argv) > 3 else 2
+    N, epochs, seq_len, mb_windows = 5, 3, 8, 2                  # a minibatch is mb_windows whole windows of seq_len steps
+    influence_weight, moa_weight = 1.0, 10.0                    # train_moa.py:142-150: moa_weight 10, influence_reward_weight 1.0
+    hyper = dict(clip_param=0.3, vf_clip_param=10.0, vf_loss_coeff=1e-4, entropy_coeff=1e-3, kl_coeff=0.0)
+    env = SSDVectorEnv(K.GAME_HARVEST, E, N, horizon=1000, seed=0)
+    policy = ConvMOAPolicy(env.engine.num_actions, num_agents=N, num_sets=N, cell_size=128, seed=0).cuda()
+    optim = torch.optim.Adam(policy.parameters(), lr=1e-4)
+
+    first = env.reset().clone()                      # sample() leaves the fragment's last observation in this buffer
+    for it in range(iterations):
+        batch = env.sample(policy, steps, state_every=seq_len, influence_weight=influence_weight, gamma=0.99, lambda_=0.95)
+        print("iteration %d: %d envs x %d agents x %d steps, reward sum %d, mean influence %.4f" %
+              (it, E, N, steps, int(batch["rew"].sum()), float(batch["influence"].mean())))
+        for epoch in range(epochs):
+            sums, count = None, 0
+            for k0 in range(0, steps, seq_len * mb_windows):
+                k1 = min(k0 + seq_len * mb_windows, steps)
+                # views: the rows' slices, the ring from the minibatch's first window, and the observation step k0 acted on
+                mb = {k: batch[k][k0:k1] for k in ("obs", "actions", "logp", "value", "advantages", "value_targets", "done", "prev_actions")}
+                mb["state"] = batch["state"][k0 // seq_len:]
+                loss, stats = ppo_loss_moa(policy, mb, seq_len=seq_len, moa_weight=moa_weight,
+                                           obs_first=first if k0 == 0 else batch["obs"][k0 - 1], **hyper)
+                optim.zero_grad()
+                loss.backward()
+                optim.step()                         # the next call packs the updated parameters
+                row = torch.stack([stats[k].mean() for k in ("total_loss", "policy_loss", "vf_loss", "entropy", "moa_loss")])
+                sums, count = row if sums is None else sums + row, count + 1
+            print("  epoch %d: total %.5f, policy %.5f, vf %.4f, entropy %.4f, moa %.4f (means over sets and minibatches)" %
+                  ((epoch,) + tuple(float(x) for x in sums / count)))
+        first = batch["obs"][steps - 1].clone()      # the next fragment's first step acts on this one's last observation
+
+
+if __name__ == "__main__":
+    main()

@@ -866,6 +866,79 @@ int ssd_policy_lstm_ppo_grad(const float *weights, int32_t num_sets, int32_t num
                              double entropy_coeff, double kl_coeff, float *scratch, float *grads, double *stats,
                              int32_t device_id, uint32_t flags, void *stream);
 
+/* ======================================================================================================================
+ * MOA PPO LOSS AND GRADIENTS -- the learner's half of the loop for the causal-influence policy (run_scripts/train_moa.py,
+ * algorithms/ppo_causal.py:36-75): PPOLoss + moa_weight * MOALoss on a sampled fragment with truncated BPTT through both
+ * Keras LSTMs, its statistics and the gradient of every parameter, in one call (csrc/ssd_policy_moa_grad.hip; DESIGN.md
+ * section 18).  Added after ABI 6 without a version bump: the call is additive.
+ *
+ * Network: that of ssd_policy_moa_forward above, the same packed weight layout (SSD_MOA_*), P = 1 or P = N sets,
+ * 2 <= N <= SSD_MOA_MAX_AGENTS, A <= 15, C = cell_size = 64, 128 or 256.  Exact float32 on v_mfma_f32_16x16x4_f32.
+ *
+ * Rows, observation shift, the PPO terms and their derivatives at the kinks: exactly those of PPO LOSS AND GRADIENTS (the
+ * same device code forms them, on the actions LSTM's logits and value).  The row loss of row (k, e, i) is
+ *   the PPO row loss  +  moa_weight * (1 / (N - 1)) * sum over j of CE(pred[j], actions[k, e, others(i)[j]]),
+ * pred [N-1][A] the MOA LSTM's prediction of the step, others(i) the agents other than i in the order of their ids sorted as
+ * strings, CE(l, a) = logsumexp(l) - l[a]; the targets are this step's actions of the other agents (the pairing of
+ * ConvMOAPolicy.moa_loss; the visibility factor is 1), clamped to 0 .. A - 1 as actions are.  The loss of a weight set is the
+ * mean of the row loss over the set's rows (K E for P = N, K E N for P = 1); the returned loss is the sum over the sets.
+ * stats f64 [P][6]: the five of PPO LOSS AND GRADIENTS (total_loss includes the weighted MOA term), then moa_loss, the mean
+ * cross-entropy (over rows and other agents) without the weight.
+ *
+ * State rule: that of RECURRENT PPO LOSS AND GRADIENTS for all four rows of state f32 [S, E, N, 4, C] = (h1, c1, h2, c2), the
+ * ring ssd_rollout_policy_moa records with state_every = T = seq_len.  prev_actions i32 [K, E, N] is the ring that call records:
+ * row (k, e, .) is the joint action step k's MOA read, by agent index.  It is data everywhere: read as stored at a window's
+ * first step (the ring holds zero at an episode start); at a step k % T != 0 after done[k - 1, e, i] != 0 the whole
+ * previous-action vector of row (k, e, i) is zero, selected and never loaded, as its state is.  A minibatch of steps
+ * k0 .. k1 - 1 with k0 % T == 0 is the slices [k0:k1] of the per-row arrays, done and prev_actions, obs_first = obs ring
+ * [k0 - 1] and state = ring + k0 / T.
+ *
+ * Gradient flows from the PPO terms through the heads, the actions LSTM (BPTT) and stack 0 into the conv, and from the
+ * cross-entropy through pred_w / pred_b, the MOA LSTM (BPTT), stack 1 and the action rows 32 .. 32 + N - 1 of the MOA kernel
+ * into the conv; conv_w and conv_b receive the sum.  The counterfactuals and the influence are not part of the loss (the
+ * influence is data inside the advantages).  grads f32 [P, SSD_MOA_SET_FLOATS(C, A, N)] in the packed layout; rows 32 + N .. 47
+ * of the MOA matrix and all padding floats are zero.
+ *
+ * Arithmetic and order: as RECURRENT PPO LOSS AND GRADIENTS.  Per window the call runs the features of both stacks, then for
+ * the actions branch and after it for the MOA branch the sequence kernel (tiles of SSD_MPPO_TILE sequences, workgroup g of
+ * SSD_MPPO_GROUPS takes tiles g, g + G, ...; the cross-entropies of a workgroup are float32 terms in float64 sums, one per
+ * (tile row, other agent), added in that order at the end) and the split sums of the LSTM matrix and bias (chunks of
+ * SSD_MPPO_CHUNK rows, split s of SSD_MPPO_SPLITS takes chunks s, s + S, ...); pred_w = h2'^T dpred and pred_b by the same
+ * partition; then the trunk's backward once per stack, stack 1 adding its conv sums to stack 0's.  The partial sums of an
+ * entry are added in order in float64, scaled by 1 / (the set's rows) and rounded once.  No atomics: the same inputs give the
+ * same bits.
+ *
+ * scratch: SSD_MPPO_SCRATCH_FLOATS(K, E, N, P, A, C, T) floats the call overwrites, 8-byte aligned; it grows with the rows of
+ * one window and the numbers of partial sums, not with K beyond min(T, K).  moa_weight: finite, >= 0.
+ *
+ * Device pointers on device_id; everything is enqueued on `stream`, no allocation, no host synchronisation.  SSD_E_INVALID
+ * before anything is launched (ssd_policy_last_error says why) for everything ssd_policy_lstm_ppo_grad refuses, fewer than 2
+ * or more than SSD_MOA_MAX_AGENTS agents, a missing or misaligned prev_actions, a moa_weight that is not finite or negative.
+ * ====================================================================================================================== */
+enum { SSD_MPPO_TILE = 16, SSD_MPPO_CHUNK = 64, SSD_MPPO_MAX_SPLITS = 32 };
+#define SSD_MPPO_GROUPS(seqs, P) SSD_RPPO_GROUPS(seqs, P)
+#define SSD_MPPO_SPLITS(window_set_rows) SSD_RPPO_SPLITS(window_set_rows)
+/* floats between the rows of dpred and of pred_w's partial sums: (N - 1) A rounded up to whole 16-column tiles */
+#define SSD_MPPO_PRED_PITCH(A, N) ((((N) - 1) * (A) + 15) / 16 * 16)
+/* per row of a whole window: both stacks' features 64, their d (logits, value) / dx 64, (h', c') 2C and gates / dz 4C (one
+ * branch at a time), dpred */
+#define SSD_MPPO_ROW_FLOATS(C, A, N) (128 + 6 * (C) + SSD_MPPO_PRED_PITCH(A, N))
+/* the blocks, in order: both LSTM matrices transposed; the window's rows; the trunk's partial sets (the MOA layout below
+ * SSD_MOA_LSTM_W); the sequence kernel's (heads, then 8 float64 statistics); the two LSTM matrices' and pred_w's splits */
+#define SSD_MPPO_SCRATCH_FLOATS(K, E, N, P, A, C, T)                                                                              \
+    ((size_t)(P) * (80 + 2 * (C)) * 4 * (C) + (size_t)SSD_RPPO_MIN(T, K) * (E) * (N) * SSD_MPPO_ROW_FLOATS(C, A, N) +            \
+     (size_t)(P) * SSD_PPO_GROUPS((int32_t)SSD_RPPO_WINDOW_SET_ROWS(K, E, N, P, T), P) * (SSD_MOA_LSTM_W(C) + SSD_PPO_STAT_FLOATS) + \
+     (size_t)(P) * SSD_MPPO_GROUPS(SSD_RPPO_SEQS(E, N, P), P) * (16 * (C) + 16 + SSD_PPO_STAT_FLOATS) +                         \
+     (size_t)(P) * SSD_MPPO_SPLITS(SSD_RPPO_WINDOW_SET_ROWS(K, E, N, P, T)) *                                                    \
+         ((80 + 2 * (C)) * 4 * (C) + 8 * (C) + ((C) + 1) * SSD_MPPO_PRED_PITCH(A, N)))
+int ssd_policy_moa_ppo_grad(const float *weights, int32_t num_sets, int32_t num_actions, int32_t cell_size, int32_t seq_len,
+                            const uint8_t *obs_first, const uint8_t *obs, const float *state, const int32_t *prev_actions,
+                            const uint8_t *done, const int32_t *actions, const float *logp_old, const float *advantages,
+                            const float *value_targets, const float *vf_preds, const float *behaviour_logits, int32_t n_steps,
+                            int32_t num_envs, int32_t num_agents, double clip_param, double vf_clip_param, double vf_loss_coeff,
+                            double entropy_coeff, double kl_coeff, double moa_weight, float *scratch, float *grads,
+                            double *stats, int32_t device_id, uint32_t flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

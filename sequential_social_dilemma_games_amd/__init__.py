@@ -11,6 +11,7 @@
     from sequential_social_dilemma_games_amd import compute_advantages          # GAE / discounted returns of a rollout batch
     from sequential_social_dilemma_games_amd import ppo_loss                    # the PPO loss and its gradients, on the device
     from sequential_social_dilemma_games_amd import ppo_loss_recurrent          # the same for the recurrent policy, with BPTT
+    from sequential_social_dilemma_games_amd import ppo_loss_moa                # PPO + MOA loss for the MOA policy, with BPTT
 
 Everything that steps an env goes through libssd_hip.so (include/ssd.h); importing this package does
 not load it, constructing an env does -- and fails loudly if it is missing.
@@ -34,7 +35,8 @@ def __getattr__(name):
     if name == "EpisodeStats":
         from .episode_stats import EpisodeStats
         return EpisodeStats
-    if name in ("ConvFCPolicy", "ConvLSTMPolicy", "ConvMOAPolicy", "WatershedLSTMPolicy", "ppo_loss", "ppo_loss_recurrent"):
+    if name in ("ConvFCPolicy", "ConvLSTMPolicy", "ConvMOAPolicy", "WatershedLSTMPolicy", "ppo_loss", "ppo_loss_recurrent",
+                "ppo_loss_moa"):
         from . import policy
         return getattr(policy, name)
     if name == "compute_advantages":

@@ -80,6 +80,29 @@ def SSD_RPPO_SCRATCH_FLOATS(K, E, N, P, A, C, T):
             + P * SSD_RPPO_SPLITS(rows) * ((32 + C) * 4 * C + 4 * C))
 
 
+# the MOA PPO loss-and-gradient call's partial sums and scratch (include/ssd.h, SSD_MPPO_*)
+SSD_MPPO_TILE, SSD_MPPO_CHUNK, SSD_MPPO_MAX_SPLITS = 16, 64, 32
+SSD_MPPO_GROUPS, SSD_MPPO_SPLITS = SSD_RPPO_GROUPS, SSD_RPPO_SPLITS
+
+
+def SSD_MPPO_PRED_PITCH(A, N):
+    return ((int(N) - 1) * int(A) + 15) // 16 * 16
+
+
+def SSD_MPPO_ROW_FLOATS(C, A, N):
+    return 128 + 6 * int(C) + SSD_MPPO_PRED_PITCH(A, N)
+
+
+def SSD_MPPO_SCRATCH_FLOATS(K, E, N, P, A, C, T):
+    K, E, N, P, A, C, T = int(K), int(E), int(N), int(P), int(A), int(C), int(T)
+    seqs = SSD_RPPO_SEQS(E, N, P)
+    rows = min(T, K) * seqs
+    return (P * (80 + 2 * C) * 4 * C + min(T, K) * E * N * SSD_MPPO_ROW_FLOATS(C, A, N)
+            + P * SSD_PPO_GROUPS(rows, P) * (SSD_MOA_LSTM_W(C) + SSD_PPO_STAT_FLOATS)
+            + P * SSD_MPPO_GROUPS(seqs, P) * (16 * C + 16 + SSD_PPO_STAT_FLOATS)
+            + P * SSD_MPPO_SPLITS(rows) * ((80 + 2 * C) * 4 * C + 8 * C + (C + 1) * SSD_MPPO_PRED_PITCH(A, N)))
+
+
 # the recurrent policy's weight layout (include/ssd.h, SSD_LSTM_*): the trunk at the SSD_POL_* offsets, then these blocks
 SSD_LSTM_W, SSD_LSTM_X, SSD_LSTM_MAX_CELLS = 33728, 32, 256
 LSTM_CELL_SIZES = (64, 128, 256)
@@ -223,7 +246,7 @@ SYMBOLS = ("ssd_create", "ssd_destroy", "ssd_reset", "ssd_step", "ssd_step_rando
            "ssd_stats_last_error", "ssd_policy_forward", "ssd_policy_last_error", "ssd_rollout_policy",
            "ssd_policy_lstm_forward", "ssd_rollout_policy_lstm", "ssd_policy_moa_forward", "ssd_rollout_policy_moa",
            "ssd_ws_policy_forward", "ssd_ws_rollout_policy", "ssd_advantages", "ssd_advantages_last_error",
-           "ssd_policy_ppo_grad", "ssd_policy_lstm_ppo_grad")
+           "ssd_policy_ppo_grad", "ssd_policy_lstm_ppo_grad", "ssd_policy_moa_ppo_grad")
 # added after ABI 6 without a version bump (the calls are additive): a library built before them lacks them
 LSTM_SYMBOLS = ("ssd_policy_lstm_forward", "ssd_rollout_policy_lstm")
 MOA_SYMBOLS = ("ssd_policy_moa_forward", "ssd_rollout_policy_moa")
@@ -231,6 +254,7 @@ WS_POLICY_SYMBOLS = ("ssd_ws_policy_forward", "ssd_ws_rollout_policy")
 ADVANTAGES_SYMBOLS = ("ssd_advantages", "ssd_advantages_last_error")
 PPO_SYMBOLS = ("ssd_policy_ppo_grad",)
 LSTM_PPO_SYMBOLS = ("ssd_policy_lstm_ppo_grad",)
+MOA_PPO_SYMBOLS = ("ssd_policy_moa_ppo_grad",)
 
 
 class SsdConfig(C.Structure):
@@ -343,7 +367,7 @@ def lib():
         L.ssd_policy_last_error.argtypes = []
         L.ssd_policy_last_error.restype = C.c_char_p
         L.ssd_rollout_policy.argtypes = [vp, vp, i32, vp, i32, i32] + [vp] * 7 + [i32, vp, u32, vp]
-        missing = [name for name in LSTM_SYMBOLS + MOA_SYMBOLS + WS_POLICY_SYMBOLS + ADVANTAGES_SYMBOLS + PPO_SYMBOLS + LSTM_PPO_SYMBOLS if not hasattr(L, name)]
+        missing = [name for name in LSTM_SYMBOLS + MOA_SYMBOLS + WS_POLICY_SYMBOLS + ADVANTAGES_SYMBOLS + PPO_SYMBOLS + LSTM_PPO_SYMBOLS + MOA_PPO_SYMBOLS if not hasattr(L, name)]
         if missing:
             raise SsdError("%s lacks %s (built before the recurrent, MOA or Watershed policy calls, the advantages call or the PPO gradient calls): rebuild it with `python -c 'import "
                            "__graft_entry__ as g; g.build()'`" % (LIB_PATH, ", ".join(missing)))
@@ -360,6 +384,8 @@ def lib():
         L.ssd_policy_ppo_grad.argtypes = [vp, i32, i32] + [vp] * 8 + [i32, i32, i32] + [C.c_double] * 5 + [vp, vp, vp, i32, u32, vp]
         L.ssd_policy_lstm_ppo_grad.argtypes = ([vp, i32, i32, i32, i32] + [vp] * 10 + [i32, i32, i32] + [C.c_double] * 5
                                                + [vp, vp, vp, i32, u32, vp])
+        L.ssd_policy_moa_ppo_grad.argtypes = ([vp, i32, i32, i32, i32] + [vp] * 11 + [i32, i32, i32] + [C.c_double] * 6
+                                              + [vp, vp, vp, i32, u32, vp])
         for name in SYMBOLS:
             getattr(L, name)
         if L.ssd_abi_version() != ABI_VERSION:

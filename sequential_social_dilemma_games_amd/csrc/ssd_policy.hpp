@@ -106,10 +106,15 @@ struct PpoGradArgs {
     const float *dx;               // [K][E][N][32] d loss / d fc2's output (after its ReLU), not yet divided by the rows
     int32_t accumulate;            // add the partial sets to what scratch holds
     int32_t w_pitch;               // floats between the weight sets of w (set_floats is the partial sets' pitch alone)
+    // launch_ppo_moa_stack_grad only
+    int32_t stack;                 // 0: the actions stack, 1: the MOA stack; dx is [K][E][N][2][32], the stack's half is read
 };
 // The same kernel as the trunk's backward alone (the recurrent policy's, ssd_policy_lstm_grad.hip): set_floats floats of a
 // partial set are the trunk's (SSD_POL_CONV_W .. SSD_POL_FC2_B); a (G, P) grid whatever set_rows is.
 hipError_t launch_ppo_trunk_grad(const PpoGradArgs &a, void *stream);
+// That backward for one tanh FC stack of the MOA policy (ssd_policy_moa_grad.hip): a partial set is the MOA layout's floats
+// below SSD_MOA_LSTM_W (set_floats); stack 1's launch adds its conv sums to those stack 0's launch left in the same scratch.
+hipError_t launch_ppo_moa_stack_grad(const PpoGradArgs &a, void *stream);
 // The calling thread's ssd_policy_last_error text; returns SSD_E_INVALID.
 int policy_fail(const char *msg);
 

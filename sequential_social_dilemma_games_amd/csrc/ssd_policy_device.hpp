@@ -1,7 +1,7 @@
 // csrc/ssd_policy_device.hpp -- the device pieces the policy kernels are built from, each defined once: the LSTM gate GEMM, the
 // two cell rules and the cell update, the start rule and the loader of the h rows, the heads, the PPO loss terms of a row, the
 // action draw, and the conv-FC trunk (conv, fc1, fc2) on a tile.  Used by ssd_policy.hip (conv-FC), ssd_policy_grad.hip,
-// ssd_policy_lstm.hip, ssd_policy_lstm_grad.hip, ssd_policy_moa.hip and ssd_ws_policy.hip; the argument blocks stay in
+// ssd_policy_lstm.hip, ssd_policy_lstm_grad.hip, ssd_policy_moa.hip, ssd_policy_moa_grad.hip and ssd_ws_policy.hip; the argument blocks stay in
 // ssd_policy.hpp, which host code reads too.  Every sum below is one chain in a fixed order, so a change here changes the
 // bits of every kernel that uses the piece, and the tests that compare kernels and paths bit for bit see it.
 //
@@ -64,6 +64,28 @@ struct KerasCell {                  // Keras: gates i, f, c~, o, no forget bias;
         *h2 = sigmoidf_(zo) * tanhf(*c2);
     }
 };
+
+// Position of agent n in the order of the ids sorted as strings ('agent-10' < 'agent-2'), for n < 100: first digit, then
+// the shorter id first, then the second digit.
+__device__ __forceinline__ int id_key(int n) { return n < 10 ? 100 * n : 100 * (n / 10) + 1 + n % 10; }
+
+// The MOA input slots of every agent, by a workgroup of at least 256 threads: s_slot[i * 16 + q] = the agent whose action sits
+// in slot q of agent i's previous-action vector: i itself for q = 0, then the others in string order (the j of pred [j][a] is
+// slot j + 1).  Entries with i or q >= N are not written.
+__device__ __forceinline__ void moa_slots(int N, int tid, int *s_slot) {
+    const int i = tid >> 4, q = tid & 15;
+    if (tid >= 256 || i >= N || q >= N) return;
+    int agent = i;
+    if (q > 0) {
+        for (int n = 0; n < N; ++n) {
+            if (n == i) continue;
+            int rank = 0;
+            for (int k = 0; k < N; ++k) rank += k != i && id_key(k) < id_key(n);
+            if (rank == q - 1) agent = n;
+        }
+    }
+    s_slot[tid] = agent;
+}
 
 // start flag of row `row` of env b: starts[row] in the forward, t == 0 in rollouts; envs past B count as starting (nothing read)
 __device__ __forceinline__ int row_start(const uint8_t *starts, const uint4 *hdr, int b, size_t row, int B) {

@@ -18,7 +18,8 @@
 // At the end a workgroup writes its partial gradient set and statistics to the caller's scratch; a second kernel adds the G
 // partials of a set in order (float64), scales by 1 / rows and rounds once.  No atomics anywhere: the same inputs give the same
 // bits.  The kernel's second instantiation is the trunk's backward alone, from a given d loss / d fc2's output: what the
-// recurrent policy's call (ssd_policy_lstm_grad.hip) runs below its cell.
+// recurrent policy's call (ssd_policy_lstm_grad.hip) runs below its cell.  The third is that backward for one tanh FC stack of
+// the MOA policy (ssd_policy_moa_grad.hip), launched once per stack.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -40,8 +41,17 @@ using GradArgs = ssd::PpoGradArgs;
 // kFromDx: the trunk's backward alone, for the recurrent policy (ssd_policy_lstm_grad.hip): steps 1 (to fc2) and 3 (from fc2
 // down) to 6, with d loss / d fc2's output read from a.dx instead of formed from the heads; nothing of the heads or the
 // statistics is summed or written, and with a.accumulate the partial set is added to what scratch holds (the windows before).
-template <bool kFromDx>
+//
+// kModeMoaStack: kModeFromDx for stack a.stack of the MOA policy: the stack's weights at SSD_MOA_FC1_W(stack), tanh for ReLU
+// after fc1 and fc2 (derivative 1 - h * h), dx rows [.][2][32] of which the stack's half is read, and a partial set in the MOA
+// layout's offsets.  The conv's gradient is linear in d conv, so stack 1's launch adds its conv sums onto what stack 0's launch
+// left in the same slot (the same workgroup, after it on the stream): the order is fixed.
+constexpr int kModeLoss = 0, kModeFromDx = 1, kModeMoaStack = 2;
+
+template <int kMode>
 __global__ void __launch_bounds__(kThreads) ssd_ppo_grad_kernel(GradArgs a) {
+    constexpr bool kFromDx = kMode != kModeLoss, kTanh = kMode == kModeMoaStack;
+    constexpr int kDxPitch = kTanh ? 64 : 32;
     __shared__ float s_norm[256];
     __shared__ float s_conv[kTile * kPitch + 8];       // the conv output; after step 5, d loss / d conv.  (+ 8: step 4's last A rows)
     __shared__ float s_obsf[(kTile * kObs + 3) / 4];   // the observation bytes
@@ -57,6 +67,8 @@ __global__ void __launch_bounds__(kThreads) ssd_ppo_grad_kernel(GradArgs a) {
     const int stride = a.P == 1 ? 1 : a.N;             // a set's row r is row r * stride + p of the [K][E][N] arrays
     const float *w_set = a.w + (size_t)p * (size_t)(kFromDx ? a.w_pitch : a.set_floats);
     const int wave = tid >> 6, lane = tid & 63, l15 = lane & 15, l4 = lane >> 4;
+    const int shift = kTanh ? SSD_MOA_FC1_W(a.stack) - SSD_POL_FC1_W : 0;   // from the trunk's FC offsets to the stack's
+    const auto dact = [](float h, float d) { return kTanh ? d * (1.f - h * h) : (h > 0.f ? d : 0.f); };
 
     s_norm[tid] = (float)(((double)tid - 128.0) / 255.0);
     if (tid < kTile * (kPitch - kFlat)) s_conv[(tid / 3) * kPitch + kFlat + tid % 3] = 0.f;
@@ -80,6 +92,7 @@ __global__ void __launch_bounds__(kThreads) ssd_ppo_grad_kernel(GradArgs a) {
         // invariant, the compiler hoists some hundreds of them out of the tile loop and spills them)
         asm volatile("" : "+s"(w_set));
         const float *__restrict__ w = w_set;
+        const float *__restrict__ ws = w_set + shift;      // the FC layers' base
         __syncthreads();                               // the previous tile's step 6 has read s_obs and s_conv
         // ---- 1. the forward ----
         {   // 16 threads a row, byte c + 16 u of it each (every load of the thread issued before the first store)
@@ -102,7 +115,7 @@ __global__ void __launch_bounds__(kThreads) ssd_ppo_grad_kernel(GradArgs a) {
         __syncthreads();
         conv_tile(w, s_obs, s_norm, s_conv, tid);
         __syncthreads();
-        fc_stack<false>(w, s_conv, s_part, s_h1, tid, s_h2, kHP, kTile);
+        fc_stack<kTanh>(ws, s_conv, s_part, s_h1, tid, s_h2, kHP, kTile);
         __syncthreads();
         if constexpr (!kFromDx) {
             const int m = tid >> 4, j = tid & 15;
@@ -128,8 +141,8 @@ __global__ void __launch_bounds__(kThreads) ssd_ppo_grad_kernel(GradArgs a) {
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const int q = tid + u * kThreads, m = q >> 5, n = q & 31;
-                const float dh = r0 + m < R ? a.dx[((size_t)(r0 + m) * stride + p) * 32 + n] : 0.f;
-                s_dh2[m * kHP + n] = s_h2[m * kHP + n] > 0.f ? dh : 0.f;
+                const float dh = r0 + m < R ? a.dx[((size_t)(r0 + m) * stride + p) * kDxPitch + (kTanh ? 32 * a.stack : 0) + n] : 0.f;
+                s_dh2[m * kHP + n] = dact(s_h2[m * kHP + n], dh);
             }
         } else {
 #pragma unroll
@@ -166,8 +179,8 @@ __global__ void __launch_bounds__(kThreads) ssd_ppo_grad_kernel(GradArgs a) {
             const int q = tid + u * kThreads, m = q >> 5, k = q & 31;
             float dh = 0.f;
 #pragma unroll 8
-            for (int n = 0; n < 32; ++n) dh = fmaf(s_dh2[m * kHP + n], w[SSD_POL_FC2_W + k * 32 + n], dh);
-            s_dh1[m * kHP + k] = s_h1[m * kHP + k] > 0.f ? dh : 0.f;
+            for (int n = 0; n < 32; ++n) dh = fmaf(s_dh2[m * kHP + n], ws[SSD_POL_FC2_W + k * 32 + n], dh);
+            s_dh1[m * kHP + k] = dact(s_h1[m * kHP + k], dh);
         }
         if (tid < 32) {
             float sum = 0.f;
@@ -207,7 +220,7 @@ __global__ void __launch_bounds__(kThreads) ssd_ppo_grad_kernel(GradArgs a) {
 #pragma unroll 2
             for (int t = 0; t < 16; ++t) {
                 const int c = 256 * wave + 16 * t + l15;
-                const float *wc = w + SSD_POL_FC1_W + (size_t)c * 32 + l4;
+                const float *wc = ws + SSD_POL_FC1_W + (size_t)c * 32 + l4;
                 float bv[8];
 #pragma unroll
                 for (int ks = 0; ks < 8; ++ks) bv[ks] = c < kFlat ? wc[4 * ks] : 0.f;
@@ -246,7 +259,7 @@ __global__ void __launch_bounds__(kThreads) ssd_ppo_grad_kernel(GradArgs a) {
     // ---- the workgroup's partial set and statistics ----
     float *part = a.scratch + ((size_t)p * a.G + g) * (size_t)(a.set_floats + kStatFloats);
     const auto put = [=](int at, float v) {            // kFromDx: onto the sums so far, carried in scratch from window to window
-        if constexpr (kFromDx) part[at] = a.accumulate ? part[at] + v : v;
+        if constexpr (kFromDx) part[at + shift] = a.accumulate ? part[at + shift] + v : v;
         else part[at] = v;
     };
     __syncthreads();
@@ -269,7 +282,8 @@ __global__ void __launch_bounds__(kThreads) ssd_ppo_grad_kernel(GradArgs a) {
         float sum = 0.f;
 #pragma unroll
         for (int sl = 0; sl < kSlices; ++sl) sum += src[sl * 6];
-        put(SSD_POL_CONV_W + tid, sum);
+        if constexpr (kTanh) part[SSD_POL_CONV_W + tid] = a.accumulate || a.stack ? part[SSD_POL_CONV_W + tid] + sum : sum;
+        else put(SSD_POL_CONV_W + tid, sum);
     }
     if (!kFromDx && tid < 5) {
         double sum = 0.0;
@@ -328,7 +342,12 @@ __global__ void __launch_bounds__(256) ssd_ppo_reduce_kernel(GradArgs a) {
 namespace ssd {
 
 hipError_t launch_ppo_trunk_grad(const PpoGradArgs &a, void *stream) {
-    hipLaunchKernelGGL(ssd_ppo_grad_kernel<true>, dim3((unsigned)a.G, (unsigned)a.P), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(ssd_ppo_grad_kernel<kModeFromDx>, dim3((unsigned)a.G, (unsigned)a.P), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+    return hipGetLastError();
+}
+
+hipError_t launch_ppo_moa_stack_grad(const PpoGradArgs &a, void *stream) {
+    hipLaunchKernelGGL(ssd_ppo_grad_kernel<kModeMoaStack>, dim3((unsigned)a.G, (unsigned)a.P), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
     return hipGetLastError();
 }
 
@@ -370,7 +389,7 @@ extern "C" int ssd_policy_ppo_grad(const float *weights, int32_t num_sets, int32
     a.clip = (float)clip_param; a.vf_clip = (float)vf_clip_param; a.vf_coeff = (float)vf_loss_coeff;
     a.ent_coeff = (float)entropy_coeff; a.kl_coeff = (float)kl_coeff;
     a.scratch = scratch; a.grads = grads; a.stats = stats;
-    hipLaunchKernelGGL(ssd_ppo_grad_kernel<false>, dim3((unsigned)a.G, (unsigned)a.P), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(ssd_ppo_grad_kernel<kModeLoss>, dim3((unsigned)a.G, (unsigned)a.P), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
     if (const hipError_t e = hipGetLastError()) return ssd::policy_launched(e);
     hipLaunchKernelGGL(ssd_ppo_reduce_kernel, dim3((unsigned)((a.set_floats + 255) / 256), (unsigned)a.P), dim3(256), 0,
                        static_cast<hipStream_t>(stream), a);

@@ -31,6 +31,7 @@ constexpr int kXM = SSD_MOA_XM;         // input rows of the MOA cell: 32 featur
 constexpr int kPredPitch = 225;         // LDS pitch of the predictions: (N - 1) A <= 15 * 15, odd
 
 using ssd::f32x4;
+using ssd::id_key;              // the agents' string order (ssd_policy_device.hpp)
 using Cell = ssd::KerasCell;             // gates i, f, c~, o, no forget bias; a state is (h, c)
 
 static_assert(SSD_MOA_FC1_W(0) >= SSD_POL_CONV_B + 6 && SSD_MOA_FC % 64 == 0 && SSD_MOA_FC_STRIDE % 64 == 0 &&
@@ -78,10 +79,6 @@ __global__ void __launch_bounds__(4 * C) ssd_policy_moa_actions_kernel(ssd::MoaA
     __syncthreads();
     ssd::pick_actions<kM>(a, s_out, a.actions_copy, tid, b0, i);
 }
-
-// Position of agent n in the order of the ids sorted as strings ('agent-10' < 'agent-2'), for n < 100: first digit, then
-// the shorter id first, then the second digit.
-__device__ __forceinline__ int id_key(int n) { return n < 10 ? 100 * n : 100 * (n / 10) + 1 + n % 10; }
 
 // ------------------------------------------------------------------------------------------------------------ MOA cell
 template <int C>

@@ -442,6 +442,12 @@ class ConvMOAPolicy(PolicyBase):
     def scratch_shape(self, rows):
         return (_capi.SSD_MOA_SCRATCH_FLOATS(rows),)
 
+    def ppo_scratch_shape(self, n_steps, num_envs, num_agents, seq_len):
+        """The float32 scratch ssd_policy_moa_ppo_grad needs for a [n_steps, num_envs, num_agents] fragment walked in windows
+        of seq_len steps (include/ssd.h, SSD_MPPO_SCRATCH_FLOATS)."""
+        return (_capi.SSD_MPPO_SCRATCH_FLOATS(n_steps, num_envs, num_agents, self.num_sets, self.num_actions, self.cell_size,
+                                              seq_len),)
+
     def _per_agent(self, name):
         """Parameter `name` with one entry per agent [N, ...] (set i, or set 0 for all when shared)."""
         t = getattr(self, name)
@@ -866,6 +872,151 @@ def ppo_loss_recurrent(policy, batch, *, seq_len, clip_param, vf_clip_param, vf_
     terms = ppo_terms(logits, value, t, *hyper)
     means = [_set_means(x, P) for x in terms]
     return means[0].sum(), {name: m.detach() for name, m in zip(PPO_STATS, means)}
+
+
+# ---- PPOLoss + moa_weight * MOALoss for the MOA policy, with truncated BPTT (include/ssd.h, MOA PPO LOSS AND GRADIENTS) ----
+
+MOA_PPO_STATS = PPO_STATS + ("moa_loss",)
+
+
+class _MOAPPOLossFunction(torch.autograd.Function):
+    """ssd_policy_moa_ppo_grad as a torch function of the policy's parameters, as _PPOLossFunction."""
+
+    @staticmethod
+    def forward(ctx, policy, t, dims, seq_len, hyper, *params):
+        import ctypes as C
+        K, E, N = dims
+        P, A = policy.num_sets, policy.num_actions
+        dev = t["actions"].device
+        weights = policy.packed()
+        need = policy.ppo_scratch_shape(K, E, N, seq_len)[0]
+        scratch = getattr(policy, "_ppo_scratch", None)          # kept between calls, as packed()'s buffer is
+        if scratch is None or scratch.device != dev or scratch.numel() < need:
+            scratch = policy._ppo_scratch = torch.empty(need, dtype=torch.float32, device=dev)
+        grads = torch.empty((P, policy.set_floats), dtype=torch.float32, device=dev)
+        stats = torch.empty((P, len(MOA_PPO_STATS)), dtype=torch.float64, device=dev)
+        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())   # noqa: E731
+        index = dev.index if dev.index is not None else torch.cuda.current_device()
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _capi.policy_check(_capi.lib().ssd_policy_moa_ppo_grad(
+            ptr(weights), P, A, policy.cell_size, seq_len, ptr(t["obs_first"]), ptr(t["obs"]), ptr(t["state"]), ptr(t["prev_actions"]),
+            ptr(t["done"]), ptr(t["actions"]), ptr(t["logp_old"]), ptr(t["advantages"]), ptr(t["value_targets"]), ptr(t["vf_pred"]),
+            ptr(t["behaviour_logits"]), K, E, N, *hyper, ptr(scratch), ptr(grads), ptr(stats), index, 0, stream))
+        ctx.policy = policy
+        ctx.save_for_backward(grads)
+        ctx.mark_non_differentiable(stats)
+        return stats[:, 0].sum().to(torch.float32), stats
+
+    @staticmethod
+    def backward(ctx, g_loss, g_stats):
+        (grads,) = ctx.saved_tensors
+        out = unpack_gradient(ctx.policy, grads, g_loss)
+        return (None, None, None, None, None) + tuple(g if needs else None for g, needs in zip(out, ctx.needs_input_grad[5:]))
+
+
+def moa_forward(policy, obs, prev_actions, state, done, seq_len):
+    """The learner's forward of a ConvMOAPolicy over a fragment, in plain torch under autograd, by the state rule of
+    include/ssd.h: obs u8 [K, E, N, 15, 15, 3] (the observation each row acted on), prev_actions int [K, E, N], the ring state
+    [S, E, N, 4, C] (detached: data), done u8 [K, E, N] or None -> (logits [K, E, N, A], value [K, E, N], moa_logits
+    [K, E, N, N-1, A]).  Window by window through forward_sequence; step k of a window resets where done[k - 1] is set."""
+    K, T = int(obs.shape[0]), int(seq_len)
+    dt = policy.conv_w.dtype
+    logits, value, moa = [], [], []
+    for w, k0 in enumerate(range(0, K, T)):
+        k1 = min(k0 + T, K)
+        resets = None
+        if done is not None and k1 - k0 > 1:
+            resets = torch.cat([torch.zeros_like(done[:1]), done[k0:k1 - 1]]).to(torch.bool)
+        lg, v, m, _ = policy.forward_sequence(obs[k0:k1], prev_actions[k0:k1], state[w].detach().to(dt), resets)
+        logits.append(lg)
+        value.append(v)
+        moa.append(m)
+    return torch.cat(logits), torch.cat(value), torch.cat(moa)
+
+
+def ppo_loss_moa(policy, batch, *, seq_len, moa_weight, clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff,
+                 obs_first=None):
+    """The causal-influence trainer's loss for a ConvMOAPolicy, PPOLoss + moa_weight * MOALoss (algorithms/ppo_causal.py:36-75),
+    with truncated backpropagation through time through both LSTMs over windows of seq_len steps -> (loss, stats): loss a
+    scalar tensor that backpropagates into every parameter, stats a dict of [P] tensors (MOA_PPO_STATS: ppo_loss's five, whose
+    total_loss includes the weighted MOA term, then moa_loss, the mean cross-entropy without the weight).  include/ssd.h (MOA
+    PPO LOSS AND GRADIENTS) states the loss and the state rule.  Per weight set the MOA term is policy.moa_loss of the set's
+    rows: the targets of row (k, e, i) are the other agents' actions of step k.  The influence reward is data: it is inside the
+    advantages sample(..., influence_weight=...) computed.
+
+        first = env.reset().clone()
+        batch = env.sample(policy, 128, state_every=16, gamma=0.99, lambda_=0.95, influence_weight=1.0)
+        loss, stats = ppo_loss_moa(policy, batch, seq_len=16, moa_weight=10.0, clip_param=0.3, vf_clip_param=10.0,
+                                   vf_loss_coeff=1e-4, entropy_coeff=1e-3, kl_coeff=0.0, obs_first=first)
+        loss.backward(); optimiser.step()
+
+    batch: the dict sample(policy, K, state_every=seq_len, gamma=...) returns -- ppo_loss_recurrent's keys with "state" f32
+    [S,E,N,4,C], and "prev_actions" i32 [K,E,N], the joint action each step's MOA read.  A minibatch of steps k0 .. k1 - 1 with
+    k0 a multiple of seq_len is the slices [k0:k1] of the per-row tensors (prev_actions among them), state[k0 // seq_len:] and
+    obs_first = obs[k0 - 1].
+    CUDA tensors go to the library (ssd_policy_moa_ppo_grad on torch's current stream, no synchronisation; the scratch is kept
+    on the policy); CPU tensors run forward_sequence per window, ppo_terms and moa_loss per set under autograd."""
+    if not isinstance(policy, ConvMOAPolicy):
+        raise ValueError("ppo_loss_moa is for a ConvMOAPolicy (ppo_loss and ppo_loss_recurrent are the other policies')")
+    if not isinstance(batch, dict):
+        raise ValueError("batch must be the dict sample() returns")
+    if isinstance(seq_len, bool) or int(seq_len) != seq_len or int(seq_len) < 1:
+        raise ValueError("seq_len must be an integer >= 1")
+    seq_len = int(seq_len)
+    hyper = tuple(float(x) for x in (clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff, moa_weight))
+    if not all(np.isfinite(hyper)) or hyper[0] < 0 or hyper[1] < 0:
+        raise ValueError("the hyper-parameters must be finite, clip_param and vf_clip_param >= 0")
+    if hyper[5] < 0:
+        raise ValueError("moa_weight must be >= 0")
+    t, (K, E, N) = _ppo_tensors(policy, batch, obs_first, hyper[4])
+    if N != policy.num_agents:
+        raise ValueError("the policy is for %d agents, the batch has %d" % (policy.num_agents, N))
+    dev, P = t["actions"].device, policy.num_sets
+    if policy.conv_w.device != dev:
+        raise ValueError("the policy is on %s, the batch on %s" % (policy.conv_w.device, dev))
+    C, S = policy.cell_size, -(-K // seq_len)
+    state = batch.get("state")
+    if state is None and seq_len >= K and batch.get("state_in") is not None:
+        state = batch["state_in"].unsqueeze(0)                        # one window: the state step 0 used
+    if not isinstance(state, torch.Tensor):
+        raise ValueError("state is required: the ring sample(..., state_every=seq_len) records (state_in serves when seq_len >= K)")
+    if state.dim() != 5 or tuple(state.shape[1:4]) != (E, N, 4) or state.shape[0] < S:
+        raise ValueError("state must be [S, %d, %d, 4, C] with S >= ceil(K / seq_len) = %d, got %s" % (E, N, S, tuple(state.shape)))
+    if state.shape[-1] != C:
+        raise ValueError("state has %d cells, the policy %d" % (state.shape[-1], C))
+    if state.dtype != torch.float32 or state.device != dev or not state.is_contiguous():
+        raise ValueError("state must be a contiguous torch.float32 tensor on %s" % (dev,))
+    done, prev = batch.get("done"), batch.get("prev_actions")
+    if done is not None:
+        if (not isinstance(done, torch.Tensor) or done.dtype != torch.uint8 or tuple(done.shape) != (K, E, N) or done.device != dev
+                or not done.is_contiguous()):
+            raise ValueError("done must be a contiguous torch.uint8 tensor of shape %s on %s" % ((K, E, N), dev))
+    if (not isinstance(prev, torch.Tensor) or prev.dtype != torch.int32 or tuple(prev.shape) != (K, E, N) or prev.device != dev
+            or not prev.is_contiguous()):
+        raise ValueError("prev_actions must be a contiguous torch.int32 tensor of shape %s on %s" % ((K, E, N), dev))
+    t["state"], t["done"], t["prev_actions"] = state, done, prev
+    if dev.type == "cuda":
+        if policy.conv_w.dtype != torch.float32:
+            raise ValueError("the device path needs a float32 policy")
+        params = tuple(getattr(policy, name) for name, _, _ in policy.layout())
+        loss, stats = _MOAPPOLossFunction.apply(policy, t, (K, E, N), seq_len, hyper, *params)
+        return loss, {name: stats[:, k] for k, name in enumerate(MOA_PPO_STATS)}
+    if dev.type != "cpu":
+        raise ValueError("the tensors must be on the CPU or on a GPU, not on %s" % (dev,))
+    logits, value, moa = moa_forward(policy, _ppo_obs(t, K), prev, state, done, seq_len)
+    terms = ppo_terms(logits, value, t, *hyper[:5])
+    A = policy.num_actions
+    acts = t["actions"].clamp(0, A - 1)
+    if P == 1:
+        ce = policy.moa_loss(moa, acts).reshape(1)
+    else:                                                             # set p's rows are agent p's: its N - 1 predictions
+        others = acts.long()[..., policy._others.to(dev)]             # [K, E, N, N-1]
+        ce = torch.stack([torch.nn.functional.cross_entropy(moa[:, :, p].reshape(-1, A), others[:, :, p].reshape(-1))
+                          for p in range(P)])
+    means = [_set_means(x, P) for x in terms]
+    means[0] = means[0] + hyper[5] * ce
+    means.append(ce)
+    return means[0].sum(), {name: m.detach() for name, m in zip(MOA_PPO_STATS, means)}
 
 
 # ---- the Watershed baselines' policy (include/ssd.h, WATERSHED POLICY ROLLOUTS; csrc/ssd_ws_policy.hip) ----
