@@ -10,7 +10,7 @@ import copy
 
 import torch
 
-from ppo_lstm_ref import DONE_MODES, bound, make_done, shifted_obs   # noqa: F401  (re-exported for the tests)
+from ppo_lstm_ref import DONE_MODES, SPLIT_SHAPES, bound, make_done, rows_mask, shifted_obs, split_rows   # noqa: F401  (re-exported)
 from ppo_ref import HYPER, MARGIN, as_numpy_u32, max_err, row_terms, set_means   # noqa: F401  (re-exported for the tests)
 from sequential_social_dilemma_games_amd.policy import MOA_PPO_STATS, ConvMOAPolicy, _conv_flat, _dense, keras_lstm, other_agents
 
@@ -18,6 +18,7 @@ CONV_MARGIN = 1e-6         # no conv pre-activation of the reference may lie thi
 MOA_WEIGHT = 10.0          # train_moa.py's default is 10.0
 VARIANTS = ("index_inputs", "index_targets", "no_stack1_conv", "cut_moa", "ignore_done_moa", "prev_not_zeroed", "ce_over_n",
             "no_moa_weight", "drop_last")
+SPLIT_SEEDS = {"A": 241, "B": 233}   # shape of SPLIT_SHAPES -> the seed of make_policy (the inputs' is 100 more), chosen on the CPU
 MOA_BRANCH = ("m_fc1_w", "m_fc1_b", "m_fc2_w", "m_fc2_b", "moa_kernel", "moa_recurrent", "moa_bias", "pred_w", "pred_b")
 ACTIONS_BRANCH = ("a_fc1_w", "a_fc1_b", "a_fc2_w", "a_fc2_b", "lstm_kernel", "lstm_recurrent", "lstm_bias", "logits_w", "logits_b",
                   "value_w", "value_b")
@@ -63,10 +64,12 @@ def step(pol, obs, prev, st, starts, variant=None):
     return logits, value, pred, torch.stack([h1, c1, h2, c2], dim=2)
 
 
-def forward(pol, obs, prev, state, done, T, variant=None):
+def forward(pol, obs, prev, state, done, T, variant=None, twin=None):
     """The state rule, step by step: obs u8 [K,E,N,15,15,3] (already shifted), prev int [K,E,N], state [S,E,N,4,C], done u8
     [K,E,N] or None -> (logits [K,E,N,A], value [K,E,N], pred [K,E,N,N-1,A]).  variant: None (the contract) or one of VARIANTS
-    ("drop_last": the rows of a last window shorter than T give zero outputs without gradient)."""
+    ("drop_last": the rows of a last window shorter than T give zero outputs without gradient).  twin: None, or (a copy of pol
+    holding the same values, mask bool [K,E,N]): the masked rows take their logits, value, pred and new state from the copy, so
+    that after backward the copy's .grad is exactly those rows' share of each weight gradient (ppo_lstm_ref.forward)."""
     K = obs.shape[0]
     dt = pol.conv_w.dtype
     outs = ([], [], [])
@@ -77,7 +80,13 @@ def forward(pol, obs, prev, state, done, T, variant=None):
             starts = None
         else:
             starts = None if done is None else done[k - 1].to(torch.bool)
-        lg, v, pr, st = step(pol, obs[k], prev[k], st, starts, variant)
+        lg, v, pr, nxt = step(pol, obs[k], prev[k], st, starts, variant)
+        if twin is not None and bool(twin[1][k].any()):
+            m = twin[1][k]
+            lg2, v2, pr2, nxt2 = step(twin[0], obs[k], prev[k], st, starts, variant)
+            lg, v = torch.where(m[..., None], lg2, lg), torch.where(m, v2, v)
+            pr, nxt = torch.where(m[..., None, None], pr2, pr), torch.where(m[..., None, None], nxt2, nxt)
+        st = nxt
         if variant == "drop_last" and K % T and k >= K - K % T:
             lg, v, pr = lg.detach() * 0, v.detach() * 0, pr.detach() * 0
         for o, x in zip(outs, (lg, v, pr)):
@@ -100,18 +109,21 @@ def _inputs(t, dtype, device):
             cast(t.get("behaviour_logits")))
 
 
-def autograd_loss(policy, t, h, obs_first, T, moa_weight=MOA_WEIGHT, dtype=torch.float64, device="cpu", variant=None, branch=None):
+def autograd_loss(policy, t, h, obs_first, T, moa_weight=MOA_WEIGHT, dtype=torch.float64, device="cpu", variant=None, branch=None,
+                  twin_rows=None):
     """The restatement under torch autograd on a copy of `policy` in `dtype` on `device` -> (loss, {stat: [P]}, {param: grad}).
     With a variant the loss is still divided by the whole fragment's rows, as a kernel with that fault would.  branch: None, or
-    "ppo" / "moa" for that term of the loss alone."""
+    "ppo" / "moa" for that term of the loss alone.  With twin_rows (bool [K,E,N], see rows_mask) the gradients are {param: (the
+    other rows' share, those rows' share)}, as in ppo_lstm_ref.autograd_loss."""
     pol = copy.deepcopy(policy).to(device=device, dtype=dtype)
     pol.zero_grad()
+    twin = None if twin_rows is None else (copy.deepcopy(pol), twin_rows.to(device))
     N, A = pol.num_agents, pol.num_actions
     K = t["actions"].shape[0]
     beh = t.get("behaviour_logits") if h["kl_coeff"] != 0 else None
     obs = shifted_obs(t["obs"], obs_first, K).to(device)
     done = None if t.get("done") is None else t["done"].to(device)
-    logits, value, pred = forward(pol, obs, t["prev_actions"].to(device), t["state"].to(device), done, T, variant)
+    logits, value, pred = forward(pol, obs, t["prev_actions"].to(device), t["state"].to(device), done, T, variant, twin)
     acts, lpo, adv, vt, vfp, b = _inputs(dict(t, behaviour_logits=beh), dtype, device)
     terms = list(row_terms(logits, value, acts, lpo, adv, vt, vfp, b, h)[:5])
     ce = moa_ce(pred, acts, N, A, variant)
@@ -134,31 +146,34 @@ def autograd_loss(policy, t, h, obs_first, T, moa_weight=MOA_WEIGHT, dtype=torch
     for name, _, _ in pol.layout():
         g = getattr(pol, name).grad
         grads[name] = torch.zeros_like(getattr(pol, name)) if g is None else g.detach().clone()
+        if twin is not None:
+            g2 = getattr(twin[0], name).grad
+            grads[name] = (grads[name], torch.zeros_like(grads[name]) if g2 is None else g2.detach().clone())
     return loss.detach(), {k: m.detach() for k, m in zip(MOA_PPO_STATS, means)}, grads
 
 
-def conv_margin(policy, obs):
+def conv_margin(policy, obs, device="cpu"):
     """The distance of every row's conv pre-activations from zero, in float64: obs u8 [..., N, 15, 15, 3] -> [..., N] (the
     smallest |pre-activation| over the row's 169 positions and 6 filters).  The conv's ReLU has a kink there: a float32 sum of
     27 products rounds by some 1e-7 in an order-dependent way, so a pre-activation nearer to zero than that is positive in one
     float32 implementation and not in another, and d loss / d conv of that position (some 1e-3 of conv_w's gradient at these
     sizes) is in or out.  As with the clip boundaries of the loss (MARGIN), the tests' inputs keep away from it."""
     N = policy.num_agents
-    pol = copy.deepcopy(policy).double()
+    pol = copy.deepcopy(policy).to(device=device, dtype=torch.float64)
     w, b = pol._per_agent("conv_w"), pol._per_agent("conv_b")
     with torch.no_grad():
-        x = ((obs.double() - 128.0) / 255.0).reshape(-1, N, 15, 15, 3)
+        x = ((obs.to(device).double() - 128.0) / 255.0).reshape(-1, N, 15, 15, 3)
         x = x.permute(0, 1, 4, 2, 3).reshape(x.shape[0], N * 3, 15, 15)
         wc = w.permute(0, 4, 3, 1, 2).reshape(N * 6, 3, 3, 3)
         pre = torch.nn.functional.conv2d(x, wc, b.reshape(N * 6), groups=N)
-        return pre.reshape(-1, N, 6 * 169).abs().amin(-1).reshape(obs.shape[:-3])
+        return pre.reshape(-1, N, 6 * 169).abs().amin(-1).reshape(obs.shape[:-3]).cpu()
 
 
-def clear_of_kinks(policy, obs, g):
+def clear_of_kinks(policy, obs, g, device="cpu"):
     """obs with every row whose conv_margin is below CONV_MARGIN drawn again from g (some 0.6 % of the rows a pass), until
     none is left."""
     for _ in range(20):
-        near = conv_margin(policy, obs) < CONV_MARGIN
+        near = conv_margin(policy, obs, device) < CONV_MARGIN
         n = int(near.sum())
         if not n:
             return obs
@@ -189,12 +204,21 @@ def make_policy(A, N, P, C, seed, recur=3.0, pred=6.0):
     return pol
 
 
-def make_inputs(policy, K, E, N, T, seed, obs_first=True, behaviour=True, done_mode="none", zero_ring=False):
+def _forward64(policy, obs, prev, state, done, T, device):
+    """The float64 forward without gradient on `device`, its outputs back on the CPU."""
+    with torch.no_grad():
+        pol = copy.deepcopy(policy).to(device=device, dtype=torch.float64)
+        out = forward(pol, obs.to(device), prev.to(device), state.to(device), None if done is None else done.to(device), T)
+    return tuple(x.cpu() for x in out)
+
+
+def make_inputs(policy, K, E, N, T, seed, obs_first=True, behaviour=True, done_mode="none", zero_ring=False, device="cpu"):
     """A fragment for `policy`: random observations (clear_of_kinks), actions (the cross-entropy's targets too), previous actions (zero where a
     done row precedes, as the rollout's ring holds them) and ring states (zero at a window start that follows a done row; all
     zero with zero_ring), done flags by `done_mode`, and logp_old / vf_pred set from the float64 forward so that the ratio and
-    value - vf_pred land in chosen regions on either side of the clip boundaries (the recipe of ppo_ref.make_inputs).  Returns
-    (t, obs_first or None)."""
+    value - vf_pred land in chosen regions on either side of the clip boundaries (the recipe of ppo_ref.make_inputs).  Every
+    random number is drawn on the CPU; `device` is where the float64 forward and conv_margin run.  Returns (t, obs_first or
+    None)."""
     g = torch.Generator().manual_seed(seed)
     A, C = policy.num_actions, policy.cell_size
     rows = (K, E, N)
@@ -213,12 +237,11 @@ def make_inputs(policy, K, E, N, T, seed, obs_first=True, behaviour=True, done_m
         ended = done[:K - 1].bool().any(-1)                      # an env whose episode ended: the whole joint action is zero
         t["prev_actions"][1:][ended] = 0
     first = torch.randint(0, 256, (E, N, 15, 15, 3), dtype=torch.uint8, generator=g) if obs_first else None
-    t["obs"] = clear_of_kinks(policy, t["obs"], g)
+    t["obs"] = clear_of_kinks(policy, t["obs"], g, device)
     if obs_first:
-        first = clear_of_kinks(policy, first, g)
+        first = clear_of_kinks(policy, first, g, device)
+    logits, value, _ = _forward64(policy, shifted_obs(t["obs"], first, K), t["prev_actions"], t["state"], done, T, device)
     with torch.no_grad():
-        logits, value, _ = forward(copy.deepcopy(policy).double(), shifted_obs(t["obs"], first, K), t["prev_actions"], t["state"],
-                                   done, T)
         logp = torch.log_softmax(logits, -1).gather(-1, t["actions"].long().unsqueeze(-1)).squeeze(-1)
     u = torch.rand(rows, generator=g, dtype=torch.float64)
     region = torch.randint(0, 4, rows, generator=g)
@@ -236,14 +259,13 @@ def make_inputs(policy, K, E, N, T, seed, obs_first=True, behaviour=True, done_m
     return {k: v.contiguous() for k, v in t.items()}, first
 
 
-def branch_report(policy, t, h, obs_first, T):
-    """On the float64 reference: the share of rows in each surrogate case (clipped or not x sign of adv) and vf branch, the
+def branch_report(policy, t, h, obs_first, T, device="cpu"):
+    """On the float64 reference (its forward on `device`): the share of rows in each surrogate case (clipped or not x sign of adv) and vf branch, the
     smallest distance of any row from a boundary where a branch could flip, and the smallest conv_margin of a row."""
     c, vc = h["clip_param"], h["vf_clip_param"]
     K = t["actions"].shape[0]
+    logits, value, _ = _forward64(policy, shifted_obs(t["obs"], obs_first, K), t["prev_actions"], t["state"], t.get("done"), T, device)
     with torch.no_grad():
-        logits, value, _ = forward(copy.deepcopy(policy).double(), shifted_obs(t["obs"], obs_first, K), t["prev_actions"], t["state"],
-                                   t.get("done"), T)
         acts, lpo, adv, vt, vfp, b = _inputs(t, torch.float64, "cpu")
         ratio = row_terms(logits, value, acts, lpo, adv, vt, vfp, None, dict(h, kl_coeff=0.0))[5]
         clipped = (ratio < 1 - c) | (ratio > 1 + c)
@@ -260,7 +282,7 @@ def branch_report(policy, t, h, obs_first, T):
     return {"clipped_pos": share(clipped & (adv > 0)), "clipped_neg": share(clipped & (adv < 0)),
             "open_pos": share(~clipped & (adv > 0)), "open_neg": share(~clipped & (adv < 0)),
             "vf_dead": share(dead), "vf_live": share(~dead), "vf_clipped_live": share(vclip & ~dead),
-            "margin": float(dist), "conv_margin": float(conv_margin(policy, shifted_obs(t["obs"], obs_first, K)).min())}
+            "margin": float(dist), "conv_margin": float(conv_margin(policy, shifted_obs(t["obs"], obs_first, K), device).min())}
 
 
 def stack_saturation(policy, obs):
@@ -304,3 +326,14 @@ def clipped_rows(policy, t, first, T):
         logp = torch.log_softmax(logits, -1).gather(-1, t["actions"].long().unsqueeze(-1)).squeeze(-1)
     return {"advantages": torch.ones(t["actions"].shape), "logp_old": (logp - float(np.log(1.5))).float().contiguous(),
             "vf_pred": (value + 2.0).float().contiguous(), "value_targets": (value + 0.2).float().contiguous()}
+
+
+def split_case(shape, C, splits, chunk):
+    """The split case (shape of SPLIT_SHAPES, ordinary inputs, A = 8) that the CPU sensitivity tests and the GPU accuracy tests
+    share -> (policy, t, obs_first, (K, T, E, N, P), split_rows' probes)."""
+    d = SPLIT_SHAPES[shape]
+    K, T, E, N, P = d["K_"], d["T"], d["E"], d["N"], d["P"]
+    probes, _, _ = split_rows(K, T, E, N, P, splits, chunk)
+    pol = make_policy(8, N, P, C, seed=SPLIT_SEEDS[shape])
+    t, first = make_inputs(pol, K, E, N, T, seed=100 + SPLIT_SEEDS[shape], done_mode="per_env")
+    return pol, t, first, (K, T, E, N, P), probes

@@ -1,7 +1,7 @@
 """ppo_loss_recurrent without a device: the CPU path against the float64 restatement (ppo_lstm_ref.py), the state rule's
 properties (T = 1, the truncation, the resets, minibatch slices), the argument checks of the Python entry point and of the ABI,
 the scratch query against the header's macro, and whether the GPU tests' bound would notice a kernel that cut BPTT, ignored
-done or dropped a ragged last window."""
+done or dropped a ragged last window, or whose split-K kernel lost or doubled rows of a second chunk."""
 import copy
 import ctypes as C
 import os
@@ -10,8 +10,8 @@ import subprocess
 import pytest
 import torch
 
-from ppo_lstm_ref import (HYPER, MARGIN, autograd_loss, bound, branch_report, forward, make_inputs, make_policy, max_err, set_means,
-                          shifted_obs)
+from ppo_lstm_ref import (HYPER, MARGIN, SPLIT_SHAPES, autograd_loss, bound, branch_report, forward, make_inputs, make_policy,
+                          max_err, rows_mask, set_means, shifted_obs, split_case)
 from ppo_ref import row_terms
 from sequential_social_dilemma_games_amd import _capi, ppo_loss_recurrent
 from sequential_social_dilemma_games_amd.policy import PPO_STATS, ConvFCPolicy, recurrent_forward
@@ -207,7 +207,8 @@ def test_abi_argument_checks_need_no_device():
 
 
 SHAPES = [(1, 1, 5, 5, 8, 64, 1), (7, 33, 5, 5, 8, 64, 3), (4, 17, 5, 1, 15, 128, 8), (128, 4096, 5, 5, 8, 128, 16), (16, 4096, 5, 5, 8, 128, 16),
-          (2, 257, 64, 64, 8, 64, 2), (3, 16, 5, 5, 9, 256, 3), (6, 1000, 3, 1, 1, 64, 1)]
+          (2, 257, 64, 64, 8, 64, 2), (3, 16, 5, 5, 9, 256, 3), (6, 1000, 3, 1, 1, 64, 1),
+          (14, 33, 5, 1, 8, 64, 13), (33, 65, 2, 2, 8, 64, 32), (14, 33, 5, 1, 8, 128, 13)]   # the last three: the split-K shapes A and B
 
 
 def test_scratch_query_matches_the_header(tmp_path):
@@ -259,3 +260,79 @@ def test_bound_separates_the_gradient_from_a_near_miss(K_, T, E, mode, seed):
             off = max_err(gv[name], g64[name])
             print("%-12s %-7s off %.3e bound %.3e ratio %.1f" % (variant, name, off, b, off / b))
             assert off >= 10 * b, (variant, name, off, b)
+
+
+# ---- would the bound notice a row lost or doubled in the split-K kernel's second pass? ----
+SPLIT_TENSORS = ("lstm_w", "lstm_b")                             # what ssd_lstm_dw_kernel writes
+SPLIT_PROBES = ("second_chunks", "last_of_first_pass", "first_of_second_pass", "last_of_ragged_chunk", "window2_first", "window2_last")
+BRANCHES = ("clipped_pos", "clipped_neg", "open_pos", "open_neg", "vf_dead", "vf_live", "vf_clipped_live")
+_SPLIT_CACHE = {}
+
+
+def _split_case(shape, kind):
+    """The GPU split case's own policy and inputs (test_ppo_lstm_gpu.py's SPLIT_CASES) with the float64 gradient and each
+    tensor's bound (et from the CPU's float32), computed once and shared (never modified)."""
+    if (shape, kind) not in _SPLIT_CACHE:
+        splits = _capi.SSD_RPPO_MAX_SPLITS
+        pol, t, first, h, (K_, T, E, N, P), (probes, _, unlit) = split_case(shape, kind, 64, splits, _capi.SSD_RPPO_CHUNK)
+        assert _capi.SSD_RPPO_SPLITS(T * (E * N // P)) == splits == 32
+        rep = branch_report(pol, t, h, first, T)
+        print("split", shape, kind, rep)
+        assert rep["margin"] > MARGIN, rep
+        if kind == "ordinary":
+            assert all(rep[k] > 0.2 for k in BRANCHES), rep
+        _, _, g64 = autograd_loss(pol, t, h, first, T)
+        _, _, g32 = autograd_loss(pol, t, h, first, T, dtype=torch.float32)
+        bounds = {name: bound(g64[name], max_err(g32[name], g64[name])) for name in g64}
+        _SPLIT_CACHE[shape, kind] = (pol, t, first, h, (K_, T, E, N, P), g64, bounds, probes, unlit)
+    return _SPLIT_CACHE[shape, kind]
+
+
+def _split_defect(case, rows, tensors, what):
+    """The rows' share of the gradient by the twin: asserts that the two shares add up to the gradient, and returns for each
+    tensor how far a kernel that dropped the rows from its sums, and one that counted them twice, would be off, over the
+    bound."""
+    pol, t, first, h, (K_, T, E, N, P), g64, bounds, _, _ = case
+    _, _, g = autograd_loss(pol, t, h, first, T, twin_rows=rows_mask(K_, T, E, N, P, rows))
+    out = {}
+    for name in tensors:
+        rest, share = g[name]
+        assert max_err(rest + share, g64[name]) <= 1e-12 * max(1.0, float(g64[name].abs().max())), name
+        out[name] = (max_err(rest, g64[name]) / bounds[name], max_err(rest + 2 * share, g64[name]) / bounds[name])
+        print("%-28s %-8s dropped / bound %.1f  twice / bound %.1f" % (what, name, *out[name]))
+    return out
+
+
+@pytest.mark.parametrize("probe", SPLIT_PROBES)
+@pytest.mark.parametrize("shape", sorted(SPLIT_SHAPES))
+def test_bound_separates_a_row_of_a_second_chunk(shape, probe):
+    """A condition on the spotlight inputs of the GPU split cases, not a measurement of the kernel: in float64, losing or
+    doubling the probed window set rows -- all rows of the second chunks, the last row of split 31's only chunk, the first row
+    of split 0's second, the last valid row of the ragged chunk, the first and the last row of the second window -- moves
+    lstm_w and lstm_b by at least 10 times the bound.  At P = N the last set is probed, which a kernel that dropped `+ p` from
+    the row would get wrong; the whole chunks also in set 0."""
+    case = _split_case(shape, "spotlight")
+    P, probes = case[4][4], case[7]
+    window, rng = probes[probe]
+    for p in sorted({P - 1, 0} if probe == "second_chunks" else {P - 1}):
+        for name, ratios in _split_defect(case, [(window, p, rng)], SPLIT_TENSORS, "%s %s set %d" % (shape, probe, p)).items():
+            assert min(ratios) >= 10.0, (shape, probe, p, name, ratios)
+
+
+@pytest.mark.parametrize("shape", sorted(SPLIT_SHAPES))
+def test_an_unlit_row_moves_nothing(shape):
+    """The spotlight's dark rows are dark: an unlit row of window 1's last step has an exactly zero share of every tensor."""
+    case = _split_case(shape, "spotlight")
+    pol, t, first, h, (K_, T, E, N, P), g64, _, _, (window, rng) = case
+    _, _, g = autograd_loss(pol, t, h, first, T, twin_rows=rows_mask(K_, T, E, N, P, [(window, P - 1, rng)]))
+    for name in g:
+        assert float(g[name][1].abs().max()) == 0.0 and torch.equal(g[name][0], g64[name]), name
+
+
+@pytest.mark.parametrize("shape", sorted(SPLIT_SHAPES))
+def test_bound_separates_whole_second_chunks_with_ordinary_rows(shape):
+    """With ordinary make_inputs rows one row in 2310 is about the bound's floor; all rows of the second chunks are not."""
+    case = _split_case(shape, "ordinary")
+    P, (window, rng) = case[4][4], case[7]["second_chunks"]
+    for name, ratios in _split_defect(case, [(window, P - 1, rng)], SPLIT_TENSORS, "%s ordinary second_chunks" % shape).items():
+        assert min(ratios) >= 10.0, (shape, name, ratios)

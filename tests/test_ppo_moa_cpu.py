@@ -2,7 +2,7 @@
 where it must not (moa_weight = 0, clipped and dead rows, the padding rows of the MOA matrix), the conv's gradient as the sum of
 the two branches', minibatch slices, the sixth statistic, the argument checks of the Python entry point and of the ABI, the
 scratch query against the header's macro, and whether the GPU tests' bound would notice a kernel with one of the faults this
-loss invites."""
+loss invites, or whose split-K kernels lost or doubled rows of a second chunk."""
 import copy
 import ctypes as C
 import os
@@ -11,8 +11,9 @@ import subprocess
 import pytest
 import torch
 
-from ppo_moa_ref import (ACTIONS_BRANCH, CONV_MARGIN, HYPER, MARGIN, MOA_BRANCH, MOA_WEIGHT, VARIANTS, autograd_loss, bound, branch_report,
-                         clipped_rows, forward, make_inputs, make_policy, max_err, moa_ce, set_means, shifted_obs, stack_saturation)
+from ppo_moa_ref import (ACTIONS_BRANCH, CONV_MARGIN, HYPER, MARGIN, MOA_BRANCH, MOA_WEIGHT, SPLIT_SHAPES, VARIANTS, autograd_loss, bound,
+                         branch_report, clipped_rows, forward, make_inputs, make_policy, max_err, moa_ce, rows_mask, set_means, shifted_obs,
+                         split_case, stack_saturation)
 from ppo_ref import row_terms
 from sequential_social_dilemma_games_amd import _capi, ppo_loss_moa
 from sequential_social_dilemma_games_amd.policy import MOA_PPO_STATS, PPO_STATS, ConvLSTMPolicy, ConvMOAPolicy
@@ -245,7 +246,8 @@ def test_abi_argument_checks_need_no_device():
 
 # (K, E, N, P, A, C, T)
 SHAPES = [(1, 1, 5, 5, 8, 64, 1), (7, 33, 5, 5, 8, 64, 3), (4, 17, 5, 1, 15, 128, 8), (128, 4096, 5, 5, 8, 128, 16), (16, 4096, 5, 5, 8, 128, 16),
-          (2, 1025, 16, 16, 8, 64, 2), (3, 16, 5, 5, 9, 256, 3), (6, 1000, 3, 1, 1, 64, 1), (7, 17, 16, 16, 15, 64, 3), (7, 17, 2, 2, 8, 64, 3)]
+          (2, 1025, 16, 16, 8, 64, 2), (3, 16, 5, 5, 9, 256, 3), (6, 1000, 3, 1, 1, 64, 1), (7, 17, 16, 16, 15, 64, 3), (7, 17, 2, 2, 8, 64, 3),
+          (14, 33, 5, 1, 8, 64, 13), (33, 65, 2, 2, 8, 64, 32), (14, 33, 5, 1, 8, 128, 13)]   # the last three: the split-K shapes A and B
 
 
 def test_scratch_query_matches_the_header(tmp_path):
@@ -340,3 +342,50 @@ def test_no_tensor_compares_against_nothing(case):
         print("zeroed %-14s |grad| / bound %.1f" % (name, ratio))
         assert ratio >= 10.0, (name, ratio)
     assert stack_saturation(pol, t["obs"]) < 0.01
+
+
+# ---- would the bound notice a row lost or doubled in the split-K kernels' second pass? ----
+# what ssd_moa_dw_kernel (once per branch) and ssd_moa_dpred_kernel write
+SPLIT_TENSORS = ("lstm_kernel", "lstm_recurrent", "lstm_bias", "moa_kernel", "moa_recurrent", "moa_bias", "pred_w", "pred_b")
+SPLIT_PROBES = ("second_chunks", "last_of_first_pass", "first_of_second_pass", "last_of_ragged_chunk", "window2_first", "window2_last")
+BRANCHES = ("clipped_pos", "clipped_neg", "open_pos", "open_neg", "vf_dead", "vf_live", "vf_clipped_live")
+_SPLIT_CACHE = {}
+
+
+def _split_case(shape):
+    """The GPU split case's own policy and (ordinary) inputs with the float64 gradient and each tensor's bound (et from the
+    CPU's float32), computed once and shared (never modified)."""
+    if shape not in _SPLIT_CACHE:
+        splits = _capi.SSD_MPPO_MAX_SPLITS
+        pol, t, first, (K_, T, E, N, P), probes = split_case(shape, 64, splits, _capi.SSD_MPPO_CHUNK)
+        assert _capi.SSD_MPPO_SPLITS(T * (E * N // P)) == splits == 32
+        rep = branch_report(pol, t, HYPER, first, T)
+        print("split", shape, rep)
+        assert rep["margin"] > MARGIN and rep["conv_margin"] >= CONV_MARGIN, rep
+        assert all(rep[k] > 0.2 for k in BRANCHES), rep
+        _, _, g64 = autograd_loss(pol, t, HYPER, first, T)
+        _, _, g32 = autograd_loss(pol, t, HYPER, first, T, dtype=torch.float32)
+        bounds = {name: bound(g64[name], max_err(g32[name], g64[name])) for name in g64}
+        _SPLIT_CACHE[shape] = (pol, t, first, (K_, T, E, N, P), g64, bounds, probes)
+    return _SPLIT_CACHE[shape]
+
+
+@pytest.mark.parametrize("probe", SPLIT_PROBES)
+@pytest.mark.parametrize("shape", sorted(SPLIT_SHAPES))
+def test_bound_separates_a_row_of_a_second_chunk(shape, probe):
+    """A condition on the inputs of the GPU split cases, not a measurement of the kernel: in float64, losing or doubling the
+    probed window set rows -- all rows of the second chunks, the last row of split 31's only chunk, the first row of split 0's
+    second, the last valid row of the ragged chunk, the first and the last row of the second window -- moves every tensor the
+    split-K kernels write by at least 10 times the bound.  The shares come from a twin of the policy (ppo_moa_ref.forward).  At
+    P = N the last set is probed, which a kernel that dropped `+ p` from the row would get wrong; the whole chunks also in
+    set 0."""
+    pol, t, first, (K_, T, E, N, P), g64, bounds, probes = _split_case(shape)
+    window, rng = probes[probe]
+    for p in sorted({P - 1, 0} if probe == "second_chunks" else {P - 1}):
+        _, _, g = autograd_loss(pol, t, HYPER, first, T, twin_rows=rows_mask(K_, T, E, N, P, [(window, p, rng)]))
+        for name in SPLIT_TENSORS:
+            rest, share = g[name]
+            assert max_err(rest + share, g64[name]) <= 1e-12 * max(1.0, float(g64[name].abs().max())), name
+            ratios = (max_err(rest, g64[name]) / bounds[name], max_err(rest + 2 * share, g64[name]) / bounds[name])
+            print("%s %-22s set %d %-14s dropped / bound %.1f  twice / bound %.1f" % (shape, probe, p, name, *ratios))
+            assert min(ratios) >= 10.0, (shape, probe, p, name, ratios)

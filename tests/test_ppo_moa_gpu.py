@@ -1,6 +1,8 @@
 """ppo_loss_moa on the MI355X (csrc/ssd_policy_moa_grad.hip, ssd_policy_moa_ppo_grad): the kernels' gradients and statistics
 against the float64 restatement (ppo_moa_ref.py) with torch's own float32 autograd on the same device as the yardstick, the
-persistent tile loop (in the row accounting), exact row accounting, exact zeros where no gradient may flow, bit-equal repeats, set isolation,
+persistent tile loop (in the row accounting, and an accuracy case with the float64 restatement on the device), the split-K kernels' second chunks (windows of
+more than 32 chunks of one set's rows: the second pass over the accumulators, a ragged last chunk that is a second chunk, splits
+that get no chunk of the second window, rows >= 2048), exact row accounting, exact zeros where no gradient may flow, bit-equal repeats, set isolation,
 moa_weight = 0, and one optimiser step end to end from sample()."""
 import copy
 import ctypes as C
@@ -10,7 +12,7 @@ import pytest
 import torch
 
 from ppo_moa_ref import (ACTIONS_BRANCH, CONV_MARGIN, HYPER, MARGIN, MOA_BRANCH, MOA_WEIGHT, as_numpy_u32, autograd_loss, branch_report, counting_inputs,
-                         forward, make_inputs, make_policy, max_err, shifted_obs, zero_policy)
+                         forward, make_inputs, make_policy, max_err, shifted_obs, split_case, zero_policy)
 from ppo_ref import COUNTING_HYPER
 from sequential_social_dilemma_games_amd import _capi
 from sequential_social_dilemma_games_amd import constants as K
@@ -83,12 +85,12 @@ def _equal_bits(a, b):
         assert np.array_equal(as_numpy_u32(ga[name]), as_numpy_u32(gb[name])), name
 
 
-def compare_with_float64(pol, t, first, h, T, own_stream=False):
-    """The kernels on (pol, t, first, h) against the float64 restatement with torch's float32 autograd on the device as the
-    yardstick -- gradients, statistics and loss under the bound --, all outputs finite, and a second call bit-equal to the
-    first."""
+def compare_with_float64(pol, t, first, h, T, own_stream=False, ref_device="cpu"):
+    """The kernels on (pol, t, first, h) against the float64 restatement (torch's float64 ops on ref_device) with torch's
+    float32 autograd on the device as the yardstick -- gradients, statistics and loss under the bound --, all outputs finite,
+    and a second call bit-equal to the first."""
     P = pol.num_sets
-    loss64, stats64, g64 = autograd_loss(pol, t, h, first, T)
+    loss64, stats64, g64 = autograd_loss(pol, t, h, first, T, device=ref_device)
     loss32, stats32, g32 = autograd_loss(pol, t, h, first, T, dtype=torch.float32, device=DEV)
     dpol, dt, dfirst = copy.deepcopy(pol).to(DEV), _to_dev(t), None if first is None else first.to(DEV)
     if own_stream:
@@ -130,15 +132,66 @@ def test_gradients_and_stats_against_float64(K_, T, E, N, P, A, C_, beh, use_fir
 
 
 # The persistent loop (more tiles than workgroups) needs 16 G + 1 sequences per set, G the exported groups macro: at P = N = 16
-# that is 1025 envs.  Its accuracy case (K = T = 2, 32 800 rows, input seed 300 chosen on the CPU: margin 2.5e-4, every branch
-# above 0.2 of the rows) passed on the MI355X under the same bound but took 14.3 s, nearly all of it the float64 reference on
-# the CPU, and is left out for that reason (the log is under profiles/r13_ppo_moa/).  The second tile is covered by the row
-# accounting below, which needs no reference.
+# that is 1025 envs.
 def _multi_tile_envs(P):
     G = _capi.SSD_MPPO_GROUPS(10 ** 6, P)
     E = 16 * G + 1
     assert _capi.SSD_MPPO_GROUPS(E, P) == G and -(-E // 16) == G + 1
     return E
+
+
+def test_persistent_loop_takes_a_second_tile():
+    """The accuracy case of the persistent loop: P = N = 16, 1025 envs, K = T = 2, 32 800 rows, input seed 300 chosen on the
+    CPU (margin 2.5e-4, every branch above 0.2 of the rows).  With the float64 restatement on the CPU it took 14.3 s; here
+    make_inputs, branch_report and the reference run torch's float64 ops on the device (the random numbers are drawn on the CPU
+    as ever).  Same bound, same factor.  What the row accounting cannot see: the carried dh / dc, the heads' register sums
+    across tiles, dpred through scratch, the trunk's third mode adding the second stack's conv sums on a second tile.
+    4.8 s on the MI355X, 4.3 s in a second run (the phases, timed once: make_inputs 1.2 s, branch_report 0.6 s, the float64 autograd 0.7 s, the float32
+    yardstick's first call at this shape 2.0 s)."""
+    P = N = 16
+    E = _multi_tile_envs(P)
+    pol = make_policy(8, N, P, 64, seed=30 + P)
+    t, first = make_inputs(pol, 2, E, N, 2, seed=300, done_mode="per_env", device=DEV)
+    rep = branch_report(pol, t, HYPER, first, 2, device=DEV)
+    print("multi-tile", (P, N, E), rep)
+    assert rep["margin"] > MARGIN and rep["conv_margin"] >= CONV_MARGIN, rep
+    for k in BRANCHES:
+        assert rep[k] > 0.2, rep
+    compare_with_float64(pol, t, first, HYPER, 2, ref_device=DEV)
+
+
+def test_inputs_do_not_depend_on_where_the_float64_forward_runs():
+    """make_inputs draws every random number on the CPU and rounds what it takes from the float64 forward to float32: the
+    fragment (the rows drawn again for the conv's kink included) is the same to the bit with that forward on the device, and
+    branch_report's figures agree."""
+    pol = make_policy(8, 5, 5, 64, seed=22)
+    t, first = make_inputs(pol, 7, 17, 5, 3, seed=122, done_mode="per_env")
+    td, firstd = make_inputs(pol, 7, 17, 5, 3, seed=122, done_mode="per_env", device=DEV)
+    assert t.keys() == td.keys() and torch.equal(first, firstd)
+    for k in t:
+        assert td[k].device.type == "cpu" and td[k].dtype == t[k].dtype and torch.equal(t[k], td[k]), k
+    rep, repd = branch_report(pol, t, HYPER, first, 3), branch_report(pol, t, HYPER, first, 3, device=DEV)
+    assert all(abs(rep[k] - repd[k]) <= 1e-12 for k in rep), (rep, repd)
+
+
+@pytest.mark.parametrize("shape", ["A", "B"])
+def test_split_k_takes_a_second_chunk(shape):
+    """`chunk += S` of ssd_moa_dw_kernel (both branches) and ssd_moa_dpred_kernel: the first window holds more than
+    SSD_MPPO_MAX_SPLITS chunks of a set's rows (A: P = 1, N = 5, 2145 rows, 34 chunks, the last of 33 rows; B: P = N = 2, 2080
+    rows a set, 33 chunks, the last of 32 rows, and one other agent: the partial prediction tile), the second window fewer chunks
+    than splits (3 and 2), so most splits must keep what the first left.  Ordinary inputs: at MOA_WEIGHT one row lost or doubled
+    is 10 bounds or more in every tensor these kernels write (test_ppo_moa_cpu.py measures it)."""
+    splits, chunk = _capi.SSD_MPPO_MAX_SPLITS, _capi.SSD_MPPO_CHUNK
+    pol, t, first, (K_, T, E, N, P), _ = split_case(shape, 64, splits, chunk)
+    rows1, rows2 = T * (E * N // P), (K_ - T) * (E * N // P)
+    assert _capi.SSD_MPPO_SPLITS(rows1) == splits == 32 and -(-rows1 // chunk) > splits and rows1 % chunk
+    assert 0 < -(-rows2 // chunk) < splits
+    rep = branch_report(pol, t, HYPER, first, T)
+    print("split", shape, rep)
+    assert rep["margin"] > MARGIN and rep["conv_margin"] >= CONV_MARGIN, rep
+    for k in BRANCHES:
+        assert rep[k] > 0.2, rep
+    compare_with_float64(pol, t, first, HYPER, T)
 
 
 @pytest.mark.parametrize("P,N,E", [(5, 5, 1), (5, 5, 16), (5, 5, 17), (5, 5, 33), (1, 5, 1), (1, 5, 16), (1, 5, 17), (1, 5, 33),
