@@ -216,15 +216,18 @@ __device__ __forceinline__ void render_views_std(const int lane, const int WP, c
     uint32_t off3 = (uint32_t)pp0 * 3u;                                 // byte offset of the lane's cells in an agent's block
     asm volatile("" : "+v"(off3));                                      // keep it in a register (else re-derived per agent)
     const rsrc_t out_r = make_rsrc(out_env, (uint32_t)NA * SSD_OBS_STRIDE);
+    // (TAB, the renderer waves: the layer's LDS base is added to the agents' window offsets once, with lane = agent, instead of by one
+    // scalar add per agent; the other kernels keep their code.  EXPERIMENTS.md, "Round 15")
+    const uint32_t a_s0v = TAB ? a_s0 + view_lds : a_s0;
     for (int ag0 = 0; ag0 < NA; ag0 += kB) {
         uint32_t addr[kB][4], px[kB][4];
 #pragma unroll
         for (int u = 0; u < kB; ++u) {
             const uint32_t k = rl(a_k, ag0 + u);
-            const uint32_t s0 = rl(a_s0, ag0 + u) + view_lds;
+            const uint32_t s0 = TAB ? rl(a_s0v, ag0 + u) : rl(a_s0, ag0 + u) + view_lds;
             const int sgn = k >= 2 ? -1 : 1;
             // wave-uniform branch on the rotation's parity instead of a per-cell select (the asm is volatile so that the two
-            // arms are not merged back into selects)
+            // arms are not merged back into selects; selects on a scalar mask were measured again in round 15: slower)
             if (k & 1) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) asm volatile("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(addr[u][q]) : "v"(L1[q]), "v"(sgn), "s"(s0));
@@ -258,10 +261,20 @@ __device__ __forceinline__ void render_views_std(const int lane, const int WP, c
 #pragma unroll
                 for (int u = 0; u < kB; ++u) store12_wt(out_r, (uint32_t)(ag0 + u) * SSD_OBS_STRIDE, off3, d[u], decltype(policy)::value);
             };
-            if (wt == 1) stores(std::integral_constant<int, 1>{});
-            else if (wt == 3) stores(std::integral_constant<int, 3>{});
-            else if (wt == 2) stores(std::integral_constant<int, 2>{});
-            else stores(std::integral_constant<int, 0>{});
+            if constexpr (TAB) {
+                // The renderer waves belong to coherent uint8 launches, for which select() leaves two policies: write-through (1), or,
+                // for a ring beyond the memory-side cache, non-temporal write-back (3).  One two-way test with the usual policy as
+                // the fall-through; of the four-way chain below the compiler makes a switch, a ladder of four branches with the
+                // usual policy at its far end.  (Any other value would store write-through: nothing of a coherent launch may
+                // stay dirty in L2.)
+                if (__builtin_expect(wt != 3, 1)) stores(std::integral_constant<int, 1>{});
+                else stores(std::integral_constant<int, 3>{});
+            } else {
+                if (wt == 1) stores(std::integral_constant<int, 1>{});
+                else if (wt == 3) stores(std::integral_constant<int, 3>{});
+                else if (wt == 2) stores(std::integral_constant<int, 2>{});
+                else stores(std::integral_constant<int, 0>{});
+            }
         }
     }
 }
