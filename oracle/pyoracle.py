@@ -42,6 +42,8 @@ def lib():
         L.ssd_oracle_observe.argtypes = [vp, C.c_int, vp]
         L.ssd_oracle_cleanup_thresholds.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.ssd_oracle_potential_waste_area.argtypes = [vp]
+        L.ssd_oracle_set_tables.argtypes = [vp, vp, vp, vp]
+        L.ssd_oracle_get_waste_count.argtypes = [vp, vp]
         L.ssd_oracle_draw.restype = C.c_uint32
         L.ssd_oracle_draw.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         _LIB = L
@@ -149,6 +151,26 @@ class Oracle:
         a, w = C.c_uint64(), C.c_uint64()
         lib().ssd_oracle_cleanup_thresholds(self._h, int(n_waste), C.byref(a), C.byref(w))
         return a.value, w.value
+
+    def set_tables(self, harvest=None, cleanup=None):
+        """Spawn tables as VecEngine's: harvest uint64 [4]; cleanup = (apple, waste), uint64 [potential_waste_area + 1] each.
+        None = the reference's constants."""
+        h = None if harvest is None else np.ascontiguousarray(harvest, dtype=np.uint64)
+        ca = cw = None
+        if h is not None and h.shape != (4,):
+            raise ValueError("harvest thresholds must have 4 entries")
+        if cleanup is not None:
+            ca, cw = (np.ascontiguousarray(x, dtype=np.uint64) for x in cleanup)
+            n = self.potential_waste_area + 1
+            if ca.shape != (n,) or cw.shape != (n,):
+                raise ValueError("cleanup thresholds must have %d entries each" % n)
+        if lib().ssd_oracle_set_tables(self._h, _p(h), _p(ca), _p(cw)):
+            raise ValueError("ssd_oracle_set_tables rejected the tables")
+
+    def waste_count(self):
+        out = np.zeros(self.E, np.uint32)
+        lib().ssd_oracle_get_waste_count(self._h, _p(out))
+        return out
 
     @property
     def potential_waste_area(self):

@@ -38,11 +38,14 @@ struct ssd_oracle {
     int n_waste, *waste_cells;   /* 'H' or 'R' cells (cleanup.py:59-60) */
     int potential_waste;         /* cleanup.py:36-38 */
     uint64_t thr_harvest[4];
+    /* caller-supplied tables (ssd_oracle_set_tables); tab_ca == NULL: the Cleanup thresholds are derived per count */
+    uint64_t *tab_ca, *tab_cw;   /* [potential_waste + 1] */
     /* state */
     char *world, *beam;          /* [E][H*W] */
     int16_t *pos;                /* [E][N][2] */
     uint8_t *orient;             /* [E][N] */
     uint32_t *episode, *t, *key; /* [E] */
+    uint32_t *waste_used;        /* [E] the 'H' count the last spawn phase computed its thresholds from */
 };
 
 /* ---------------- shared PRNG (prng.py) ---------------- */
@@ -109,6 +112,45 @@ void ssd_oracle_cleanup_thresholds(const ssd_oracle *o, int n_waste, uint64_t *t
 }
 int ssd_oracle_potential_waste_area(const ssd_oracle *o) { return o->potential_waste; }
 
+/* harvest.py:13 SPAWN_PROB as thresholds */
+static void default_harvest(uint64_t *thr) {
+    const double sp[4] = {0, 0.005, 0.02, 0.05};
+    for (int i = 0; i < 4; ++i) thr[i] = threshold(sp[i]);
+}
+
+int ssd_oracle_set_tables(ssd_oracle *o, const uint64_t *harvest, const uint64_t *cleanup_apple,
+                          const uint64_t *cleanup_waste) {
+    if ((cleanup_apple == NULL) != (cleanup_waste == NULL)) return -1;
+    if (harvest) memcpy(o->thr_harvest, harvest, sizeof(o->thr_harvest));
+    else default_harvest(o->thr_harvest);
+    free(o->tab_ca); free(o->tab_cw);
+    o->tab_ca = o->tab_cw = NULL;
+    if (cleanup_apple) {
+        size_t n = (size_t)o->potential_waste + 1;
+        o->tab_ca = (uint64_t *)malloc(n * sizeof(uint64_t));
+        o->tab_cw = (uint64_t *)malloc(n * sizeof(uint64_t));
+        memcpy(o->tab_ca, cleanup_apple, n * sizeof(uint64_t));
+        memcpy(o->tab_cw, cleanup_waste, n * sizeof(uint64_t));
+    }
+    return 0;
+}
+
+/* The thresholds the spawn phase uses at `n_h` cells of 'H': the caller's table, indexed past its end as the
+ * kernel clamps (the last entry), or the derivation above. */
+static void spawn_thresholds(const ssd_oracle *o, int n_h, uint64_t *thr_apple, uint64_t *thr_waste) {
+    if (o->tab_ca) {
+        int i = n_h < o->potential_waste ? n_h : o->potential_waste;
+        *thr_apple = o->tab_ca[i]; *thr_waste = o->tab_cw[i];
+    } else {
+        ssd_oracle_cleanup_thresholds(o, n_h, thr_apple, thr_waste);
+    }
+}
+
+int ssd_oracle_get_waste_count(const ssd_oracle *o, uint32_t *out) {
+    memcpy(out, o->waste_used, (size_t)o->E * sizeof(uint32_t));
+    return 0;
+}
+
 /* ---------------- construction ---------------- */
 ssd_oracle *ssd_oracle_create(int game, int H, int W, const char *base_map, int num_envs, int num_agents,
                               int view_len, int beam_len, uint64_t seed, uint32_t env_base,
@@ -138,8 +180,7 @@ ssd_oracle *ssd_oracle_create(int game, int H, int W, const char *base_map, int 
         if (game == 1 && (ch == 'H' || ch == 'R')) o->waste_cells[o->n_waste++] = i;
     }
     o->potential_waste = o->n_waste;
-    const double sp[4] = {0, 0.005, 0.02, 0.05}; /* harvest.py:13 SPAWN_PROB */
-    for (int i = 0; i < 4; ++i) o->thr_harvest[i] = threshold(sp[i]);
+    default_harvest(o->thr_harvest);
     size_t E = (size_t)num_envs;
     o->world = (char *)malloc(E * hw);
     o->beam = (char *)calloc(E * hw, 1);
@@ -149,6 +190,7 @@ ssd_oracle *ssd_oracle_create(int game, int H, int W, const char *base_map, int 
     o->episode = (uint32_t *)malloc(E * sizeof(uint32_t));
     o->t = (uint32_t *)calloc(E, sizeof(uint32_t));
     o->key = (uint32_t *)calloc(E, sizeof(uint32_t));
+    o->waste_used = (uint32_t *)calloc(E, sizeof(uint32_t));
     for (size_t e = 0; e < E; ++e) {
         o->episode[e] = 0xFFFFFFFFu; /* "never reset"; the first reset wraps it to 0 */
         o->key[e] = env_key(seed, env_base + (uint32_t)e, o->episode[e]);
@@ -160,7 +202,8 @@ void ssd_oracle_destroy(ssd_oracle *o) {
     if (!o) return;
     free(o->base); free(o->spawn_cells); free(o->apple_cells); free(o->waste_cells);
     free(o->world); free(o->beam); free(o->pos); free(o->orient);
-    free(o->episode); free(o->t); free(o->key);
+    free(o->episode); free(o->t); free(o->key); free(o->waste_used);
+    free(o->tab_ca); free(o->tab_cw);
     free(o);
 }
 
@@ -172,6 +215,7 @@ typedef struct {
     uint8_t *orient;
     int32_t rew[MAXN];
     uint32_t key, t;
+    uint32_t *waste_used;
 } envref;
 
 /* agent_by_pos = {pos: id for agents in index order} (map_env.py:397,482,495,603): the LAST
@@ -382,7 +426,8 @@ static void spawn_phase(envref *E) {
         int n_h = 0;                                             /* cleanup.py:175-177 */
         for (int i = 0; i < H * W; ++i) n_h += world[i] == 'H';
         uint64_t thr_apple, thr_waste;
-        ssd_oracle_cleanup_thresholds(o, n_h, &thr_apple, &thr_waste);   /* :115 */
+        *E->waste_used = (uint32_t)n_h;
+        spawn_thresholds(o, n_h, &thr_apple, &thr_waste);        /* :115 */
         for (int i = 0; i < o->n_apple; ++i) {                   /* :135-141 */
             int cell = o->apple_cells[i], row = cell / W, col = cell % W;
             if (last_agent_at(E->pos, N, row, col) >= 0 || world[cell] == 'A') continue;
@@ -470,6 +515,7 @@ static envref make_ref(ssd_oracle *o, int e) {
     E.orient = o->orient + (size_t)e * o->N;
     E.key = o->key[e];
     E.t = o->t[e];
+    E.waste_used = o->waste_used + e;
     return E;
 }
 

@@ -60,6 +60,18 @@ void ssd_oracle_cleanup_thresholds(const ssd_oracle *o, int n_waste, uint64_t *t
                                    uint64_t *thr_waste);
 int ssd_oracle_potential_waste_area(const ssd_oracle *o);
 
+/* Optional spawn tables, as ssd_config's: `harvest` 4 thresholds by min(#neighbour apples, 3); `cleanup_apple` /
+ * `cleanup_waste` potential_waste_area + 1 thresholds each, by the number of 'H' cells (a count past the end uses
+ * the last entry, as the kernel clamps).  A draw u32 succeeds when draw < threshold (64-bit compare: 2^32 and above
+ * = always).  NULL = the reference's constants (the two Cleanup pointers: both or neither).  Without a call the
+ * oracle behaves as it always did; ssd_oracle_cleanup_thresholds() keeps returning the derived values. */
+int ssd_oracle_set_tables(ssd_oracle *o, const uint64_t *harvest, const uint64_t *cleanup_apple,
+                          const uint64_t *cleanup_waste);
+
+/* u32 [E]: the number of 'H' cells the last step or reset of each env computed its Cleanup thresholds from
+ * (after a reset: the reset world's count); 0 for Harvest and before the first reset. */
+int ssd_oracle_get_waste_count(const ssd_oracle *o, uint32_t *out);
+
 /* One draw of the shared PRNG (sequential_social_dilemma_games_amd/prng.py). */
 uint32_t ssd_oracle_draw(uint64_t seed, uint32_t env, uint32_t episode, uint32_t t,
                          uint32_t stream, uint32_t index);

@@ -25,7 +25,13 @@ def _ptr(a):
 
 class VecEngine(object):
     def __init__(self, game, ascii_map=None, num_envs=1, num_agents=1, view_len=K.VIEW_LEN, beam_len=K.BEAM_LEN,
-                 seed=0, env_index_base=0, device=0, keep_beams=False, color_map=None):
+                 seed=0, env_index_base=0, device=0, keep_beams=False, color_map=None, harvest_thresholds=None,
+                 cleanup_thresholds=None, library_tables=False):
+        """harvest_thresholds: uint64 [4], the spawn thresholds by min(#neighbour apples, 3) (a u32 draw succeeds when it is below
+        the threshold; 2^32 and above = always); cleanup_thresholds: (apple, waste), uint64 [potential_waste_area + 1] each, by
+        the number of 'H' cells.  None: the reference's constants, derived here.  library_tables=True passes NULL for the three
+        tables and the colour table -- the library derives them itself -- and excludes the other two and
+        color_map."""
         self.game = int(game)
         if ascii_map is None:
             ascii_map = K.HARVEST_MAP if self.game == K.GAME_HARVEST else K.CLEANUP_MAP
@@ -37,19 +43,30 @@ class VecEngine(object):
         self.keep_beams = bool(keep_beams)
         self.num_actions = 8 if self.game == K.GAME_HARVEST else 9     # harvest.py:44, cleanup.py:70
         self._lut = np.ascontiguousarray(cfgmod.make_lut(color_map))
-        self._thr_h = cfgmod.harvest_thresholds()
         self.potential_waste_area = cfgmod.potential_waste_area(self.ascii_map) if self.game == K.GAME_CLEANUP else 0
-        self._thr_ca, self._thr_cw = cfgmod.cleanup_thresholds(self.potential_waste_area)
+        self.library_tables = bool(library_tables)
+        if self.library_tables and (harvest_thresholds is not None or cleanup_thresholds is not None or color_map is not None):
+            raise ValueError("library_tables=True excludes harvest_thresholds, cleanup_thresholds and color_map")
+        self._thr_h = self._table(harvest_thresholds, 4, "harvest_thresholds") if harvest_thresholds is not None \
+            else cfgmod.harvest_thresholds()
+        if cleanup_thresholds is not None:
+            if not isinstance(cleanup_thresholds, (tuple, list)) or len(cleanup_thresholds) != 2:
+                raise ValueError("cleanup_thresholds must be a pair (apple thresholds, waste thresholds)")
+            self._thr_ca, self._thr_cw = (self._table(a, self.potential_waste_area + 1, "cleanup_thresholds[%d]" % i)
+                                          for i, a in enumerate(cleanup_thresholds))
+        else:
+            self._thr_ca, self._thr_cw = cfgmod.cleanup_thresholds(self.potential_waste_area)
         self._flat = flat
         c = _capi.SsdConfig()
         c.struct_size = C.sizeof(_capi.SsdConfig)
         c.game, c.height, c.width, c.base_map = self.game, self.H, self.W, flat
         c.num_envs, c.num_agents, c.view_len, c.beam_len = self.E, self.N, self.view_len, self.beam_len
         c.seed, c.env_index_base, c.device_id, c.keep_beams = self.seed, self.env_index_base, self.device, int(self.keep_beams)
-        c.color_lut = self._lut.ctypes.data
-        c.harvest_thresholds = self._thr_h.ctypes.data
-        c.cleanup_apple_thresholds = self._thr_ca.ctypes.data
-        c.cleanup_waste_thresholds = self._thr_cw.ctypes.data
+        if not self.library_tables:                  # (else NULL: the library's own derivation, ssd_create)
+            c.color_lut = self._lut.ctypes.data
+            c.harvest_thresholds = self._thr_h.ctypes.data
+            c.cleanup_apple_thresholds = self._thr_ca.ctypes.data
+            c.cleanup_waste_thresholds = self._thr_cw.ctypes.data
         self._h = C.c_void_p()
         L = _capi.lib()
         _capi.check(L.ssd_create(C.byref(c), C.byref(self._h)))
@@ -64,6 +81,13 @@ class VecEngine(object):
         self._scratch_bufs = {}                      # _scratch(): key -> (the buffer, its view of the shape last asked for)
         if L.ssd_potential_waste_area(self._h) != self.potential_waste_area:
             raise _capi.SsdError("potential_waste_area mismatch between host and library")
+
+    @staticmethod
+    def _table(a, n, name):
+        """A caller's threshold table: a uint64 array of n entries (checked here, before the library sees a pointer)."""
+        if not isinstance(a, np.ndarray) or a.dtype != np.uint64 or a.shape != (n,):
+            raise ValueError("%s must be a uint64 array of %d entries" % (name, n))
+        return np.ascontiguousarray(a).copy()
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:

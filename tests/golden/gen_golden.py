@@ -2,7 +2,8 @@
 """Generate the golden transition vectors in tests/golden/*.npz from the REFERENCE itself.
 
 Runs only in the build container (needs /root/reference); the fixtures it writes are
-committed, the reference is never copied.  Usage:  python tests/golden/gen_golden.py
+committed, the reference is never copied.  Usage:  python tests/golden/gen_golden.py          (every fixture)
+                                                   python tests/golden/gen_golden.py tables   (only the t??_*.npz below)
 
 How the reference is run
 ------------------------
@@ -27,7 +28,13 @@ actions, action order) -> (post-state, beam overlay, rewards, uint8 observation)
 `env.reset()` becomes a reset vector.  Scenarios are (i) the reference's own unit tests
 (tests/test_envs.py) restated as scripts, with their literal expectations asserted here,
 (ii) random-action rollouts on the shipped and synthetic maps, (iii) crowded small maps
-with random action subsets and orders (exercises the overlap quirk of map_env.py:480-483).
+with random action subsets and orders (exercises the overlap quirk of map_env.py:480-483),
+(iv) spawn-table scenarios (t??_*.npz): the reference's module constants -- harvest.SPAWN_PROB,
+cleanup.appleRespawnProbability / wasteSpawnProbability / thresholdDepletion / thresholdRestoration --
+rebound in the imported modules for the length of a scenario (the same way `np` / `random` are; the
+reference's files stay untouched), so that the spawn phase decides something at every step.  Such a
+fixture carries the probabilities it was recorded under and the threshold tables they make
+(tab_* arrays), which the replays hand to the oracle / the engine.
 """
 import os
 import sys
@@ -196,11 +203,11 @@ class Recorder(object):
     def __init__(self):
         self.groups = {}
 
-    def group(self, game, ascii_map, N, view_len, seed, env_index):
-        key = (game, tuple(ascii_map), N, view_len, seed, env_index)
+    def group(self, game, ascii_map, N, view_len, seed, env_index, tables=None):
+        key = (game, tuple(ascii_map), N, view_len, seed, env_index, tables["tag"] if tables else None)
         if key not in self.groups:
             self.groups[key] = dict(game=game, map=list(ascii_map), N=N, view_len=view_len, seed=seed,
-                                    env=env_index, steps=[], resets=[])
+                                    env=env_index, steps=[], resets=[], tables=tables)
         return self.groups[key]
 
 
@@ -210,8 +217,9 @@ REC = Recorder()
 class Driver(object):
     """Wraps one reference env; drives it under CTX and records what it does."""
 
-    def __init__(self, env, game, ascii_map, seed=0, env_index=0, view_len=7):
+    def __init__(self, env, game, ascii_map, seed=0, env_index=0, view_len=7, tables=None):
         self.env, self.game, self.map = env, game, list(ascii_map)
+        self.tables = tables                     # spawn-table scenarios: what the module constants were rebound to
         self.seed, self.env_index, self.view_len = seed, env_index, view_len
         self.episode = -1
         self.t = 0
@@ -240,7 +248,7 @@ class Driver(object):
             assert np.array_equal(obs, obs_to_u8(ret, ids, 15)), "re-rendered reset obs differ from reset()'s"
         if record:
             world, beam, pos, orient = snapshot(self.env)
-            g = REC.group(self.game, self.map, len(self.env.agents), self.view_len, self.seed, self.env_index)
+            g = REC.group(self.game, self.map, len(self.env.agents), self.view_len, self.seed, self.env_index, self.tables)
             g["resets"].append(dict(episode=self.episode, world=world, pos=pos, orient=orient, obs=obs))
 
     def _render(self, rotate):
@@ -279,7 +287,7 @@ class Driver(object):
                 order[k] = i
             world, beam, pos, orient = snapshot(env)
             V = 2 * self.view_len + 1
-            g = REC.group(self.game, self.map, N, self.view_len, self.seed, self.env_index)
+            g = REC.group(self.game, self.map, N, self.view_len, self.seed, self.env_index, self.tables)
             g["steps"].append(dict(episode=max(self.episode, 0), t=self.t, act=act, order=order,
                                    pre_world=pre[0], pre_pos=pre[2], pre_orient=pre[3],
                                    world=world, beam=beam, pos=pos, orient=orient,
@@ -631,14 +639,129 @@ def scen_crowded(ref):
 
 
 # ----------------------------------------------------------------------------------------
+# spawn-table scenarios
+# ----------------------------------------------------------------------------------------
+TABLE_HARVEST_MAP = ['@@@@@@@@@@@@', '@P AAAAAA P@', '@ AAAAAAAA @', '@ AAAAAAAA @', '@ AAAAAAAA @', '@ AAAAAAAA @',
+                     '@P AAAAAA P@', '@@@@@@@@@@@@']
+
+
+def harvest_tables(tag, probs):
+    return dict(tag=tag, harvest_p=np.array(probs, dtype=np.float64),
+                harvest=np.array([prng.threshold(p) for p in probs], dtype=np.uint64))
+
+
+def cleanup_tables(tag, potential, apple_p, waste_p, depletion, restoration):
+    """The thresholds by waste count that compute_probabilities (cleanup.py:156-171) makes of the four constants: the same
+    float operations in the same order (what config.cleanup_probabilities does for the constants as shipped).  Every recorded
+    step checks the reference's own current_*_spawn_prob against its row (table_step)."""
+    ta, tw = np.zeros(potential + 1, np.uint64), np.zeros(potential + 1, np.uint64)
+    for n in range(potential + 1):
+        density = 0
+        if potential > 0:
+            density = 1 - (potential - n) / potential
+        if density >= depletion:
+            pa, pw = 0, 0
+        elif density <= restoration:
+            pa, pw = apple_p, waste_p
+        else:
+            pa, pw = (1 - (density - restoration) / (depletion - restoration)) * apple_p, waste_p
+        ta[n], tw[n] = prng.threshold(pa), prng.threshold(pw)
+    return dict(tag=tag, cleanup_consts=np.array([apple_p, waste_p, depletion, restoration], dtype=np.float64),
+                cleanup_apple=ta, cleanup_waste=tw)
+
+
+def table_step(d, actions):
+    """One recorded step of a Cleanup table scenario.  The reference's own probabilities, at the waste count its
+    compute_probabilities (cleanup.py:156-171) saw, must be the table's row for that count."""
+    env, t = d.env, d.tables
+    seen = []
+    orig = type(env).compute_probabilities
+
+    def spy():
+        orig(env)
+        seen.append((env.potential_waste_area - env.compute_permitted_area(), env.current_apple_spawn_prob,
+                     env.current_waste_spawn_prob))
+    env.compute_probabilities = spy              # (an attribute of this instance; the class and its file stay as they are)
+    try:
+        d.step(actions)
+    finally:
+        del env.compute_probabilities
+    assert len(seen) == 1, seen
+    n, pa, pw = seen[0]
+    assert int(t["cleanup_apple"][n]) == prng.threshold(pa) and int(t["cleanup_waste"][n]) == prng.threshold(pw), seen
+    return n
+
+
+def scen_tables(ref):
+    _, harvest, cleanup, _ = ref
+    saved = (harvest.SPAWN_PROB, cleanup.appleRespawnProbability, cleanup.wasteSpawnProbability,
+             cleanup.thresholdDepletion, cleanup.thresholdRestoration)
+    try:
+        # Harvest: count-decided (1/64, 1, 0, 1) and draw-decided dense (0.25, 0.5, 0.75, 1) tables, on a small synthetic map
+        # and on the shipped 16 x 38 map from a partly emptied world
+        for ti, (tag, probs) in enumerate((("count", [1.0 / 64, 1.0, 0.0, 1.0]), ("dense", [0.25, 0.5, 0.75, 1.0]))):
+            harvest.SPAWN_PROB = list(probs)
+            tabs = harvest_tables(tag, probs)
+            for mi, (amap, n, v, steps, keep) in enumerate(((TABLE_HARVEST_MAP, 3, 2, 120, 4), (K.HARVEST_MAP, 5, 7, 60, 3))):
+                seed = 301 + 2 * ti + mi
+                CTX.W = len(amap[0])
+                d = Driver(harvest.HarvestEnv(amap, num_agents=n), 0, amap, seed=seed, env_index=mi, view_len=v, tables=tabs)
+                d.reset()
+                # partly emptied: every apple whose draw is not below 1 / keep leaves the reset world
+                for k, (r, c) in enumerate(d.env.apple_points):
+                    if prng.randint(prng.draw(seed * 31 + 7, k), keep) != 0:
+                        d.env.world_map[r, c] = ' '
+                for s in range(steps):
+                    d.step(random_actions(d, 8))
+                    if s == steps // 2:
+                        d.reset()
+        harvest.SPAWN_PROB = saved[0]
+        # Cleanup: (a) apples 0.5, waste 1.0, depletion raised to 1.0 -- every count below "all waste" spawns; (b) waste 0
+        for ti, (tag, consts) in enumerate((("allspawn", (0.5, 1.0, 1.0, 0.0)), ("nowaste", (0.05, 0.0, 0.4, 0.0)))):
+            (cleanup.appleRespawnProbability, cleanup.wasteSpawnProbability, cleanup.thresholdDepletion,
+             cleanup.thresholdRestoration) = consts
+            amap, n, seed = K.CLEANUP_MAP, 5, 311 + ti
+            tabs = cleanup_tables(tag, sum(r.count('H') + r.count('R') for r in amap), *consts)
+            CTX.W = len(amap[0])
+            d = Driver(cleanup.CleanupEnv(amap, num_agents=n), 1, amap, seed=seed, env_index=ti, view_len=7, tables=tabs)
+            d.reset()
+            assert d.env.potential_waste_area + 1 == len(tabs["cleanup_apple"])
+            if tag == "nowaste":                 # from half the waste: below the depletion threshold, where apples grow
+                for k, (r, c) in enumerate(d.env.waste_points):
+                    if d.env.world_map[r, c] == 'H' and k % 2:
+                        d.env.world_map[r, c] = 'R'
+            counts = set()
+            for s in range(60):
+                a = random_actions(d, 9)         # two in three actions CLEAN: the count moves in both directions (a), falls (b)
+                a = {k: (8 if prng.draw(seed, d.t * 16 + i) % 3 else x) for i, (k, x) in enumerate(a.items())}
+                counts.add(table_step(d, a))
+                if s == 40:
+                    d.reset()
+            print("  cleanup %s: waste counts used %s" % (tag, sorted(int(x) for x in counts)))
+    finally:
+        (harvest.SPAWN_PROB, cleanup.appleRespawnProbability, cleanup.wasteSpawnProbability,
+         cleanup.thresholdDepletion, cleanup.thresholdRestoration) = saved
+
+
+# ----------------------------------------------------------------------------------------
 def write_fixtures():
     os.makedirs(HERE, exist_ok=True)
     index = []
-    for gi, g in enumerate(REC.groups.values()):
-        name = "g%02d_%s_%dx%d_n%d_v%d" % (gi, "harvest" if g["game"] == 0 else "cleanup", len(g["map"]),
-                                            len(g["map"][0]), g["N"], g["view_len"])
+    gi = ti = 0
+    for g in REC.groups.values():
+        shape = "%s_%dx%d_n%d_v%d" % ("harvest" if g["game"] == 0 else "cleanup", len(g["map"]), len(g["map"][0]), g["N"],
+                                      g["view_len"])
         out = dict(game=np.int32(g["game"]), map=np.array(g["map"]), N=np.int32(g["N"]),
                    view_len=np.int32(g["view_len"]), seed=np.uint64(g["seed"]), env=np.uint32(g["env"]))
+        if g["tables"]:                          # the fixtures of the default constants keep their numbering
+            name = "t%02d_%s_%s" % (ti, shape, g["tables"]["tag"])
+            ti += 1
+            for k, v in g["tables"].items():
+                if k != "tag":
+                    out["tab_" + k] = v
+        else:
+            name = "g%02d_%s" % (gi, shape)
+            gi += 1
         st, rs = g["steps"], g["resets"]
         if st:
             for k in st[0]:
@@ -656,7 +779,8 @@ def write_fixtures():
 
 def main():
     ref = import_reference()
-    for f in (scen_map_env, scen_harvest, scen_cleanup, scen_rollouts, scen_crowded):
+    only_tables = sys.argv[1:] == ["tables"]
+    for f in ((scen_tables,) if only_tables else (scen_map_env, scen_harvest, scen_cleanup, scen_rollouts, scen_crowded, scen_tables)):
         print(f.__name__)
         f(ref)
     write_fixtures()

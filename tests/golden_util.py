@@ -31,6 +31,18 @@ class Group(object):
         self.resets = {k[2:]: z[k] for k in z.files if k.startswith("r_")}
         self.n_steps = len(self.steps["t"]) if self.steps else 0
         self.n_resets = len(self.resets["episode"]) if self.resets else 0
+        # spawn-table fixtures (t??_*.npz): the probabilities the reference's constants were rebound to and their thresholds
+        self.tables = {k[4:]: z[k] for k in z.files if k.startswith("tab_")}
+
+    @property
+    def harvest_thresholds(self):
+        """uint64 [4] or None (the reference's constants)."""
+        return self.tables.get("harvest")
+
+    @property
+    def cleanup_thresholds(self):
+        """(apple, waste) uint64 [potential_waste_area + 1] each, or None."""
+        return (self.tables["cleanup_apple"], self.tables["cleanup_waste"]) if "cleanup_apple" in self.tables else None
 
 
 def groups():

@@ -16,7 +16,8 @@ pytestmark = pytest.mark.gpu
 def test_hip_replays_reference_transitions(name):
     g = G.load(name)
     eng = VecEngine(g.game, g.map, num_envs=1, num_agents=g.N, view_len=g.view_len, seed=g.seed,
-                    env_index_base=g.env, keep_beams=True)
+                    env_index_base=g.env, keep_beams=True, harvest_thresholds=g.harvest_thresholds,
+                    cleanup_thresholds=g.cleanup_thresholds)     # (None but for the spawn-table fixtures, which carry theirs)
     s = g.steps
     zero_beam = np.zeros((1, eng.H, eng.W), np.int8)
     for k in range(g.n_steps):

@@ -4,7 +4,11 @@ env counts, stepped five ways -- call by call with random action subsets / order
 fused rollout kernel, ssd_rollout_actions (caller-supplied action and order rings; chains and fused), and with SSD_AUTO_RESET --
 against the C oracle, bit for bit.  First line: the library that ran and the SSD_* settings (tools/_label.py).
 
-    python tools/fuzz_parity.py [n_configs] [seed]"""
+    python tools/fuzz_parity.py [n_configs] [seed]
+
+FUZZ_TABLES=1: every configuration also gets random spawn tables (ssd_config's harvest / cleanup thresholds: zeros, 2^32 and
+above, and draw-decided entries), handed to the engine and to the oracle's setter.  They are drawn from the configuration's
+second generator, before its action rings: what `draw` consumes -- and so configuration k of a seed -- stays what it was."""
 import os
 import sys
 
@@ -74,10 +78,24 @@ def draw(rng, idx, fixed=None):
     return c
 
 
+def random_table(rng2, n):
+    """n thresholds: a quarter never, a quarter always (2^32, or wider: up to 2^63), the rest decided by the draw."""
+    kind = rng2.randint(0, 4, size=n)
+    t = rng2.randint(0, 2 ** 32, size=n, dtype=np.uint64)
+    t[kind == 0] = 0
+    t[kind == 1] = np.uint64(1) << rng2.randint(32, 64, size=int((kind == 1).sum())).astype(np.uint64)
+    return t
+
+
 def run(c, quiet=False):
     game, N, v, L, E, amap, keep, seed, tag = c["game"], c["N"], c["v"], c["L"], c["E"], c["amap"], c["keep"], c["seed"], c["tag"]
+    rng2 = np.random.RandomState((seed ^ 0x5A5A5A) & 0x7FFFFFFF)     # the configuration's second generator (tables, action rings)
+    tables = {}
+    if os.environ.get("FUZZ_TABLES") == "1":
+        n_thr = sum(r.count("H") + r.count("R") for r in amap) + 1 if game == K.GAME_CLEANUP else 1
+        tables = dict(harvest_thresholds=random_table(rng2, 4), cleanup_thresholds=(random_table(rng2, n_thr), random_table(rng2, n_thr)))
     try:
-        eng = VecEngine(game, amap, num_envs=E, num_agents=N, view_len=v, beam_len=L, seed=seed, keep_beams=keep)
+        eng = VecEngine(game, amap, num_envs=E, num_agents=N, view_len=v, beam_len=L, seed=seed, keep_beams=keep, **tables)
     except Exception as ex:                                   # e.g. LDS budget: not a parity matter
         if not c["too_big"]:
             raise
@@ -86,6 +104,8 @@ def run(c, quiet=False):
         return
     assert not c["too_big"], tag
     ora = pyoracle.Oracle(game, amap, E, N, G.default_lut(), view_len=v, beam_len=L, seed=seed)
+    if tables:
+        ora.set_tables(harvest=tables["harvest_thresholds"], cleanup=tables["cleanup_thresholds"])
     V = 2 * v + 1
     assert np.array_equal(eng.reset_host(), ora.reset()), tag + " reset"
     # (1) call by call, explicit subsets / orders every other step
@@ -121,8 +141,7 @@ def run(c, quiet=False):
         check_state(eng, ora, tag + " after rollout fused=%d" % fused)
         step0 += n
     # (3b) ssd_rollout_actions: caller-supplied actions, and every other call the action dicts' orders (a generator of its own, keyed
-    #      by the configuration's seed: what `draw` consumes stays what it always was)
-    rng2 = np.random.RandomState((seed ^ 0x5A5A5A) & 0x7FFFFFFF)
+    #      by the configuration's seed -- rng2, above: what `draw` consumes stays what it always was)
     na = 8 if game == K.GAME_HARVEST else 9
     for call, fused in enumerate((False, True, False, True)):
         n2, aring = int(rng2.randint(1, 8)), int(rng2.randint(1, 6))
