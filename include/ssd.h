@@ -939,6 +939,69 @@ int ssd_policy_moa_ppo_grad(const float *weights, int32_t num_sets, int32_t num_
                             double entropy_coeff, double kl_coeff, double moa_weight, float *scratch, float *grads,
                             double *stats, int32_t device_id, uint32_t flags, void *stream);
 
+/* ======================================================================================================================
+ * A3C LOSS AND GRADIENTS -- the learner's half of the loop under the baseline's default algorithm (run_scripts/
+ * train_baseline.py:23; algorithms/a3c_causal.py:28-46 and :60-76) for the three policies: ssd_policy_ac_grad (conv-FC),
+ * ssd_policy_lstm_ac_grad (recurrent) and ssd_policy_moa_ac_grad (MOA), `ac` for the actor-critic loss.  Each is the PPO call
+ * of the same policy above with another row loss and another last step: the same kernels compiled with the A3C row terms,
+ * the same host code (csrc/ssd_policy_grad.hip, ssd_policy_lstm_grad.hip, ssd_policy_moa_grad.hip).
+ * Added after ABI 6 without a version bump: the calls are additive.  advantages and value_targets are what ssd_advantages
+ * returns with use_gae = 0 (discounted returns), or any other.
+ *
+ * Networks, rows, the observation shift, the state rule, prev_actions, windows of seq_len and the minibatch slices: exactly
+ * those of PPO LOSS AND GRADIENTS, RECURRENT PPO LOSS AND GRADIENTS and MOA PPO LOSS AND GRADIENTS, for the matching call.
+ * logp_old, vf_preds and behaviour_logits are not inputs, and there are no clip or KL hyper-parameters.
+ *
+ * Loss.  Per row, with (logits, value) the network's outputs, a = actions[row] clamped to 0 .. A - 1:
+ *   logp = log_softmax(logits)[a]        pi  = -logp * adv
+ *   vf   = 0.5 * (value - vt)^2          ent = the entropy of softmax(logits)
+ *   row_loss = (pi + vf_loss_coeff * vf) - entropy_coeff * ent
+ *   d row_loss / d logits[k] = -adv * ([k = a] - p_k) + entropy_coeff * p_k * (logp_k + ent)
+ *   d row_loss / d value     = vf_loss_coeff * (value - vt)
+ * loss_p is the SUM of row_loss over set p's rows (the reference reduces with reduce_sum), and the call's scalar is the sum
+ * of loss_p over the sets.  The loss has no clip kinks; ReLU's derivative at 0 is 0.
+ *
+ * The MOA policy (a3c_causal.py:70-71): total += moa_weight * MOALoss, and MOALoss is a MEAN (common_funcs.py:96) while the
+ * A3C terms are sums.  So the MOA term of row (k, e, i) is the cross-entropy term of MOA PPO LOSS AND GRADIENTS (the same
+ * pairing, the same string-sorted others, the same clamped targets, visibility 1) times 1 / (the set's rows):
+ *   row_loss + moa_weight * (1 / (N - 1)) * (1 / rows) * sum over j of CE(pred[j], actions[k, e, others(i)[j]]).
+ * The three factors are one float32 scale on d loss / d pred, formed in double as moa_weight / ((N - 1) * rows) and rounded
+ * once: the conv's gradient adds both branches into one slot before the reduction, so the factor cannot wait for it.
+ *
+ * Arithmetic and order.  Exact float32, the row terms in float64 sums, and every sum in exactly the matching PPO call's
+ * order: the same tiles, groups, chunks and splits.  The one difference is the last step: the float64 total of an entry is
+ * rounded to float32 as it is, without the division by the set's rows.  No atomics: the same inputs give the same bits.
+ *
+ * Outputs.  grads in the policy's packed layout, padding floats zero.  stats f64 [P][4] for ssd_policy_ac_grad and
+ * ssd_policy_lstm_ac_grad: the set SUMS of row_loss, pi, vf and ent (the reference's total_loss, policy_loss, vf_loss and
+ * policy_entropy; the explained variance stays out).  stats f64 [P][5] for ssd_policy_moa_ac_grad: those four, total_loss
+ * including moa_weight * moa_loss, then moa_loss, the mean cross-entropy over rows and other agents without the weight (the
+ * one statistic that is divided by the set's rows).
+ *
+ * scratch: SSD_PPO_SCRATCH_FLOATS, SSD_RPPO_SCRATCH_FLOATS and SSD_MPPO_SCRATCH_FLOATS of the same shape, for the matching
+ * call; one buffer serves a policy's PPO and A3C calls.
+ *
+ * SSD_E_INVALID before anything is launched (ssd_policy_last_error says why) for everything the matching PPO call refuses,
+ * less the arguments that are gone: the required per-row pointers are actions, advantages and value_targets, the
+ * hyper-parameters that must be finite are vf_loss_coeff and entropy_coeff (and moa_weight, finite and >= 0), flags other
+ * than 0.
+ * ====================================================================================================================== */
+int ssd_policy_ac_grad(const float *weights, int32_t num_sets, int32_t num_actions, const uint8_t *obs_first, const uint8_t *obs,
+                       const int32_t *actions, const float *advantages, const float *value_targets, int32_t n_steps,
+                       int32_t num_envs, int32_t num_agents, double vf_loss_coeff, double entropy_coeff, float *scratch,
+                       float *grads, double *stats, int32_t device_id, uint32_t flags, void *stream);
+int ssd_policy_lstm_ac_grad(const float *weights, int32_t num_sets, int32_t num_actions, int32_t cell_size, int32_t seq_len,
+                            const uint8_t *obs_first, const uint8_t *obs, const float *state, const uint8_t *done,
+                            const int32_t *actions, const float *advantages, const float *value_targets, int32_t n_steps,
+                            int32_t num_envs, int32_t num_agents, double vf_loss_coeff, double entropy_coeff, float *scratch,
+                            float *grads, double *stats, int32_t device_id, uint32_t flags, void *stream);
+int ssd_policy_moa_ac_grad(const float *weights, int32_t num_sets, int32_t num_actions, int32_t cell_size, int32_t seq_len,
+                           const uint8_t *obs_first, const uint8_t *obs, const float *state, const int32_t *prev_actions,
+                           const uint8_t *done, const int32_t *actions, const float *advantages, const float *value_targets,
+                           int32_t n_steps, int32_t num_envs, int32_t num_agents, double vf_loss_coeff, double entropy_coeff,
+                           double moa_weight, float *scratch, float *grads, double *stats, int32_t device_id, uint32_t flags,
+                           void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,8 @@
     from sequential_social_dilemma_games_amd import ppo_loss                    # the PPO loss and its gradients, on the device
     from sequential_social_dilemma_games_amd import ppo_loss_recurrent          # the same for the recurrent policy, with BPTT
     from sequential_social_dilemma_games_amd import ppo_loss_moa                # PPO + MOA loss for the MOA policy, with BPTT
+    from sequential_social_dilemma_games_amd import a3c_loss, a3c_loss_recurrent, a3c_loss_moa   # the A3C loss, likewise
+    from sequential_social_dilemma_games_amd import clip_grad_by_set_norm       # A3C's gradient clip, per weight set
 
 Everything that steps an env goes through libssd_hip.so (include/ssd.h); importing this package does
 not load it, constructing an env does -- and fails loudly if it is missing.
@@ -36,7 +38,8 @@ def __getattr__(name):
         from .episode_stats import EpisodeStats
         return EpisodeStats
     if name in ("ConvFCPolicy", "ConvLSTMPolicy", "ConvMOAPolicy", "WatershedLSTMPolicy", "ppo_loss", "ppo_loss_recurrent",
-                "ppo_loss_moa"):
+                "ppo_loss_moa", "a3c_loss", "a3c_loss_recurrent", "a3c_loss_moa", "clip_grad_by_set_norm", "A3C_STATS",
+                "MOA_A3C_STATS"):
         from . import policy
         return getattr(policy, name)
     if name == "compute_advantages":

@@ -188,7 +188,8 @@ __device__ __forceinline__ void heads(const Args &a, const float *s_h, int pitch
 // The loss terms of one row (include/ssd.h, PPO LOSS AND GRADIENTS), one thread per row: l = the row's logits 0..A-1 and its
 // value at A, act its action (already within 0 .. A-1), bl its behaviour logits or null.  The five terms are float32 and are
 // added to st (total, policy, vf, kl, entropy); d[0..A] receives d row_loss / d (logits, value) with the contract's derivatives
-// at the kinks.  Used by the PPO gradient kernels of both policies (ssd_policy_grad.hip, ssd_policy_lstm_grad.hip).
+// at the kinks.  Used by the PPO gradient kernels of the three policies (ssd_policy_grad.hip, ssd_policy_lstm_grad.hip,
+// ssd_policy_moa_grad.hip).
 struct PpoHyper {
     float clip, vf_clip, vf_coeff, ent_coeff, kl_coeff;
 };
@@ -240,6 +241,39 @@ __device__ __forceinline__ void ppo_row(const float *l, float *d, int A, int act
         d[k] = dk;
     }
     d[A] = a.vf_coeff * dvf;
+}
+
+// ------------------------------------------------------------------------------------------------------------ the A3C loss
+// Which loss a gradient kernel forms per row: a compile-time parameter of the kernels that call ppo_row, so that the PPO
+// instantiations keep their instruction text.
+constexpr int kLossPpo = 0, kLossAc = 1;
+
+// The A3C terms of one row (include/ssd.h, A3C LOSS AND GRADIENTS), as ppo_row: l, d, act, st as there; only vf_coeff and
+// ent_coeff of the hyper-parameters are read.  st receives total, policy, vf, entropy in 0..3 (st[4] is left alone).  No kinks.
+__device__ __forceinline__ void a3c_row(const float *l, float *d, int A, int act, float adv, float vt, const PpoHyper &a,
+                                        double (&st)[5]) {
+    const float value = l[A];
+    float mx = l[0];
+    for (int k = 1; k < A; ++k) mx = fmaxf(mx, l[k]);
+    float s = 0.f;
+    for (int k = 0; k < A; ++k) s += expf(l[k] - mx);
+    const float lse = mx + logf(s);
+    float ent = 0.f;
+    for (int k = 0; k < A; ++k) {
+        const float lp = l[k] - lse;
+        ent -= expf(lp) * lp;
+    }
+    const float logp = l[act] - lse;
+    const float pi = -(logp * adv);
+    const float d1 = value - vt;
+    const float vf = 0.5f * (d1 * d1);
+    const float row_loss = (pi + a.vf_coeff * vf) - a.ent_coeff * ent;
+    st[0] += (double)row_loss; st[1] += (double)pi; st[2] += (double)vf; st[3] += (double)ent;
+    for (int k = 0; k < A; ++k) {
+        const float lp = l[k] - lse, pk = expf(lp);
+        d[k] = -adv * ((k == act ? 1.f : 0.f) - pk) + a.ent_coeff * (pk * (lp + ent));
+    }
+    d[A] = a.vf_coeff * d1;
 }
 
 // -------------------------------------------------------------------------------------------------------------- the action

@@ -20,6 +20,10 @@
 // bits.  The kernel's second instantiation is the trunk's backward alone, from a given d loss / d fc2's output: what the
 // recurrent policy's call (ssd_policy_lstm_grad.hip) runs below its cell.  The third is that backward for one tanh FC stack of
 // the MOA policy (ssd_policy_moa_grad.hip), launched once per stack.
+//
+// ssd_policy_ac_grad is the same call with the A3C row loss (include/ssd.h, A3C LOSS AND GRADIENTS): the
+// loss kernel and the reduce compiled once more with ssd::kLossAc -- a3c_row for ppo_row, and the float64 totals rounded as they
+// are, without the division by the rows -- from the same host code.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -48,7 +52,9 @@ using GradArgs = ssd::PpoGradArgs;
 // left in the same slot (the same workgroup, after it on the stream): the order is fixed.
 constexpr int kModeLoss = 0, kModeFromDx = 1, kModeMoaStack = 2;
 
-template <int kMode>
+// kLoss (kModeLoss only): the row loss of step 2, ssd::kLossPpo or ssd::kLossAc (the A3C terms: a3c_row in ppo_row's place, four
+// statistics).  Everything else is the same code.
+template <int kMode, int kLoss = ssd::kLossPpo>
 __global__ void __launch_bounds__(kThreads) ssd_ppo_grad_kernel(GradArgs a) {
     constexpr bool kFromDx = kMode != kModeLoss, kTanh = kMode == kModeMoaStack;
     constexpr int kDxPitch = kTanh ? 64 : 32;
@@ -131,8 +137,12 @@ __global__ void __launch_bounds__(kThreads) ssd_ppo_grad_kernel(GradArgs a) {
             const size_t row = (size_t)(r0 + tid) * stride + p;
             int act = a.actions[row];
             act = act < 0 ? 0 : (act >= A ? A - 1 : act);
-            ssd::ppo_row(s_out + tid * 16, s_dout + tid * 16, A, act, a.adv[row], a.vt[row], a.vf_pred[row], a.logp_old[row],
-                         a.beh ? a.beh + row * A : nullptr, ssd::PpoHyper{a.clip, a.vf_clip, a.vf_coeff, a.ent_coeff, a.kl_coeff}, st);
+            const ssd::PpoHyper hyper{a.clip, a.vf_clip, a.vf_coeff, a.ent_coeff, a.kl_coeff};
+            if constexpr (kLoss == ssd::kLossAc)
+                ssd::a3c_row(s_out + tid * 16, s_dout + tid * 16, A, act, a.adv[row], a.vt[row], hyper, st);
+            else
+                ssd::ppo_row(s_out + tid * 16, s_dout + tid * 16, A, act, a.adv[row], a.vt[row], a.vf_pred[row], a.logp_old[row],
+                             a.beh ? a.beh + row * A : nullptr, hyper, st);
         }
         __syncthreads();
 
@@ -319,7 +329,11 @@ __global__ void __launch_bounds__(kThreads) ssd_ppo_grad_kernel(GradArgs a) {
 }
 
 // The G partials of a set added in order g = 0 .. G - 1 in float64, times 1 / rows, rounded once; the padding floats are zero.
+// kLossAc: the sums as they are (the A3C loss is a sum over rows), and the four statistics of a3c_row to stats [P][4].
+template <int kLoss>
 __global__ void __launch_bounds__(256) ssd_ppo_reduce_kernel(GradArgs a) {
+    constexpr bool kSum = kLoss == ssd::kLossAc;
+    constexpr int kStats = kSum ? 4 : 5;
     const int idx = blockIdx.x * 256 + threadIdx.x, p = blockIdx.y, S = a.set_floats;
     const size_t pitch = (size_t)S + kStatFloats;
     const float *part = a.scratch + (size_t)p * a.G * pitch;
@@ -328,12 +342,12 @@ __global__ void __launch_bounds__(256) ssd_ppo_reduce_kernel(GradArgs a) {
         double sum = 0.0;
         if (!pad)
             for (int g = 0; g < a.G; ++g) sum += (double)part[g * pitch + idx];
-        a.grads[(size_t)p * S + idx] = (float)(sum / (double)a.set_rows);
+        a.grads[(size_t)p * S + idx] = kSum ? (float)sum : (float)(sum / (double)a.set_rows);
     }
-    if (blockIdx.x == 0 && threadIdx.x < 5) {
+    if (blockIdx.x == 0 && threadIdx.x < kStats) {
         double sum = 0.0;
         for (int g = 0; g < a.G; ++g) sum += reinterpret_cast<const double *>(part + g * pitch + S)[threadIdx.x];
-        a.stats[p * 5 + threadIdx.x] = sum / (double)a.set_rows;
+        a.stats[p * kStats + threadIdx.x] = kSum ? sum : sum / (double)a.set_rows;
     }
 }
 
@@ -353,20 +367,25 @@ hipError_t launch_ppo_moa_stack_grad(const PpoGradArgs &a, void *stream) {
 
 }  // namespace ssd
 
-extern "C" int ssd_policy_ppo_grad(const float *weights, int32_t num_sets, int32_t num_actions, const uint8_t *obs_first,
-                                   const uint8_t *obs, const int32_t *actions, const float *logp_old, const float *advantages,
-                                   const float *value_targets, const float *vf_preds, const float *behaviour_logits, int32_t n_steps,
-                                   int32_t num_envs, int32_t num_agents, double clip_param, double vf_clip_param,
-                                   double vf_loss_coeff, double entropy_coeff, double kl_coeff, float *scratch, float *grads,
-                                   double *stats, int32_t device_id, uint32_t flags, void *stream) {
+namespace {
+
+// Both entry points below: the checks and the two launches, with the row loss `loss` (the A3C call passes no logp_old, vf_preds
+// or behaviour_logits and zeros for the hyper-parameters it does not have, which pass their checks).
+int conv_fc_grad(int loss, const float *weights, int32_t num_sets, int32_t num_actions, const uint8_t *obs_first, const uint8_t *obs,
+                 const int32_t *actions, const float *logp_old, const float *advantages, const float *value_targets,
+                 const float *vf_preds, const float *behaviour_logits, int32_t n_steps, int32_t num_envs, int32_t num_agents,
+                 double clip_param, double vf_clip_param, double vf_loss_coeff, double entropy_coeff, double kl_coeff,
+                 float *scratch, float *grads, double *stats, int32_t device_id, uint32_t flags, void *stream) {
     using ssd::policy_fail;
+    const bool ac = loss == ssd::kLossAc;
     if (!weights) return policy_fail("weights are required");
     if (const char *why = ssd::check_policy_net(ssd::kNetConvFc, weights, num_sets, num_agents, num_actions)) return policy_fail(why);
     if (n_steps < 1 || num_envs < 1) return policy_fail("n_steps and num_envs must be >= 1");
     const int64_t rows = (int64_t)n_steps * num_envs * num_agents;
     if (rows > INT32_MAX - 16) return policy_fail("n_steps * num_envs * num_agents must be at most 2^31 - 17");   // (row + 15 is an int)
     if (!obs && !(obs_first && n_steps == 1)) return policy_fail("obs is required (it may be null only with obs_first and n_steps 1)");
-    if (!actions || !logp_old || !advantages || !value_targets || !vf_preds)
+    if (ac && (!actions || !advantages || !value_targets)) return policy_fail("actions, advantages and value_targets are required");
+    if (!ac && (!actions || !logp_old || !advantages || !value_targets || !vf_preds))
         return policy_fail("actions, logp_old, advantages, value_targets and vf_preds are required");
     if (!scratch || !grads || !stats) return policy_fail("scratch, grads and stats are required");
     if ((reinterpret_cast<uintptr_t>(scratch) & 7u) || (reinterpret_cast<uintptr_t>(stats) & 7u))
@@ -389,9 +408,34 @@ extern "C" int ssd_policy_ppo_grad(const float *weights, int32_t num_sets, int32
     a.clip = (float)clip_param; a.vf_clip = (float)vf_clip_param; a.vf_coeff = (float)vf_loss_coeff;
     a.ent_coeff = (float)entropy_coeff; a.kl_coeff = (float)kl_coeff;
     a.scratch = scratch; a.grads = grads; a.stats = stats;
-    hipLaunchKernelGGL(ssd_ppo_grad_kernel<kModeLoss>, dim3((unsigned)a.G, (unsigned)a.P), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+    const dim3 grid((unsigned)a.G, (unsigned)a.P), reduce_grid((unsigned)((a.set_floats + 255) / 256), (unsigned)a.P);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (ac) hipLaunchKernelGGL((ssd_ppo_grad_kernel<kModeLoss, ssd::kLossAc>), grid, dim3(kThreads), 0, s, a);
+    else hipLaunchKernelGGL((ssd_ppo_grad_kernel<kModeLoss, ssd::kLossPpo>), grid, dim3(kThreads), 0, s, a);
     if (const hipError_t e = hipGetLastError()) return ssd::policy_launched(e);
-    hipLaunchKernelGGL(ssd_ppo_reduce_kernel, dim3((unsigned)((a.set_floats + 255) / 256), (unsigned)a.P), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), a);
+    if (ac) hipLaunchKernelGGL(ssd_ppo_reduce_kernel<ssd::kLossAc>, reduce_grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(ssd_ppo_reduce_kernel<ssd::kLossPpo>, reduce_grid, dim3(256), 0, s, a);
     return ssd::policy_launched(hipGetLastError());
+}
+
+}  // namespace
+
+extern "C" int ssd_policy_ppo_grad(const float *weights, int32_t num_sets, int32_t num_actions, const uint8_t *obs_first,
+                                   const uint8_t *obs, const int32_t *actions, const float *logp_old, const float *advantages,
+                                   const float *value_targets, const float *vf_preds, const float *behaviour_logits, int32_t n_steps,
+                                   int32_t num_envs, int32_t num_agents, double clip_param, double vf_clip_param,
+                                   double vf_loss_coeff, double entropy_coeff, double kl_coeff, float *scratch, float *grads,
+                                   double *stats, int32_t device_id, uint32_t flags, void *stream) {
+    return conv_fc_grad(ssd::kLossPpo, weights, num_sets, num_actions, obs_first, obs, actions, logp_old, advantages, value_targets,
+                        vf_preds, behaviour_logits, n_steps, num_envs, num_agents, clip_param, vf_clip_param, vf_loss_coeff,
+                        entropy_coeff, kl_coeff, scratch, grads, stats, device_id, flags, stream);
+}
+
+extern "C" int ssd_policy_ac_grad(const float *weights, int32_t num_sets, int32_t num_actions, const uint8_t *obs_first,
+                                  const uint8_t *obs, const int32_t *actions, const float *advantages, const float *value_targets,
+                                  int32_t n_steps, int32_t num_envs, int32_t num_agents, double vf_loss_coeff, double entropy_coeff,
+                                  float *scratch, float *grads, double *stats, int32_t device_id, uint32_t flags, void *stream) {
+    return conv_fc_grad(ssd::kLossAc, weights, num_sets, num_actions, obs_first, obs, actions, nullptr, advantages, value_targets,
+                        nullptr, nullptr, n_steps, num_envs, num_agents, 0.0, 0.0, vf_loss_coeff, entropy_coeff, 0.0, scratch,
+                        grads, stats, device_id, flags, stream);
 }

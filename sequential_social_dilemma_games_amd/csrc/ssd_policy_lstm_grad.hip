@@ -20,6 +20,9 @@
 // Every kernel adds its partial sums to what scratch holds from the windows before (the first window stores).  At the end
 // ssd_lstm_reduce_kernel adds the partials of every entry in order in float64, scales by 1 / set rows and rounds once.  No
 // atomics anywhere: the same inputs give the same bits.
+//
+// ssd_policy_lstm_ac_grad is the same walk with the A3C row loss (include/ssd.h, A3C LOSS AND GRADIENTS):
+// the sequence kernel and the reduce compiled once more with ssd::kLossAc (a3c_row for ppo_row; no division by the rows).
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -75,7 +78,8 @@ __global__ void __launch_bounds__(256) ssd_lstm_transpose_kernel(const float *w,
 }
 
 // ------------------------------------------------------------------------------------------------- the sequence kernel
-template <int C>
+// kLoss: the row loss, ssd::kLossPpo (ppo_row) or ssd::kLossAc (a3c_row: the A3C terms, four statistics).
+template <int C, int kLoss = ssd::kLossPpo>
 __global__ void __launch_bounds__(4 * C) ssd_lstm_seq_kernel(WinArgs a) {
     constexpr int kThreads = 4 * C;
     constexpr int kK = kX + C;          // rows of lstm_w
@@ -157,8 +161,11 @@ __global__ void __launch_bounds__(4 * C) ssd_lstm_seq_kernel(WinArgs a) {
                 float d[16];
 #pragma unroll
                 for (int j = 0; j < 16; ++j) d[j] = 0.f;
-                ssd::ppo_row(s_out + tid * 16, d, A, act, a.adv[r], a.vt[r], a.vf_pred[r], a.logp_old[r],
-                             a.beh ? a.beh + r * A : nullptr, a.h, st);
+                if constexpr (kLoss == ssd::kLossAc)
+                    ssd::a3c_row(s_out + tid * 16, d, A, act, a.adv[r], a.vt[r], a.h, st);
+                else
+                    ssd::ppo_row(s_out + tid * 16, d, A, act, a.adv[r], a.vt[r], a.vf_pred[r], a.logp_old[r],
+                                 a.beh ? a.beh + r * A : nullptr, a.h, st);
 #pragma unroll
                 for (int j = 0; j < 16; ++j) a.dx[r * kX + j] = d[j];
             }
@@ -351,7 +358,11 @@ struct ReduceArgs {
 };
 
 // The partials of every entry added in order in float64, times 1 / set rows, rounded once; the padding floats are zero.
+// kLossAc: the sums as they are (the A3C loss is a sum over rows), and the four statistics of a3c_row to stats [P][4].
+template <int kLoss>
 __global__ void __launch_bounds__(256) ssd_lstm_reduce_kernel(ReduceArgs a) {
+    constexpr bool kSum = kLoss == ssd::kLossAc;
+    constexpr int kStats = kSum ? 4 : 5;
     const int idx = blockIdx.x * 256 + threadIdx.x, p = blockIdx.y, C = a.C, A = a.A;
     const int seq_pitch = 16 * C + 16 + kStatFloats, w_floats = (kX + C) * 4 * C, w_pitch = w_floats + 4 * C;
     const float *pseq = a.part_seq + (size_t)p * a.Gs * seq_pitch;
@@ -377,34 +388,35 @@ __global__ void __launch_bounds__(256) ssd_lstm_reduce_kernel(ReduceArgs a) {
         }
         double sum = 0.0;
         for (int g = 0; g < n; ++g) sum += (double)src[g * pitch];
-        a.grads[(size_t)p * a.set_floats + idx] = (float)(sum / (double)a.set_rows);
+        a.grads[(size_t)p * a.set_floats + idx] = kSum ? (float)sum : (float)(sum / (double)a.set_rows);
     }
-    if (blockIdx.x == 0 && threadIdx.x < 5) {
+    if (blockIdx.x == 0 && threadIdx.x < kStats) {
         double sum = 0.0;
         for (int g = 0; g < a.Gs; ++g) sum += reinterpret_cast<const double *>(pseq + (size_t)g * seq_pitch + 16 * C + 16)[threadIdx.x];
-        a.stats[p * 5 + threadIdx.x] = sum / (double)a.set_rows;
+        a.stats[p * kStats + threadIdx.x] = kSum ? sum : sum / (double)a.set_rows;
     }
 }
 
 template <int C>
-hipError_t launch_window(const WinArgs &a, hipStream_t stream) {
-    hipLaunchKernelGGL((ssd_lstm_seq_kernel<C>), dim3((unsigned)a.G, (unsigned)a.P), dim3(4 * C), 0, stream, a);
+hipError_t launch_window(int loss, const WinArgs &a, hipStream_t stream) {
+    const dim3 grid((unsigned)a.G, (unsigned)a.P);
+    if (loss == ssd::kLossAc) hipLaunchKernelGGL((ssd_lstm_seq_kernel<C, ssd::kLossAc>), grid, dim3(4 * C), 0, stream, a);
+    else hipLaunchKernelGGL((ssd_lstm_seq_kernel<C, ssd::kLossPpo>), grid, dim3(4 * C), 0, stream, a);
     if (const hipError_t e = hipGetLastError()) return e;
     hipLaunchKernelGGL((ssd_lstm_dw_kernel<C>), dim3(4 * C / 64, (unsigned)a.S, (unsigned)a.P), dim3(256), 0, stream, a);
     return hipGetLastError();
 }
 
-}  // namespace
-
-extern "C" int ssd_policy_lstm_ppo_grad(const float *weights, int32_t num_sets, int32_t num_actions, int32_t cell_size,
-                                        int32_t seq_len, const uint8_t *obs_first, const uint8_t *obs, const float *state,
-                                        const uint8_t *done, const int32_t *actions, const float *logp_old,
-                                        const float *advantages, const float *value_targets, const float *vf_preds,
-                                        const float *behaviour_logits, int32_t n_steps, int32_t num_envs, int32_t num_agents,
-                                        double clip_param, double vf_clip_param, double vf_loss_coeff, double entropy_coeff,
-                                        double kl_coeff, float *scratch, float *grads, double *stats, int32_t device_id,
-                                        uint32_t flags, void *stream_) {
+// Both entry points below: the checks, the window walk and the launches, with the row loss `loss` (the A3C call passes no
+// logp_old, vf_preds or behaviour_logits and zeros for the hyper-parameters it does not have, which pass their checks).
+int lstm_grad(int loss, const float *weights, int32_t num_sets, int32_t num_actions, int32_t cell_size, int32_t seq_len,
+              const uint8_t *obs_first, const uint8_t *obs, const float *state, const uint8_t *done, const int32_t *actions,
+              const float *logp_old, const float *advantages, const float *value_targets, const float *vf_preds,
+              const float *behaviour_logits, int32_t n_steps, int32_t num_envs, int32_t num_agents, double clip_param,
+              double vf_clip_param, double vf_loss_coeff, double entropy_coeff, double kl_coeff, float *scratch, float *grads,
+              double *stats, int32_t device_id, uint32_t flags, void *stream_) {
     using ssd::policy_fail;
+    const bool ac = loss == ssd::kLossAc;
     if (!weights) return policy_fail("weights are required");
     if (const char *why = ssd::check_policy_net(ssd::kNetLstm, weights, num_sets, num_agents, num_actions, cell_size)) return policy_fail(why);
     if (n_steps < 1 || num_envs < 1) return policy_fail("n_steps and num_envs must be >= 1");
@@ -414,7 +426,8 @@ extern "C" int ssd_policy_lstm_ppo_grad(const float *weights, int32_t num_sets, 
     if (!obs && !(obs_first && n_steps == 1)) return policy_fail("obs is required (it may be null only with obs_first and n_steps 1)");
     if (!state) return policy_fail("state is required");
     if (reinterpret_cast<uintptr_t>(state) & 3u) return policy_fail("state must be 4-byte aligned");
-    if (!actions || !logp_old || !advantages || !value_targets || !vf_preds)
+    if (ac && (!actions || !advantages || !value_targets)) return policy_fail("actions, advantages and value_targets are required");
+    if (!ac && (!actions || !logp_old || !advantages || !value_targets || !vf_preds))
         return policy_fail("actions, logp_old, advantages, value_targets and vf_preds are required");
     if (!scratch || !grads || !stats) return policy_fail("scratch, grads and stats are required");
     if ((reinterpret_cast<uintptr_t>(scratch) & 7u) || (reinterpret_cast<uintptr_t>(stats) & 7u))
@@ -485,12 +498,13 @@ extern "C" int ssd_policy_lstm_ppo_grad(const float *weights, int32_t num_sets, 
         a.ring = state + (size_t)(k0 / T) * SR * 2 * C;
         a.done_prev = done ? done + (size_t)k0 * SR : nullptr;      // step t > 0 of the window looks at done[k0 + t - 1]
         const size_t r0 = (size_t)k0 * SR;
-        a.actions = actions + r0; a.logp_old = logp_old + r0; a.adv = advantages + r0; a.vt = value_targets + r0;
-        a.vf_pred = vf_preds + r0; a.beh = behaviour_logits ? behaviour_logits + r0 * A : nullptr;
+        a.actions = actions + r0; a.adv = advantages + r0; a.vt = value_targets + r0;
+        a.logp_old = logp_old ? logp_old + r0 : nullptr; a.vf_pred = vf_preds ? vf_preds + r0 : nullptr;
+        a.beh = behaviour_logits ? behaviour_logits + r0 * A : nullptr;
         switch (C) {
-        case 64: e = launch_window<64>(a, stream); break;
-        case 128: e = launch_window<128>(a, stream); break;
-        default: e = launch_window<256>(a, stream); break;
+        case 64: e = launch_window<64>(loss, a, stream); break;
+        case 128: e = launch_window<128>(loss, a, stream); break;
+        default: e = launch_window<256>(loss, a, stream); break;
         }
         if (e != hipSuccess) return ssd::policy_launched(e);
         // 4. the trunk's backward from dx
@@ -504,6 +518,34 @@ extern "C" int ssd_policy_lstm_ppo_grad(const float *weights, int32_t num_sets, 
     ReduceArgs r{};
     r.P = P; r.A = A; r.C = C; r.set_floats = a.set_floats; r.set_rows = (int32_t)(rows / P); r.Gt = Gt; r.Gs = a.G; r.S = a.S;
     r.part_trunk = part_trunk; r.part_seq = a.part_seq; r.part_w = a.part_w; r.grads = grads; r.stats = stats;
-    hipLaunchKernelGGL(ssd_lstm_reduce_kernel, dim3((unsigned)((a.set_floats + 255) / 256), (unsigned)P), dim3(256), 0, stream, r);
+    const dim3 reduce_grid((unsigned)((a.set_floats + 255) / 256), (unsigned)P);
+    if (ac) hipLaunchKernelGGL(ssd_lstm_reduce_kernel<ssd::kLossAc>, reduce_grid, dim3(256), 0, stream, r);
+    else hipLaunchKernelGGL(ssd_lstm_reduce_kernel<ssd::kLossPpo>, reduce_grid, dim3(256), 0, stream, r);
     return ssd::policy_launched(hipGetLastError());
+}
+
+}  // namespace
+
+extern "C" int ssd_policy_lstm_ppo_grad(const float *weights, int32_t num_sets, int32_t num_actions, int32_t cell_size,
+                                        int32_t seq_len, const uint8_t *obs_first, const uint8_t *obs, const float *state,
+                                        const uint8_t *done, const int32_t *actions, const float *logp_old,
+                                        const float *advantages, const float *value_targets, const float *vf_preds,
+                                        const float *behaviour_logits, int32_t n_steps, int32_t num_envs, int32_t num_agents,
+                                        double clip_param, double vf_clip_param, double vf_loss_coeff, double entropy_coeff,
+                                        double kl_coeff, float *scratch, float *grads, double *stats, int32_t device_id,
+                                        uint32_t flags, void *stream) {
+    return lstm_grad(ssd::kLossPpo, weights, num_sets, num_actions, cell_size, seq_len, obs_first, obs, state, done, actions,
+                     logp_old, advantages, value_targets, vf_preds, behaviour_logits, n_steps, num_envs, num_agents, clip_param,
+                     vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff, scratch, grads, stats, device_id, flags, stream);
+}
+
+extern "C" int ssd_policy_lstm_ac_grad(const float *weights, int32_t num_sets, int32_t num_actions, int32_t cell_size,
+                                       int32_t seq_len, const uint8_t *obs_first, const uint8_t *obs, const float *state,
+                                       const uint8_t *done, const int32_t *actions, const float *advantages,
+                                       const float *value_targets, int32_t n_steps, int32_t num_envs, int32_t num_agents,
+                                       double vf_loss_coeff, double entropy_coeff, float *scratch, float *grads, double *stats,
+                                       int32_t device_id, uint32_t flags, void *stream) {
+    return lstm_grad(ssd::kLossAc, weights, num_sets, num_actions, cell_size, seq_len, obs_first, obs, state, done, actions, nullptr,
+                     advantages, value_targets, nullptr, nullptr, n_steps, num_envs, num_agents, 0.0, 0.0, vf_loss_coeff,
+                     entropy_coeff, 0.0, scratch, grads, stats, device_id, flags, stream);
 }

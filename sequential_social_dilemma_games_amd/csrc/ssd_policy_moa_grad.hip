@@ -26,6 +26,10 @@
 // The sequence and split kernels restate ssd_policy_lstm_grad.hip's for the Keras cell (gate order i, f, c~, o, no forget
 // bias, state order (h, c) inside a four-row state), an input of 32 or 48 columns and either head; that file's kernels are
 // left as they are, so the recurrent policy's call keeps its code and its bits.
+//
+// ssd_policy_moa_ac_grad is the same walk with the A3C row loss (include/ssd.h, A3C LOSS AND GRADIENTS):
+// the actions branch's sequence kernel and the reduce compiled once more with ssd::kLossAc.  The A3C terms are sums over a set's
+// rows and MOALoss a mean, so the MOA branch's scale on dpred carries 1 / rows too; its kernels are the PPO call's as they are.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -67,7 +71,7 @@ struct WinArgs {
     const int32_t *prev;           // [steps][E][N]: the joint action each step's MOA read, by agent index
     const float *logp_old, *adv, *vt, *vf_pred, *beh;
     ssd::PpoHyper h;
-    float moa_scale;               // moa_weight / (N - 1)
+    float moa_scale;               // moa_weight / (N - 1); the A3C call: moa_weight / ((N - 1) set rows), MOALoss being a mean
     float *feat;                   // [steps][E][N][2][32]
     float *dx;                     // [steps][E][N][2][32]: stack 0's half holds d row_loss / d (logits, value) in 0..15 first
     float *st;                     // [steps][E][N][2][C]: (h', c') of every row, of the branch in hand
@@ -92,8 +96,10 @@ __global__ void __launch_bounds__(256) ssd_moa_transpose_kernel(const float *w, 
 // ------------------------------------------------------------------------------------------------- the sequence kernel
 // kMoa false: the actions LSTM on stack 0 with the PPO head; true: the MOA LSTM on [stack 1, previous actions] with the
 // prediction head.  A workgroup of 4 C threads takes 16 sequences of one weight set (persistent over tiles g, g + G, ...).
-template <int C, bool kMoa>
+// kLoss (the actions branch only): the row loss, ssd::kLossPpo (ppo_row) or ssd::kLossAc (a3c_row: the A3C terms, four statistics).
+template <int C, bool kMoa, int kLoss = ssd::kLossPpo>
 __global__ void __launch_bounds__(4 * C) ssd_moa_seq_kernel(WinArgs a) {
+    static_assert(!kMoa || kLoss == ssd::kLossPpo, "the MOA branch has one instantiation: the loss kind reaches it through a.moa_scale");
     constexpr int kThreads = 4 * C;
     constexpr int kIn = kMoa ? kXM : kX;            // input columns
     constexpr int kK = kIn + C;                     // rows of the LSTM matrix
@@ -202,8 +208,11 @@ __global__ void __launch_bounds__(4 * C) ssd_moa_seq_kernel(WinArgs a) {
                     float d[16];
 #pragma unroll
                     for (int j = 0; j < 16; ++j) d[j] = 0.f;
-                    ssd::ppo_row(s_out + tid * 16, d, A, act, a.adv[r], a.vt[r], a.vf_pred[r], a.logp_old[r],
-                                 a.beh ? a.beh + r * A : nullptr, a.h, st);
+                    if constexpr (kLoss == ssd::kLossAc)
+                        ssd::a3c_row(s_out + tid * 16, d, A, act, a.adv[r], a.vt[r], a.h, st);
+                    else
+                        ssd::ppo_row(s_out + tid * 16, d, A, act, a.adv[r], a.vt[r], a.vf_pred[r], a.logp_old[r],
+                                     a.beh ? a.beh + r * A : nullptr, a.h, st);
 #pragma unroll
                     for (int j = 0; j < 16; ++j) a.dx[r * 2 * kX + j] = d[j];
                 }
@@ -543,8 +552,12 @@ struct ReduceArgs {
 };
 
 // The partials of every entry added in order in float64, times 1 / set rows, rounded once; the padding floats and the rows
-// 32 + N .. 47 of the MOA matrix are zero.
+// 32 + N .. 47 of the MOA matrix are zero.  kLossAc: the sums as they are (the A3C terms are sums over rows, and the MOA branch's
+// entries carry 1 / set rows from a.moa_scale already); stats [P][5]: a3c_row's four, total with moa_weight * moa_loss, then
+// moa_loss, the one statistic still divided by the set's rows.
+template <int kLoss>
 __global__ void __launch_bounds__(256) ssd_moa_reduce_kernel(ReduceArgs a) {
+    constexpr bool kSum = kLoss == ssd::kLossAc;
     const int idx = blockIdx.x * 256 + threadIdx.x, p = blockIdx.y, C = a.C, A = a.A, N = a.N, NA = (N - 1) * A, PP = a.pred_pitch;
     const int seq_pitch = 16 * C + 16 + kStatFloats, trunk_pitch = SSD_MOA_LSTM_W(C) + kStatFloats;
     const int wa_floats = (kX + C) * 4 * C, wa_pitch = wa_floats + 4 * C, wm_floats = (kXM + C) * 4 * C, wm_pitch = wm_floats + 4 * C;
@@ -584,9 +597,21 @@ __global__ void __launch_bounds__(256) ssd_moa_reduce_kernel(ReduceArgs a) {
         }
         double sum = 0.0;
         for (int g = 0; g < n; ++g) sum += (double)src[g * pitch];
-        a.grads[(size_t)p * a.set_floats + idx] = (float)(sum / (double)a.set_rows);
+        a.grads[(size_t)p * a.set_floats + idx] = kSum ? (float)sum : (float)(sum / (double)a.set_rows);
     }
-    if (blockIdx.x == 0 && threadIdx.x < 6) {
+    if (kSum && blockIdx.x == 0 && threadIdx.x < 5) {
+        const int k = threadIdx.x;
+        double sum = 0.0, moa = 0.0;
+        for (int g = 0; g < a.Gs; ++g) {
+            const double *st = reinterpret_cast<const double *>(pseq + (size_t)g * seq_pitch + 16 * C + 16);
+            sum += st[k];
+            moa += st[5];
+        }
+        moa /= (double)a.set_rows;
+        if (k == 0) sum += a.moa_weight * moa;
+        a.stats[p * 5 + k] = k == 4 ? moa : sum;
+    }
+    if (!kSum && blockIdx.x == 0 && threadIdx.x < 6) {
         const int k = threadIdx.x;
         double sum = 0.0, moa = 0.0;
         for (int g = 0; g < a.Gs; ++g) {
@@ -600,15 +625,17 @@ __global__ void __launch_bounds__(256) ssd_moa_reduce_kernel(ReduceArgs a) {
 }
 
 template <int C>
-hipError_t launch_window(WinArgs a, const float *wT_act, const float *wT_moa, float *part_wa, float *part_wm, hipStream_t stream) {
+hipError_t launch_window(int loss, WinArgs a, const float *wT_act, const float *wT_moa, float *part_wa, float *part_wm,
+                         hipStream_t stream) {
     const dim3 seq_grid((unsigned)a.G, (unsigned)a.P), w_grid(4 * C / 64, (unsigned)a.S, (unsigned)a.P);
     a.wT = wT_act; a.part_w = part_wa;
-    hipLaunchKernelGGL((ssd_moa_seq_kernel<C, false>), seq_grid, dim3(4 * C), 0, stream, a);
+    if (loss == ssd::kLossAc) hipLaunchKernelGGL((ssd_moa_seq_kernel<C, false, ssd::kLossAc>), seq_grid, dim3(4 * C), 0, stream, a);
+    else hipLaunchKernelGGL((ssd_moa_seq_kernel<C, false, ssd::kLossPpo>), seq_grid, dim3(4 * C), 0, stream, a);
     if (const hipError_t e = hipGetLastError()) return e;
     hipLaunchKernelGGL((ssd_moa_dw_kernel<C, false>), w_grid, dim3(256), 0, stream, a);
     if (const hipError_t e = hipGetLastError()) return e;
     a.wT = wT_moa; a.part_w = part_wm;
-    hipLaunchKernelGGL((ssd_moa_seq_kernel<C, true>), seq_grid, dim3(4 * C), 0, stream, a);
+    hipLaunchKernelGGL((ssd_moa_seq_kernel<C, true, ssd::kLossPpo>), seq_grid, dim3(4 * C), 0, stream, a);
     if (const hipError_t e = hipGetLastError()) return e;
     hipLaunchKernelGGL((ssd_moa_dw_kernel<C, true>), w_grid, dim3(256), 0, stream, a);
     if (const hipError_t e = hipGetLastError()) return e;
@@ -617,17 +644,16 @@ hipError_t launch_window(WinArgs a, const float *wT_act, const float *wT_moa, fl
     return hipGetLastError();
 }
 
-}  // namespace
-
-extern "C" int ssd_policy_moa_ppo_grad(const float *weights, int32_t num_sets, int32_t num_actions, int32_t cell_size,
-                                       int32_t seq_len, const uint8_t *obs_first, const uint8_t *obs, const float *state,
-                                       const int32_t *prev_actions, const uint8_t *done, const int32_t *actions,
-                                       const float *logp_old, const float *advantages, const float *value_targets,
-                                       const float *vf_preds, const float *behaviour_logits, int32_t n_steps, int32_t num_envs,
-                                       int32_t num_agents, double clip_param, double vf_clip_param, double vf_loss_coeff,
-                                       double entropy_coeff, double kl_coeff, double moa_weight, float *scratch, float *grads,
-                                       double *stats, int32_t device_id, uint32_t flags, void *stream_) {
+// Both entry points below: the checks, the window walk and the launches, with the row loss `loss` (the A3C call passes no
+// logp_old, vf_preds or behaviour_logits and zeros for the hyper-parameters it does not have, which pass their checks).
+int moa_grad(int loss, const float *weights, int32_t num_sets, int32_t num_actions, int32_t cell_size, int32_t seq_len,
+             const uint8_t *obs_first, const uint8_t *obs, const float *state, const int32_t *prev_actions, const uint8_t *done,
+             const int32_t *actions, const float *logp_old, const float *advantages, const float *value_targets,
+             const float *vf_preds, const float *behaviour_logits, int32_t n_steps, int32_t num_envs, int32_t num_agents,
+             double clip_param, double vf_clip_param, double vf_loss_coeff, double entropy_coeff, double kl_coeff, double moa_weight,
+             float *scratch, float *grads, double *stats, int32_t device_id, uint32_t flags, void *stream_) {
     using ssd::policy_fail;
+    const bool ac = loss == ssd::kLossAc;
     if (!weights) return policy_fail("weights are required");
     if (const char *why = ssd::check_policy_net(ssd::kNetMoa, weights, num_sets, num_agents, num_actions, cell_size)) return policy_fail(why);
     if (n_steps < 1 || num_envs < 1) return policy_fail("n_steps and num_envs must be >= 1");
@@ -639,7 +665,8 @@ extern "C" int ssd_policy_moa_ppo_grad(const float *weights, int32_t num_sets, i
     if (reinterpret_cast<uintptr_t>(state) & 3u) return policy_fail("state must be 4-byte aligned");
     if (!prev_actions) return policy_fail("prev_actions is required");
     if (reinterpret_cast<uintptr_t>(prev_actions) & 3u) return policy_fail("prev_actions must be 4-byte aligned");
-    if (!actions || !logp_old || !advantages || !value_targets || !vf_preds)
+    if (ac && (!actions || !advantages || !value_targets)) return policy_fail("actions, advantages and value_targets are required");
+    if (!ac && (!actions || !logp_old || !advantages || !value_targets || !vf_preds))
         return policy_fail("actions, logp_old, advantages, value_targets and vf_preds are required");
     if (!scratch || !grads || !stats) return policy_fail("scratch, grads and stats are required");
     if ((reinterpret_cast<uintptr_t>(scratch) & 7u) || (reinterpret_cast<uintptr_t>(stats) & 7u))
@@ -668,7 +695,8 @@ extern "C" int ssd_policy_moa_ppo_grad(const float *weights, int32_t num_sets, i
     const int Gt = SSD_PPO_GROUPS((int32_t)(W * (int64_t)seqs), P);
     a.seqs = seqs; a.step_rows = (int32_t)SR;
     a.h = ssd::PpoHyper{(float)clip_param, (float)vf_clip_param, (float)vf_loss_coeff, (float)entropy_coeff, (float)kl_coeff};
-    a.moa_scale = (float)(moa_weight / (double)(N - 1));
+    // (the A3C terms are sums over a set's rows and MOALoss a mean: its 1 / rows is folded in here, in double, rounded once)
+    a.moa_scale = ac ? (float)(moa_weight / ((double)(N - 1) * (double)(rows / P))) : (float)(moa_weight / (double)(N - 1));
     const size_t wa_floats = (size_t)(kX + C) * 4 * C, wm_floats = (size_t)(kXM + C) * 4 * C;
     float *at = scratch;
     float *wT_act = at; at += (size_t)P * wa_floats;
@@ -720,12 +748,13 @@ extern "C" int ssd_policy_moa_ppo_grad(const float *weights, int32_t num_sets, i
         a.ring = state + (size_t)(k0 / T) * SR * 4 * C;
         a.done_prev = done ? done + (size_t)k0 * SR : nullptr;      // step t > 0 of the window looks at done[k0 + t - 1]
         const size_t r0 = (size_t)k0 * SR;
-        a.actions = actions + r0; a.prev = prev_actions + r0; a.logp_old = logp_old + r0; a.adv = advantages + r0;
-        a.vt = value_targets + r0; a.vf_pred = vf_preds + r0; a.beh = behaviour_logits ? behaviour_logits + r0 * A : nullptr;
+        a.actions = actions + r0; a.prev = prev_actions + r0; a.adv = advantages + r0; a.vt = value_targets + r0;
+        a.logp_old = logp_old ? logp_old + r0 : nullptr; a.vf_pred = vf_preds ? vf_preds + r0 : nullptr;
+        a.beh = behaviour_logits ? behaviour_logits + r0 * A : nullptr;
         switch (C) {
-        case 64: e = launch_window<64>(a, wT_act, wT_moa, part_wa, part_wm, stream); break;
-        case 128: e = launch_window<128>(a, wT_act, wT_moa, part_wa, part_wm, stream); break;
-        default: e = launch_window<256>(a, wT_act, wT_moa, part_wa, part_wm, stream); break;
+        case 64: e = launch_window<64>(loss, a, wT_act, wT_moa, part_wa, part_wm, stream); break;
+        case 128: e = launch_window<128>(loss, a, wT_act, wT_moa, part_wa, part_wm, stream); break;
+        default: e = launch_window<256>(loss, a, wT_act, wT_moa, part_wa, part_wm, stream); break;
         }
         if (e != hipSuccess) return ssd::policy_launched(e);
         // 4. the trunk's backward from dx, once per stack
@@ -744,6 +773,35 @@ extern "C" int ssd_policy_moa_ppo_grad(const float *weights, int32_t num_sets, i
     r.pred_pitch = a.pred_pitch; r.moa_weight = moa_weight;
     r.part_trunk = part_trunk; r.part_seq = a.part_seq; r.part_wa = part_wa; r.part_wm = part_wm; r.part_pred = a.part_pred;
     r.grads = grads; r.stats = stats;
-    hipLaunchKernelGGL(ssd_moa_reduce_kernel, dim3((unsigned)((a.set_floats + 255) / 256), (unsigned)P), dim3(256), 0, stream, r);
+    const dim3 reduce_grid((unsigned)((a.set_floats + 255) / 256), (unsigned)P);
+    if (ac) hipLaunchKernelGGL(ssd_moa_reduce_kernel<ssd::kLossAc>, reduce_grid, dim3(256), 0, stream, r);
+    else hipLaunchKernelGGL(ssd_moa_reduce_kernel<ssd::kLossPpo>, reduce_grid, dim3(256), 0, stream, r);
     return ssd::policy_launched(hipGetLastError());
+}
+
+}  // namespace
+
+extern "C" int ssd_policy_moa_ppo_grad(const float *weights, int32_t num_sets, int32_t num_actions, int32_t cell_size,
+                                       int32_t seq_len, const uint8_t *obs_first, const uint8_t *obs, const float *state,
+                                       const int32_t *prev_actions, const uint8_t *done, const int32_t *actions,
+                                       const float *logp_old, const float *advantages, const float *value_targets,
+                                       const float *vf_preds, const float *behaviour_logits, int32_t n_steps, int32_t num_envs,
+                                       int32_t num_agents, double clip_param, double vf_clip_param, double vf_loss_coeff,
+                                       double entropy_coeff, double kl_coeff, double moa_weight, float *scratch, float *grads,
+                                       double *stats, int32_t device_id, uint32_t flags, void *stream) {
+    return moa_grad(ssd::kLossPpo, weights, num_sets, num_actions, cell_size, seq_len, obs_first, obs, state, prev_actions, done,
+                    actions, logp_old, advantages, value_targets, vf_preds, behaviour_logits, n_steps, num_envs, num_agents,
+                    clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff, moa_weight, scratch, grads, stats, device_id,
+                    flags, stream);
+}
+
+extern "C" int ssd_policy_moa_ac_grad(const float *weights, int32_t num_sets, int32_t num_actions, int32_t cell_size,
+                                      int32_t seq_len, const uint8_t *obs_first, const uint8_t *obs, const float *state,
+                                      const int32_t *prev_actions, const uint8_t *done, const int32_t *actions,
+                                      const float *advantages, const float *value_targets, int32_t n_steps, int32_t num_envs,
+                                      int32_t num_agents, double vf_loss_coeff, double entropy_coeff, double moa_weight,
+                                      float *scratch, float *grads, double *stats, int32_t device_id, uint32_t flags, void *stream) {
+    return moa_grad(ssd::kLossAc, weights, num_sets, num_actions, cell_size, seq_len, obs_first, obs, state, prev_actions, done,
+                    actions, nullptr, advantages, value_targets, nullptr, nullptr, n_steps, num_envs, num_agents, 0.0, 0.0,
+                    vf_loss_coeff, entropy_coeff, 0.0, moa_weight, scratch, grads, stats, device_id, flags, stream);
 }

@@ -565,19 +565,30 @@ PPO_STATS = ("total_loss", "policy_loss", "vf_loss", "kl", "entropy")      # the
 _PPO_KEYS = (("obs", ("obs",)), ("actions", ("actions",)), ("logp_old", ("logp_old", "logp")),
              ("advantages", ("advantages",)), ("value_targets", ("value_targets",)), ("vf_pred", ("vf_pred", "value")),
              ("behaviour_logits", ("behaviour_logits", "logits")))
+_A3C_ROWS = ("advantages", "value_targets")                                # the A3C loss's float per-row inputs
 
 
-def _ppo_tensors(policy, batch, obs_first, kl_coeff):
+def _ppo_tensors(policy, batch, obs_first, kl_coeff, a3c=False):
     """The loss's inputs by their contract names from the dict sample() returns (logp as logp_old, value as vf_pred, logits
-    as behaviour_logits) or a tuple in _PPO_KEYS' order, checked against each other: K from actions [K, E, N]."""
+    as behaviour_logits) or a tuple in _PPO_KEYS' order, checked against each other: K from actions [K, E, N].  a3c: the A3C
+    loss's inputs -- logp_old, vf_pred and behaviour_logits are not looked at (None); a tuple is (obs, actions, advantages,
+    value_targets)."""
+    per_row = _A3C_ROWS if a3c else ("logp_old", "advantages", "value_targets", "vf_pred")
     if isinstance(batch, dict):
         t = {name: next((batch[k] for k in keys if k in batch), None) for name, keys in _PPO_KEYS}
+    elif a3c:
+        vals = tuple(batch)
+        if len(vals) != 4:
+            raise ValueError("the tensors are (obs, actions, advantages, value_targets)")
+        t = dict(zip(("obs", "actions") + _A3C_ROWS, vals))
     else:
         vals = tuple(batch)
         if not 6 <= len(vals) <= 7:
             raise ValueError("the tensors are (obs, actions, logp_old, advantages, value_targets, vf_pred[, behaviour_logits])")
         t = dict(zip((name for name, _ in _PPO_KEYS), vals + (None,) * (7 - len(vals))))
-    for name in ("actions", "logp_old", "advantages", "value_targets", "vf_pred"):
+    if a3c:
+        t["logp_old"] = t["vf_pred"] = t["behaviour_logits"] = None
+    for name in ("actions",) + per_row:
         if not isinstance(t[name], torch.Tensor):
             raise ValueError("%s is required" % name)
     acts = t["actions"]
@@ -598,7 +609,7 @@ def _ppo_tensors(policy, batch, obs_first, kl_coeff):
         if not isinstance(x, torch.Tensor) or x.dtype != dtype or tuple(x.shape) != shape or x.device != dev or not x.is_contiguous():
             raise ValueError("%s must be a contiguous %s tensor of shape %s on %s" % (name, dtype, shape, dev))
     check(acts, torch.int32, (K, E, N), "actions")
-    for name in ("logp_old", "advantages", "value_targets", "vf_pred"):
+    for name in per_row:
         check(t[name], torch.float32, (K, E, N), name)
     if t["behaviour_logits"] is not None:
         check(t["behaviour_logits"], torch.float32, (K, E, N, A), "behaviour_logits")
@@ -879,6 +890,31 @@ def ppo_loss_recurrent(policy, batch, *, seq_len, clip_param, vf_clip_param, vf_
 MOA_PPO_STATS = PPO_STATS + ("moa_loss",)
 
 
+def _moa_tensors(policy, batch, K, E, N, seq_len, dev):
+    """The state ring [S, E, N, 4, C], done [K, E, N] (or None) and prev_actions [K, E, N] of a MOA fragment, checked."""
+    C, S = policy.cell_size, -(-K // seq_len)
+    state = batch.get("state")
+    if state is None and seq_len >= K and batch.get("state_in") is not None:
+        state = batch["state_in"].unsqueeze(0)                        # one window: the state step 0 used
+    if not isinstance(state, torch.Tensor):
+        raise ValueError("state is required: the ring sample(..., state_every=seq_len) records (state_in serves when seq_len >= K)")
+    if state.dim() != 5 or tuple(state.shape[1:4]) != (E, N, 4) or state.shape[0] < S:
+        raise ValueError("state must be [S, %d, %d, 4, C] with S >= ceil(K / seq_len) = %d, got %s" % (E, N, S, tuple(state.shape)))
+    if state.shape[-1] != C:
+        raise ValueError("state has %d cells, the policy %d" % (state.shape[-1], C))
+    if state.dtype != torch.float32 or state.device != dev or not state.is_contiguous():
+        raise ValueError("state must be a contiguous torch.float32 tensor on %s" % (dev,))
+    done, prev = batch.get("done"), batch.get("prev_actions")
+    if done is not None:
+        if (not isinstance(done, torch.Tensor) or done.dtype != torch.uint8 or tuple(done.shape) != (K, E, N) or done.device != dev
+                or not done.is_contiguous()):
+            raise ValueError("done must be a contiguous torch.uint8 tensor of shape %s on %s" % ((K, E, N), dev))
+    if (not isinstance(prev, torch.Tensor) or prev.dtype != torch.int32 or tuple(prev.shape) != (K, E, N) or prev.device != dev
+            or not prev.is_contiguous()):
+        raise ValueError("prev_actions must be a contiguous torch.int32 tensor of shape %s on %s" % ((K, E, N), dev))
+    return state, done, prev
+
+
 class _MOAPPOLossFunction(torch.autograd.Function):
     """ssd_policy_moa_ppo_grad as a torch function of the policy's parameters, as _PPOLossFunction."""
 
@@ -974,26 +1010,7 @@ def ppo_loss_moa(policy, batch, *, seq_len, moa_weight, clip_param, vf_clip_para
     dev, P = t["actions"].device, policy.num_sets
     if policy.conv_w.device != dev:
         raise ValueError("the policy is on %s, the batch on %s" % (policy.conv_w.device, dev))
-    C, S = policy.cell_size, -(-K // seq_len)
-    state = batch.get("state")
-    if state is None and seq_len >= K and batch.get("state_in") is not None:
-        state = batch["state_in"].unsqueeze(0)                        # one window: the state step 0 used
-    if not isinstance(state, torch.Tensor):
-        raise ValueError("state is required: the ring sample(..., state_every=seq_len) records (state_in serves when seq_len >= K)")
-    if state.dim() != 5 or tuple(state.shape[1:4]) != (E, N, 4) or state.shape[0] < S:
-        raise ValueError("state must be [S, %d, %d, 4, C] with S >= ceil(K / seq_len) = %d, got %s" % (E, N, S, tuple(state.shape)))
-    if state.shape[-1] != C:
-        raise ValueError("state has %d cells, the policy %d" % (state.shape[-1], C))
-    if state.dtype != torch.float32 or state.device != dev or not state.is_contiguous():
-        raise ValueError("state must be a contiguous torch.float32 tensor on %s" % (dev,))
-    done, prev = batch.get("done"), batch.get("prev_actions")
-    if done is not None:
-        if (not isinstance(done, torch.Tensor) or done.dtype != torch.uint8 or tuple(done.shape) != (K, E, N) or done.device != dev
-                or not done.is_contiguous()):
-            raise ValueError("done must be a contiguous torch.uint8 tensor of shape %s on %s" % ((K, E, N), dev))
-    if (not isinstance(prev, torch.Tensor) or prev.dtype != torch.int32 or tuple(prev.shape) != (K, E, N) or prev.device != dev
-            or not prev.is_contiguous()):
-        raise ValueError("prev_actions must be a contiguous torch.int32 tensor of shape %s on %s" % ((K, E, N), dev))
+    state, done, prev = _moa_tensors(policy, batch, K, E, N, seq_len, dev)
     t["state"], t["done"], t["prev_actions"] = state, done, prev
     if dev.type == "cuda":
         if policy.conv_w.dtype != torch.float32:
@@ -1017,6 +1034,213 @@ def ppo_loss_moa(policy, batch, *, seq_len, moa_weight, clip_param, vf_clip_para
     means[0] = means[0] + hyper[5] * ce
     means.append(ce)
     return means[0].sum(), {name: m.detach() for name, m in zip(MOA_PPO_STATS, means)}
+
+
+# ---- the A3C loss of the three policies (include/ssd.h, A3C LOSS AND GRADIENTS) ----
+
+A3C_STATS = ("total_loss", "policy_loss", "vf_loss", "policy_entropy")      # the columns of the library's stats, in order
+MOA_A3C_STATS = A3C_STATS + ("moa_loss",)
+
+
+def a3c_terms(logits, value, t, vf_loss_coeff, entropy_coeff):
+    """The reference's A3C loss (algorithms/a3c_causal.py:28-46) per row in plain torch, in the dtype of logits: (row_loss, pi,
+    vf, ent), each of actions' shape.  t: actions (clamped to 0 .. A - 1), advantages and value_targets by their contract names."""
+    dt = logits.dtype
+    logp_all = torch.log_softmax(logits, dim=-1)
+    acts = t["actions"].long().clamp(0, logits.shape[-1] - 1)
+    logp = logp_all.gather(-1, acts.unsqueeze(-1)).squeeze(-1)
+    pi = -(logp * t["advantages"].to(dt))
+    vf = 0.5 * (value - t["value_targets"].to(dt)).square()
+    ent = -(logp_all.exp() * logp_all).sum(-1)
+    return (pi + vf_loss_coeff * vf) - entropy_coeff * ent, pi, vf, ent
+
+
+def _set_sums(x, P):
+    """The sums of x [K, E, N] over each weight set's rows: [P]."""
+    return x.sum().reshape(1) if P == 1 else x.reshape(-1, P).sum(0)
+
+
+class _A3CLossFunction(torch.autograd.Function):
+    """ssd_policy_ac_grad, ssd_policy_lstm_ac_grad or ssd_policy_moa_ac_grad (by the policy's class) as a torch function of the
+    policy's parameters, as _PPOLossFunction: the same scratch kept on the policy, the same unpacking."""
+
+    @staticmethod
+    def forward(ctx, policy, t, dims, seq_len, hyper, *params):
+        import ctypes as C
+        K, E, N = dims
+        P, A = policy.num_sets, policy.num_actions
+        dev = t["actions"].device
+        weights = policy.packed()
+        moa, conv_fc = isinstance(policy, ConvMOAPolicy), isinstance(policy, ConvFCPolicy)
+        need = policy.ppo_scratch_shape(K * E * N // P)[0] if conv_fc else policy.ppo_scratch_shape(K, E, N, seq_len)[0]
+        scratch = getattr(policy, "_ppo_scratch", None)          # one buffer serves the policy's PPO and A3C calls
+        if scratch is None or scratch.device != dev or scratch.numel() < need:
+            scratch = policy._ppo_scratch = torch.empty(need, dtype=torch.float32, device=dev)
+        grads = torch.empty((P, policy.set_floats), dtype=torch.float32, device=dev)
+        stats = torch.empty((P, len(MOA_A3C_STATS if moa else A3C_STATS)), dtype=torch.float64, device=dev)
+        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())   # noqa: E731
+        index = dev.index if dev.index is not None else torch.cuda.current_device()
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        rows = (ptr(t["actions"]), ptr(t["advantages"]), ptr(t["value_targets"]), K, E, N)
+        tail = (ptr(scratch), ptr(grads), ptr(stats), index, 0, stream)
+        L = _capi.lib()
+        if conv_fc:
+            rc = L.ssd_policy_ac_grad(ptr(weights), P, A, ptr(t["obs_first"]), ptr(t["obs"]), *rows, *hyper, *tail)
+        elif moa:
+            rc = L.ssd_policy_moa_ac_grad(ptr(weights), P, A, policy.cell_size, seq_len, ptr(t["obs_first"]), ptr(t["obs"]),
+                                          ptr(t["state"]), ptr(t["prev_actions"]), ptr(t["done"]), *rows, *hyper, *tail)
+        else:
+            rc = L.ssd_policy_lstm_ac_grad(ptr(weights), P, A, policy.cell_size, seq_len, ptr(t["obs_first"]), ptr(t["obs"]),
+                                           ptr(t["state"]), ptr(t["done"]), *rows, *hyper, *tail)
+        _capi.policy_check(rc)
+        ctx.policy = policy
+        ctx.save_for_backward(grads)
+        ctx.mark_non_differentiable(stats)
+        return stats[:, 0].sum().to(torch.float32), stats
+
+    @staticmethod
+    def backward(ctx, g_loss, g_stats):
+        (grads,) = ctx.saved_tensors
+        out = unpack_gradient(ctx.policy, grads, g_loss)
+        return (None, None, None, None, None) + tuple(g if needs else None for g, needs in zip(out, ctx.needs_input_grad[5:]))
+
+
+def _a3c_prepare(policy, batch, obs_first, seq_len, hyper):
+    """The checks the three A3C functions share -> (t, (K, E, N), seq_len, dev)."""
+    if seq_len is not None:
+        if not isinstance(batch, dict):
+            raise ValueError("batch must be the dict sample() returns")
+        if isinstance(seq_len, bool) or int(seq_len) != seq_len or int(seq_len) < 1:
+            raise ValueError("seq_len must be an integer >= 1")
+        seq_len = int(seq_len)
+    if not all(np.isfinite(hyper)):
+        raise ValueError("the hyper-parameters must be finite")
+    t, dims = _ppo_tensors(policy, batch, obs_first, 0.0, a3c=True)
+    dev = t["actions"].device
+    if policy.conv_w.device != dev:
+        raise ValueError("the policy is on %s, the batch on %s" % (policy.conv_w.device, dev))
+    if dev.type not in ("cuda", "cpu"):
+        raise ValueError("the tensors must be on the CPU or on a GPU, not on %s" % (dev,))
+    if dev.type == "cuda" and policy.conv_w.dtype != torch.float32:
+        raise ValueError("the device path needs a float32 policy")
+    return t, dims, seq_len, dev
+
+
+def _a3c_device(policy, t, dims, seq_len, hyper, names):
+    params = tuple(getattr(policy, name) for name, _, _ in policy.layout())
+    loss, stats = _A3CLossFunction.apply(policy, t, dims, seq_len, hyper, *params)
+    return loss, {name: stats[:, k] for k, name in enumerate(names)}
+
+
+def a3c_loss(policy, batch, *, vf_loss_coeff, entropy_coeff, obs_first=None):
+    """The reference's A3C loss (algorithms/a3c_causal.py:28-46, the baseline's default algorithm) of a ConvFCPolicy on a
+    sampled fragment -> (loss, stats), as ppo_loss: loss a scalar tensor that backpropagates into the policy's parameters,
+    stats a dict of [P] tensors (A3C_STATS: the set SUMS of the total, policy, value-function and entropy terms).  include/ssd.h
+    (A3C LOSS AND GRADIENTS) states the loss: per row -logp * adv + vf_loss_coeff * 0.5 (value - vt)^2 - entropy_coeff * ent,
+    summed (not averaged) over a weight set's rows, then over the sets.
+
+        first = env.reset().clone()
+        batch = env.sample(policy, 128, gamma=0.99, use_gae=False)
+        loss, stats = a3c_loss(policy, batch, vf_loss_coeff=0.5, entropy_coeff=0.01, obs_first=first)
+        loss.backward(); clip_grad_by_set_norm(policy, 40.0); optimiser.step()
+
+    batch: the dict sample() returns (obs, actions, advantages and value_targets are read; logp, value and logits are
+    ignored), or the tuple (obs, actions, advantages, value_targets).  obs_first and minibatches: as ppo_loss.
+    CUDA tensors go to the library (ssd_policy_ac_grad: two launches on torch's current stream); CPU tensors run a3c_terms in
+    plain torch under autograd."""
+    if not isinstance(policy, ConvFCPolicy):
+        raise ValueError("a3c_loss is for a ConvFCPolicy (a3c_loss_recurrent and a3c_loss_moa are the other policies')")
+    hyper = (float(vf_loss_coeff), float(entropy_coeff))
+    t, (K, E, N), _, dev = _a3c_prepare(policy, batch, obs_first, None, hyper)
+    if dev.type == "cuda":
+        return _a3c_device(policy, t, (K, E, N), 0, hyper, A3C_STATS)
+    logits, value = policy(_ppo_obs(t, K))
+    sums = [_set_sums(x, policy.num_sets) for x in a3c_terms(logits, value, t, *hyper)]
+    return sums[0].sum(), {name: m.detach() for name, m in zip(A3C_STATS, sums)}
+
+
+def a3c_loss_recurrent(policy, batch, *, seq_len, vf_loss_coeff, entropy_coeff, obs_first=None):
+    """a3c_loss for a ConvLSTMPolicy (the baseline's default: A3C on the recurrent policy), with truncated backpropagation
+    through time over windows of seq_len steps as ppo_loss_recurrent -> (loss, stats).  The state rule, the batch's keys
+    ("state", "done") and the minibatch slices are ppo_loss_recurrent's.
+
+        batch = env.sample(policy, 128, state_every=16, gamma=0.99, use_gae=False)
+        loss, stats = a3c_loss_recurrent(policy, batch, seq_len=16, vf_loss_coeff=0.5, entropy_coeff=0.01, obs_first=first)
+
+    CUDA tensors go to the library (ssd_policy_lstm_ac_grad); CPU tensors run recurrent_forward and a3c_terms under autograd."""
+    if not isinstance(policy, ConvLSTMPolicy):
+        raise ValueError("a3c_loss_recurrent is for a ConvLSTMPolicy (a3c_loss is the ConvFCPolicy's)")
+    hyper = (float(vf_loss_coeff), float(entropy_coeff))
+    t, (K, E, N), seq_len, dev = _a3c_prepare(policy, batch, obs_first, seq_len, hyper)
+    t["state"], t["done"] = _recurrent_tensors(policy, batch, K, E, N, seq_len, dev)
+    if dev.type == "cuda":
+        return _a3c_device(policy, t, (K, E, N), seq_len, hyper, A3C_STATS)
+    logits, value = recurrent_forward(policy, _ppo_obs(t, K), t["state"], t["done"], seq_len)
+    sums = [_set_sums(x, policy.num_sets) for x in a3c_terms(logits, value, t, *hyper)]
+    return sums[0].sum(), {name: m.detach() for name, m in zip(A3C_STATS, sums)}
+
+
+def a3c_loss_moa(policy, batch, *, seq_len, moa_weight, vf_loss_coeff, entropy_coeff, obs_first=None):
+    """The causal-influence trainer's A3C loss for a ConvMOAPolicy, the A3C terms + moa_weight * MOALoss (algorithms/
+    a3c_causal.py:60-76), with truncated BPTT through both LSTMs as ppo_loss_moa -> (loss, stats): stats a dict of [P] tensors
+    (MOA_A3C_STATS: a3c_loss's four sums, total_loss including the weighted MOA term, then moa_loss).  The A3C terms are SUMS
+    over a set's rows while MOALoss is the MEAN cross-entropy of the set's rows, as in the reference.  The batch's keys
+    ("state", "done", "prev_actions"), the pairing of predictions and targets and the minibatch slices are ppo_loss_moa's.
+
+        batch = env.sample(policy, 128, state_every=16, gamma=0.99, use_gae=False, influence_weight=1.0)
+        loss, stats = a3c_loss_moa(policy, batch, seq_len=16, moa_weight=10.0, vf_loss_coeff=0.5, entropy_coeff=0.01,
+                                   obs_first=first)
+
+    CUDA tensors go to the library (ssd_policy_moa_ac_grad); CPU tensors run moa_forward, a3c_terms and moa_loss per set."""
+    if not isinstance(policy, ConvMOAPolicy):
+        raise ValueError("a3c_loss_moa is for a ConvMOAPolicy (a3c_loss and a3c_loss_recurrent are the other policies')")
+    hyper = (float(vf_loss_coeff), float(entropy_coeff), float(moa_weight))
+    t, (K, E, N), seq_len, dev = _a3c_prepare(policy, batch, obs_first, seq_len, hyper)
+    if hyper[2] < 0:
+        raise ValueError("moa_weight must be >= 0")
+    if N != policy.num_agents:
+        raise ValueError("the policy is for %d agents, the batch has %d" % (policy.num_agents, N))
+    t["state"], t["done"], t["prev_actions"] = _moa_tensors(policy, batch, K, E, N, seq_len, dev)
+    P, A = policy.num_sets, policy.num_actions
+    if dev.type == "cuda":
+        return _a3c_device(policy, t, (K, E, N), seq_len, hyper, MOA_A3C_STATS)
+    logits, value, moa = moa_forward(policy, _ppo_obs(t, K), t["prev_actions"], t["state"], t["done"], seq_len)
+    sums = [_set_sums(x, P) for x in a3c_terms(logits, value, t, *hyper[:2])]
+    acts = t["actions"].clamp(0, A - 1)
+    if P == 1:
+        ce = policy.moa_loss(moa, acts).reshape(1)
+    else:                                                             # set p's rows are agent p's: its N - 1 predictions
+        others = acts.long()[..., policy._others.to(dev)]             # [K, E, N, N-1]
+        ce = torch.stack([torch.nn.functional.cross_entropy(moa[:, :, p].reshape(-1, A), others[:, :, p].reshape(-1))
+                          for p in range(P)])
+    sums[0] = sums[0] + hyper[2] * ce
+    sums.append(ce)
+    return sums[0].sum(), {name: m.detach() for name, m in zip(MOA_A3C_STATS, sums)}
+
+
+def clip_grad_by_set_norm(policy, max_norm):
+    """tf.clip_by_global_norm of algorithms/a3c_causal.py:125-131, per weight set and in place on the parameters' .grad: each
+    agent's policy is its own graph in the reference, so each set is clipped on its own (torch.nn.utils.clip_grad_norm_ would
+    clip over all sets at once).  Set p's gradient is scaled by max_norm / max(norm_p, max_norm), norm_p the 2-norm over every
+    parameter's entry that set p reads.  Returns the [P] norms before clipping (the reference's grad_gnorm).  A parameter with
+    fewer entries than sets (unpack_gradient's case) counts in the norm of each set that reads it, and is scaled by the smallest
+    factor among them.  Parameters without a gradient are skipped."""
+    max_norm = float(max_norm)
+    if not np.isfinite(max_norm) or max_norm <= 0:
+        raise ValueError("max_norm must be finite and > 0")
+    P = policy.num_sets
+    grads = [g for g in (getattr(policy, name).grad for name, _, _ in policy.layout()) if g is not None]
+    if not grads:
+        raise ValueError("no parameter of the policy has a gradient")
+    sq = torch.zeros(P, dtype=grads[0].dtype, device=grads[0].device)
+    for g in grads:
+        sq = sq + g.reshape(g.shape[0], -1).square().sum(1).repeat(P // g.shape[0])      # set s reads entry s % entries
+    norms = sq.sqrt()
+    scale = max_norm / norms.clamp(min=max_norm)
+    for g in grads:
+        f = scale.reshape(P // g.shape[0], g.shape[0]).min(0).values
+        g.mul_(f.reshape((-1,) + (1,) * (g.dim() - 1)))
+    return norms
 
 
 # ---- the Watershed baselines' policy (include/ssd.h, WATERSHED POLICY ROLLOUTS; csrc/ssd_ws_policy.hip) ----
