@@ -16,8 +16,8 @@
 // is in a fixed order, so two calls on the same input agree bit for bit.  kModeFeatures stops after fc2 and writes its output
 // instead: the trunk of the recurrent policy (ssd_policy_lstm.hip).  kModeMoa runs fc_stack once per FC stack of the MOA
 // policy, with tanh for ReLU, on the same conv output and writes both outputs (ssd_policy_moa.hip).  This file also holds the
-// argument checks every policy entry point shares (check_policy_net, check_state_out, select_device; declared in
-// ssd_policy.hpp).
+// argument checks every policy entry point shares (check_policy_net, check_state_out, select_device), those of the six
+// loss-and-gradient entry points (check_policy_grad) and the BPTT calls' per-window helpers (declared in ssd_policy.hpp).
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -142,6 +142,65 @@ const char *check_policy_net(PolicyNet net, const float *weights, int32_t num_se
     if (num_sets != 1 && num_sets != num_agents) return "num_sets must be 1 or num_agents";
     if (num_actions < 1 || num_actions > SSD_POL_MAX_ACTIONS) return "num_actions must be 1..15";
     return nullptr;
+}
+
+const char *check_policy_grad(const GradCall &c) {
+    const bool bptt = c.net != kNetConvFc;
+    if (!c.weights) return "weights are required";
+    if (const char *why = check_policy_net(c.net, c.weights, c.num_sets, c.num_agents, c.num_actions, c.cell_size)) return why;
+    if (c.n_steps < 1 || c.num_envs < 1) return "n_steps and num_envs must be >= 1";
+    if (bptt && c.seq_len < 1) return "seq_len must be >= 1";
+    if ((int64_t)c.n_steps * c.num_envs * c.num_agents > INT32_MAX - 16)      // (row + 15 is an int)
+        return "n_steps * num_envs * num_agents must be at most 2^31 - 17";
+    if (!c.obs && !(c.obs_first && c.n_steps == 1)) return "obs is required (it may be null only with obs_first and n_steps 1)";
+    if (bptt && !c.state) return "state is required";
+    if (bptt && (reinterpret_cast<uintptr_t>(c.state) & 3u)) return "state must be 4-byte aligned";
+    if (c.net == kNetMoa && !c.prev_actions) return "prev_actions is required";
+    if (c.net == kNetMoa && (reinterpret_cast<uintptr_t>(c.prev_actions) & 3u)) return "prev_actions must be 4-byte aligned";
+    if (c.ac && (!c.actions || !c.advantages || !c.value_targets)) return "actions, advantages and value_targets are required";
+    if (!c.ac && (!c.actions || !c.logp_old || !c.advantages || !c.value_targets || !c.vf_preds))
+        return "actions, logp_old, advantages, value_targets and vf_preds are required";
+    if (!c.scratch || !c.grads || !c.stats) return "scratch, grads and stats are required";
+    if ((reinterpret_cast<uintptr_t>(c.scratch) & 7u) || (reinterpret_cast<uintptr_t>(c.stats) & 7u))
+        return "scratch and stats must be 8-byte aligned";
+    if (reinterpret_cast<uintptr_t>(c.grads) & 3u) return "grads must be 4-byte aligned";
+    if (!(isfinite(c.clip_param) && isfinite(c.vf_clip_param) && isfinite(c.vf_loss_coeff) && isfinite(c.entropy_coeff) &&
+          isfinite(c.kl_coeff)))
+        return "the hyper-parameters must be finite";
+    if (c.clip_param < 0.0 || c.vf_clip_param < 0.0) return "clip_param and vf_clip_param must be >= 0";
+    if (c.net == kNetMoa && (!isfinite(c.moa_weight) || c.moa_weight < 0.0)) return "moa_weight must be finite and >= 0";
+    if ((c.kl_coeff != 0.0) != (c.behaviour_logits != nullptr)) return "behaviour_logits must be given if and only if kl_coeff is not 0";
+    if (c.flags) return "flags must be 0";
+    return nullptr;
+}
+
+GradWindow grad_window(const uint8_t *obs_first, const uint8_t *obs, int k0, size_t step_rows) {
+    const size_t obs_step = step_rows * 675;
+    if (!obs_first) return {nullptr, obs + (size_t)k0 * obs_step};            // row k reads obs[k]: `rest` from step 0
+    if (k0 == 0) return {obs_first, obs};
+    return {obs + (size_t)(k0 - 1) * obs_step, obs + (size_t)k0 * obs_step};
+}
+
+hipError_t launch_window_features(PolicyArgs f, bool moa, const GradWindow &o, int steps, int num_envs, size_t step_floats, void *stream) {
+    const auto launch = moa ? launch_policy_moa_features : launch_policy_features;
+    if (!o.first) {
+        f.B = steps * num_envs; f.obs = o.rest;
+        return launch(f, stream);
+    }
+    f.B = num_envs; f.obs = o.first;
+    if (const hipError_t e = launch(f, stream)) return e;
+    if (steps == 1) return hipSuccess;
+    f.B = (steps - 1) * num_envs; f.obs = o.rest; f.feat += step_floats;
+    return launch(f, stream);
+}
+
+PpoGradArgs window_trunk_args(const PolicyArgs &f, const GradWindow &o, int trunk_floats, int groups, int set_rows, int step_rows,
+                              float *part_trunk, const float *dx, int accumulate) {
+    PpoGradArgs tg{};
+    tg.w = f.w; tg.P = f.P; tg.A = f.A; tg.N = f.N; tg.set_floats = trunk_floats; tg.w_pitch = f.set_floats; tg.G = groups;
+    tg.set_rows = set_rows; tg.step_rows = step_rows;
+    tg.obs_first = o.first; tg.obs = o.rest; tg.scratch = part_trunk; tg.dx = dx; tg.accumulate = accumulate;
+    return tg;
 }
 
 const char *check_state_out(const float *state_in, const float *state_out, size_t bytes) {

@@ -1,7 +1,7 @@
 // csrc/ssd_policy.hpp -- the policy kernels' argument blocks, their launchers and the argument checks every policy entry point
 // shares (host-readable; the device pieces the kernels share are in ssd_policy_device.hpp).  Used by ssd_policy.hip (trunk kernel,
-// ssd_policy_forward), ssd_policy_lstm.hip, ssd_policy_moa.hip, ssd_ws_policy.hip and ssd_capi.hip (the rollouts, which interleave
-// the launches with the step kernel).
+// ssd_policy_forward), ssd_policy_lstm.hip, ssd_policy_moa.hip, ssd_ws_policy.hip, ssd_capi.hip (the rollouts, which interleave
+// the launches with the step kernel) and the three gradient files (check_policy_grad and the BPTT calls' window helpers).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -124,6 +124,41 @@ int policy_fail(const char *msg);
 enum PolicyNet { kNetConvFc, kNetLstm, kNetMoa };
 const char *check_policy_net(PolicyNet net, const float *weights, int32_t num_sets, int32_t num_agents, int32_t num_actions,
                              int32_t cell_size = 0, const float *moa_scratch = nullptr);
+// What the six loss-and-gradient entry points (ssd_policy_{,lstm_,moa_}{ppo,ac}_grad) check alike, in the order callers have
+// always seen it reported: null = fine, else the error text.  kNetConvFc has no seq_len and no state, only kNetMoa has
+// prev_actions and moa_weight; the A3C calls (ac) pass no logp_old, vf_preds or behaviour_logits and zeros for the
+// hyper-parameters they do not have, which pass.
+struct GradCall {
+    PolicyNet net;
+    bool ac;
+    const float *weights;
+    int32_t num_sets, num_actions, cell_size, seq_len;
+    const uint8_t *obs_first, *obs;
+    const float *state;
+    const int32_t *prev_actions, *actions;
+    const float *logp_old, *advantages, *value_targets, *vf_preds, *behaviour_logits;
+    int32_t n_steps, num_envs, num_agents;
+    double clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff, moa_weight;
+    const float *scratch, *grads;
+    const double *stats;
+    uint32_t flags;
+};
+const char *check_policy_grad(const GradCall &c);
+
+// The BPTT calls' window of `steps` steps from step k0 of the fragment.  The observations its rows acted on (the shift of
+// include/ssd.h): `first` [E][N][675] for its step 0 and `rest` from step 1, or first null and `rest` from step 0.
+struct GradWindow {
+    const uint8_t *first, *rest;
+};
+GradWindow grad_window(const uint8_t *obs_first, const uint8_t *obs, int k0, size_t step_rows);
+// The features of the window's rows to f.feat, step_floats floats a step (f: w, P, A, N, set_floats, feat given): one launch of
+// launch_policy_features (moa: launch_policy_moa_features), two where `first` splits the rows.
+hipError_t launch_window_features(PolicyArgs f, bool moa, const GradWindow &o, int steps, int num_envs, size_t step_floats, void *stream);
+// The trunk's backward of the window from dx (launch_ppo_trunk_grad, launch_ppo_moa_stack_grad): its arguments, with f as above
+// and trunk_floats the floats of a partial set.
+PpoGradArgs window_trunk_args(const PolicyArgs &f, const GradWindow &o, int trunk_floats, int groups, int set_rows, int step_rows,
+                              float *part_trunk, const float *dx, int accumulate);
+
 // state_out may be state_in itself (in place) or a buffer that does not overlap its `bytes` bytes: null = fine
 const char *check_state_out(const float *state_in, const float *state_out, size_t bytes);
 // Makes device_id the calling thread's device unless it is already: hipSuccess, or hipSetDevice's error.

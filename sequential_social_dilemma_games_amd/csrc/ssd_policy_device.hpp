@@ -1,7 +1,8 @@
 // csrc/ssd_policy_device.hpp -- the device pieces the policy kernels are built from, each defined once: the LSTM gate GEMM, the
 // two cell rules and the cell update, the start rule and the loader of the h rows, the heads, the PPO loss terms of a row, the
 // action draw, and the conv-FC trunk (conv, fc1, fc2) on a tile.  Used by ssd_policy.hip (conv-FC), ssd_policy_grad.hip,
-// ssd_policy_lstm.hip, ssd_policy_lstm_grad.hip, ssd_policy_moa.hip, ssd_policy_moa_grad.hip and ssd_ws_policy.hip; the argument blocks stay in
+// ssd_policy_lstm.hip, ssd_policy_moa.hip, ssd_ws_policy.hip and ssd_bptt_device.hpp (the pieces of the BPTT gradient kernels,
+// through which ssd_policy_lstm_grad.hip and ssd_policy_moa_grad.hip reach these); the argument blocks stay in
 // ssd_policy.hpp, which host code reads too.  Every sum below is one chain in a fixed order, so a change here changes the
 // bits of every kernel that uses the piece, and the tests that compare kernels and paths bit for bit see it.
 //
@@ -50,18 +51,28 @@ __device__ __forceinline__ void lstm_gates(const float *s_in, const float *__res
 }
 
 // The two cell rules: the order of the four gate columns z0..z3 (bias added), and where c and h sit in a state's two rows.
+// kI, kJ, kF, kO: the columns of the input gate, the candidate, the forget gate and the output gate.  gates: the four
+// activations in column order as update forms them, which the BPTT kernels keep for the backward (ssd_bptt_device.hpp).
 struct RllibCell {                  // RLlib 0.7.6: gates i, j, f, o with forget bias 1; a state is (c, h)
     static constexpr int kRowC = 0, kRowH = 1;
+    static constexpr int kI = 0, kJ = 1, kF = 2, kO = 3;
     static __device__ __forceinline__ void update(float zi, float zj, float zf, float zo, float c, float *c2, float *h2) {
         *c2 = sigmoidf_(zf + 1.f) * c + sigmoidf_(zi) * tanhf(zj);
         *h2 = sigmoidf_(zo) * tanhf(*c2);
     }
+    static __device__ __forceinline__ void gates(float zi, float zj, float zf, float zo, float (&g)[4]) {
+        g[0] = sigmoidf_(zi); g[1] = tanhf(zj); g[2] = sigmoidf_(zf + 1.f); g[3] = sigmoidf_(zo);
+    }
 };
 struct KerasCell {                  // Keras: gates i, f, c~, o, no forget bias; a state is (h, c)
     static constexpr int kRowH = 0, kRowC = 1;
+    static constexpr int kI = 0, kF = 1, kJ = 2, kO = 3;
     static __device__ __forceinline__ void update(float zi, float zf, float zc, float zo, float c, float *c2, float *h2) {
         *c2 = sigmoidf_(zf) * c + sigmoidf_(zi) * tanhf(zc);
         *h2 = sigmoidf_(zo) * tanhf(*c2);
+    }
+    static __device__ __forceinline__ void gates(float zi, float zf, float zc, float zo, float (&g)[4]) {
+        g[0] = sigmoidf_(zi); g[1] = sigmoidf_(zf); g[2] = tanhf(zc); g[3] = sigmoidf_(zo);
     }
 };
 
@@ -188,8 +199,8 @@ __device__ __forceinline__ void heads(const Args &a, const float *s_h, int pitch
 // The loss terms of one row (include/ssd.h, PPO LOSS AND GRADIENTS), one thread per row: l = the row's logits 0..A-1 and its
 // value at A, act its action (already within 0 .. A-1), bl its behaviour logits or null.  The five terms are float32 and are
 // added to st (total, policy, vf, kl, entropy); d[0..A] receives d row_loss / d (logits, value) with the contract's derivatives
-// at the kinks.  Used by the PPO gradient kernels of the three policies (ssd_policy_grad.hip, ssd_policy_lstm_grad.hip,
-// ssd_policy_moa_grad.hip).
+// at the kinks.  Used by the PPO gradient kernels of the three policies (ssd_policy_grad.hip; bptt_policy_forward of
+// ssd_bptt_device.hpp for the recurrent and the MOA policy).
 struct PpoHyper {
     float clip, vf_clip, vf_coeff, ent_coeff, kl_coeff;
 };

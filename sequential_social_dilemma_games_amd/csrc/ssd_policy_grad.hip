@@ -376,27 +376,12 @@ int conv_fc_grad(int loss, const float *weights, int32_t num_sets, int32_t num_a
                  const float *vf_preds, const float *behaviour_logits, int32_t n_steps, int32_t num_envs, int32_t num_agents,
                  double clip_param, double vf_clip_param, double vf_loss_coeff, double entropy_coeff, double kl_coeff,
                  float *scratch, float *grads, double *stats, int32_t device_id, uint32_t flags, void *stream) {
-    using ssd::policy_fail;
     const bool ac = loss == ssd::kLossAc;
-    if (!weights) return policy_fail("weights are required");
-    if (const char *why = ssd::check_policy_net(ssd::kNetConvFc, weights, num_sets, num_agents, num_actions)) return policy_fail(why);
-    if (n_steps < 1 || num_envs < 1) return policy_fail("n_steps and num_envs must be >= 1");
+    const ssd::GradCall call{ssd::kNetConvFc, ac, weights, num_sets, num_actions, 0, 0, obs_first, obs, nullptr, nullptr, actions, logp_old,
+                             advantages, value_targets, vf_preds, behaviour_logits, n_steps, num_envs, num_agents, clip_param,
+                             vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff, 0.0, scratch, grads, stats, flags};
+    if (const char *why = ssd::check_policy_grad(call)) return ssd::policy_fail(why);
     const int64_t rows = (int64_t)n_steps * num_envs * num_agents;
-    if (rows > INT32_MAX - 16) return policy_fail("n_steps * num_envs * num_agents must be at most 2^31 - 17");   // (row + 15 is an int)
-    if (!obs && !(obs_first && n_steps == 1)) return policy_fail("obs is required (it may be null only with obs_first and n_steps 1)");
-    if (ac && (!actions || !advantages || !value_targets)) return policy_fail("actions, advantages and value_targets are required");
-    if (!ac && (!actions || !logp_old || !advantages || !value_targets || !vf_preds))
-        return policy_fail("actions, logp_old, advantages, value_targets and vf_preds are required");
-    if (!scratch || !grads || !stats) return policy_fail("scratch, grads and stats are required");
-    if ((reinterpret_cast<uintptr_t>(scratch) & 7u) || (reinterpret_cast<uintptr_t>(stats) & 7u))
-        return policy_fail("scratch and stats must be 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(grads) & 3u) return policy_fail("grads must be 4-byte aligned");
-    if (!(isfinite(clip_param) && isfinite(vf_clip_param) && isfinite(vf_loss_coeff) && isfinite(entropy_coeff) && isfinite(kl_coeff)))
-        return policy_fail("the hyper-parameters must be finite");
-    if (clip_param < 0.0 || vf_clip_param < 0.0) return policy_fail("clip_param and vf_clip_param must be >= 0");
-    if ((kl_coeff != 0.0) != (behaviour_logits != nullptr))
-        return policy_fail("behaviour_logits must be given if and only if kl_coeff is not 0");
-    if (flags) return policy_fail("flags must be 0");
     if (const int rc = ssd::policy_use_device(device_id)) return rc;
     GradArgs a{};
     a.w = weights; a.P = num_sets; a.A = num_actions; a.N = num_agents; a.set_floats = SSD_POL_SET_FLOATS(num_actions);

@@ -263,7 +263,7 @@ def test_bound_separates_the_gradient_from_a_near_miss(K_, T, E, mode, seed):
 
 
 # ---- would the bound notice a row lost or doubled in the split-K kernel's second pass? ----
-SPLIT_TENSORS = ("lstm_w", "lstm_b")                             # what ssd_lstm_dw_kernel writes
+SPLIT_TENSORS = ("lstm_w", "lstm_b")                             # what ssd_bptt_dw_kernel writes
 SPLIT_PROBES = ("second_chunks", "last_of_first_pass", "first_of_second_pass", "last_of_ragged_chunk", "window2_first", "window2_last")
 BRANCHES = ("clipped_pos", "clipped_neg", "open_pos", "open_neg", "vf_dead", "vf_live", "vf_clipped_live")
 _SPLIT_CACHE = {}

@@ -178,7 +178,7 @@ SPLIT_CASES = [("A", "ordinary", 64), ("A", "spotlight", 64), ("A", "spotlight",
 
 @pytest.mark.parametrize("shape,inputs,C_", SPLIT_CASES)
 def test_split_k_takes_a_second_chunk(shape, inputs, C_):
-    """ssd_lstm_dw_kernel's `chunk += S`: the first window holds more than SSD_RPPO_MAX_SPLITS chunks of a set's rows (A: P = 1,
+    """ssd_bptt_dw_kernel's `chunk += S`: the first window holds more than SSD_RPPO_MAX_SPLITS chunks of a set's rows (A: P = 1,
     2145 rows, 34 chunks, the last of 33 rows; B: P = N = 2, 2080 rows a set, 33 chunks, the last of 32 rows), the second window
     fewer chunks than splits (3 and 2), so most splits must keep what the first left."""
     splits, chunk = _capi.SSD_RPPO_MAX_SPLITS, _capi.SSD_RPPO_CHUNK

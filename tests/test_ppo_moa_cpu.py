@@ -345,7 +345,7 @@ def test_no_tensor_compares_against_nothing(case):
 
 
 # ---- would the bound notice a row lost or doubled in the split-K kernels' second pass? ----
-# what ssd_moa_dw_kernel (once per branch) and ssd_moa_dpred_kernel write
+# what ssd_bptt_dw_kernel (once per branch) and ssd_moa_dpred_kernel write
 SPLIT_TENSORS = ("lstm_kernel", "lstm_recurrent", "lstm_bias", "moa_kernel", "moa_recurrent", "moa_bias", "pred_w", "pred_b")
 SPLIT_PROBES = ("second_chunks", "last_of_first_pass", "first_of_second_pass", "last_of_ragged_chunk", "window2_first", "window2_last")
 BRANCHES = ("clipped_pos", "clipped_neg", "open_pos", "open_neg", "vf_dead", "vf_live", "vf_clipped_live")

@@ -176,7 +176,7 @@ def test_inputs_do_not_depend_on_where_the_float64_forward_runs():
 
 @pytest.mark.parametrize("shape", ["A", "B"])
 def test_split_k_takes_a_second_chunk(shape):
-    """`chunk += S` of ssd_moa_dw_kernel (both branches) and ssd_moa_dpred_kernel: the first window holds more than
+    """`chunk += S` of ssd_bptt_dw_kernel (both branches) and ssd_moa_dpred_kernel: the first window holds more than
     SSD_MPPO_MAX_SPLITS chunks of a set's rows (A: P = 1, N = 5, 2145 rows, 34 chunks, the last of 33 rows; B: P = N = 2, 2080
     rows a set, 33 chunks, the last of 32 rows, and one other agent: the partial prediction tile), the second window fewer chunks
     than splits (3 and 2), so most splits must keep what the first left.  Ordinary inputs: at MOA_WEIGHT one row lost or doubled
