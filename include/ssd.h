@@ -1002,6 +1002,50 @@ int ssd_policy_moa_ac_grad(const float *weights, int32_t num_sets, int32_t num_a
                            double moa_weight, float *scratch, float *grads, double *stats, int32_t device_id, uint32_t flags,
                            void *stream);
 
+/* ======================================================================================================================
+ * V-TRACE TARGETS -- what the IMPALA trainer (algorithms/impala_causal.py; RLlib 0.7.6's VTraceLoss) does between evaluating
+ * a fragment under the learner's current weights and its loss: vtrace.from_importance_weights (Espeholt et al. 2018) with
+ * discounts = (1 - done) * gamma, computed on the device from the [ring, ...] rings of the policy rollouts above
+ * (csrc/ssd_vtrace.hip).  Added after ABI 6 without a version bump: the call is additive.
+ *
+ * Lanes are trajectories: L = lanes (E * N for the rollouts' rings), lane l is column l of the [ring, L] rings.  Row k of a
+ * call is slot (step0 + k) % ring.  Every operation is one IEEE float64 operation in the order written here (no fused
+ * multiply-add); the two results are rounded to float32 once, when they are stored.  The truncation level of the trace
+ * coefficients (c bar) is fixed at 1, as in RLlib.  With K = n_steps and bootstrap = (double)bootstrap_value, walking
+ * k = K - 1 ... 0, per lane:
+ *   r       = (double)rew[k], or (double)rew[k] + bonus_weight * (double)bonus[k] with a bonus (multiply, then add)
+ *   disc    = 0.0 if done[k] != 0, else gamma
+ *   v       = (double)value[k]            rho = (double)rhos[k]
+ *   v_next  = bootstrap for k = K - 1, else (double)value[k + 1]
+ *   vs_next = bootstrap for k = K - 1, else the unrounded vs of row k + 1
+ *   delta   = min(clip_rho_threshold, rho) * ((r + disc * v_next) - v)
+ *   dc      = disc * min(1.0, rho)
+ *   acc     = delta + dc * (0.0 for k = K - 1, else the acc of row k + 1)
+ *   vs[k]            = (float)(v + acc)
+ *   pg_advantages[k] = (float)(min(clip_pg_rho_threshold, rho) * ((r + disc * vs_next) - v))
+ * value and bootstrap_value are the TARGET policy's (the learner's current weights), not what the rollout recorded; rhos is
+ * pi / mu of the taken actions, exp(logp_target - logp_behaviour), formed by the caller (the kernel computes no exp), assumed
+ * finite and >= 0.  done[k] != 0 says that the episode ended with step k and row k + 1 belongs to the next one.  NULL done:
+ * no episode ends.  NULL bootstrap_value: 0.  NULL bonus: none (bonus_weight is not read).  A threshold of +inf means no
+ * clip.  Inputs are assumed finite.
+ *
+ * One difference from the reference's trainer, on the caller's side: RLlib cuts the batch into sequences of T rows, drops each
+ * sequence's last row from the loss and bootstraps from that row's value.  Here every row of the call is a target row, as in
+ * every other call of this library; the reference's targets of one T-row sequence are this call on its first T - 1 rows with
+ * bootstrap_value = the current value of row T - 1.  There is no row mask.
+ *
+ * rew i32, bonus f32, value f32, rhos f32, done u8, vs f32 and pg_advantages f32 are [ring, L]; bootstrap_value f32 is [L];
+ * device pointers on device_id.  One launch on `stream`, no allocation, no synchronisation.  SSD_E_INVALID before any device
+ * call (ssd_vtrace_last_error says why) for lanes < 1, ring < 1, n_steps < 1 or > ring, step0 < 0, flags other than 0, a
+ * missing rew, value, rhos or output pointer, a gamma that is not finite, a threshold that is NaN or <= 0, a bonus with a
+ * bonus_weight that is not finite; SSD_E_DEVICE without a usable HIP device.
+ * ====================================================================================================================== */
+int ssd_vtrace(const int32_t *rew, const float *bonus, double bonus_weight, const float *value, const float *rhos,
+               const uint8_t *done, const float *bootstrap_value, int32_t lanes, int32_t ring, int32_t step0, int32_t n_steps,
+               double gamma, double clip_rho_threshold, double clip_pg_rho_threshold, uint32_t flags, float *vs,
+               float *pg_advantages, int32_t device_id, void *stream);
+const char *ssd_vtrace_last_error(void);   /* the calling thread's last ssd_vtrace error */
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,8 @@
     from sequential_social_dilemma_games_amd import ppo_loss_moa                # PPO + MOA loss for the MOA policy, with BPTT
     from sequential_social_dilemma_games_amd import a3c_loss, a3c_loss_recurrent, a3c_loss_moa   # the A3C loss, likewise
     from sequential_social_dilemma_games_amd import clip_grad_by_set_norm       # A3C's gradient clip, per weight set
+    from sequential_social_dilemma_games_amd import vtrace, evaluate_fragment   # IMPALA's V-trace targets of a fragment
+    from sequential_social_dilemma_games_amd import impala_loss, impala_loss_recurrent, impala_loss_moa   # the IMPALA loss
 
 Everything that steps an env goes through libssd_hip.so (include/ssd.h); importing this package does
 not load it, constructing an env does -- and fails loudly if it is missing.
@@ -39,12 +41,12 @@ def __getattr__(name):
         return EpisodeStats
     if name in ("ConvFCPolicy", "ConvLSTMPolicy", "ConvMOAPolicy", "WatershedLSTMPolicy", "ppo_loss", "ppo_loss_recurrent",
                 "ppo_loss_moa", "a3c_loss", "a3c_loss_recurrent", "a3c_loss_moa", "clip_grad_by_set_norm", "A3C_STATS",
-                "MOA_A3C_STATS"):
+                "MOA_A3C_STATS", "evaluate_fragment", "impala_loss", "impala_loss_recurrent", "impala_loss_moa"):
         from . import policy
         return getattr(policy, name)
-    if name == "compute_advantages":
-        from .postprocessing import compute_advantages
-        return compute_advantages
+    if name in ("compute_advantages", "vtrace"):
+        from . import postprocessing
+        return getattr(postprocessing, name)
     if name == "MapEnv":
         from .map_env import MapEnv
         return MapEnv

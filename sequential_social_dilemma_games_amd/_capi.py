@@ -247,7 +247,7 @@ SYMBOLS = ("ssd_create", "ssd_destroy", "ssd_reset", "ssd_step", "ssd_step_rando
            "ssd_policy_lstm_forward", "ssd_rollout_policy_lstm", "ssd_policy_moa_forward", "ssd_rollout_policy_moa",
            "ssd_ws_policy_forward", "ssd_ws_rollout_policy", "ssd_advantages", "ssd_advantages_last_error",
            "ssd_policy_ppo_grad", "ssd_policy_lstm_ppo_grad", "ssd_policy_moa_ppo_grad",
-           "ssd_policy_ac_grad", "ssd_policy_lstm_ac_grad", "ssd_policy_moa_ac_grad")
+           "ssd_policy_ac_grad", "ssd_policy_lstm_ac_grad", "ssd_policy_moa_ac_grad", "ssd_vtrace", "ssd_vtrace_last_error")
 # added after ABI 6 without a version bump (the calls are additive): a library built before them lacks them
 LSTM_SYMBOLS = ("ssd_policy_lstm_forward", "ssd_rollout_policy_lstm")
 MOA_SYMBOLS = ("ssd_policy_moa_forward", "ssd_rollout_policy_moa")
@@ -257,6 +257,7 @@ PPO_SYMBOLS = ("ssd_policy_ppo_grad",)
 LSTM_PPO_SYMBOLS = ("ssd_policy_lstm_ppo_grad",)
 MOA_PPO_SYMBOLS = ("ssd_policy_moa_ppo_grad",)
 A3C_SYMBOLS = ("ssd_policy_ac_grad", "ssd_policy_lstm_ac_grad", "ssd_policy_moa_ac_grad")
+VTRACE_SYMBOLS = ("ssd_vtrace", "ssd_vtrace_last_error")
 
 
 class SsdConfig(C.Structure):
@@ -369,9 +370,9 @@ def lib():
         L.ssd_policy_last_error.argtypes = []
         L.ssd_policy_last_error.restype = C.c_char_p
         L.ssd_rollout_policy.argtypes = [vp, vp, i32, vp, i32, i32] + [vp] * 7 + [i32, vp, u32, vp]
-        missing = [name for name in LSTM_SYMBOLS + MOA_SYMBOLS + WS_POLICY_SYMBOLS + ADVANTAGES_SYMBOLS + PPO_SYMBOLS + LSTM_PPO_SYMBOLS + MOA_PPO_SYMBOLS + A3C_SYMBOLS if not hasattr(L, name)]
+        missing = [name for name in LSTM_SYMBOLS + MOA_SYMBOLS + WS_POLICY_SYMBOLS + ADVANTAGES_SYMBOLS + PPO_SYMBOLS + LSTM_PPO_SYMBOLS + MOA_PPO_SYMBOLS + A3C_SYMBOLS + VTRACE_SYMBOLS if not hasattr(L, name)]
         if missing:
-            raise SsdError("%s lacks %s (built before the recurrent, MOA or Watershed policy calls, the advantages call or the PPO or A3C gradient calls): rebuild it with `python -c 'import "
+            raise SsdError("%s lacks %s (built before the recurrent, MOA or Watershed policy calls, the advantages call, the PPO or A3C gradient calls or the V-trace call): rebuild it with `python -c 'import "
                            "__graft_entry__ as g; g.build()'`" % (LIB_PATH, ", ".join(missing)))
         L.ssd_policy_lstm_forward.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, u32, vp]
         L.ssd_rollout_policy_lstm.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, vp, i32, i32] + [vp] * 8 + [i32, vp, u32, vp]
@@ -393,6 +394,9 @@ def lib():
                                               + [vp, vp, vp, i32, u32, vp])
         L.ssd_policy_moa_ac_grad.argtypes = ([vp, i32, i32, i32, i32] + [vp] * 8 + [i32, i32, i32] + [C.c_double] * 3
                                              + [vp, vp, vp, i32, u32, vp])
+        L.ssd_vtrace.argtypes = [vp, vp, C.c_double, vp, vp, vp, vp, i32, i32, i32, i32, C.c_double, C.c_double, C.c_double, u32, vp, vp, i32, vp]
+        L.ssd_vtrace_last_error.argtypes = []
+        L.ssd_vtrace_last_error.restype = C.c_char_p
         for name in SYMBOLS:
             getattr(L, name)
         if L.ssd_abi_version() != ABI_VERSION:
@@ -423,6 +427,12 @@ def advantages_check(rc):
     if rc != SSD_OK:
         msg = lib().ssd_advantages_last_error()
         raise SsdError("libssd_hip advantages call failed (%d): %s" % (rc, msg.decode() if msg else "?"))
+
+
+def vtrace_check(rc):
+    if rc != SSD_OK:
+        msg = lib().ssd_vtrace_last_error()
+        raise SsdError("libssd_hip V-trace call failed (%d): %s" % (rc, msg.decode() if msg else "?"))
 
 
 def check(rc, handle=None):

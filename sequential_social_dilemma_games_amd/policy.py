@@ -1218,6 +1218,240 @@ def a3c_loss_moa(policy, batch, *, seq_len, moa_weight, vf_loss_coeff, entropy_c
     return sums[0].sum(), {name: m.detach() for name, m in zip(MOA_A3C_STATS, sums)}
 
 
+# ---- the IMPALA loss of the three policies: V-trace targets under the current weights, then the A3C loss's path
+# ---- (include/ssd.h, V-TRACE TARGETS) ----
+
+def _fragment_tensors(policy, batch, obs_first, seq_len):
+    """What evaluate_fragment reads of the dict sample() returns, checked -> (t, (K, E, N), seq_len).  The observations must
+    reach one row further than a loss call's: the bootstrap reads obs[K - 1] (obs[K] without obs_first)."""
+    if not isinstance(batch, dict):
+        raise ValueError("batch must be the dict sample() returns")
+    acts, obs = batch.get("actions"), batch.get("obs")
+    if not isinstance(acts, torch.Tensor) or acts.dim() != 3 or acts.numel() == 0:
+        raise ValueError("actions must be an int32 tensor [K, E, N]")
+    K, E, N = (int(n) for n in acts.shape)
+    dev, P = acts.device, policy.num_sets
+    if P not in (1, N):
+        raise ValueError("the policy must have 1 or N = %d weight sets, not %d" % (N, P))
+    if (K + 1) * E * N > 2 ** 31 - 17:
+        raise ValueError("the fragment must have fewer than 2^31 - 17 rows")
+    if acts.dtype != torch.int32 or not acts.is_contiguous():
+        raise ValueError("actions must be a contiguous torch.int32 tensor")
+    need = K if obs_first is not None else K + 1
+    if (not isinstance(obs, torch.Tensor) or obs.dim() != 6 or obs.shape[0] < need or obs.dtype != torch.uint8 or obs.device != dev
+            or tuple(obs.shape[1:]) != (E, N, VIEW, VIEW, 3) or not obs.is_contiguous()):
+        raise ValueError("obs must be a contiguous uint8 tensor [R, %d, %d, 15, 15, 3] on %s with R >= %d: the bootstrap reads the "
+                         "observation after the last row" % (E, N, dev, need))
+    if obs_first is not None:
+        if (not isinstance(obs_first, torch.Tensor) or obs_first.dtype != torch.uint8 or obs_first.device != dev
+                or tuple(obs_first.shape) != (E, N, VIEW, VIEW, 3) or not obs_first.is_contiguous()):
+            raise ValueError("obs_first must be a contiguous uint8 tensor of shape %s on %s" % ((E, N, VIEW, VIEW, 3), dev))
+    if policy.conv_w.device != dev:
+        raise ValueError("the policy is on %s, the batch on %s" % (policy.conv_w.device, dev))
+    if dev.type not in ("cuda", "cpu"):
+        raise ValueError("the tensors must be on the CPU or on a GPU, not on %s" % (dev,))
+    if dev.type == "cuda" and policy.conv_w.dtype != torch.float32:
+        raise ValueError("the device path needs a float32 policy")
+    t = {"actions": acts, "obs": obs, "obs_first": obs_first}
+    if isinstance(policy, ConvFCPolicy):
+        return t, (K, E, N), None
+    if seq_len is None or isinstance(seq_len, bool) or int(seq_len) != seq_len or int(seq_len) < 1:
+        raise ValueError("seq_len must be an integer >= 1")
+    seq_len = int(seq_len)
+    if isinstance(policy, ConvMOAPolicy):
+        if N != policy.num_agents:
+            raise ValueError("the policy is for %d agents, the batch has %d" % (policy.num_agents, N))
+        t["state"], t["done"], t["prev_actions"] = _moa_tensors(policy, batch, K, E, N, seq_len, dev)
+    else:
+        t["state"], t["done"] = _recurrent_tensors(policy, batch, K, E, N, seq_len, dev)
+    return t, (K, E, N), seq_len
+
+
+def _evaluate_device(policy, t, dims, T):
+    """evaluate_fragment through the library's forward entry points on torch's current stream, rows 0 .. K - 1 and the
+    bootstrap as row K of one allocation."""
+    import ctypes as C
+    K, E, N = dims
+    A, P, dev = policy.num_actions, policy.num_sets, t["actions"].device
+    weights = policy.packed()
+    logits = torch.empty((K + 1, E, N, A), dtype=torch.float32, device=dev)
+    value = torch.empty((K + 1, E, N), dtype=torch.float32, device=dev)
+    ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())   # noqa: E731
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    L = _capi.lib()
+    obs, first = t["obs"], t["obs_first"]
+    if isinstance(policy, ConvFCPolicy):                          # one launch, or two: obs_first's row, then obs[0 .. K - 1]
+        if first is None:
+            calls = ((obs, (K + 1) * E, logits, value),)
+        else:
+            calls = ((first, E, logits[0], value[0]), (obs, K * E, logits[1:], value[1:]))
+        for o, B, lg, v in calls:
+            _capi.policy_check(L.ssd_policy_forward(ptr(weights), P, A, ptr(o), B, N, ptr(lg), ptr(v), index, 0, stream))
+        return logits[:K], value[:K], value[K]
+    moa = isinstance(policy, ConvMOAPolicy)
+    Cs, done = policy.cell_size, t["done"]
+    need = int(np.prod(policy.scratch_shape(E * N)))
+    scratch = getattr(policy, "_eval_scratch", None)              # kept between calls, as _ppo_scratch is
+    if scratch is None or scratch.device != dev or scratch.numel() < need:
+        scratch = policy._eval_scratch = torch.empty(need, dtype=torch.float32, device=dev)
+    carry = torch.empty((E, N, policy.STATE_ROWS, Cs), dtype=torch.float32, device=dev)
+    for k in range(K + 1):                                        # one launch per step; row K is the bootstrap
+        boot = k == K
+        o = obs[k] if first is None else (first if k == 0 else obs[k - 1])
+        if not boot and k % T == 0:
+            s_in, starts = t["state"][k // T], None               # the ring's entry, as stored
+        else:
+            s_in, starts = carry, (None if done is None else done[k - 1])
+        s_out, lg = (None, None) if boot else (carry, logits[k])
+        if moa:
+            prev = t["actions"][K - 1] if boot else t["prev_actions"][k]
+            rc = L.ssd_policy_moa_forward(ptr(weights), P, A, Cs, ptr(o), ptr(prev), ptr(s_in), ptr(starts), E, N, ptr(scratch),
+                                          ptr(s_out), ptr(lg), ptr(value[k]), None, None, None, None, 0.0, index, 0, stream)
+        else:
+            rc = L.ssd_policy_lstm_forward(ptr(weights), P, A, Cs, ptr(o), ptr(s_in), ptr(starts), E, N, ptr(scratch), ptr(s_out),
+                                           ptr(lg), ptr(value[k]), index, 0, stream)
+        _capi.policy_check(rc)
+    return logits[:K], value[:K], value[K]
+
+
+def _evaluate_host(policy, t, dims, T):
+    """evaluate_fragment in plain torch: the loss calls' forwards window by window, and one more step for the bootstrap."""
+    K, E, N = dims
+    obs, first, dt = t["obs"], t["obs_first"], policy.conv_w.dtype
+    rows = obs[:K] if first is None else _ppo_obs(t, K)
+    last = obs[K] if first is None else obs[K - 1]
+    if isinstance(policy, ConvFCPolicy):
+        logits, value = policy(rows)
+        return logits, value, policy(last)[1]
+    moa = isinstance(policy, ConvMOAPolicy)
+    done, logits, value, st = t["done"], [], [], None
+    for w, k0 in enumerate(range(0, K, T)):
+        k1 = min(k0 + T, K)
+        resets = None
+        if done is not None and k1 - k0 > 1:
+            resets = torch.cat([torch.zeros_like(done[:1]), done[k0:k1 - 1]]).to(torch.bool)
+        args = (rows[k0:k1], t["prev_actions"][k0:k1]) if moa else (rows[k0:k1],)
+        out = policy.forward_sequence(*args, t["state"][w].to(dt), resets)
+        logits.append(out[0])
+        value.append(out[1])
+        st = out[-1]
+    starts = None if done is None else done[K - 1].to(torch.bool)
+    boot = policy(last, t["actions"][K - 1], st, starts)[1] if moa else policy(last, st, starts)[1]
+    return torch.cat(logits), torch.cat(value), boot
+
+
+def evaluate_fragment(policy, batch, obs_first=None, seq_len=None):
+    """A sampled fragment under the policy's CURRENT weights -> (logits [K,E,N,A], value [K,E,N], bootstrap_value [E,N]),
+    without gradient: what V-trace needs of the target policy (postprocessing.vtrace) when the weights have moved since
+    sample() ran.  Row k reads obs_first for k = 0 and obs[k - 1] otherwise (the loss calls' shift, by address; obs_first None:
+    row k reads obs[k]), and bootstrap_value is the value of the observation after the last row: obs[K - 1], which this call
+    does read (obs[K] without obs_first).
+
+    batch: the dict sample() returns.  ConvFCPolicy: "obs" and "actions" (for the shape), seq_len unused.  ConvLSTMPolicy and
+    ConvMOAPolicy: seq_len = T and the keys of ppo_loss_recurrent / ppo_loss_moa ("state", "done", "prev_actions"), under the
+    state rule of include/ssd.h (RECURRENT PPO LOSS AND GRADIENTS): step k uses state[k // T] as stored when k % T == 0, else
+    the state step k - 1 computed, zero where done[k - 1]; the bootstrap row uses the carried state with the start rule of
+    done[K - 1], never a ring entry.  The MOA policy reads prev_actions[k] as stored (actions[K - 1] for the bootstrap row,
+    whose value does not depend on it).
+    CUDA tensors go to the library's forward entry points on torch's current stream, no synchronisation: one or two launches
+    of ssd_policy_forward for the whole fragment, K + 1 launches of ssd_policy_lstm_forward / ssd_policy_moa_forward (their
+    feature scratch is kept on the policy).  With unchanged weights on a fresh sample(..., state_every=T) they give back
+    batch["value"] and batch["last_value"] to the bit.  CPU tensors run the modules' forwards under no_grad."""
+    if not isinstance(policy, (ConvFCPolicy, ConvLSTMPolicy, ConvMOAPolicy)):
+        raise ValueError("evaluate_fragment is for a ConvFCPolicy, ConvLSTMPolicy or ConvMOAPolicy")
+    t, dims, T = _fragment_tensors(policy, batch, obs_first, seq_len)
+    with torch.no_grad():
+        if t["actions"].device.type == "cuda":
+            return _evaluate_device(policy, t, dims, T)
+        return _evaluate_host(policy, t, dims, T)
+
+
+def _impala_targets(policy, batch, obs_first, seq_len, gamma, clip_rho_threshold, clip_pg_rho_threshold, bonus_key=None,
+                    bonus_weight=1.0):
+    """Steps 1 to 3 of the IMPALA calls -> the batch with "advantages" = pg_advantages and "value_targets" = vs (data)."""
+    from .postprocessing import vtrace
+    if not isinstance(batch, dict):
+        raise ValueError("batch must be the dict sample() returns")
+    for key in ("logp", "rew") + ((bonus_key,) if bonus_key else ()):
+        if not isinstance(batch.get(key), torch.Tensor):
+            raise ValueError("%s is required" % key)
+    logits, value, boot = evaluate_fragment(policy, batch, obs_first, seq_len)
+    acts, logp = batch["actions"], batch["logp"]
+    if logp.dtype != torch.float32 or tuple(logp.shape) != tuple(acts.shape) or logp.device != acts.device:
+        raise ValueError("logp must be a torch.float32 tensor of shape %s on %s" % (tuple(acts.shape), acts.device))
+    with torch.no_grad():
+        a = acts.long().clamp(0, logits.shape[-1] - 1).unsqueeze(-1)
+        logp_target = torch.log_softmax(logits, dim=-1).gather(-1, a).squeeze(-1)      # float32 torch for a float32 policy
+        rhos = torch.exp(logp_target - logp).float()
+        vs, pg = vtrace(batch["rew"], value.float().contiguous(), rhos, boot.float().contiguous(), batch.get("done"), gamma=gamma,
+                        clip_rho_threshold=clip_rho_threshold, clip_pg_rho_threshold=clip_pg_rho_threshold,
+                        bonus=batch[bonus_key] if bonus_key else None, bonus_weight=bonus_weight)
+    return dict(batch, advantages=pg, value_targets=vs)
+
+
+def impala_loss(policy, batch, *, gamma=0.99, vf_loss_coeff=0.5, entropy_coeff=0.01, clip_rho_threshold=1.0,
+                clip_pg_rho_threshold=1.0, obs_first=None):
+    """The reference's IMPALA loss (algorithms/impala_causal.py; RLlib 0.7.6's VTraceLoss) of a ConvFCPolicy on a sampled
+    fragment -> (loss, stats), as a3c_loss: -sum logp * pg_advantages + vf_loss_coeff * 0.5 sum (value - vs)^2 - entropy_coeff
+    * sum entropy, where vs and pg_advantages are the V-trace targets (stop-gradient data) of the fragment under the policy's
+    CURRENT weights.  For a learner whose weights have moved since the fragment was sampled: several passes over one
+    fragment, or actors that lag the learner.
+
+        first = env.reset().clone()
+        batch = env.sample(policy, 128)
+        for _ in range(passes):
+            loss, stats = impala_loss(policy, batch, gamma=0.99, vf_loss_coeff=0.5, entropy_coeff=0.01, obs_first=first)
+            optimiser.zero_grad(); loss.backward(); clip_grad_by_set_norm(policy, 40.0); optimiser.step()
+
+    The call is (1) evaluate_fragment, (2) logp_target = log_softmax(logits)[a] and rhos = exp(logp_target - batch["logp"]) in
+    float32 torch, (3) postprocessing.vtrace(batch["rew"], value, rhos, bootstrap_value, batch["done"], ...), (4) a3c_loss's
+    path with advantages = pg_advantages and value_targets = vs; stats are A3C_STATS.  batch: the dict sample() returns, of
+    which obs (one row further than a3c_loss reads: the bootstrap's), actions, logp, rew and, where present, done are read;
+    the recorded value, last_value, advantages and value_targets are not.  obs_first and minibatches: as ppo_loss.
+    One difference from the reference: RLlib cuts the batch into sequences of T rows, drops each sequence's last row from the
+    loss and bootstraps from its value; here every row is a loss row and the bootstrap is the current value of the
+    observation after the fragment (include/ssd.h, V-TRACE TARGETS).  There is no row mask.
+    CUDA tensors stay on the device, on torch's current stream without a host synchronisation."""
+    if not isinstance(policy, ConvFCPolicy):
+        raise ValueError("impala_loss is for a ConvFCPolicy (impala_loss_recurrent and impala_loss_moa are the other policies')")
+    batch = _impala_targets(policy, batch, obs_first, None, gamma, clip_rho_threshold, clip_pg_rho_threshold)
+    return a3c_loss(policy, batch, vf_loss_coeff=vf_loss_coeff, entropy_coeff=entropy_coeff, obs_first=obs_first)
+
+
+def impala_loss_recurrent(policy, batch, *, seq_len, gamma=0.99, vf_loss_coeff=0.5, entropy_coeff=0.01, clip_rho_threshold=1.0,
+                          clip_pg_rho_threshold=1.0, obs_first=None):
+    """impala_loss for a ConvLSTMPolicy, with truncated BPTT over windows of seq_len steps as a3c_loss_recurrent -> (loss,
+    stats).  The evaluation under the current weights follows the same state rule as the loss (evaluate_fragment): K + 1
+    forward launches on the device.  The batch's keys ("state", "done") and the minibatch slices are ppo_loss_recurrent's.
+
+        batch = env.sample(policy, 128, state_every=16)
+        loss, stats = impala_loss_recurrent(policy, batch, seq_len=16, gamma=0.99, vf_loss_coeff=0.5, entropy_coeff=0.01,
+                                            clip_rho_threshold=1.0, clip_pg_rho_threshold=1.0, obs_first=first)"""
+    if not isinstance(policy, ConvLSTMPolicy):
+        raise ValueError("impala_loss_recurrent is for a ConvLSTMPolicy (impala_loss is the ConvFCPolicy's)")
+    batch = _impala_targets(policy, batch, obs_first, seq_len, gamma, clip_rho_threshold, clip_pg_rho_threshold)
+    return a3c_loss_recurrent(policy, batch, seq_len=seq_len, vf_loss_coeff=vf_loss_coeff, entropy_coeff=entropy_coeff,
+                              obs_first=obs_first)
+
+
+def impala_loss_moa(policy, batch, *, seq_len, moa_weight, influence_weight=1.0, gamma=0.99, vf_loss_coeff=0.5, entropy_coeff=0.01,
+                    clip_rho_threshold=1.0, clip_pg_rho_threshold=1.0, obs_first=None):
+    """The causal-influence trainer's IMPALA loss for a ConvMOAPolicy: impala_loss_recurrent's terms + moa_weight * MOALoss as
+    a3c_loss_moa -> (loss, stats), stats MOA_A3C_STATS.  The V-trace reward is rew + influence_weight * batch["influence"]
+    (the reference's causal_postprocess_trajectory), formed in float64 inside the scan.  The batch's keys ("state", "done",
+    "prev_actions", and "influence") and the minibatch slices are ppo_loss_moa's.
+
+        batch = env.sample(policy, 128, state_every=16)
+        loss, stats = impala_loss_moa(policy, batch, seq_len=16, moa_weight=10.0, influence_weight=1.0, obs_first=first)"""
+    if not isinstance(policy, ConvMOAPolicy):
+        raise ValueError("impala_loss_moa is for a ConvMOAPolicy (impala_loss and impala_loss_recurrent are the other policies')")
+    batch = _impala_targets(policy, batch, obs_first, seq_len, gamma, clip_rho_threshold, clip_pg_rho_threshold, "influence",
+                            influence_weight)
+    return a3c_loss_moa(policy, batch, seq_len=seq_len, moa_weight=moa_weight, vf_loss_coeff=vf_loss_coeff,
+                        entropy_coeff=entropy_coeff, obs_first=obs_first)
+
+
 def clip_grad_by_set_norm(policy, max_norm):
     """tf.clip_by_global_norm of algorithms/a3c_causal.py:125-131, per weight set and in place on the parameters' .grad: each
     agent's policy is its own graph in the reference, so each set is clipped on its own (torch.nn.utils.clip_grad_norm_ would
