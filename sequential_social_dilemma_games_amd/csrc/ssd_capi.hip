@@ -78,14 +78,14 @@ struct AqlState {
     uint32_t *timed_out_host = nullptr, *timed_out_dev = nullptr;
     struct Key {
         const void *obs = nullptr, *rew = nullptr, *done = nullptr;
-        int32_t ring = 0, f32 = 0, num_actions = 0, chains = 0, horizon = 0, coherent = 0, split = 0;
+        int32_t ring = 0, f32 = 0, num_actions = 0, chains = 0, horizon = 0, coherent = 0, split = 0, pairs = 0;
         const void *actions = nullptr, *order = nullptr; int32_t action_ring = 0;  // caller-supplied actions: part of every step launch's arguments
         int32_t slots = 0;                                       // argument blocks per chain and kind: lcm(ring, action_ring)
         const void *stamps = nullptr; uint32_t dbg_skip = 0;     // (diagnostic builds: part of the kernel arguments too)
         const void *world = nullptr;                             // sets that are not split: the state buffer their blocks name
         bool operator==(const Key &o) const {
             return stamps == o.stamps && dbg_skip == o.dbg_skip && world == o.world && obs == o.obs && rew == o.rew && done == o.done && ring == o.ring && f32 == o.f32 && num_actions == o.num_actions &&
-                   chains == o.chains && horizon == o.horizon && coherent == o.coherent && split == o.split && actions == o.actions && order == o.order &&
+                   chains == o.chains && horizon == o.horizon && coherent == o.coherent && split == o.split && pairs == o.pairs && actions == o.actions && order == o.order &&
                    action_ring == o.action_ring && slots == o.slots;
         }
     };
@@ -95,7 +95,7 @@ struct AqlState {
         Key key;
         uint8_t *dev = nullptr;                     // [chains][slots][kKinds] blocks of kBlock bytes
         size_t cap = 0;
-        Geo geo[8][12];                             // per chain and kind (kKinds: asserted below)
+        Geo geo[8][22];                             // per chain and kind (kKinds: asserted below)
         uint64_t last_use[8] = {};                  // index of the last join packet after a use, per chain (+1)
         uint64_t stamp = 0;
     };
@@ -105,17 +105,26 @@ struct AqlState {
     //   kRn  reset that renders nothing (inside a split rollout), in place
     //   kA   the first step of a split rollout: env waves only                        kAB  env waves + renderer workgroups for the step before
     //   kB   renderer workgroups only, for the step that produced buffer o (ends a split rollout, and precedes a reset inside one)
-    enum Kind { kS = 0, kR = 1, kRn = 2, kA = 3, kAB = 4, kB = 5, kKindsPerO = 6, kKinds = 12 };
+    // Step pairs (key.pairs; the step-pair kernel, ssd::kModeStepPair): a launch whose env waves take two steps -- block i then
+    // serves steps i and i + 1 -- and the launches that follow one, whose renderer workgroups deliver both steps' observations:
+    //   kP   pair, env waves only             kPB  pair + renderers for the single step before      kPBB  pair + renderers for the pair before
+    //   kABB single step + renderers for the pair before (an odd remainder, the step ahead of a reset)
+    //   kBB  renderer workgroups only, for the pair that produced buffer o
+    enum Kind { kS = 0, kR = 1, kRn = 2, kA = 3, kAB = 4, kB = 5, kP = 6, kPB = 7, kPBB = 8, kABB = 9, kBB = 10, kKindsPerO = 11, kKinds = 22 };
     static_assert(sizeof(Set::geo[0]) / sizeof(Geo) == kKinds, "Set::geo holds one entry per kind");
     uint8_t *world_buf[2] = {};                     // split rollouts: the pair of state buffers ([0]: the handle's original ones)
     uint32_t *agents_buf[2] = {};
     uint32_t *beam_list[2] = {};                    // [2][E][64] beam marks left by a launch of orientation o (second half: a second pass's)
     uint8_t *snap_grid[2] = {};                     // [E][S] overlay snapshot left by a launch of orientation o (rare steps)
+    // the same four for what the FIRST step of a pair launch of orientation o left (read by the next launch's renderers alone)
+    uint8_t *mid_world[2] = {}, *mid_snap[2] = {};
+    uint32_t *mid_agents[2] = {}, *mid_list[2] = {};
     static constexpr int kSets = 4;
-    static constexpr size_t kBlock = 512;           // >= sizeof(ssd::KernArgs), a multiple of 64
+    static constexpr size_t kBlock = 640;           // >= sizeof(ssd::PairKernArgs), a multiple of 64
     Set sets[kSets];
     uint64_t clock = 0;
 };
+static_assert(AqlState::kBlock >= sizeof(ssd::PairKernArgs), "an argument block holds the largest kernarg segment");
 
 struct ssd_env {
     int game = 0, H = 0, W = 0, WP = 0, S = 0, E = 0, N = 0, view_len = 7, V = 15, beam_len = 5;
@@ -733,6 +742,8 @@ static void aql_teardown(ssd_env *env) {
     for (int i = 0; i < 2; ++i) { if (A.snap_grid[i]) (void)hipFree(A.snap_grid[i]); if (A.beam_list[i]) (void)hipFree(A.beam_list[i]); }
     if (A.world_buf[1]) (void)hipFree(A.world_buf[1]);
     if (A.agents_buf[1]) (void)hipFree(A.agents_buf[1]);
+    for (int i = 0; i < 2; ++i)
+        for (void *m : {(void *)A.mid_world[i], (void *)A.mid_snap[i], (void *)A.mid_agents[i], (void *)A.mid_list[i]}) if (m) (void)hipFree(m);
     env->aql.reset();
 }
 
@@ -796,23 +807,30 @@ static inline void aql_wait_consumed(ssd::aql::Queue *q, uint64_t idx_plus_1) {
     while (idx_plus_1 && ssd::aql::read_index(q) < idx_plus_1 && !ssd::aql::queue_failed(q)) __builtin_ia32_pause();
 }
 
-// The second state buffers and the render side buffers of split rollouts, once per handle: all six or none.
+// The second state buffers, the render side buffers of split rollouts and the two `mid` sets of step pairs, once per handle: all
+// fourteen or none.
 static bool aql_split_buffers(ssd_env *env) {
     AqlState &A = *env->aql;
-    if (A.world_buf[1] && A.agents_buf[1] && A.snap_grid[0] && A.snap_grid[1] && A.beam_list[0] && A.beam_list[1]) return true;
-    const size_t sizes[6] = {(size_t)env->E * env->S, (size_t)env->E * (env->N ? env->N : 1) * 4, (size_t)env->E * env->S, (size_t)env->E * env->S,
-                             (size_t)env->E * 128 * 4, (size_t)env->E * 128 * 4};     // (beam lists: [E][64] + a second [E][64] for steps whose beams took two passes)
-    void *buf[6] = {};
-    for (int i = 0; i < 6; ++i)
+    if (A.world_buf[1]) return true;                                // (set last, below)
+    const size_t grid = (size_t)env->E * env->S, agents = (size_t)env->E * (env->N ? env->N : 1) * 4;
+    const size_t lists = (size_t)env->E * 128 * 4;                  // (beam lists: [E][64] + a second [E][64] for steps whose beams took two passes)
+    const size_t sizes[14] = {grid, agents, grid, grid, lists, lists, grid, grid, grid, grid, agents, agents, lists, lists};
+    void *buf[14] = {};
+    for (int i = 0; i < 14; ++i)
         if (hipMalloc(&buf[i], sizes[i]) != hipSuccess) {
             (void)hipGetLastError();
             for (int j = 0; j < i; ++j) (void)hipFree(buf[j]);
             return false;
         }
     A.world_buf[0] = env->p.world; A.agents_buf[0] = env->p.agents;
-    A.world_buf[1] = static_cast<uint8_t *>(buf[0]); A.agents_buf[1] = static_cast<uint32_t *>(buf[1]);
+    A.agents_buf[1] = static_cast<uint32_t *>(buf[1]);
     A.snap_grid[0] = static_cast<uint8_t *>(buf[2]); A.snap_grid[1] = static_cast<uint8_t *>(buf[3]);
     A.beam_list[0] = static_cast<uint32_t *>(buf[4]); A.beam_list[1] = static_cast<uint32_t *>(buf[5]);
+    for (int i = 0; i < 2; ++i) {
+        A.mid_world[i] = static_cast<uint8_t *>(buf[6 + i]); A.mid_snap[i] = static_cast<uint8_t *>(buf[8 + i]);
+        A.mid_agents[i] = static_cast<uint32_t *>(buf[10 + i]); A.mid_list[i] = static_cast<uint32_t *>(buf[12 + i]);
+    }
+    A.world_buf[1] = static_cast<uint8_t *>(buf[0]);
     return true;
 }
 
@@ -845,10 +863,12 @@ static AqlState::Set *aql_set(ssd_env *env, const AqlState::Key &key, int chains
             const int r = i % key.ring;
             for (int kind = 0; kind < kKinds; ++kind) {
                 const int o = kind / AqlState::kKindsPerO, base = kind % AqlState::kKindsPerO;
-                const bool split_kind = base >= AqlState::kRn;
+                const bool split_kind = base >= AqlState::kRn, pair_kind = base >= AqlState::kP;
                 if (split_kind && !key.split) continue;
+                if (pair_kind && !key.pairs) continue;
                 if (!key.split && o == 1) continue;              // (without the pair there is one orientation)
                 Params p = cur.p;
+                ssd::PairParams q{};
                 if (key.split) { p.world = A.world_buf[o]; p.agents = A.agents_buf[o]; }     // the launch reads buffer o
                 p.obs = cur.obs ? cur.obs + (size_t)r * cur.ob : nullptr;
                 // (test hook: launches of orientation 1 use the other geometry)
@@ -861,7 +881,30 @@ static AqlState::Set *aql_set(ssd_env *env, const AqlState::Key &key, int chains
                     p.mode = ssd::kModeStep; p.rotate = 1;
                     cursor_actions(cur, p, (size_t)i);
                     p.rew = cur.rew ? cur.rew + (size_t)r * cur.en : nullptr; p.done = cur.done ? cur.done + (size_t)r * cur.en : nullptr;
-                    if (base >= AqlState::kA) {
+                    if (pair_kind) {
+                        // Block i serves steps i and i + 1 (output slots r and r1, action slots likewise).  The env waves read buffer o,
+                        // leave their first step in mid set o and their second in buffer 1 - o with its marks in list o, as a single
+                        // step's.  The renderer workgroups deliver the launch before (orientation 1 - o): a pair's first step from mid
+                        // set 1 - o, its second -- or a single step -- from buffer o and list 1 - o; into the slots before r (kBB: the
+                        // pair is this block's own: slots r and r1).
+                        const int r1 = (r + 1) % key.ring, rm1 = (r + key.ring - 1) % key.ring, rm2 = (r + 2 * key.ring - 2) % key.ring;
+                        auto slot_obs = [&](int sl) { return cur.obs ? cur.obs + (size_t)sl * cur.ob : nullptr; };
+                        const bool env_two = base == AqlState::kP || base == AqlState::kPB || base == AqlState::kPBB;
+                        const bool render_two = base == AqlState::kPBB || base == AqlState::kABB || base == AqlState::kBB;
+                        p.mode = ssd::kModeStepPair;
+                        p.obs = nullptr;
+                        p.snap_mode = (base == AqlState::kBB ? 4 : 1) | (base != AqlState::kP ? 2 : 0) | (render_two ? 8 : 0) | (env_two ? 0 : 16);
+                        p.world_out = A.world_buf[1 - o]; p.agents_out = A.agents_buf[1 - o];
+                        p.beam_list = A.beam_list[o]; p.snap = A.snap_grid[o];
+                        p.beam_list_in = A.beam_list[1 - o]; p.snap_in = A.snap_grid[1 - o];
+                        q.world_mid = A.mid_world[o]; q.agents_mid = A.mid_agents[o]; q.beam_list_mid = A.mid_list[o]; q.snap_mid = A.mid_snap[o];
+                        q.world_mid_in = A.mid_world[1 - o]; q.agents_mid_in = A.mid_agents[1 - o]; q.beam_list_mid_in = A.mid_list[1 - o];
+                        q.snap_mid_in = A.mid_snap[1 - o];
+                        p.obs_b = slot_obs(base == AqlState::kBB ? r1 : rm1);
+                        q.obs_b0 = slot_obs(base == AqlState::kBB ? r : rm2);
+                        q.actions2 = cur.actions ? cur.actions + ((size_t)(i + 1) % (size_t)cur.action_ring) * cur.en : nullptr;
+                        q.rew2 = cur.rew ? cur.rew + (size_t)r1 * cur.en : nullptr; q.done2 = cur.done ? cur.done + (size_t)r1 * cur.en : nullptr;
+                    } else if (base >= AqlState::kA) {
                         // env waves: read buffer o, write buffer 1 - o, leave their beam marks in list o.  Renderer workgroups of
                         // a kAB launch: the step before produced buffer o (a launch of orientation 1 - o: its marks are in list
                         // 1 - o), its observations go to the ring slot before this one; of a kB launch: the same for THIS slot.
@@ -879,13 +922,13 @@ static AqlState::Set *aql_set(ssd_env *env, const AqlState::Key &key, int chains
                     }
                 }
                 ssd::Launch L;
-                if (!ssd::select(p, env->game, &L)) return nullptr;
+                if (!ssd::select(p, env->game, &L, &q)) return nullptr;
                 AqlState::Geo &g = st.geo[c][kind];
                 if (i == 0) {
                     if (!ssd::aql::lookup(env->device, L.fn, &g.k) || g.k.kernarg_size > AqlState::kBlock || g.k.kernarg_size < sizeof(ssd::KernArgs)) return nullptr;
                     g.grid_x = L.grid_x; g.block_x = L.block_x; g.lds = L.lds;
                 }
-                std::memcpy(host.data() + (((size_t)c * key.slots + i) * kKinds + kind) * AqlState::kBlock, &L.args, sizeof(ssd::KernArgs));
+                std::memcpy(host.data() + (((size_t)c * key.slots + i) * kKinds + kind) * AqlState::kBlock, &L.args, L.args_bytes());
             }
         }
     }
@@ -910,7 +953,7 @@ static int rollout_aql(ssd_env *env, int chains, const ChainJob *jobs, hipStream
     {   // one argument block per chain, kind and residue of the step index modulo lcm(output ring, action ring)
         const long long ar = key.action_ring > 0 ? key.action_ring : 1;
         const long long l = (long long)key.ring / gcd_i(key.ring, (int)ar) * ar;
-        if (l * chains > 2048) return 1;                            // (12 x 512 B per chain and block index)
+        if (l * chains > 2048) return 1;                            // (22 x 640 B per chain and block index)
         key.slots = (int32_t)l;
     }
     key.stamps = env->p.stamps; key.dbg_skip = env->p.dbg_skip;
@@ -944,6 +987,14 @@ static int rollout_aql(ssd_env *env, int chains, const ChainJob *jobs, hipStream
     const int split_cap = chains == 1 ? 3072 : 2304;
     key.split = (coherent && env_split != 0 && j0.obs != nullptr && per_launch <= split_cap) ? 1 : 0;   // (the argument set holds both forms' launches)
     const bool split = key.split && j0.n_steps >= 4;
+    // Step pairs: a split chain's launches advance their envs by TWO steps each wherever two steps remain before the call's end
+    // and before the next reset -- half the dependent launches, and the second step starts from the env as it stands in LDS and
+    // registers, without a prologue.  Every step still lands in its ring slot and is rendered by the next launch's extra workgroups,
+    // two steps per renderer wave.  Where a step-pair kernel exists (ssd_kernels.hip, pair_profile); the argument set then holds
+    // both forms' launches.  (Test-hook build: SSD_AQL_PAIRS=0 keeps single steps -- same results.)
+    static const int env_pairs = SSD_HOOK("SSD_AQL_PAIRS", 1);
+    key.pairs = (key.split && env_pairs != 0 && ssd::pair_profile(env->p, env->game)) ? 1 : 0;
+    const bool pairs = split && key.pairs;
     // (a split set holds its launches for both orientations of the state pair; any other set names the buffer that is current now)
     key.world = key.split ? nullptr : env->p.world;
     AqlState::Set *st = aql_set(env, key, chains, jobs);
@@ -1024,36 +1075,50 @@ static int rollout_aql(ssd_env *env, int chains, const ChainJob *jobs, hipStream
     // orientation: which buffer of the pair holds the current state (always 0 until the first split rollout of the handle)
     int o = (A.world_buf[1] && env->p.world == A.world_buf[1]) ? 1 : 0;
     const int KO = AqlState::kKindsPerO;
-    bool pending = false;                                 // a step's observations are still to be rendered (split rollouts)
+    int pending = 0;                                      // steps of the launch before whose observations are still to be rendered (split rollouts)
     size_t i_prev = 0;
-    for (int k = 0; k < j0.n_steps; ++k) {
+    int launches = 0;                                     // step launches so far, per chain
+    bool any_pair = false;
+    for (int k = 0; k < j0.n_steps;) {
         const size_t i = (size_t)((step0 + k) % slots);   // argument block of this step (output slot i % ring, action slot i % action_ring)
         const bool reset = reset_every > 0 && (step0 + k) % reset_every == 0;
+        // (a pair never spans a reset or the call's end: odd remainders and the step ahead of a reset are single launches)
+        const bool two = pairs && k + 1 < j0.n_steps && !(reset_every > 0 && (step0 + k + 1) % reset_every == 0);
+        const int n = two ? 2 : 1;
+        const bool last = k + n >= j0.n_steps;
         for (int c = 0; c < chains; ++c) {
             const int acq = k == 0 ? 1 : kAcq;                                 // (the call's first launch of the chain)
             if (reset) {
-                // (a reset works in place: the step before it must have been rendered from that buffer first)
-                if (split && pending) put(c, i_prev, o * KO + AqlState::kB, true, kAcq, kRel);
+                // (a reset works in place: the launch before it must have been rendered from that buffer first)
+                if (split && pending) put(c, i_prev, o * KO + (pending == 2 ? AqlState::kBB : AqlState::kB), true, kAcq, kRel);
                 put(c, i, o * KO + (split ? AqlState::kRn : AqlState::kR), true, acq, kRel);
             }
-            const int base = !split ? AqlState::kS : (pending && !reset) ? AqlState::kAB : AqlState::kA;
+            const int rendered = reset ? 0 : pending;
+            const int base = !split ? AqlState::kS
+                             : two  ? (rendered == 2 ? AqlState::kPBB : rendered == 1 ? AqlState::kPB : AqlState::kP)
+                                    : (rendered == 2 ? AqlState::kABB : rendered == 1 ? AqlState::kAB : AqlState::kA);
             // (an output ring past the memory-side cache is written with write-back stores, ssd_kernels.hip select(): one launch per
             // round of the ring releases at agent scope, so that whatever of a slot still sits dirty in an L2 is in memory before
-            // the slot's bytes are written again -- possibly through another XCD's L2)
-            const int rel = (obs_wb && (step0 + k) % j0.ring == 0) ? 1 : kRel;
+            // the slot's bytes are written again -- possibly through another XCD's L2; a pair releases for either of its steps)
+            const bool round = (step0 + k) % j0.ring == 0 || (two && (step0 + k + 1) % j0.ring == 0);
+            const int rel = (obs_wb && round) ? 1 : kRel;
             put(c, i, o * KO + base, true, reset ? kAcq : acq, rel);
-            if (split && k == j0.n_steps - 1) put(c, i, (1 - o) * KO + AqlState::kB, true, kAcq, kRel);   // (renders the buffer this step wrote)
-            // (the doorbell -- an uncached write across the bus, 0.3 - 0.5 us -- after the first two steps, so that the device starts
+            if (split && last) put(c, i, (1 - o) * KO + (two ? AqlState::kBB : AqlState::kB), true, kAcq, kRel);   // (renders the buffer this launch wrote)
+            // (the doorbell -- an uncached write across the bus, 0.3 - 0.5 us -- after the first two launches, so that the device starts
             // at once, and then after every fourth: the device needs 5 us per step, the host under 1, it never runs dry; the join
             // rings for the rest)
 #if SSD_RING_EVERY > 1
-            if (!coherent || k < 2 || (k % SSD_RING_EVERY) == SSD_RING_EVERY - 1) ssd::aql::ring(A.q[c]);   // (large launches: every step, as ever)
+            if (!coherent || launches < 2 || (launches % SSD_RING_EVERY) == SSD_RING_EVERY - 1) ssd::aql::ring(A.q[c]);   // (large launches: every step, as ever)
 #else
             ssd::aql::ring(A.q[c]);
 #endif
         }
-        if (split) { o = 1 - o; pending = true; i_prev = i; }
+        if (split) { o = 1 - o; pending = n; i_prev = i; }
+        any_pair = any_pair || two;
+        launches++;
+        k += n;
     }
+    if (any_pair) env->last_path |= SSD_PATH_PAIRS;
     if (split) {                                          // the current state now sits in buffer o
         env->p.world = A.world_buf[o]; env->p.agents = A.agents_buf[o];
     }
@@ -1154,7 +1219,7 @@ static int rollout(ssd_env *env, const int32_t *actions, const uint8_t *order, i
             const int rc = rollout_aql(env, chains, jobs, s);
             env->last_path |= ssd::aql::pool_report(env->device);
             if (rc <= 0) return rc;
-            env->last_path &= ~(SSD_PATH_AQL | SSD_PATH_COHERENT | SSD_PATH_SPLIT | SSD_PATH_SYNC | SSD_PATH_FORKED);
+            env->last_path &= ~(SSD_PATH_AQL | SSD_PATH_COHERENT | SSD_PATH_SPLIT | SSD_PATH_PAIRS | SSD_PATH_SYNC | SSD_PATH_FORKED);
             // (this call created a queue that failed its probe: an automatic chain count is chosen again for the pool that is left)
             if (!automatic || ssd::aql::pool_size(env->device) >= pool_before) break;
             chains = by_size();

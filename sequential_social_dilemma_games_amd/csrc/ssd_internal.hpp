@@ -1,6 +1,7 @@
 // csrc/ssd_internal.hpp -- kernel parameter block shared by ssd_kernels.hip and ssd_capi.hip.
 #pragma once
 #include <stdint.h>
+#include <stddef.h>
 #include <stdlib.h>
 
 namespace ssd {
@@ -29,7 +30,9 @@ constexpr int kListRegsHarvest = 3, kListRegsCleanup = 8;   // per-lane register
 enum Mode : int32_t {
     kModeStep = 0, kModeReset = 1, kModeObserve = 2,
     kModeRollout = 3,      // n_steps random-action steps in ONE launch
-    kModeStepAuto = 4      // a step that also resets, in the same launch, the envs that reach the horizon (SSD_AUTO_RESET)
+    kModeStepAuto = 4,     // a step that also resets, in the same launch, the envs that reach the horizon (SSD_AUTO_RESET)
+    kModeStepPair = 5      // split rollouts: the env waves take TWO consecutive steps per launch, the env resident in LDS and registers
+                           // between them (the map-specific coherent kernels only; ssd_capi.hip, rollout_aql)
 };
 
 // PRNG streams (sequential_social_dilemma_games_amd/prng.py)
@@ -107,6 +110,22 @@ struct Params {
     uint8_t *obs_b;                // [E][N][V][V][3]  where the renderer workgroups write
 };
 
+// What a step-pair launch (kModeStepPair, ssd_env_pair_kernel) names beside Params.  Further Params::snap_mode bits there: 8 = the
+// launch before was a pair -- the renderer workgroups render its two steps, the first from the `*_mid_in` set into `obs_b0`, then the
+// second as a single step's; 16 = the env waves take one step only (a single step behind a pair: its renderers need this kernel).
+// The env waves' FIRST step leaves grid and agents in `world_mid` / `agents_mid`, its beam marks in `beam_list_mid`, a rare overlay
+// snapshot in `snap_mid` and its rewards and dones in Params::rew / done; the second step writes world_out / agents_out, beam_list,
+// snap and the header as a single step does, its rewards and dones go to `rew2` / `done2`, and caller-supplied actions come from
+// `actions2`.
+struct PairParams {
+    uint8_t *world_mid; uint32_t *agents_mid; uint32_t *beam_list_mid; uint8_t *snap_mid;
+    const uint8_t *world_mid_in; const uint32_t *agents_mid_in; const uint32_t *beam_list_mid_in; const uint8_t *snap_mid_in;
+    uint8_t *obs_b0;
+    const int32_t *actions2;
+    int32_t *rew2;
+    uint8_t *done2;
+};
+
 // The kernarg segment of ssd_env_kernel: its nine leading arguments (repeated Params fields, 56 bytes: preloaded into SGPRs
 // by the command processor) followed by the parameter block.  Natural C layout == the code object's argument offsets.
 struct KernArgs {
@@ -116,13 +135,19 @@ struct KernArgs {
     Params p;
 };
 static_assert(sizeof(KernArgs) == 56 + sizeof(Params), "kernarg layout");
+// ... and of ssd_env_pair_kernel: the same, then the pair's block
+struct PairKernArgs { KernArgs k; PairParams q; };
+static_assert(sizeof(PairKernArgs) == sizeof(KernArgs) + sizeof(PairParams), "kernarg layout");
 
 // One launch, fully resolved: instantiation (host stub of the __global__), geometry, dynamic LDS bytes, kernel arguments.
 struct Launch {
     const void *fn = nullptr;
     uint32_t grid_x = 0, block_x = 0, lds = 0;
     KernArgs args;
+    PairParams pair{};             // (kModeStepPair: lies right behind `args`, together the kernel's PairKernArgs)
+    size_t args_bytes() const { return args.p.mode == kModeStepPair ? sizeof(PairKernArgs) : sizeof(KernArgs); }
 };
+static_assert(offsetof(Launch, pair) == offsetof(Launch, args) + sizeof(KernArgs), "Launch::args + Launch::pair == PairKernArgs");
 
 // Agent indices in the order of their ids sorted as strings ('agent-0', 'agent-1', 'agent-10', 'agent-11', 'agent-2', ...: what
 // `sorted(actions.keys())` gives, map_env.py:202), and each index's rank in that order.
@@ -133,7 +158,8 @@ void launch_agent_action_obs(const int32_t *actions, const uint8_t *done_mask, l
 size_t lds_bytes(const Params &p, int envs_per_block, bool f32);
 int envs_per_block(const Params &p, bool f32);
 int fast_profile(const Params &p, int game);    // which map-specific step kernel a launch gets (0: the general ones)
-bool select(const Params &p, int game, Launch *out);   // resolve a launch without issuing it
+bool pair_profile(const Params &p, int game);   // whether a coherent step launch of this form has a two-steps-per-launch kernel
+bool select(const Params &p, int game, Launch *out, const PairParams *pair = nullptr);   // resolve a launch without issuing it (kModeStepPair: with its block)
 void launch(const Launch &L, void *stream);            // hipLaunchKernel of a resolved launch
 void launch(const Params &p, int game, void *stream);
 const void *flag_kernel_fn();                          // ssd_flag_kernel's host stub (AQL join)

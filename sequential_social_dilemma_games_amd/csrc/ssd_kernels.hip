@@ -16,8 +16,9 @@
 //     the uint8 obs tensor; the padded layout makes a view cell one multiply-add away from its LDS address
 //     (map_env.py:189-199);
 //   * waves never touch each other's LDS: the kernel has no workgroup barrier.
-// One source, four modes (template parameter): step, reset, observe -- one pass over the env per launch -- and
-// rollout, which loops [reset pass,] step pass, ... with the env resident in LDS / registers (SSD_ROLLOUT_FUSED).
+// One source, five modes (template parameter): step, reset, observe -- one pass over the env per launch -- and
+// rollout, which loops [reset pass,] step pass, ... with the env resident in LDS / registers (SSD_ROLLOUT_FUSED); and the step
+// pair of split rollouts, two step passes per launch with each step's state handed to the next launch's renderer workgroups.
 // At 4096 envs (4 waves per SIMD) a per-step launch lasts as long as its SLOWEST wave plus launch and store-drain
 // time, so the code minimises a single wave's dynamic instruction count and wait chain --
 // every global load is issued in the prologue, cross-lane reductions use DPP / scalar code instead of LDS-crossbar
@@ -364,10 +365,23 @@ template <int GAME, int MODE, bool F32, int NA, bool STD, int FAST, bool COH = f
 // The leading arguments repeat the Params fields the first global loads need (14 dwords).  Built with
 // -mllvm -amdgpu-kernarg-preload-count=14 the command processor delivers them in SGPRs when the wave starts, so the
 // loads of the env's state go out without first waiting ~0.3 us for a scalar load of the kernel arguments.
-__global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const a_world,
+// The step-pair kernels (kModeStepPair) are held to eight waves per SIMD: a step's two launches fill the device's wave slots exactly
+// (DESIGN.md section 5).  (0, 0 = no attribute: the other kernels are compiled as ever.)
+__global__ __launch_bounds__(64 * kMaxEnvsPerBlock) __attribute__((amdgpu_waves_per_eu(MODE == kModeStepPair ? 8 : 0, MODE == kModeStepPair ? 8 : 0)))
+void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const a_world,
                                                                         const int a_E, const int a_e_begin, const int a_epb, const int a_n_apple,
                                                                         const uint32_t *const a_apple_cells, const uint32_t *const a_lut,
                                                                         const Params p) {
+    // A step-pair launch's own block (PairParams) lies behind the declared arguments in the kernarg segment -- the library's own
+    // dispatch (ssd_capi.hip, aql_set) writes a PairKernArgs -- so that the other kernels keep their signature, argument offsets and code.
+    [[maybe_unused]] PairParams q{};
+    if constexpr (MODE == kModeStepPair) {
+        struct Words { uint64_t w[sizeof(PairParams) / 8]; } words;
+        const auto *src = (const __attribute__((address_space(4))) uint64_t *)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(KernArgs));
+#pragma unroll
+        for (unsigned i = 0; i < sizeof(PairParams) / 8; ++i) words.w[i] = src[i];
+        q = __builtin_bit_cast(PairParams, words);
+    }
     uint8_t *const a_obs = p.obs;
     extern __shared__ __align__(16) uint8_t smem[];
 #ifdef SSD_STAMPS
@@ -397,7 +411,10 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
     // A step whose launch also resets the envs that reach the horizon (SSD_AUTO_RESET): the step pass, then -- for those
     // envs -- a reset pass whose (unrotated) observations replace the step's rows.  Laid out like a plain step.
     constexpr bool auto_mode = MODE == kModeStepAuto;
-    constexpr bool stepping = MODE == kModeStep || auto_mode;       // the launch takes actions
+    // Two steps per launch (split rollouts, the map-specific coherent kernels): the step pass twice, the env resident in LDS and
+    // registers in between as in a rollout launch, every step's state handed to the renderer workgroups of the next launch.
+    constexpr bool pair = MODE == kModeStepPair;
+    constexpr bool stepping = MODE == kModeStep || auto_mode || pair;   // the launch takes actions
     uint32_t *s_lut = reinterpret_cast<uint32_t *>(smem + (size_t)wv * (512 + 256 + (F32 ? 2048 : 0) + (size_t)A0 + (size_t)A1 +
                                                                             (roll ? 4 : 3) * (size_t)S));
     uint32_t *s_tmp = s_lut + 128;                                  // 64 list entries of scratch (respawn compaction)
@@ -495,8 +512,101 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
             return;
         }
     }
+    // ---- the same role in the step-pair kernels: the launch before took one step (as above) or two (snap_mode bit 8): then both are
+    //      rendered here, in order -- the first from the `mid` set that launch's env waves left (state + list / snapshot), the second
+    //      from the buffer this launch steps from.  Both steps' loads go out before the first use, each step has an LDS layer of its own.
+    //      With a ring of one slot both passes store the same bytes from the same lanes with the same policy, in program order. ----
+    if constexpr (pair && COH && STD && NA > 0 && NA % 5 == 0 && !F32 && FAST != 0) {
+        if ((p.snap_mode & 2) && blk >= p.blocks_a) {
+            const int eb = a_e_begin + (blk - p.blocks_a) * a_epb + wv;
+            if (eb < a_E) {
+                typedef __attribute__((address_space(3))) const uint8_t lds_u8;
+                constexpr int kGridLoads = (fm.S + 1023) / 1024;
+                constexpr bool kTwoLists = GAME == 1 && NA > 5;
+                const bool two = (p.snap_mode & 8) != 0;               // (wave-uniform: a kernel argument)
+                struct StepIn { u32x4_t g[kGridLoads]; uint32_t areg, entry, entry2; };
+                // one step's state as its env wave left it: grid, agents (flags in agent 0's bits 20..22), first beam list
+                auto fetch = [&](const uint8_t *world, const uint32_t *agents, const uint32_t *list) {
+                    StepIn s;
+                    const rsrc_t grid_r = make_rsrc(world + (size_t)eb * S, (uint32_t)S);
+#pragma unroll
+                    for (int j = 0; j < kGridLoads; ++j) s.g[j] = load16_sc1(grid_r, (uint32_t)(lane * 16 + j * 1024));
+                    s.areg = 0; s.entry2 = 0;
+                    if (lane < N) s.areg = __hip_atomic_load(agents + (size_t)eb * N + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    s.entry = __hip_atomic_load(list + (size_t)eb * 64 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    return s;
+                };
+                // the rare extras, once the flags are known: the second list of a two-pass step, the snapshot instead of the state
+                auto fetch_rare = [&](StepIn &s, const uint32_t *list, const uint8_t *snap) {
+                    const uint32_t flags = rfl(s.areg) >> 20;
+                    if (kTwoLists && (flags & 4u)) s.entry2 = __hip_atomic_load(list + ((size_t)p.E_total + eb) * 64 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (flags & 2u) {
+                        const rsrc_t snap_r = make_rsrc(snap + (size_t)eb * S, (uint32_t)S);
+#pragma unroll
+                        for (int j = 0; j < kGridLoads; ++j) s.g[j] = load16_sc1(snap_r, (uint32_t)(lane * 16 + j * 1024));
+                    }
+                };
+                const uint32_t lut_a = a_lut[lane], lut_b = a_lut[lane + 64];
+                const uint4 vt0 = reinterpret_cast<const uint4 *>(p.view_tab)[2 * lane], vt1 = reinterpret_cast<const uint4 *>(p.view_tab)[2 * lane + 1];
+                // (two layers with aprons in the wave's LDS region, one per step: the second lies over the beam and occupancy layers,
+                // which a renderer wave does not use -- so both steps' loads can leave their registers before the first view is rendered)
+                static_assert(fm.S >= fm.A0 + fm.A1, "the renderer's second layer fits the beam and occupancy layers");
+                uint8_t *const s_world2 = s_world + S + A1 + A0;
+                StepIn sb = fetch(a_world, a_agents, p.beam_list_in);
+                StepIn sa = sb;
+                if (two) sa = fetch(q.world_mid_in, q.agents_mid_in, q.beam_list_mid_in);
+                {   // the aprons of the layers: '0' (void) cells
+                    const uint4 z = make_uint4(0x30303030u, 0x30303030u, 0x30303030u, 0x30303030u);
+                    const int n0 = A0 >> 4, n1 = A1 >> 4;
+                    for (int i = lane; i < n0 + n1; i += 64) {
+                        const int at = i < n0 ? i * 16 - A0 : S + (i - n0) * 16;
+                        *reinterpret_cast<uint4 *>(s_world + at) = z;
+                        if (two) *reinterpret_cast<uint4 *>(s_world2 + at) = z;
+                    }
+                }
+                s_lut[lane] = lut_a; s_lut[lane + 64] = lut_b;
+                fetch_rare(sb, p.beam_list_in, p.snap_in);
+                if (two) fetch_rare(sa, q.beam_list_mid_in, q.snap_mid_in);
+                // layer <- state <- agents <- beam marks (or the snapshot as it is)
+                auto fill = [&](const StepIn &s, uint8_t *layer) {
+                    const uint32_t flags = rfl(s.areg) >> 20;
+#pragma unroll
+                    for (int j = 0; j < kGridLoads; ++j) {
+                        if (lane * 16 + j * 1024 < S) *reinterpret_cast<uint4 *>(layer + lane * 16 + j * 1024) = make_uint4(s.g[j].x, s.g[j].y, s.g[j].z, s.g[j].w);
+                    }
+                    wave_sync();
+                    if (!(flags & 2u)) {
+                        if (lane < N && (s.areg & (1u << 19))) layer[s.areg & 0xFFFFu] = agent_glyph((uint32_t)lane);
+                        wave_sync();
+                        if (flags & 1u) {
+                            if (s.entry) layer[s.entry & 0xFFFFu] = (uint8_t)(s.entry >> 16);
+                            wave_sync();
+                            if constexpr (kTwoLists) {
+                                if (s.entry2) layer[s.entry2 & 0xFFFFu] = (uint8_t)(s.entry2 >> 16);
+                                wave_sync();
+                            }
+                        }
+                    }
+                };
+                fill(sb, s_world);
+                if (two) fill(sa, s_world2);
+                // the N views of a layer (lane = agent: its cell and orientation)
+                auto views = [&](const uint32_t areg, const uint8_t *layer, uint8_t *obs_to) {
+                    const uint32_t cellb = areg & 0xFFFFu, orientb = (areg >> 16) & 3u;
+                    const uint32_t kq = (0x8Du >> (2u * orientb)) & 3u;
+                    const uint32_t s0 = (uint32_t)((int)cellb - 7 * (WP + 1) + (kq >= 2 ? 14 * (WP + 1) : 0));
+                    render_views_std<NA, true>(lane, WP, kq, s0, (uint32_t)(uintptr_t)(lds_u8 *)layer, s_lut, obs_to + (size_t)eb * N * SSD_OBS_STRIDE, p.obs_wt,
+                                               vt0, vt1);
+                };
+                if (two) views(sa.areg, s_world2, q.obs_b0);
+                views(sb.areg, s_world, p.obs_b);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+            return;
+        }
+    }
     const int e = a_e_begin + blk * a_epb + wv;             // (a_epb = blockDim.x / 64, without the implicit-argument load)
-    constexpr int mode = MODE;                               // compile-time: step / reset / observe
+    constexpr int mode = pair ? (int)kModeStep : MODE;       // compile-time: step / reset / observe (a pair's passes are steps)
     bool active = e < a_E;                                   // wave-uniform
     if (active && mode == kModeReset && p.mask) active = p.mask[e] != 0;
     SSD_STAMP_RT(10);
@@ -528,7 +638,7 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
         // 5.97 -> 5.90.  (What was tried on top of it and dropped: EXPERIMENTS.md, "kPre: orders of loads".)
         // A lesson kept: a load the compiler cannot see must not sit under a divergent branch, nor have much code between it and its
         // wait -- the compiler is free to copy or reuse its destination register before the data lands.
-        constexpr bool kPre = GAME == 1 && MODE == kModeStep && COH && FAST != 0;
+        constexpr bool kPre = GAME == 1 && MODE == kModeStep && COH && FAST != 0;   // (not the step-pair kernels: the window's four registers are what they lack)
         uint4 hdr;
         if (kCoh) {
             const uint32_t hv = cload(reinterpret_cast<const uint32_t *>(a_hdr + e) + (lane & 3));
@@ -545,6 +655,7 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
         }
         uint32_t areg = 0;
         int act_in = -1;
+        [[maybe_unused]] int act_in2 = -1;
         uint32_t ord_in = 0xFFu;
         // (the env's offset in every [E][N] array -- agents, actions, rewards, dones -- computed ONCE and kept in a scalar register: left
         // to the compiler it is re-derived inside every predicated block that uses it, a 64-bit multiply each)
@@ -602,6 +713,9 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
             // invalidates a CU's L1, and the same action buffer may have held another call's actions a moment ago)
             if (p.num_actions_random <= 0) act_in = (int)cload(reinterpret_cast<const uint32_t *>(p.actions) + eN + lane);
             if (has_order) ord_in = p.order[eN + lane];
+            // (a pair's second step: its slot of the caller's action ring, fetched with the first)
+            if constexpr (pair)
+                if (p.num_actions_random <= 0 && !(p.snap_mode & 16)) act_in2 = (int)cload(reinterpret_cast<const uint32_t *>(q.actions2) + eN + lane);
         }
 #pragma unroll
         for (int j = 0; j < kLR; ++j) {
@@ -666,12 +780,17 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
         // (`top_bit`, per lane: bit 19 of the agent's word = "the highest index on its cell" -- what shows on the cell,
         // map_env.py:289-297 -- for the renderer workgroups of the next launch: they then need not compare the agents' cells pair by
         // pair again)
+        // (a step-pair launch: the pass under way is the pair's first -- its state goes to the `mid` set, for the renderers alone)
+        [[maybe_unused]] bool mid_pass = false;
+        if constexpr (pair) mid_pass = !(p.snap_mode & 16);
         auto write_state = [&](const uint32_t render_flags, const uint32_t top_bit = 0u) {
             uint8_t *gw = a_world + (size_t)e * S;
             if constexpr (kCoh) {
                 // (split rollouts: grid and agents go to the other buffer of the pair, this launch's renderer waves read the input)
                 uint32_t *ga = a_agents;
                 if (p.world_out) { gw = p.world_out + (size_t)e * S; ga = p.agents_out; }
+                if constexpr (pair)
+                    if (mid_pass) { gw = q.world_mid + (size_t)e * S; ga = q.agents_mid; }
                 // (render_flags, split rollouts: what the renderer will find beside this state -- bits 20 / 21 of agent 0's
                 // word: a list of beam marks / an overlay snapshot; readers of the word take bits 0..17)
                 auto cstore = [](uint32_t *ptr, uint32_t v) { __hip_atomic_store(ptr, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
@@ -699,6 +818,7 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
                     store16_sc1(out_r, (uint32_t)i, v);                 // one 16-byte write-through store
                 }
                 if (is_agent) cstore(ga + eN + lane, cell | (orient << 16) | top_bit | (lane == 0 ? render_flags : 0u));
+                if (!pair || !mid_pass)                                  // (a pair writes the header once, after its second step)
                 {   // the header's four words, one per lane: three v_writelane into a register that holds the fourth everywhere (as a
                     // chain of selects on the lane index the compiler made ~20 instructions of nested exec-mask branches of it)
                     uint32_t hw = waste_last | (waste_cur << 16) | (share ? 1u << 31 : 0u);
@@ -722,6 +842,7 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
         // ---- One pass = one reset or one step of the env.  A step / reset / observe launch makes one pass.  A rollout
         //      launch (rollout.py:58-70) loops: [reset pass when one is due,] step pass, ... with the env resident in LDS
         //      and registers; every step pass writes its observations / rewards / dones to its slot of the output ring. ----
+        [[maybe_unused]] bool pass_b = false;                 // the second step of a step-pair launch is under way
         int k_step = 0;                                       // steps done so far (rollout)
         int to_reset = -1;                                    // steps until the next reset is due (rollout; < 0: never)
         uint32_t slot = 0;                                    // output ring slot of the current step (rollout)
@@ -756,7 +877,7 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
             const bool is_reset = (roll || auto_mode) ? in_reset : (mode == kModeReset);
             const bool is_step = (roll || auto_mode) ? !in_reset : (mode == kModeStep);
             const size_t slot_en = roll ? slot_en_run : 0;   // element offset of the slot in rew / done (rollout: a running sum, below)
-            if (roll || (auto_mode && in_reset)) {
+            if (roll || (auto_mode && in_reset) || (pair && pass_b)) {
                 // a fresh pass over the resident env: default priority, empty beam / occupancy layers, and on a reset
                 // the grid of reset_map() (:560-564) + custom_reset
                 __builtin_amdgcn_s_setprio(0);
@@ -834,6 +955,7 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
                     }
                 } else {                                         // (drawn actions are valid by construction: ssd_step_random checks n)
                     act = act_in;
+                    if constexpr (pair) act = pass_b ? act_in2 : act_in;
                     const bool bad = is_agent && (act < -1 || act >= kNumActions);
                     if (ballot(bad)) { status |= kStBadAction; if (bad) act = -1; }
                 }
@@ -1522,7 +1644,7 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
                 if (!roll) {
                     uint32_t render_flags = 0;
                     if constexpr (stepping && COH) {
-                        if ((p.snap_mode & 1) && is_step) {
+                        if ((pair || (p.snap_mode & 1)) && is_step) {
                             render_flags = (!keep_beams && beams_in_regs) ? (ballot(b_cov | (kTwoPasses & b_cov0)) ? 1u << 20 : 0u) : 1u << 21;
                             if constexpr (kTwoPasses)
                                 if (!keep_beams && beams_in_regs && ballot(b_cov0)) render_flags |= 1u << 22;   // (a second list: the later pass's marks)
@@ -1533,7 +1655,12 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
                 if (is_agent && is_step) {
                     // compute_reward (:208); get_done -> False (:209); with a horizon set, the episode ends after `horizon` steps
                     const uint8_t dn = (p.horizon > 0 && t >= (uint32_t)p.horizon) ? 1 : 0;
-                    if constexpr (COH) {                                                // (write-through: nothing stays dirty in L2)
+                    if constexpr (pair) {                                               // (each step of a pair to its own ring slot)
+                        int32_t *const rew_to = pass_b ? q.rew2 : p.rew;
+                        uint8_t *const done_to = pass_b ? q.done2 : p.done;
+                        if (rew_to) __hip_atomic_store(rew_to + eN + lane, rew, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        if (done_to) __hip_atomic_store(done_to + eN + lane, dn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    } else if constexpr (COH) {                                         // (write-through: nothing stays dirty in L2)
                         if (p.rew) __hip_atomic_store(p.rew + slot_en + eN + lane, rew, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         if (p.done) __hip_atomic_store(p.done + slot_en + eN + lane, dn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     } else {
@@ -1559,7 +1686,7 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
             // step) thereby leaves the chain of dependent launches.
             bool leave_overlay = false;                       // wave-uniform
             if constexpr (stepping && COH) {
-                if ((p.snap_mode & 1) && is_step) {
+                if ((pair || (p.snap_mode & 1)) && is_step) {
                     leave_overlay = patch;
                     // (which of the two the step left is said by two spare bits of agent 0's state word, written with the state
                     // above; the list is only written when there is a mark at all.  One dword per lane: staging it through LDS
@@ -1567,10 +1694,12 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
                     // (two passes: the earlier pass's entries in the list proper, the later one's in a second list behind all envs' first)
                     const bool two = kTwoPasses && ballot(b_cov0) != 0;
                     const uint32_t ent = b_cov ? ((uint32_t)b_idx | (b_chr << 16)) : 0u, ent0 = b_cov0 ? ((uint32_t)b_idx0 | (b_chr0 << 16)) : 0u;
+                    uint32_t *list_to = p.beam_list;
+                    if constexpr (pair) list_to = mid_pass ? q.beam_list_mid : p.beam_list;
                     if (patch && ballot(b_cov | b_cov0))
-                        __hip_atomic_store(p.beam_list + (size_t)e * 64 + lane, two ? ent0 : ent, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        __hip_atomic_store(list_to + (size_t)e * 64 + lane, two ? ent0 : ent, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     if (patch && two)
-                        __hip_atomic_store(p.beam_list + ((size_t)p.E_total + e) * 64 + lane, ent, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        __hip_atomic_store(list_to + ((size_t)p.E_total + e) * 64 + lane, ent, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
             }
             if (leave_overlay) {
@@ -1589,14 +1718,17 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
                 const uint32_t mo = nonzero_bytes(o), mb = nonzero_bytes(b);
                 uint32_t v = (w & ~mo) | (o & mo);
                 v = (v & ~mb) | (b & mb);
-                *reinterpret_cast<uint32_t *>(s_view + i) = v;
+                // (a step-pair launch steps on from the world layer: its rare overlay is built over the beam layer instead)
+                *reinterpret_cast<uint32_t *>((pair ? s_beam : s_view) + i) = v;
             }
             wave_sync();
             if constexpr (stepping && COH) {
-                if ((p.snap_mode & 1) && is_step && !patch) {                 // (the rare form: the overlay as a snapshot)
-                    const rsrc_t snap_r = make_rsrc(p.snap + (size_t)e * S, (uint32_t)S);
+                if ((pair || (p.snap_mode & 1)) && is_step && !patch) {                 // (the rare form: the overlay as a snapshot)
+                    uint8_t *snap_to = p.snap;
+                    if constexpr (pair) snap_to = mid_pass ? q.snap_mid : p.snap;
+                    const rsrc_t snap_r = make_rsrc(snap_to + (size_t)e * S, (uint32_t)S);
                     for (int i = lane * 16; i < S; i += 64 * 16) {
-                        const uint4 v4 = *reinterpret_cast<const uint4 *>(s_view + i);
+                        const uint4 v4 = *reinterpret_cast<const uint4 *>((pair ? s_beam : s_view) + i);
                         store16_sc1(snap_r, (uint32_t)i, u32x4_t{v4.x, v4.y, v4.z, v4.w});
                     }
                 }
@@ -1612,7 +1744,7 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
             //      Thanks to the padded grid layout a view cell is ONE multiply-add away from its LDS address.
             //      An agent's block starts at a multiple of V*V*3 = 675 bytes, i.e. at any byte alignment:
             //      the 12-byte stores rely on gfx9's unaligned global access. ----
-            if (a_obs && (!roll || is_step)) {
+            if (!pair && a_obs && (!roll || is_step)) {           // (a pair's env waves never render)
                 typedef __attribute__((address_space(3))) const uint8_t lds_u8;
                 const int V = STD ? 15 : p.V, v = STD ? 7 : p.view_len, VV = V * V;
                 // (diagnostic builds, skip bit 4: all envs write the first 64 envs' blocks -- same instructions, no HBM write stream)
@@ -1782,6 +1914,11 @@ __global__ __launch_bounds__(64 * kMaxEnvsPerBlock) void ssd_env_kernel(uint4 *c
                 if (is_step && p.horizon > 0 && t >= (uint32_t)p.horizon) { in_reset = true; continue; }
                 break;
             }
+            if constexpr (pair) {                             // the second step, from the env as it stands in LDS and registers
+                if (!mid_pass) break;
+                mid_pass = false; pass_b = true;
+                continue;
+            }
             if (!roll) break;
             if (in_reset) { in_reset = false; continue; }     // the step this reset was due before comes next
             if (++k_step >= p.n_steps) break;
@@ -1837,6 +1974,13 @@ static const void *select_step(const Params &p) {
     } else if (p.mode == kModeStepAuto) {
         if constexpr (!F32) return kernel_fn<GAME, kModeStepAuto, false, NA, STD, FAST>();
         return nullptr;
+    } else if (p.mode == kModeStepPair) {
+        // (only where the step kernel has a renderer role, the map-specific coherent ones -- and of those not Cleanup 48 x 36's: held
+        // to eight waves per SIMD it spills 19 vector registers to scratch memory; pair_profile() below says the same)
+        if constexpr ((GAME == 0 || FAST == 1) && !F32 && FAST != 0 && STD && NA > 0) {
+            if (p.coherent) return kernel_fn<GAME, kModeStepPair, false, NA, STD, FAST, true>();
+        }
+        return nullptr;
     } else {
         if constexpr (!F32 && FAST != 0) {           // (the kernels rollouts of the known maps use)
             if (p.coherent) return kernel_fn<GAME, kModeStep, false, NA, STD, FAST, true>();
@@ -1861,9 +2005,15 @@ int fast_profile(const Params &p, int game) {
     return fast;
 }
 
+// Whether launches with these parameters have a step-pair kernel (kModeStepPair).
+bool pair_profile(const Params &p, int game) {
+    const int fast = fast_profile(p, game);
+    return !p.obs_f32 && fast > 0 && (game == 0 || fast == 1);
+}
+
 template <int GAME, bool F32>
 static const void *select_game(const Params &p) {
-    if (p.mode == kModeStep || p.mode == kModeRollout || p.mode == kModeStepAuto) {
+    if (p.mode == kModeStep || p.mode == kModeRollout || p.mode == kModeStepAuto || p.mode == kModeStepPair) {
         // specialised step kernels for the reference's configurations (view 7, beam 5; 5 or 10 agents), and
         // among those the FAST ones for the game's shipped map called in the plain way
         const bool std_view = p.view_len == 7 && p.beam_len == 5;
@@ -1887,7 +2037,7 @@ static const void *select_game(const Params &p) {
 
 // Everything one launch of the fused kernel needs: which instantiation, its geometry, and the kernel arguments laid out as the
 // kernel's kernarg segment (KernArgs: 56 bytes of leading arguments the command processor preloads into SGPRs, then Params).
-bool select(const Params &p_in, int game, Launch *out) {
+bool select(const Params &p_in, int game, Launch *out, const PairParams *pair) {
     Params p = p_in;
     static const int forced_wt = SSD_HOOK("SSD_OBS_WT", -1);   // (test-hook build: tuning override)
     // per launch (rollouts run two launches at a time); float32 observations are 4x the bytes: a quarter of the envs
@@ -1924,10 +2074,12 @@ bool select(const Params &p_in, int game, Launch *out) {
     KernArgs &k = out->args;
     k.hdr = p.hdr; k.agents = p.agents; k.world = p.world; k.E = p.E; k.e_begin = p.e_begin; k.epb = epb; k.n_apple = p.n_apple;
     k.apple_cells = p.apple_cells; k.lut = p.lut; k.p = p;
+    if (p.mode == kModeStepPair) { if (!pair) return false; out->pair = *pair; }
     return out->fn != nullptr;
 }
 
 void launch(const Launch &L, void *stream) {
+    if (L.args.p.mode == kModeStepPair) return;             // (its PairKernArgs only travel in the library's own packets)
     KernArgs &k = const_cast<KernArgs &>(L.args);
     void *args[] = {&k.hdr, &k.agents, &k.world, &k.E, &k.e_begin, &k.epb, &k.n_apple, &k.apple_cells, &k.lut, &k.p};
     (void)hipLaunchKernel(L.fn, dim3(L.grid_x), dim3(L.block_x), args, L.lds, static_cast<hipStream_t>(stream));

@@ -17,9 +17,10 @@ def funcs(path):
         elif l.startswith(".Lfunc_end"):
             cur = None
         elif cur:
-            t = l.strip()
-            if t and not t.startswith(";") and not t.startswith(".loc"):
-                d[cur].append(t)
+            t = l.split(";")[0].strip()                # (trailing comments: loop notes on label lines, which name labels too)
+            if t and not t.startswith(".loc"):
+                # (local labels carry the function's number in the listing, which shifts when kernels are added: .LBB17_4 -> .LBB_4)
+                d[cur].append(re.sub(r"\.LBB\d+_", ".LBB_", t))
     return d
 
 
