@@ -897,13 +897,22 @@ static AqlState::Set *aql_set(ssd_env *env, const AqlState::Key &key, int chains
                         p.world_out = A.world_buf[1 - o]; p.agents_out = A.agents_buf[1 - o];
                         p.beam_list = A.beam_list[o]; p.snap = A.snap_grid[o];
                         p.beam_list_in = A.beam_list[1 - o]; p.snap_in = A.snap_grid[1 - o];
-                        q.world_mid = A.mid_world[o]; q.agents_mid = A.mid_agents[o]; q.beam_list_mid = A.mid_list[o]; q.snap_mid = A.mid_snap[o];
+                        // (the env waves' records, one per pass of the launch: a first step of two into mid set o, the launch's last
+                        // step as a single step's -- each with the ring slots of its own step)
+                        const ssd::PassRec last_rec{p.world_out, p.agents_out, p.beam_list, p.snap,
+                                                    cur.rew ? cur.rew + (size_t)(env_two ? r1 : r) * cur.en : nullptr,
+                                                    cur.done ? cur.done + (size_t)(env_two ? r1 : r) * cur.en : nullptr};
+                        if (env_two) {
+                            q.pass[0] = ssd::PassRec{A.mid_world[o], A.mid_agents[o], A.mid_list[o], A.mid_snap[o], p.rew, p.done};
+                            q.pass[1] = last_rec;
+                            q.actions2 = cur.actions ? cur.actions + ((size_t)(i + 1) % (size_t)cur.action_ring) * cur.en : nullptr;
+                        } else {
+                            q.pass[0] = last_rec;
+                        }
                         q.world_mid_in = A.mid_world[1 - o]; q.agents_mid_in = A.mid_agents[1 - o]; q.beam_list_mid_in = A.mid_list[1 - o];
                         q.snap_mid_in = A.mid_snap[1 - o];
                         p.obs_b = slot_obs(base == AqlState::kBB ? r1 : rm1);
                         q.obs_b0 = slot_obs(base == AqlState::kBB ? r : rm2);
-                        q.actions2 = cur.actions ? cur.actions + ((size_t)(i + 1) % (size_t)cur.action_ring) * cur.en : nullptr;
-                        q.rew2 = cur.rew ? cur.rew + (size_t)r1 * cur.en : nullptr; q.done2 = cur.done ? cur.done + (size_t)r1 * cur.en : nullptr;
                     } else if (base >= AqlState::kA) {
                         // env waves: read buffer o, write buffer 1 - o, leave their beam marks in list o.  Renderer workgroups of
                         // a kAB launch: the step before produced buffer o (a launch of orientation 1 - o: its marks are in list

@@ -113,17 +113,25 @@ struct Params {
 // What a step-pair launch (kModeStepPair, ssd_env_pair_kernel) names beside Params.  Further Params::snap_mode bits there: 8 = the
 // launch before was a pair -- the renderer workgroups render its two steps, the first from the `*_mid_in` set into `obs_b0`, then the
 // second as a single step's; 16 = the env waves take one step only (a single step behind a pair: its renderers need this kernel).
-// The env waves' FIRST step leaves grid and agents in `world_mid` / `agents_mid`, its beam marks in `beam_list_mid`, a rare overlay
-// snapshot in `snap_mid` and its rewards and dones in Params::rew / done; the second step writes world_out / agents_out, beam_list,
-// snap and the header as a single step does, its rewards and dones go to `rew2` / `done2`, and caller-supplied actions come from
-// `actions2`.
+// The env waves read ONE RECORD PER PASS (PassRec), pass[k] for the launch's k-th pass, with scalar loads a phase ahead of the pass
+// that needs it: a pass then holds one set of output pointers in registers and selects nothing at its uses.  The FIRST step of two
+// leaves grid and agents in the `mid` set, its beam marks and rare overlay snapshot in the mid list / mid snapshot; the launch's LAST
+// step -- the second of two, or the only one (bit 16: then it is pass[0]) -- writes the other state buffer, the list and the snapshot
+// as a single step's launch does, and the header behind them.  Either step's rewards and dones are those of its own ring slot.  A
+// run of more steps per launch would be more records of the first kind, nothing else.
+// Caller-supplied actions are not in the records: both steps' are loaded in the prologue, the first step's from Params::actions,
+// the second step's from `actions2`.
+// The renderer workgroups read their five inputs (`*_mid_in`, `obs_b0`) inside their own branch.
+struct PassRec {
+    uint8_t *world; uint32_t *agents;      // [E][S], [E][N]: where the pass leaves the env
+    uint32_t *beam_list; uint8_t *snap;    // [2][E][64], [E][S]
+    int32_t *rew; uint8_t *done;           // [E][N] of the step's ring slot (null: not wanted)
+};
 struct PairParams {
-    uint8_t *world_mid; uint32_t *agents_mid; uint32_t *beam_list_mid; uint8_t *snap_mid;
+    PassRec pass[2];
+    const int32_t *actions2;               // [E][N] the second step's slot of the action ring (null: drawn actions)
     const uint8_t *world_mid_in; const uint32_t *agents_mid_in; const uint32_t *beam_list_mid_in; const uint8_t *snap_mid_in;
     uint8_t *obs_b0;
-    const int32_t *actions2;
-    int32_t *rew2;
-    uint8_t *done2;
 };
 
 // The kernarg segment of ssd_env_kernel: its nine leading arguments (repeated Params fields, 56 bytes: preloaded into SGPRs

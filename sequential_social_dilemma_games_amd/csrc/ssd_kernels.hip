@@ -374,14 +374,20 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
                                                                         const Params p) {
     // A step-pair launch's own block (PairParams) lies behind the declared arguments in the kernarg segment -- the library's own
     // dispatch (ssd_capi.hip, aql_set) writes a PairKernArgs -- so that the other kernels keep their signature, argument offsets and code.
-    [[maybe_unused]] PairParams q{};
-    if constexpr (MODE == kModeStepPair) {
-        struct Words { uint64_t w[sizeof(PairParams) / 8]; } words;
-        const auto *src = (const __attribute__((address_space(4))) uint64_t *)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(KernArgs));
-#pragma unroll
-        for (unsigned i = 0; i < sizeof(PairParams) / 8; ++i) words.w[i] = src[i];
-        q = __builtin_bit_cast(PairParams, words);
-    }
+    // Nothing of it is copied here: a pass of the env role fetches its own record (PassRec) a phase ahead of its first use, the
+    // renderer role its five inputs inside its branch -- scalar loads of what the role under way needs, and of nothing else.
+    typedef const __attribute__((address_space(4))) uint64_t karg_u64;
+    [[maybe_unused]] karg_u64 *const qargs = (karg_u64 *)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(KernArgs));
+    // (one pointer of the block, by its byte offset in PairParams)
+    [[maybe_unused]] auto qptr = [&](size_t at, auto *like) { return reinterpret_cast<decltype(like)>(qargs[at / 8]); };
+    [[maybe_unused]] auto load_rec = [&](int k) {
+        const size_t at = offsetof(PairParams, pass) + (size_t)k * sizeof(PassRec);
+        PassRec r;
+        r.world = qptr(at + offsetof(PassRec, world), r.world); r.agents = qptr(at + offsetof(PassRec, agents), r.agents);
+        r.beam_list = qptr(at + offsetof(PassRec, beam_list), r.beam_list); r.snap = qptr(at + offsetof(PassRec, snap), r.snap);
+        r.rew = qptr(at + offsetof(PassRec, rew), r.rew); r.done = qptr(at + offsetof(PassRec, done), r.done);
+        return r;
+    };
     uint8_t *const a_obs = p.obs;
     extern __shared__ __align__(16) uint8_t smem[];
 #ifdef SSD_STAMPS
@@ -524,6 +530,12 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
                 constexpr int kGridLoads = (fm.S + 1023) / 1024;
                 constexpr bool kTwoLists = GAME == 1 && NA > 5;
                 const bool two = (p.snap_mode & 8) != 0;               // (wave-uniform: a kernel argument)
+                // (the role's own part of the pair's block, requested with the role's first kernel arguments)
+                const uint8_t *const q_world_mid_in = qptr(offsetof(PairParams, world_mid_in), (const uint8_t *)nullptr);
+                const uint32_t *const q_agents_mid_in = qptr(offsetof(PairParams, agents_mid_in), (const uint32_t *)nullptr);
+                const uint32_t *const q_beam_list_mid_in = qptr(offsetof(PairParams, beam_list_mid_in), (const uint32_t *)nullptr);
+                const uint8_t *const q_snap_mid_in = qptr(offsetof(PairParams, snap_mid_in), (const uint8_t *)nullptr);
+                uint8_t *const q_obs_b0 = qptr(offsetof(PairParams, obs_b0), (uint8_t *)nullptr);
                 struct StepIn { u32x4_t g[kGridLoads]; uint32_t areg, entry, entry2; };
                 // one step's state as its env wave left it: grid, agents (flags in agent 0's bits 20..22), first beam list
                 auto fetch = [&](const uint8_t *world, const uint32_t *agents, const uint32_t *list) {
@@ -554,7 +566,7 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
                 uint8_t *const s_world2 = s_world + S + A1 + A0;
                 StepIn sb = fetch(a_world, a_agents, p.beam_list_in);
                 StepIn sa = sb;
-                if (two) sa = fetch(q.world_mid_in, q.agents_mid_in, q.beam_list_mid_in);
+                if (two) sa = fetch(q_world_mid_in, q_agents_mid_in, q_beam_list_mid_in);
                 {   // the aprons of the layers: '0' (void) cells
                     const uint4 z = make_uint4(0x30303030u, 0x30303030u, 0x30303030u, 0x30303030u);
                     const int n0 = A0 >> 4, n1 = A1 >> 4;
@@ -566,7 +578,7 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
                 }
                 s_lut[lane] = lut_a; s_lut[lane + 64] = lut_b;
                 fetch_rare(sb, p.beam_list_in, p.snap_in);
-                if (two) fetch_rare(sa, q.beam_list_mid_in, q.snap_mid_in);
+                if (two) fetch_rare(sa, q_beam_list_mid_in, q_snap_mid_in);
                 // layer <- state <- agents <- beam marks (or the snapshot as it is)
                 auto fill = [&](const StepIn &s, uint8_t *layer) {
                     const uint32_t flags = rfl(s.areg) >> 20;
@@ -598,7 +610,7 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
                     render_views_std<NA, true>(lane, WP, kq, s0, (uint32_t)(uintptr_t)(lds_u8 *)layer, s_lut, obs_to + (size_t)eb * N * SSD_OBS_STRIDE, p.obs_wt,
                                                vt0, vt1);
                 };
-                if (two) views(sa.areg, s_world2, q.obs_b0);
+                if (two) views(sa.areg, s_world2, q_obs_b0);
                 views(sb.areg, s_world, p.obs_b);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
@@ -638,10 +650,22 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
         // 5.97 -> 5.90.  (What was tried on top of it and dropped: EXPERIMENTS.md, "kPre: orders of loads".)
         // A lesson kept: a load the compiler cannot see must not sit under a divergent branch, nor have much code between it and its
         // wait -- the compiler is free to copy or reuse its destination register before the data lands.
-        constexpr bool kPre = GAME == 1 && MODE == kModeStep && COH && FAST != 0;   // (not the step-pair kernels: the window's four registers are what they lack)
+        // The step-pair kernels (round 19, once the pair block's spills had gone: 63 VGPRs with the window, no scratch): ONE window
+        // serves both passes.  It is centred one count higher -- lane l holds the entries of (count in the header + 1 - l) -- because
+        // the first pass may have spawned a waste cell; a pass reads lane (count in the header + 1 - its own count), whatever both
+        // passes cleaned and spawned so far.  Cleanup 25 x 18 x 4096, alternating fresh processes: 5.01 -> 4.74 us per step.
+        constexpr bool kPre = GAME == 1 && (MODE == kModeStep || pair) && COH && FAST != 0;
+        constexpr int kPreUp = pair ? 1 : 0;
         uint4 hdr;
+        // (a step-pair launch: where the pass under way leaves its state and outputs -- the record of the launch's first pass comes
+        // with the prologue's other argument fetches, the second pass's at the top of that pass)
+        [[maybe_unused]] PassRec rec{};
         if (kCoh) {
             const uint32_t hv = cload(reinterpret_cast<const uint32_t *>(a_hdr + e) + (lane & 3));
+            if constexpr (pair) {
+                rec = load_rec(0);
+                asm volatile("" ::"s"(rec.world), "s"(rec.agents), "s"(rec.beam_list), "s"(rec.snap), "s"(rec.rew), "s"(rec.done));
+            }
             // (these kernel arguments are fetched while the header is on its way)
             if constexpr (kPre) asm volatile("" ::"s"(p.waste_cells), "s"(p.thr_ca), "s"(p.thr_cw), "s"(p.n_thr));
             // ... and so are the ones the rest of the prologue and the respawn need (the pins further down): requested only after
@@ -715,7 +739,8 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
             if (has_order) ord_in = p.order[eN + lane];
             // (a pair's second step: its slot of the caller's action ring, fetched with the first)
             if constexpr (pair)
-                if (p.num_actions_random <= 0 && !(p.snap_mode & 16)) act_in2 = (int)cload(reinterpret_cast<const uint32_t *>(q.actions2) + eN + lane);
+                if (p.num_actions_random <= 0 && !(p.snap_mode & 16))
+                    act_in2 = (int)cload(qptr(offsetof(PairParams, actions2), (const uint32_t *)nullptr) + eN + lane);
         }
 #pragma unroll
         for (int j = 0; j < kLR; ++j) {
@@ -727,7 +752,7 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
         // less what this step's CLEAN beams clean (cleanup.py:115 after :94-111), almost always within the window
         uint64_t thr_pa = 0, thr_pw = 0;
         if constexpr (kPre) {
-            int ti = (int)((rfl(hdr.w) >> 16) & 0x7FFFu) - lane;
+            int ti = (int)((rfl(hdr.w) >> 16) & 0x7FFFu) + kPreUp - lane;
             ti = ti < 0 ? 0 : ti;
             ti = ti < p.n_thr ? ti : p.n_thr - 1;
             thr_pa = p.thr_ca[ti]; thr_pw = p.thr_cw[ti];
@@ -773,6 +798,7 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
         // the last spawn pass used, ssd_get_waste_count): a step only changes it by the cells its CLEAN beams clean and the
         // one waste cell it may spawn, so compute_permitted_area (cleanup.py:173-179) need not recount the grid.
         uint32_t waste_cur = GAME == 1 ? (rfl(hdr.w) >> 16) & 0x7FFFu : 0u;
+        [[maybe_unused]] const uint32_t waste0 = waste_cur;   // (a pair's threshold window is laid out from the launch's first count)
         // Bit 31 of hdr.w: "two agents may share a cell" in the stored state (possible only after a contested cell was entered
         // while its occupant was still there, map_env.py:480-483; never after a reset; ssd_set_state computes it).  Exact after
         // every step's consume phase; lets the move phase of a step that finds its agents apart skip the pair-by-pair look.
@@ -788,9 +814,8 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
             if constexpr (kCoh) {
                 // (split rollouts: grid and agents go to the other buffer of the pair, this launch's renderer waves read the input)
                 uint32_t *ga = a_agents;
-                if (p.world_out) { gw = p.world_out + (size_t)e * S; ga = p.agents_out; }
-                if constexpr (pair)
-                    if (mid_pass) { gw = q.world_mid + (size_t)e * S; ga = q.agents_mid; }
+                if constexpr (pair) { gw = rec.world + (size_t)e * S; ga = rec.agents; }   // (the pass's own record)
+                else if (p.world_out) { gw = p.world_out + (size_t)e * S; ga = p.agents_out; }
                 // (render_flags, split rollouts: what the renderer will find beside this state -- bits 20 / 21 of agent 0's
                 // word: a list of beam marks / an overlay snapshot; readers of the word take bits 0..17)
                 auto cstore = [](uint32_t *ptr, uint32_t v) { __hip_atomic_store(ptr, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
@@ -882,12 +907,16 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
                 // the grid of reset_map() (:560-564) + custom_reset
                 __builtin_amdgcn_s_setprio(0);
                 rew = 0;
+                // (a pair's second pass: its record is requested here, ahead of the layer clears, and is in registers when their wait
+                // is over -- the first pass's pointers end with that pass)
+                if constexpr (pair) rec = load_rec(1);
                 for (int i = lane * 16; i < S; i += 64 * 16) {
                     if (is_reset) *reinterpret_cast<uint4 *>(s_world + i) = *reinterpret_cast<const uint4 *>(p.reset_world + i);
                     *reinterpret_cast<uint4 *>(s_beam + i) = make_uint4(0, 0, 0, 0);
                     *reinterpret_cast<uint4 *>(s_occ + i) = make_uint4(0, 0, 0, 0);
                 }
                 wave_sync();
+                if constexpr (pair) asm volatile("" ::"s"(rec.world), "s"(rec.agents), "s"(rec.beam_list), "s"(rec.snap), "s"(rec.rew), "s"(rec.done));
             }
             uint32_t cleaned = 0;                                 // 'H' cells turned into 'R' by this pass's CLEAN beams
             if (is_reset) {
@@ -1574,7 +1603,7 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
                     uint64_t thr_a = 0, thr_w = 0;
                     bool thr_have = false;                                              // (wave-uniform) the prologue's window serves
                     if constexpr (kPre) {
-                        const uint32_t back = rfl(cleaned);                             // the window's lane: cells cleaned this step
+                        const uint32_t back = pair ? rfl(waste0 + 1u - nh) : rfl(cleaned); // the window's lane: cells cleaned this step (a pair: see kPre)
                         if (back < 64u) {
                             thr_a = (uint64_t)rl((uint32_t)thr_pa, back) | ((uint64_t)rl((uint32_t)(thr_pa >> 32), back) << 32);
                             thr_w = (uint64_t)rl((uint32_t)thr_pw, back) | ((uint64_t)rl((uint32_t)(thr_pw >> 32), back) << 32);
@@ -1656,8 +1685,8 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
                     // compute_reward (:208); get_done -> False (:209); with a horizon set, the episode ends after `horizon` steps
                     const uint8_t dn = (p.horizon > 0 && t >= (uint32_t)p.horizon) ? 1 : 0;
                     if constexpr (pair) {                                               // (each step of a pair to its own ring slot)
-                        int32_t *const rew_to = pass_b ? q.rew2 : p.rew;
-                        uint8_t *const done_to = pass_b ? q.done2 : p.done;
+                        int32_t *const rew_to = rec.rew;
+                        uint8_t *const done_to = rec.done;
                         if (rew_to) __hip_atomic_store(rew_to + eN + lane, rew, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         if (done_to) __hip_atomic_store(done_to + eN + lane, dn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     } else if constexpr (COH) {                                         // (write-through: nothing stays dirty in L2)
@@ -1695,7 +1724,7 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
                     const bool two = kTwoPasses && ballot(b_cov0) != 0;
                     const uint32_t ent = b_cov ? ((uint32_t)b_idx | (b_chr << 16)) : 0u, ent0 = b_cov0 ? ((uint32_t)b_idx0 | (b_chr0 << 16)) : 0u;
                     uint32_t *list_to = p.beam_list;
-                    if constexpr (pair) list_to = mid_pass ? q.beam_list_mid : p.beam_list;
+                    if constexpr (pair) list_to = rec.beam_list;
                     if (patch && ballot(b_cov | b_cov0))
                         __hip_atomic_store(list_to + (size_t)e * 64 + lane, two ? ent0 : ent, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     if (patch && two)
@@ -1725,7 +1754,7 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
             if constexpr (stepping && COH) {
                 if ((pair || (p.snap_mode & 1)) && is_step && !patch) {                 // (the rare form: the overlay as a snapshot)
                     uint8_t *snap_to = p.snap;
-                    if constexpr (pair) snap_to = mid_pass ? q.snap_mid : p.snap;
+                    if constexpr (pair) snap_to = rec.snap;
                     const rsrc_t snap_r = make_rsrc(snap_to + (size_t)e * S, (uint32_t)S);
                     for (int i = lane * 16; i < S; i += 64 * 16) {
                         const uint4 v4 = *reinterpret_cast<const uint4 *>((pair ? s_beam : s_view) + i);
