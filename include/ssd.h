@@ -1048,6 +1048,98 @@ int ssd_vtrace(const int32_t *rew, const float *bonus, double bonus_weight, cons
                float *pg_advantages, int32_t device_id, void *stream);
 const char *ssd_vtrace_last_error(void);   /* the calling thread's last ssd_vtrace error */
 
+/* ======================================================================================================================
+ * WATERSHED PPO LOSS AND GRADIENTS -- the learner's half of the loop for the Watershed baselines' policy (LSTMFCNet, WATERSHED
+ * POLICY ROLLOUTS above), whose launchers default to PPO (run_scripts/train_watershed_baseline.py,
+ * train_watershed_comm_baseline.py): RLlib 0.7.6's PPO loss on sequences the caller has gathered, with truncated
+ * backpropagation through time, its statistics and the gradient of every parameter of one agent id's weight set, in one call
+ * (csrc/ssd_ws_policy_grad.hip).  Added after ABI 6 without a version bump: the call is additive.
+ *
+ * One call is one agent id, and so one weight set: in the reference each agent's policy is its own graph and its own loss, so
+ * a learner makes one call per id.  Network: that of ssd_ws_policy_forward, the same packed layout (SSD_WSP_*); weights are all
+ * num_sets sets, of which set agent_id is read.  C = cell_size = 64, 128 or 256.  (variant, agent_id) decide the head as in
+ * WATERSHED POLICY ROLLOUTS: SSD_WS_SEQ_COMM ids 0-3 are comm agents, every other id is an action agent.
+ *
+ * Rows.  M = n_steps is the number of the agent's OWN steps, in order; Q = num_seqs the number of sequences, a sequence being
+ * one env's trajectory of this agent.  Every per-row array is [M, Q]: actions f32 (the message index as a float for a comm
+ * agent, clamped to 0 .. 4; the UNCLIPPED Gaussian sample for an action agent: what the rollouts record), logp_old,
+ * advantages, value_targets, vf_preds f32.  obs is f32 [M, Q, 12]: the observation each step acted on, already gathered (no
+ * shift by address here); dense0 reads all 12 columns, the rows of dense0_w beyond the agent's observation length meet the
+ * zero padding.  behaviour_dist is f32 [M, Q, 5] (the dist the actions were drawn from), or NULL when kl_coeff == 0 (with
+ * kl_coeff == 0 it is not read).  Which reward is credited to which step, advantages and value targets are the caller's
+ * (ssd_advantages accepts any [R, L] arrays).
+ *
+ * State rule: that of RECURRENT PPO LOSS AND GRADIENTS with T = seq_len and starts u8 [M, Q] in the place of done[k - 1].
+ * state is f32 [ceil(M / T), Q, 2, C] in (h, c) order, as the rollouts' state ring holds it.  Step m of sequence q uses
+ *   state[m / T] as stored, when m % T == 0: data, no gradient flows into it (starts[m] is NOT looked at there);
+ *   zero, when m % T != 0 and starts[m, q] != 0 (selected, never loaded);
+ *   the (h', c') this call computed for step m - 1 with the current weights, otherwise.
+ * starts may be NULL.  A fragment that is no multiple of T ends in a shorter window; no padding, no mask.
+ *
+ * Row loss: PPO LOSS AND GRADIENTS' terms (ratio, surr, vf, the derivatives at the kinks, row_loss and the statistics) with
+ * the head's distribution in the place of the Categorical over A actions.
+ *   comm agent:   Categorical over dist[0:5]: exactly the row terms of PPO LOSS AND GRADIENTS with A = 5 (the same device code).
+ *   action agent: a one-dimensional DiagGaussian, mean = dist[0], log_std = dist[1]; dist[2:5] are unused and their gradient
+ *     is exactly zero.  With a = actions[row], std = expf(log_std), z = (a - mean) / std:
+ *       logp = ((-0.5f * (z * z)) - log_std) - 0.9189385f            (the rollout's expression)
+ *       ent  = log_std + 1.4189385f
+ *       kl   = ((log_std - log_std_old) + 0.5f * q) - 0.5f,  q = (expf(2 log_std_old) + (mean_old - mean)^2) / expf(2 log_std)
+ *              (RLlib's prev_dist.kl(curr_dist); 0 without behaviour_dist)
+ *       d logp / d mean = z / std     d logp / d log_std = z^2 - 1     d ent / d log_std = 1
+ *       d kl / d mean = -(mean_old - mean) / expf(2 log_std)           d kl / d log_std = 1 - q
+ *     These three formulas are stated from memory of RLlib 0.7.6's DiagGaussian (ray is not available to check against), as
+ *     the Categorical's are above.
+ * loss is the mean of row_loss over the M Q rows.  ReLU's derivative at 0 is 0.
+ *
+ * Arithmetic and order.  The forward is exact float32 from the device pieces of the rollout (the dense chains, gates, cell,
+ * heads); the per-row loss terms are float32 and enter float64 sums.  Every sum has a fixed order that is a function of
+ * (M, Q, C, T) alone; the windows are walked in order and every partial sum is continued from window to window:
+ *   heads' kernels and biases, statistics: the sequences are cut into tiles of SSD_WSPPO_TILE; workgroup g of the
+ *     SSD_WSPPO_GROUPS(Q) takes tiles g, g + G, ...; per tile it walks the window's steps backwards (forwards for the
+ *     statistics) and adds each step's sum over the tile to the sum carried so far (float32; float64 for the statistics);
+ *   lstm_w, lstm_b: the window's rows in (m, q) order are cut into chunks of SSD_WSPPO_CHUNK rows; split s of the
+ *     SSD_WSPPO_SPLITS(a whole window's rows) takes chunks s, s + S, ... as one accumulator in row order (lstm_b: four
+ *     accumulators of every fourth row, added in order at the end of a window);
+ *   dense0, dense1: the window's rows are cut into tiles of SSD_WSPPO_TILE rows; workgroup g of the
+ *     SSD_WSPPO_TRUNK_GROUPS(a whole window's rows) takes tiles g, g + TG, ..., a sum per tile added to the sum carried so far.
+ * A whole window has min(T, M) steps.  The partial sums of an entry are then added in order in float64, scaled by 1 / (M Q)
+ * and rounded to float32 once.  No atomics: the same inputs give the same bits.
+ *
+ * Outputs.  grads f32 [SSD_WSP_SET_FLOATS(C)]: set agent_id's gradient in the packed layout, padding floats zero (the other
+ * sets' gradients are zero and not written anywhere).  stats f64 [5]: the means of row_loss, -surr, vf, kl and ent.  scratch:
+ * SSD_WSPPO_SCRATCH_FLOATS(M, Q, C, T) floats the call overwrites, 8-byte aligned as stats is; it grows with the rows of one
+ * window and the numbers of partial sums, not with M beyond min(T, M).
+ *
+ * Device pointers on device_id; everything is enqueued on `stream` (1 + 3 per window + 1 launches), no allocation, no host
+ * synchronisation.  SSD_E_INVALID before anything is launched (ssd_policy_last_error says why) for an unknown variant, a
+ * num_sets that is not the variant's, an agent_id outside 0 .. num_sets - 1, a cell_size other than 64, 128 or 256, seq_len,
+ * n_steps or num_seqs < 1, more than 2^31 - 17 rows, a NULL weights, obs, state, actions, logp_old, advantages, value_targets,
+ * vf_preds, scratch, grads or stats, a NULL behaviour_dist with kl_coeff != 0, a hyper-parameter that is not finite, a
+ * negative clip_param or vf_clip_param, a misaligned scratch, stats or float buffer, flags other than 0.
+ * ====================================================================================================================== */
+enum { SSD_WSPPO_TILE = 16, SSD_WSPPO_CHUNK = 64, SSD_WSPPO_MAX_GROUPS = 1024, SSD_WSPPO_MAX_SPLITS = 32, SSD_WSPPO_MAX_TRUNK_GROUPS = 256 };
+#define SSD_WSPPO_MIN(a, b) ((a) < (b) ? (a) : (b))
+/* workgroups (partial sums) of the sequence kernel; splits of lstm_w's; workgroups of the dense layers' */
+#define SSD_WSPPO_GROUPS(Q) SSD_WSPPO_MIN(((Q) + SSD_WSPPO_TILE - 1) / SSD_WSPPO_TILE, SSD_WSPPO_MAX_GROUPS)
+#define SSD_WSPPO_SPLITS(window_rows) \
+    ((int)SSD_WSPPO_MIN(((window_rows) + SSD_WSPPO_CHUNK - 1) / SSD_WSPPO_CHUNK, SSD_WSPPO_MAX_SPLITS))
+#define SSD_WSPPO_TRUNK_GROUPS(window_rows) \
+    ((int)SSD_WSPPO_MIN(((window_rows) + SSD_WSPPO_TILE - 1) / SSD_WSPPO_TILE, SSD_WSPPO_MAX_TRUNK_GROUPS))
+/* per row of a whole window: dense0's output 16, dense1's 16, d (dist, value) / dx 16, (h', c') 2C, gates / dz 4C */
+#define SSD_WSPPO_ROW_FLOATS(C) (48 + 6 * (C))
+#define SSD_WSPPO_WINDOW_ROWS(M, Q, T) ((int64_t)SSD_WSPPO_MIN(T, M) * (Q))
+#define SSD_WSPPO_SCRATCH_FLOATS(M, Q, C, T)                                                                  \
+    ((size_t)(16 + (C)) * 4 * (C) + (size_t)SSD_WSPPO_WINDOW_ROWS(M, Q, T) * SSD_WSPPO_ROW_FLOATS(C) +      \
+     (size_t)SSD_WSPPO_TRUNK_GROUPS(SSD_WSPPO_WINDOW_ROWS(M, Q, T)) * SSD_WSP_LSTM_W +                       \
+     (size_t)SSD_WSPPO_GROUPS(Q) * (8 * (C) + 8 + SSD_PPO_STAT_FLOATS) +                                     \
+     (size_t)SSD_WSPPO_SPLITS(SSD_WSPPO_WINDOW_ROWS(M, Q, T)) * ((16 + (C)) * 4 * (C) + 4 * (C)))
+int ssd_ws_policy_ppo_grad(const float *weights, int32_t num_sets, int32_t cell_size, int32_t variant, int32_t agent_id,
+                           int32_t seq_len, const float *obs, const float *state, const uint8_t *starts, const float *actions,
+                           const float *logp_old, const float *advantages, const float *value_targets, const float *vf_preds,
+                           const float *behaviour_dist, int32_t n_steps, int32_t num_seqs, double clip_param,
+                           double vf_clip_param, double vf_loss_coeff, double entropy_coeff, double kl_coeff, float *scratch,
+                           float *grads, double *stats, int32_t device_id, uint32_t flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

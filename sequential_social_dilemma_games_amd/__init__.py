@@ -12,6 +12,7 @@
     from sequential_social_dilemma_games_amd import ppo_loss                    # the PPO loss and its gradients, on the device
     from sequential_social_dilemma_games_amd import ppo_loss_recurrent          # the same for the recurrent policy, with BPTT
     from sequential_social_dilemma_games_amd import ppo_loss_moa                # PPO + MOA loss for the MOA policy, with BPTT
+    from sequential_social_dilemma_games_amd import ppo_loss_watershed          # the PPO loss for the Watershed policy, with BPTT
     from sequential_social_dilemma_games_amd import a3c_loss, a3c_loss_recurrent, a3c_loss_moa   # the A3C loss, likewise
     from sequential_social_dilemma_games_amd import clip_grad_by_set_norm       # A3C's gradient clip, per weight set
     from sequential_social_dilemma_games_amd import vtrace, evaluate_fragment   # IMPALA's V-trace targets of a fragment
@@ -40,7 +41,7 @@ def __getattr__(name):
         from .episode_stats import EpisodeStats
         return EpisodeStats
     if name in ("ConvFCPolicy", "ConvLSTMPolicy", "ConvMOAPolicy", "WatershedLSTMPolicy", "ppo_loss", "ppo_loss_recurrent",
-                "ppo_loss_moa", "a3c_loss", "a3c_loss_recurrent", "a3c_loss_moa", "clip_grad_by_set_norm", "A3C_STATS",
+                "ppo_loss_moa", "ppo_loss_watershed", "ws_ppo_terms", "a3c_loss", "a3c_loss_recurrent", "a3c_loss_moa", "clip_grad_by_set_norm", "A3C_STATS",
                 "MOA_A3C_STATS", "evaluate_fragment", "impala_loss", "impala_loss_recurrent", "impala_loss_moa"):
         from . import policy
         return getattr(policy, name)

@@ -236,6 +236,33 @@ def SSD_WSP_SET_FLOATS(C):
     return SSD_WSP_ALIGN(SSD_WSP_VALUE_B(C) + 1)
 
 
+# the Watershed PPO loss-and-gradient call's partial sums and scratch (include/ssd.h, SSD_WSPPO_*)
+SSD_WSPPO_TILE, SSD_WSPPO_CHUNK, SSD_WSPPO_MAX_GROUPS, SSD_WSPPO_MAX_SPLITS, SSD_WSPPO_MAX_TRUNK_GROUPS = 16, 64, 1024, 32, 256
+
+
+def SSD_WSPPO_GROUPS(Q):
+    return min((int(Q) + SSD_WSPPO_TILE - 1) // SSD_WSPPO_TILE, SSD_WSPPO_MAX_GROUPS)
+
+
+def SSD_WSPPO_SPLITS(window_rows):
+    return min((int(window_rows) + SSD_WSPPO_CHUNK - 1) // SSD_WSPPO_CHUNK, SSD_WSPPO_MAX_SPLITS)
+
+
+def SSD_WSPPO_TRUNK_GROUPS(window_rows):
+    return min((int(window_rows) + SSD_WSPPO_TILE - 1) // SSD_WSPPO_TILE, SSD_WSPPO_MAX_TRUNK_GROUPS)
+
+
+def SSD_WSPPO_ROW_FLOATS(C):
+    return 48 + 6 * int(C)
+
+
+def SSD_WSPPO_SCRATCH_FLOATS(M, Q, C, T):
+    M, Q, C, T = int(M), int(Q), int(C), int(T)
+    rows = min(T, M) * Q
+    return ((16 + C) * 4 * C + rows * SSD_WSPPO_ROW_FLOATS(C) + SSD_WSPPO_TRUNK_GROUPS(rows) * SSD_WSP_LSTM_W
+            + SSD_WSPPO_GROUPS(Q) * (8 * C + 8 + SSD_PPO_STAT_FLOATS) + SSD_WSPPO_SPLITS(rows) * ((16 + C) * 4 * C + 4 * C))
+
+
 # every symbol include/ssd.h declares
 SYMBOLS = ("ssd_create", "ssd_destroy", "ssd_reset", "ssd_step", "ssd_step_random", "ssd_rollout_random", "ssd_rollout_actions", "ssd_rollout_path", "ssd_set_rollout_chains",
            "ssd_profiler_attached", "ssd_observe",
@@ -248,7 +275,8 @@ SYMBOLS = ("ssd_create", "ssd_destroy", "ssd_reset", "ssd_step", "ssd_step_rando
            "ssd_policy_lstm_forward", "ssd_rollout_policy_lstm", "ssd_policy_moa_forward", "ssd_rollout_policy_moa",
            "ssd_ws_policy_forward", "ssd_ws_rollout_policy", "ssd_advantages", "ssd_advantages_last_error",
            "ssd_policy_ppo_grad", "ssd_policy_lstm_ppo_grad", "ssd_policy_moa_ppo_grad",
-           "ssd_policy_ac_grad", "ssd_policy_lstm_ac_grad", "ssd_policy_moa_ac_grad", "ssd_vtrace", "ssd_vtrace_last_error")
+           "ssd_policy_ac_grad", "ssd_policy_lstm_ac_grad", "ssd_policy_moa_ac_grad", "ssd_vtrace", "ssd_vtrace_last_error",
+           "ssd_ws_policy_ppo_grad")
 # added after ABI 6 without a version bump (the calls are additive): a library built before them lacks them
 LSTM_SYMBOLS = ("ssd_policy_lstm_forward", "ssd_rollout_policy_lstm")
 MOA_SYMBOLS = ("ssd_policy_moa_forward", "ssd_rollout_policy_moa")
@@ -259,6 +287,7 @@ LSTM_PPO_SYMBOLS = ("ssd_policy_lstm_ppo_grad",)
 MOA_PPO_SYMBOLS = ("ssd_policy_moa_ppo_grad",)
 A3C_SYMBOLS = ("ssd_policy_ac_grad", "ssd_policy_lstm_ac_grad", "ssd_policy_moa_ac_grad")
 VTRACE_SYMBOLS = ("ssd_vtrace", "ssd_vtrace_last_error")
+WS_PPO_SYMBOLS = ("ssd_ws_policy_ppo_grad",)
 
 
 class SsdConfig(C.Structure):
@@ -371,9 +400,9 @@ def lib():
         L.ssd_policy_last_error.argtypes = []
         L.ssd_policy_last_error.restype = C.c_char_p
         L.ssd_rollout_policy.argtypes = [vp, vp, i32, vp, i32, i32] + [vp] * 7 + [i32, vp, u32, vp]
-        missing = [name for name in LSTM_SYMBOLS + MOA_SYMBOLS + WS_POLICY_SYMBOLS + ADVANTAGES_SYMBOLS + PPO_SYMBOLS + LSTM_PPO_SYMBOLS + MOA_PPO_SYMBOLS + A3C_SYMBOLS + VTRACE_SYMBOLS if not hasattr(L, name)]
+        missing = [name for name in LSTM_SYMBOLS + MOA_SYMBOLS + WS_POLICY_SYMBOLS + ADVANTAGES_SYMBOLS + PPO_SYMBOLS + LSTM_PPO_SYMBOLS + MOA_PPO_SYMBOLS + A3C_SYMBOLS + VTRACE_SYMBOLS + WS_PPO_SYMBOLS if not hasattr(L, name)]
         if missing:
-            raise SsdError("%s lacks %s (built before the recurrent, MOA or Watershed policy calls, the advantages call, the PPO or A3C gradient calls or the V-trace call): rebuild it with `python -c 'import "
+            raise SsdError("%s lacks %s (built before the recurrent, MOA or Watershed policy calls, the advantages call, the PPO or A3C gradient calls, the V-trace call or the Watershed PPO gradient call): rebuild it with `python -c 'import "
                            "__graft_entry__ as g; g.build()'`" % (LIB_PATH, ", ".join(missing)))
         L.ssd_policy_lstm_forward.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, u32, vp]
         L.ssd_rollout_policy_lstm.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, vp, i32, i32] + [vp] * 8 + [i32, vp, u32, vp]
@@ -398,6 +427,8 @@ def lib():
         L.ssd_vtrace.argtypes = [vp, vp, C.c_double, vp, vp, vp, vp, i32, i32, i32, i32, C.c_double, C.c_double, C.c_double, u32, vp, vp, i32, vp]
         L.ssd_vtrace_last_error.argtypes = []
         L.ssd_vtrace_last_error.restype = C.c_char_p
+        L.ssd_ws_policy_ppo_grad.argtypes = ([vp, i32, i32, i32, i32, i32] + [vp] * 9 + [i32, i32] + [C.c_double] * 5
+                                             + [vp, vp, vp, i32, u32, vp])
         for name in SYMBOLS:
             getattr(L, name)
         if L.ssd_abi_version() != ABI_VERSION:

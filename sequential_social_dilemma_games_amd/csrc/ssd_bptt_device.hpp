@@ -3,7 +3,8 @@
 // heads, the cell's backward over a lane's rows, dz W^T with the carried dh, the partial sums), the sequence kernel itself, the
 // split-K kernel d W = [x, h_prev]^T dz, the column-sum epilogue and the transposer.  Used by ssd_policy_lstm_grad.hip (the
 // recurrent policy) and ssd_policy_moa_grad.hip (the MOA policy's two branches); include/ssd.h states the contract, DESIGN.md
-// sections 17 and 18 the shape.
+// sections 17 and 18 the shape.  ssd_ws_policy_grad.hip (the Watershed policy, section 21) has kernels of its own and calls the
+// inline pieces that fit it as they are: cell_state, cell_backward, bptt_column_sum and the transposer.
 //
 // A user is a Branch, compile-time constants only:
 //   Cell                 ssd::RllibCell or ssd::KerasCell (gate order, forget bias, where c and h sit in a state's two rows)

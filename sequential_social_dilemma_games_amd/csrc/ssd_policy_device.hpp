@@ -2,7 +2,7 @@
 // two cell rules and the cell update, the start rule and the loader of the h rows, the heads, the PPO loss terms of a row, the
 // action draw, and the conv-FC trunk (conv, fc1, fc2) on a tile.  Used by ssd_policy.hip (conv-FC), ssd_policy_grad.hip,
 // ssd_policy_lstm.hip, ssd_policy_moa.hip, ssd_ws_policy.hip and ssd_bptt_device.hpp (the pieces of the BPTT gradient kernels,
-// through which ssd_policy_lstm_grad.hip and ssd_policy_moa_grad.hip reach these); the argument blocks stay in
+// through which ssd_policy_lstm_grad.hip and ssd_policy_moa_grad.hip reach these) and ssd_ws_policy_grad.hip; the argument blocks stay in
 // ssd_policy.hpp, which host code reads too.  Every sum below is one chain in a fixed order, so a change here changes the
 // bits of every kernel that uses the piece, and the tests that compare kernels and paths bit for bit see it.
 //

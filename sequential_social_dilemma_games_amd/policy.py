@@ -659,17 +659,26 @@ def _ppo_obs(t, K):
     return t["obs_first"].unsqueeze(0) if K == 1 else torch.cat([t["obs_first"].unsqueeze(0), t["obs"][:K - 1]])
 
 
-def unpack_gradient(policy, grads, scale=None):
+def unpack_gradient(policy, grads, scale=None, only_set=None):
     """A packed gradient [P, set_floats] (the layout packed() writes) as one tensor per parameter of policy.layout(), in its
     order and the parameter's shape, times scale where given.  For a parameter with fewer entries than sets -- packed() wrote
     entry k into sets k, k + entries, ... -- the sets' gradients are summed (no ConvFCPolicy parameter is shared this way; a
-    WatershedLSTMPolicy's dense1 with share_comm_layer is)."""
+    WatershedLSTMPolicy's dense1 with share_comm_layer is).  only_set: grads is [set_floats], the gradient of that one weight
+    set (ssd_ws_policy_ppo_grad's); it goes to entry only_set % entries of each parameter, every other entry is exactly zero."""
     P = policy.num_sets
     out = []
     for name, shape, off in policy.layout():
         n = int(np.prod(shape))
-        g = grads[:, off:off + n]
         entries = getattr(policy, name).shape[0]
+        if only_set is not None:
+            g = grads.reshape(-1)[off:off + n]
+            if scale is not None:
+                g = g * scale
+            full = torch.zeros((entries, n), dtype=g.dtype, device=g.device)
+            full[int(only_set) % entries] = g
+            out.append(full.reshape((entries,) + tuple(shape)))
+            continue
+        g = grads[:, off:off + n]
         if entries != P:
             g = g.reshape(P // entries, entries, n).sum(0)
         if scale is not None:
@@ -1646,3 +1655,181 @@ class WatershedLSTMPolicy(PolicyBase):
             return d.reshape(lead + (WS_OUT,)), v.reshape(lead), (h, c)
         dists, values, hc = _unroll(step, T, (st[:, 0], st[:, 1]), resets)
         return dists, values, torch.stack(hc, dim=1).reshape(lead + (2, C))
+
+
+# ---- the PPO loss for the Watershed policy, one agent id a call (include/ssd.h, WATERSHED PPO LOSS AND GRADIENTS) ----
+
+def ws_ppo_terms(dist, value, t, is_comm, clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff):
+    """RLlib 0.7.6's PPO loss per row for a Watershed head in plain torch, in the dtype of dist: (row_loss, -surr, vf, kl, ent),
+    each of actions' shape.  dist [..., 5], value [...]; t: actions, logp_old, advantages, value_targets, vf_pred and, for the
+    KL term, behaviour_dist.  is_comm: Categorical over the 5 outputs (ppo_terms with A = 5; actions hold the message index),
+    else a one-dimensional DiagGaussian with mean = dist[..., 0], log_std = dist[..., 1] (actions hold the unclipped sample):
+    logp = -0.5 z^2 - log_std - 0.9189385 with z = (a - mean) / exp(log_std), entropy = log_std + 1.4189385 and
+    kl = log_std - log_std_old + (exp(2 log_std_old) + (mean_old - mean)^2) / (2 exp(2 log_std)) - 0.5 (the behaviour's against
+    the current one, RLlib's prev_dist.kl(curr_dist))."""
+    dt = dist.dtype
+    if is_comm:
+        tt = dict(t)
+        tt["actions"] = t["actions"].to(torch.int64).clamp(0, WS_OUT - 1)
+        tt["behaviour_logits"] = t.get("behaviour_dist")
+        return ppo_terms(dist, value, tt, clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff)
+    mean, log_std = dist[..., 0], dist[..., 1]
+    z = (t["actions"].to(dt) - mean) / torch.exp(log_std)
+    logp = -0.5 * (z * z) - log_std - torch.tensor(np.float32(0.9189385), dtype=dt)
+    ent = log_std + torch.tensor(np.float32(1.4189385), dtype=dt)
+    adv, vt, vfp = t["advantages"].to(dt), t["value_targets"].to(dt), t["vf_pred"].to(dt)
+    ratio = torch.exp(logp - t["logp_old"].to(dt))
+    surr = torch.minimum(adv * ratio, adv * ratio.clamp(1.0 - clip_param, 1.0 + clip_param))
+    if t.get("behaviour_dist") is not None:
+        b = t["behaviour_dist"].to(dt)
+        kl = (log_std - b[..., 1]) + 0.5 * (torch.exp(2.0 * b[..., 1]) + (b[..., 0] - mean).square()) / torch.exp(2.0 * log_std) - 0.5
+    else:
+        kl = torch.zeros_like(ent)
+    vf1 = (value - vt).square()
+    vf2 = (vfp + (value - vfp).clamp(-vf_clip_param, vf_clip_param) - vt).square()
+    vf = torch.maximum(vf1, vf2)
+    return -surr + kl_coeff * kl + vf_loss_coeff * vf - entropy_coeff * ent, -surr, vf, kl, ent
+
+
+_WS_PPO_KEYS = (("obs", ("obs",)), ("actions", ("actions",)), ("logp_old", ("logp_old", "logp")), ("advantages", ("advantages",)),
+                ("value_targets", ("value_targets",)), ("vf_pred", ("vf_pred", "value")),
+                ("behaviour_dist", ("behaviour_dist", "dist")), ("starts", ("starts",)), ("state", ("state",)))
+
+
+def _ws_ppo_tensors(policy, seq, seq_len, kl_coeff):
+    """The Watershed loss's inputs by their contract names from a dict of [M, Q, ...] tensors, checked against each other."""
+    if not isinstance(seq, dict):
+        raise ValueError("seq must be a dict of [M, Q, ...] tensors")
+    t = {name: next((seq[k] for k in keys if seq.get(k) is not None), None) for name, keys in _WS_PPO_KEYS}
+    acts = t["actions"]
+    if not isinstance(acts, torch.Tensor) or acts.dim() != 2 or acts.numel() == 0:
+        raise ValueError("actions must be a float32 tensor [M, Q]")
+    M, Q = (int(n) for n in acts.shape)
+    C, T, dev = policy.cell_size, int(seq_len), acts.device
+    if M * Q > 2 ** 31 - 17:
+        raise ValueError("the sequences must have at most 2^31 - 17 rows")
+    if float(kl_coeff) == 0.0:
+        t["behaviour_dist"] = None                           # not part of the loss
+    elif t["behaviour_dist"] is None:
+        raise ValueError("kl_coeff != 0 needs dist (the dist the actions were sampled from)")
+
+    def check(x, dtype, shape, name):
+        if not isinstance(x, torch.Tensor) or x.dtype != dtype or tuple(x.shape) != shape or x.device != dev or not x.is_contiguous():
+            raise ValueError("%s must be a contiguous %s tensor of shape %s on %s" % (name, dtype, shape, dev))
+    for name in ("actions", "logp_old", "advantages", "value_targets", "vf_pred"):
+        check(t[name], torch.float32, (M, Q), name)
+    check(t["obs"], torch.float32, (M, Q, WS_OBS), "obs")
+    if t["behaviour_dist"] is not None:
+        check(t["behaviour_dist"], torch.float32, (M, Q, WS_OUT), "dist")
+    if t["starts"] is not None:
+        if t["starts"].dtype == torch.bool:
+            t["starts"] = t["starts"].to(torch.uint8)
+        check(t["starts"], torch.uint8, (M, Q), "starts")
+    S = -(-M // T)
+    st = t["state"]
+    if not isinstance(st, torch.Tensor) or st.dim() != 4 or st.shape[0] < S or tuple(st.shape[1:]) != (Q, 2, C):
+        raise ValueError("state must be [S, %d, 2, %d] with S >= ceil(M / seq_len) = %d" % (Q, C, S))
+    check(st, torch.float32, tuple(st.shape), "state")
+    return t, (M, Q)
+
+
+def ws_forward_windows(policy, agent_id, obs, state, starts, seq_len):
+    """The learner's forward of a WatershedLSTMPolicy over one agent's sequences, in plain torch under autograd, by the state
+    rule of include/ssd.h: obs [M, Q, 12], state [S, Q, 2, C] (detached: data), starts u8/bool [M, Q] or None -> (dist [M, Q, 5],
+    value [M, Q]).  Window by window through forward_sequence; starts at a window's first step are not looked at."""
+    M, T = int(obs.shape[0]), int(seq_len)
+    dt = policy.dense0_w.dtype
+    dists, values = [], []
+    for w, m0 in enumerate(range(0, M, T)):
+        m1 = min(m0 + T, M)
+        resets = None
+        if starts is not None and m1 - m0 > 1:
+            resets = torch.cat([torch.zeros_like(starts[:1]), starts[m0 + 1:m1]]).to(torch.bool)
+        d, v, _ = policy.forward_sequence(agent_id, obs[m0:m1], state[w].detach().to(dt), resets)
+        dists.append(d)
+        values.append(v)
+    return torch.cat(dists), torch.cat(values)
+
+
+class _WatershedPPOLossFunction(torch.autograd.Function):
+    """ssd_ws_policy_ppo_grad as a torch function of the policy's parameters, as _RecurrentPPOLossFunction: the packed
+    gradient of set agent_id goes to entry agent_id of every parameter (a shared dense1: entry agent_id % 4)."""
+
+    @staticmethod
+    def forward(ctx, policy, agent_id, t, dims, seq_len, hyper, *params):
+        import ctypes as C
+        M, Q = dims
+        dev = t["actions"].device
+        weights = policy.packed()
+        need = _capi.SSD_WSPPO_SCRATCH_FLOATS(M, Q, policy.cell_size, seq_len)
+        scratch = getattr(policy, "_ppo_scratch", None)          # kept between calls, as packed()'s buffer is
+        if scratch is None or scratch.device != dev or scratch.numel() < need:
+            scratch = policy._ppo_scratch = torch.empty(need, dtype=torch.float32, device=dev)
+        grads = torch.empty((policy.set_floats,), dtype=torch.float32, device=dev)
+        stats = torch.empty((len(PPO_STATS),), dtype=torch.float64, device=dev)
+        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())   # noqa: E731
+        index = dev.index if dev.index is not None else torch.cuda.current_device()
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _capi.policy_check(_capi.lib().ssd_ws_policy_ppo_grad(
+            ptr(weights), policy.num_sets, policy.cell_size, policy.variant, agent_id, seq_len, ptr(t["obs"]), ptr(t["state"]),
+            ptr(t["starts"]), ptr(t["actions"]), ptr(t["logp_old"]), ptr(t["advantages"]), ptr(t["value_targets"]),
+            ptr(t["vf_pred"]), ptr(t["behaviour_dist"]), M, Q, *hyper, ptr(scratch), ptr(grads), ptr(stats), index, 0, stream))
+        ctx.policy, ctx.agent_id = policy, agent_id
+        ctx.save_for_backward(grads)
+        ctx.mark_non_differentiable(stats)
+        return stats[0].to(torch.float32), stats
+
+    @staticmethod
+    def backward(ctx, g_loss, g_stats):
+        (grads,) = ctx.saved_tensors
+        out = unpack_gradient(ctx.policy, grads, g_loss, only_set=ctx.agent_id)
+        return (None,) * 6 + tuple(g if needs else None for g, needs in zip(out, ctx.needs_input_grad[6:]))
+
+
+def ppo_loss_watershed(policy, agent_id, seq, *, seq_len, clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff):
+    """RLlib 0.7.6's PPO loss of ONE agent id of a WatershedLSTMPolicy on that agent's own steps, with truncated backpropagation
+    through time over windows of seq_len steps -> (loss, stats): loss a scalar tensor that backpropagates into row agent_id of
+    every parameter (every other row's gradient is exactly zero; a shared dense1 gets entry agent_id % 4), stats a dict of
+    scalar tensors (PPO_STATS).  In the reference each agent's policy has its own loss, so a learner makes one call per id.
+    include/ssd.h (WATERSHED PPO LOSS AND GRADIENTS) states the rows, the state rule and the two heads' terms.
+
+        loss, stats = ppo_loss_watershed(policy, 5, seq, seq_len=16, clip_param=0.3, vf_clip_param=10.0, vf_loss_coeff=1e-4,
+                                         entropy_coeff=1e-3, kl_coeff=0.0)
+        loss.backward(); optimiser.step()
+
+    seq: a dict of tensors over the agent's M own steps of Q sequences (one env's trajectory each), gathered by the caller:
+    obs f32 [M,Q,12] (the observation each step acted on), actions f32 [M,Q] (the message index for a comm agent, the unclipped
+    Gaussian sample for an action agent: what sample() records), logp (or logp_old), advantages, value_targets, value (or
+    vf_pred) f32 [M,Q], state f32 [ceil(M / seq_len),Q,2,C] (the (h, c) each window starts from), optionally dist (or
+    behaviour_dist) f32 [M,Q,5] (needed if kl_coeff != 0) and starts u8 or bool [M,Q] (the state step m uses is zero; not looked
+    at where m is a window's first step, whose state is the recorded one).  Which reward is credited to which step is the
+    caller's choice: advantages and value_targets are inputs (compute_advantages accepts any [R, L] tensors).
+    CUDA tensors go to the library (ssd_ws_policy_ppo_grad on torch's current stream, no synchronisation; the scratch is kept
+    on the policy); CPU tensors run forward_sequence per window and ws_ppo_terms under autograd."""
+    if not isinstance(policy, WatershedLSTMPolicy):
+        raise ValueError("ppo_loss_watershed is for a WatershedLSTMPolicy")
+    if isinstance(agent_id, bool) or int(agent_id) != agent_id or not 0 <= int(agent_id) < policy.num_sets:
+        raise ValueError("agent_id must be 0..%d" % (policy.num_sets - 1))
+    agent_id = int(agent_id)
+    if isinstance(seq_len, bool) or int(seq_len) != seq_len or int(seq_len) < 1:
+        raise ValueError("seq_len must be an integer >= 1")
+    seq_len = int(seq_len)
+    hyper = tuple(float(x) for x in (clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff))
+    if not all(np.isfinite(hyper)) or hyper[0] < 0 or hyper[1] < 0:
+        raise ValueError("the hyper-parameters must be finite, clip_param and vf_clip_param >= 0")
+    t, (M, Q) = _ws_ppo_tensors(policy, seq, seq_len, hyper[4])
+    dev = t["actions"].device
+    if policy.dense0_w.device != dev:
+        raise ValueError("the policy is on %s, the sequences on %s" % (policy.dense0_w.device, dev))
+    if dev.type == "cuda":
+        if policy.dense0_w.dtype != torch.float32:
+            raise ValueError("the device path needs a float32 policy")
+        params = tuple(getattr(policy, name) for name, _, _ in policy.layout())
+        loss, stats = _WatershedPPOLossFunction.apply(policy, agent_id, t, (M, Q), seq_len, hyper, *params)
+        return loss, {name: stats[k] for k, name in enumerate(PPO_STATS)}
+    if dev.type != "cpu":
+        raise ValueError("the tensors must be on the CPU or on a GPU, not on %s" % (dev,))
+    dist, value = ws_forward_windows(policy, agent_id, t["obs"], t["state"], t["starts"], seq_len)
+    terms = ws_ppo_terms(dist, value, t, bool(ws_is_comm(policy.variant, agent_id)), *hyper)
+    means = [x.mean() for x in terms]
+    return means[0], {name: m.detach() for name, m in zip(PPO_STATS, means)}
