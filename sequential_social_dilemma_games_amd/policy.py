@@ -15,6 +15,8 @@ NHWC --, fc1 1014 -> 32 + ReLU, fc2 32 -> 32 + ReLU, logits 32 -> A, and a value
 value_function() of a v1 Model).  The parameters are stored in TF's layouts (conv kernel [kh, kw, c_in, c_out], dense kernels
 [in, out]) with a leading weight-set axis, so they map one to one onto a TF checkpoint's and onto the packed layout.
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -568,6 +570,45 @@ _PPO_KEYS = (("obs", ("obs",)), ("actions", ("actions",)), ("logp_old", ("logp_o
 _A3C_ROWS = ("advantages", "value_targets")                                # the A3C loss's float per-row inputs
 
 
+# The argument checks the loss functions share.  Each function calls them in its own order (the PPO functions look at the state
+# ring before the device's type, the A3C functions after it), so which of two faults is named stays as it was.
+
+def _check_seq_len(seq_len):
+    if isinstance(seq_len, bool) or int(seq_len) != seq_len or int(seq_len) < 1:
+        raise ValueError("seq_len must be an integer >= 1")
+    return int(seq_len)
+
+
+def _check_hyper(hyper, clips):
+    """Finite hyper-parameters; clips: the first two are the PPO loss's clip parameters, which must not be negative."""
+    finite = all(np.isfinite(hyper))
+    if clips and (not finite or hyper[0] < 0 or hyper[1] < 0):
+        raise ValueError("the hyper-parameters must be finite, clip_param and vf_clip_param >= 0")
+    if not finite:
+        raise ValueError("the hyper-parameters must be finite")
+
+
+def _check_same_device(policy, dev, what="batch"):
+    ref = getattr(policy, policy.REF_PARAM)
+    if ref.device != dev:
+        raise ValueError("the policy is on %s, the %s on %s" % (ref.device, what, dev))
+
+
+def _check_device_type(dev):
+    if dev.type not in ("cuda", "cpu"):
+        raise ValueError("the tensors must be on the CPU or on a GPU, not on %s" % (dev,))
+
+
+def _check_float32(policy, dev):
+    if dev.type == "cuda" and getattr(policy, policy.REF_PARAM).dtype != torch.float32:
+        raise ValueError("the device path needs a float32 policy")
+
+
+def _check_tensor(x, dtype, shape, name, dev):
+    if not isinstance(x, torch.Tensor) or x.dtype != dtype or tuple(x.shape) != shape or x.device != dev or not x.is_contiguous():
+        raise ValueError("%s must be a contiguous %s tensor of shape %s on %s" % (name, dtype, shape, dev))
+
+
 def _ppo_tensors(policy, batch, obs_first, kl_coeff, a3c=False):
     """The loss's inputs by their contract names from the dict sample() returns (logp as logp_old, value as vf_pred, logits
     as behaviour_logits) or a tuple in _PPO_KEYS' order, checked against each other: K from actions [K, E, N].  a3c: the A3C
@@ -604,23 +645,19 @@ def _ppo_tensors(policy, batch, obs_first, kl_coeff, a3c=False):
         t["behaviour_logits"] = None                        # not part of the loss
     elif t["behaviour_logits"] is None:
         raise ValueError("kl_coeff != 0 needs behaviour_logits (the logits the actions were sampled from)")
-
-    def check(x, dtype, shape, name):
-        if not isinstance(x, torch.Tensor) or x.dtype != dtype or tuple(x.shape) != shape or x.device != dev or not x.is_contiguous():
-            raise ValueError("%s must be a contiguous %s tensor of shape %s on %s" % (name, dtype, shape, dev))
-    check(acts, torch.int32, (K, E, N), "actions")
+    _check_tensor(acts, torch.int32, (K, E, N), "actions", dev)
     for name in per_row:
-        check(t[name], torch.float32, (K, E, N), name)
+        _check_tensor(t[name], torch.float32, (K, E, N), name, dev)
     if t["behaviour_logits"] is not None:
-        check(t["behaviour_logits"], torch.float32, (K, E, N, A), "behaviour_logits")
+        _check_tensor(t["behaviour_logits"], torch.float32, (K, E, N, A), "behaviour_logits", dev)
     obs = t["obs"]
     need = K if obs_first is None else K - 1                # with obs_first the last row of obs is never read
     if need or obs is not None:
         if not isinstance(obs, torch.Tensor) or obs.dim() != 6 or obs.shape[0] < need:
             raise ValueError("obs must be a uint8 tensor [K, E, N, 15, 15, 3] of at least %d steps" % need)
-        check(obs, torch.uint8, (int(obs.shape[0]), E, N, VIEW, VIEW, 3), "obs")
+        _check_tensor(obs, torch.uint8, (int(obs.shape[0]), E, N, VIEW, VIEW, 3), "obs", dev)
     if obs_first is not None:
-        check(obs_first, torch.uint8, (E, N, VIEW, VIEW, 3), "obs_first")
+        _check_tensor(obs_first, torch.uint8, (E, N, VIEW, VIEW, 3), "obs_first", dev)
     t["obs_first"] = obs_first
     return t, (K, E, N)
 
@@ -687,41 +724,90 @@ def unpack_gradient(policy, grads, scale=None, only_set=None):
     return out
 
 
-class _PPOLossFunction(torch.autograd.Function):
-    """ssd_policy_ppo_grad as a torch function of the policy's parameters: forward enqueues the library's two launches on the
-    current stream and keeps the packed gradient, backward scatters it into the parameters' shapes by layout()."""
+def _state_tensors(policy, batch, K, E, N, seq_len, dev):
+    """The state ring [S, E, N, STATE_ROWS, C], done [K, E, N] (or None) and, for a ConvMOAPolicy, prev_actions [K, E, N] (else
+    None) of a recurrent fragment, checked."""
+    C, R, S = policy.cell_size, policy.STATE_ROWS, -(-K // seq_len)
+    state = batch.get("state")
+    if state is None and seq_len >= K and batch.get("state_in") is not None:
+        state = batch["state_in"].unsqueeze(0)                    # one window: the state step 0 used
+    if not isinstance(state, torch.Tensor):
+        raise ValueError("state is required: the ring sample(..., state_every=seq_len) records (state_in serves when seq_len >= K)")
+    if state.dim() != 5 or tuple(state.shape[1:4]) != (E, N, R) or state.shape[0] < S:
+        raise ValueError("state must be [S, %d, %d, %d, C] with S >= ceil(K / seq_len) = %d, got %s" % (E, N, R, S, tuple(state.shape)))
+    if state.shape[-1] != C:
+        raise ValueError("state has %d cells, the policy %d" % (state.shape[-1], C))
+    if state.dtype != torch.float32 or state.device != dev or not state.is_contiguous():
+        raise ValueError("state must be a contiguous torch.float32 tensor on %s" % (dev,))
+    done, prev = batch.get("done"), None
+    if done is not None:
+        _check_tensor(done, torch.uint8, (K, E, N), "done", dev)
+    if isinstance(policy, ConvMOAPolicy):
+        prev = batch.get("prev_actions")
+        _check_tensor(prev, torch.int32, (K, E, N), "prev_actions", dev)
+    return state, done, prev
 
-    @staticmethod
-    def forward(ctx, policy, t, dims, hyper, *params):
-        import ctypes as C
-        K, E, N = dims
-        P, A = policy.num_sets, policy.num_actions
-        dev = t["actions"].device
-        weights = policy.packed()
-        set_rows = K * E * N // P
-        need = policy.ppo_scratch_shape(set_rows)[0]
-        scratch = getattr(policy, "_ppo_scratch", None)          # kept between calls, as packed()'s buffer is
-        if scratch is None or scratch.device != dev or scratch.numel() < need:
-            scratch = policy._ppo_scratch = torch.empty(need, dtype=torch.float32, device=dev)
-        grads = torch.empty((P, policy.set_floats), dtype=torch.float32, device=dev)
-        stats = torch.empty((P, len(PPO_STATS)), dtype=torch.float64, device=dev)
-        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())   # noqa: E731
-        index = dev.index if dev.index is not None else torch.cuda.current_device()
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _capi.policy_check(_capi.lib().ssd_policy_ppo_grad(
-            ptr(weights), P, A, ptr(t["obs_first"]), ptr(t["obs"]), ptr(t["actions"]), ptr(t["logp_old"]), ptr(t["advantages"]),
-            ptr(t["value_targets"]), ptr(t["vf_pred"]), ptr(t["behaviour_logits"]), K, E, N, *hyper, ptr(scratch), ptr(grads),
-            ptr(stats), index, 0, stream))
-        ctx.policy = policy
-        ctx.save_for_backward(grads)
-        ctx.mark_non_differentiable(stats)
-        return stats[:, 0].sum().to(torch.float32), stats
 
-    @staticmethod
-    def backward(ctx, g_loss, g_stats):
-        (grads,) = ctx.saved_tensors
-        out = unpack_gradient(ctx.policy, grads, g_loss)
-        return (None, None, None, None) + tuple(g if needs else None for g, needs in zip(out, ctx.needs_input_grad[4:]))
+def _forward_windows(policy, obs, prev_actions, state, done, seq_len):
+    """The window walk of the state rule of include/ssd.h: forward_sequence on steps k0 .. k1 - 1 of each window from ring entry
+    state[w] (data), step k of a window reset where done[k - 1] is set -> forward_sequence's outputs joined over the windows,
+    then the state after the last step.  prev_actions: None for a ConvLSTMPolicy."""
+    K, T = int(obs.shape[0]), int(seq_len)
+    dt = policy.conv_w.dtype
+    windows = []
+    for w, k0 in enumerate(range(0, K, T)):
+        k1 = min(k0 + T, K)
+        resets = None
+        if done is not None and k1 - k0 > 1:
+            resets = torch.cat([torch.zeros_like(done[:1]), done[k0:k1 - 1]]).to(torch.bool)
+        rows = (obs[k0:k1],) if prev_actions is None else (obs[k0:k1], prev_actions[k0:k1])
+        *out, last = policy.forward_sequence(*rows, state[w].detach().to(dt), resets)
+        windows.append(out)
+    return tuple(torch.cat(col) for col in zip(*windows)) + (last,)
+
+
+def _moa_set_ce(policy, moa_logits, actions):
+    """policy.moa_loss of each weight set's rows [P]: the mean cross-entropy of moa_logits [K, E, N, N-1, A] against the other
+    agents' actions [K, E, N] (clamped to 0 .. A - 1) of the same step."""
+    A, P = policy.num_actions, policy.num_sets
+    acts = actions.clamp(0, A - 1)
+    if P == 1:
+        return policy.moa_loss(moa_logits, acts).reshape(1)
+    others = acts.long()[..., policy._others.to(acts.device)]       # [K, E, N, N-1]; set p's rows are agent p's: its N - 1 predictions
+    return torch.stack([torch.nn.functional.cross_entropy(moa_logits[:, :, p].reshape(-1, A), others[:, :, p].reshape(-1))
+                        for p in range(P)])
+
+
+def _cpu_result(per_set, names, ce=None, moa_weight=0.0):
+    """The end of a CPU path: per_set, the loss's terms reduced over each weight set's rows ([P] each, the total first), and
+    for the MOA policy the sets' cross-entropy ce [P], added to the total with its weight -> (loss, stats by `names`)."""
+    if ce is not None:
+        per_set[0] = per_set[0] + moa_weight * ce
+        per_set.append(ce)
+    return per_set[0].sum(), {name: m.detach() for name, m in zip(names, per_set)}
+
+
+def _ppo_prepare(policy, batch, obs_first, seq_len, hyper):
+    """The checks the three PPO functions share -> (t, (K, E, N), seq_len, hyper as floats, dev).  seq_len None: the conv-FC
+    policy's call; hyper: the five of PPOLoss and, for the MOA policy, moa_weight."""
+    if seq_len is not None:
+        if not isinstance(batch, dict):
+            raise ValueError("batch must be the dict sample() returns")
+        seq_len = _check_seq_len(seq_len)
+    hyper = tuple(float(x) for x in hyper)
+    _check_hyper(hyper, clips=True)
+    if len(hyper) > 5 and hyper[5] < 0:
+        raise ValueError("moa_weight must be >= 0")
+    t, (K, E, N) = _ppo_tensors(policy, batch, obs_first, hyper[4])
+    if isinstance(policy, ConvMOAPolicy) and N != policy.num_agents:
+        raise ValueError("the policy is for %d agents, the batch has %d" % (policy.num_agents, N))
+    dev = t["actions"].device
+    _check_same_device(policy, dev)
+    if seq_len is not None:
+        t["state"], t["done"], t["prev_actions"] = _state_tensors(policy, batch, K, E, N, seq_len, dev)
+    _check_float32(policy, dev)
+    _check_device_type(dev)
+    return t, (K, E, N), seq_len, hyper, dev
 
 
 def ppo_loss(policy, batch, *, clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff, obs_first=None):
@@ -747,104 +833,22 @@ def ppo_loss(policy, batch, *, clip_param, vf_clip_param, vf_loss_coeff, entropy
     activation kept); CPU tensors run the same loss in plain torch under autograd."""
     if not isinstance(policy, ConvFCPolicy):
         raise ValueError("ppo_loss is for a ConvFCPolicy (the recurrent policies need backpropagation through time)")
-    hyper = tuple(float(x) for x in (clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff))
-    if not all(np.isfinite(hyper)) or hyper[0] < 0 or hyper[1] < 0:
-        raise ValueError("the hyper-parameters must be finite, clip_param and vf_clip_param >= 0")
-    t, (K, E, N) = _ppo_tensors(policy, batch, obs_first, hyper[4])
-    dev, P = t["actions"].device, policy.num_sets
-    if policy.conv_w.device != dev:
-        raise ValueError("the policy is on %s, the batch on %s" % (policy.conv_w.device, dev))
+    hyper = (clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff)
+    t, (K, E, N), _, hyper, dev = _ppo_prepare(policy, batch, obs_first, None, hyper)
     if dev.type == "cuda":
-        if policy.conv_w.dtype != torch.float32:
-            raise ValueError("the device path needs a float32 policy")
-        params = tuple(getattr(policy, name) for name, _, _ in policy.layout())
-        loss, stats = _PPOLossFunction.apply(policy, t, (K, E, N), hyper, *params)
-        return loss, {name: stats[:, k] for k, name in enumerate(PPO_STATS)}
-    if dev.type != "cpu":
-        raise ValueError("the tensors must be on the CPU or on a GPU, not on %s" % (dev,))
+        return _device_loss(policy, (ConvFCPolicy, "ppo"), t, (K, E, N), 0, hyper)
     logits, value = policy(_ppo_obs(t, K))
-    terms = ppo_terms(logits, value, t, *hyper)
-    means = [_set_means(x, P) for x in terms]
-    return means[0].sum(), {name: m.detach() for name, m in zip(PPO_STATS, means)}
+    return _cpu_result([_set_means(x, policy.num_sets) for x in ppo_terms(logits, value, t, *hyper)], PPO_STATS)
 
 
 # ---- the same loss for the recurrent policy, with truncated BPTT (include/ssd.h, RECURRENT PPO LOSS AND GRADIENTS) ----
-
-def _recurrent_tensors(policy, batch, K, E, N, seq_len, dev):
-    """The state ring [S, E, N, 2, C] and done [K, E, N] (or None) of a recurrent fragment, checked."""
-    C, T = policy.cell_size, int(seq_len)
-    S = -(-K // T)
-    state = batch.get("state")
-    if state is None and T >= K and batch.get("state_in") is not None:
-        state = batch["state_in"].unsqueeze(0)                    # one window: the state step 0 used
-    if not isinstance(state, torch.Tensor):
-        raise ValueError("state is required: the ring sample(..., state_every=seq_len) records (state_in serves when seq_len >= K)")
-    if state.dim() != 5 or tuple(state.shape[1:4]) != (E, N, 2) or state.shape[0] < S:
-        raise ValueError("state must be [S, %d, %d, 2, C] with S >= ceil(K / seq_len) = %d, got %s" % (E, N, S, tuple(state.shape)))
-    if state.shape[-1] != C:
-        raise ValueError("state has %d cells, the policy %d" % (state.shape[-1], C))
-    if state.dtype != torch.float32 or state.device != dev or not state.is_contiguous():
-        raise ValueError("state must be a contiguous torch.float32 tensor on %s" % (dev,))
-    done = batch.get("done")
-    if done is not None:
-        if (not isinstance(done, torch.Tensor) or done.dtype != torch.uint8 or tuple(done.shape) != (K, E, N) or done.device != dev
-                or not done.is_contiguous()):
-            raise ValueError("done must be a contiguous torch.uint8 tensor of shape %s on %s" % ((K, E, N), dev))
-    return state, done
-
-
-class _RecurrentPPOLossFunction(torch.autograd.Function):
-    """ssd_policy_lstm_ppo_grad as a torch function of the policy's parameters, as _PPOLossFunction."""
-
-    @staticmethod
-    def forward(ctx, policy, t, dims, seq_len, hyper, *params):
-        import ctypes as C
-        K, E, N = dims
-        P, A = policy.num_sets, policy.num_actions
-        dev = t["actions"].device
-        weights = policy.packed()
-        need = policy.ppo_scratch_shape(K, E, N, seq_len)[0]
-        scratch = getattr(policy, "_ppo_scratch", None)          # kept between calls, as packed()'s buffer is
-        if scratch is None or scratch.device != dev or scratch.numel() < need:
-            scratch = policy._ppo_scratch = torch.empty(need, dtype=torch.float32, device=dev)
-        grads = torch.empty((P, policy.set_floats), dtype=torch.float32, device=dev)
-        stats = torch.empty((P, len(PPO_STATS)), dtype=torch.float64, device=dev)
-        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())   # noqa: E731
-        index = dev.index if dev.index is not None else torch.cuda.current_device()
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _capi.policy_check(_capi.lib().ssd_policy_lstm_ppo_grad(
-            ptr(weights), P, A, policy.cell_size, seq_len, ptr(t["obs_first"]), ptr(t["obs"]), ptr(t["state"]), ptr(t["done"]),
-            ptr(t["actions"]), ptr(t["logp_old"]), ptr(t["advantages"]), ptr(t["value_targets"]), ptr(t["vf_pred"]),
-            ptr(t["behaviour_logits"]), K, E, N, *hyper, ptr(scratch), ptr(grads), ptr(stats), index, 0, stream))
-        ctx.policy = policy
-        ctx.save_for_backward(grads)
-        ctx.mark_non_differentiable(stats)
-        return stats[:, 0].sum().to(torch.float32), stats
-
-    @staticmethod
-    def backward(ctx, g_loss, g_stats):
-        (grads,) = ctx.saved_tensors
-        out = unpack_gradient(ctx.policy, grads, g_loss)
-        return (None, None, None, None, None) + tuple(g if needs else None for g, needs in zip(out, ctx.needs_input_grad[5:]))
-
 
 def recurrent_forward(policy, obs, state, done, seq_len):
     """The learner's forward of a ConvLSTMPolicy over a fragment, in plain torch under autograd, by the state rule of
     include/ssd.h: obs u8 [K, E, N, 15, 15, 3] (the observation each row acted on), the ring state [S, E, N, 2, C] (detached:
     data), done u8 [K, E, N] or None -> (logits [K, E, N, A], value [K, E, N]).  Window by window through forward_sequence;
     step k of a window resets where done[k - 1] is set."""
-    K, T = int(obs.shape[0]), int(seq_len)
-    dt = policy.conv_w.dtype
-    logits, value = [], []
-    for w, k0 in enumerate(range(0, K, T)):
-        k1 = min(k0 + T, K)
-        resets = None
-        if done is not None and k1 - k0 > 1:
-            resets = torch.cat([torch.zeros_like(done[:1]), done[k0:k1 - 1]]).to(torch.bool)
-        lg, v, _ = policy.forward_sequence(obs[k0:k1], state[w].detach().to(dt), resets)
-        logits.append(lg)
-        value.append(v)
-    return torch.cat(logits), torch.cat(value)
+    return _forward_windows(policy, obs, None, state, done, seq_len)[:2]
 
 
 def ppo_loss_recurrent(policy, batch, *, seq_len, clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff, obs_first=None):
@@ -867,31 +871,12 @@ def ppo_loss_recurrent(policy, batch, *, seq_len, clip_param, vf_clip_param, vf_
     kept on the policy); CPU tensors run forward_sequence per window and ppo_terms under autograd."""
     if not isinstance(policy, ConvLSTMPolicy):
         raise ValueError("ppo_loss_recurrent is for a ConvLSTMPolicy (ppo_loss is the ConvFCPolicy's)")
-    if not isinstance(batch, dict):
-        raise ValueError("batch must be the dict sample() returns")
-    if isinstance(seq_len, bool) or int(seq_len) != seq_len or int(seq_len) < 1:
-        raise ValueError("seq_len must be an integer >= 1")
-    seq_len = int(seq_len)
-    hyper = tuple(float(x) for x in (clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff))
-    if not all(np.isfinite(hyper)) or hyper[0] < 0 or hyper[1] < 0:
-        raise ValueError("the hyper-parameters must be finite, clip_param and vf_clip_param >= 0")
-    t, (K, E, N) = _ppo_tensors(policy, batch, obs_first, hyper[4])
-    dev, P = t["actions"].device, policy.num_sets
-    if policy.conv_w.device != dev:
-        raise ValueError("the policy is on %s, the batch on %s" % (policy.conv_w.device, dev))
-    t["state"], t["done"] = _recurrent_tensors(policy, batch, K, E, N, seq_len, dev)
+    hyper = (clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff)
+    t, (K, E, N), seq_len, hyper, dev = _ppo_prepare(policy, batch, obs_first, seq_len, hyper)
     if dev.type == "cuda":
-        if policy.conv_w.dtype != torch.float32:
-            raise ValueError("the device path needs a float32 policy")
-        params = tuple(getattr(policy, name) for name, _, _ in policy.layout())
-        loss, stats = _RecurrentPPOLossFunction.apply(policy, t, (K, E, N), seq_len, hyper, *params)
-        return loss, {name: stats[:, k] for k, name in enumerate(PPO_STATS)}
-    if dev.type != "cpu":
-        raise ValueError("the tensors must be on the CPU or on a GPU, not on %s" % (dev,))
+        return _device_loss(policy, (ConvLSTMPolicy, "ppo"), t, (K, E, N), seq_len, hyper)
     logits, value = recurrent_forward(policy, _ppo_obs(t, K), t["state"], t["done"], seq_len)
-    terms = ppo_terms(logits, value, t, *hyper)
-    means = [_set_means(x, P) for x in terms]
-    return means[0].sum(), {name: m.detach() for name, m in zip(PPO_STATS, means)}
+    return _cpu_result([_set_means(x, policy.num_sets) for x in ppo_terms(logits, value, t, *hyper)], PPO_STATS)
 
 
 # ---- PPOLoss + moa_weight * MOALoss for the MOA policy, with truncated BPTT (include/ssd.h, MOA PPO LOSS AND GRADIENTS) ----
@@ -899,84 +884,12 @@ def ppo_loss_recurrent(policy, batch, *, seq_len, clip_param, vf_clip_param, vf_
 MOA_PPO_STATS = PPO_STATS + ("moa_loss",)
 
 
-def _moa_tensors(policy, batch, K, E, N, seq_len, dev):
-    """The state ring [S, E, N, 4, C], done [K, E, N] (or None) and prev_actions [K, E, N] of a MOA fragment, checked."""
-    C, S = policy.cell_size, -(-K // seq_len)
-    state = batch.get("state")
-    if state is None and seq_len >= K and batch.get("state_in") is not None:
-        state = batch["state_in"].unsqueeze(0)                        # one window: the state step 0 used
-    if not isinstance(state, torch.Tensor):
-        raise ValueError("state is required: the ring sample(..., state_every=seq_len) records (state_in serves when seq_len >= K)")
-    if state.dim() != 5 or tuple(state.shape[1:4]) != (E, N, 4) or state.shape[0] < S:
-        raise ValueError("state must be [S, %d, %d, 4, C] with S >= ceil(K / seq_len) = %d, got %s" % (E, N, S, tuple(state.shape)))
-    if state.shape[-1] != C:
-        raise ValueError("state has %d cells, the policy %d" % (state.shape[-1], C))
-    if state.dtype != torch.float32 or state.device != dev or not state.is_contiguous():
-        raise ValueError("state must be a contiguous torch.float32 tensor on %s" % (dev,))
-    done, prev = batch.get("done"), batch.get("prev_actions")
-    if done is not None:
-        if (not isinstance(done, torch.Tensor) or done.dtype != torch.uint8 or tuple(done.shape) != (K, E, N) or done.device != dev
-                or not done.is_contiguous()):
-            raise ValueError("done must be a contiguous torch.uint8 tensor of shape %s on %s" % ((K, E, N), dev))
-    if (not isinstance(prev, torch.Tensor) or prev.dtype != torch.int32 or tuple(prev.shape) != (K, E, N) or prev.device != dev
-            or not prev.is_contiguous()):
-        raise ValueError("prev_actions must be a contiguous torch.int32 tensor of shape %s on %s" % ((K, E, N), dev))
-    return state, done, prev
-
-
-class _MOAPPOLossFunction(torch.autograd.Function):
-    """ssd_policy_moa_ppo_grad as a torch function of the policy's parameters, as _PPOLossFunction."""
-
-    @staticmethod
-    def forward(ctx, policy, t, dims, seq_len, hyper, *params):
-        import ctypes as C
-        K, E, N = dims
-        P, A = policy.num_sets, policy.num_actions
-        dev = t["actions"].device
-        weights = policy.packed()
-        need = policy.ppo_scratch_shape(K, E, N, seq_len)[0]
-        scratch = getattr(policy, "_ppo_scratch", None)          # kept between calls, as packed()'s buffer is
-        if scratch is None or scratch.device != dev or scratch.numel() < need:
-            scratch = policy._ppo_scratch = torch.empty(need, dtype=torch.float32, device=dev)
-        grads = torch.empty((P, policy.set_floats), dtype=torch.float32, device=dev)
-        stats = torch.empty((P, len(MOA_PPO_STATS)), dtype=torch.float64, device=dev)
-        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())   # noqa: E731
-        index = dev.index if dev.index is not None else torch.cuda.current_device()
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _capi.policy_check(_capi.lib().ssd_policy_moa_ppo_grad(
-            ptr(weights), P, A, policy.cell_size, seq_len, ptr(t["obs_first"]), ptr(t["obs"]), ptr(t["state"]), ptr(t["prev_actions"]),
-            ptr(t["done"]), ptr(t["actions"]), ptr(t["logp_old"]), ptr(t["advantages"]), ptr(t["value_targets"]), ptr(t["vf_pred"]),
-            ptr(t["behaviour_logits"]), K, E, N, *hyper, ptr(scratch), ptr(grads), ptr(stats), index, 0, stream))
-        ctx.policy = policy
-        ctx.save_for_backward(grads)
-        ctx.mark_non_differentiable(stats)
-        return stats[:, 0].sum().to(torch.float32), stats
-
-    @staticmethod
-    def backward(ctx, g_loss, g_stats):
-        (grads,) = ctx.saved_tensors
-        out = unpack_gradient(ctx.policy, grads, g_loss)
-        return (None, None, None, None, None) + tuple(g if needs else None for g, needs in zip(out, ctx.needs_input_grad[5:]))
-
-
 def moa_forward(policy, obs, prev_actions, state, done, seq_len):
     """The learner's forward of a ConvMOAPolicy over a fragment, in plain torch under autograd, by the state rule of
     include/ssd.h: obs u8 [K, E, N, 15, 15, 3] (the observation each row acted on), prev_actions int [K, E, N], the ring state
     [S, E, N, 4, C] (detached: data), done u8 [K, E, N] or None -> (logits [K, E, N, A], value [K, E, N], moa_logits
     [K, E, N, N-1, A]).  Window by window through forward_sequence; step k of a window resets where done[k - 1] is set."""
-    K, T = int(obs.shape[0]), int(seq_len)
-    dt = policy.conv_w.dtype
-    logits, value, moa = [], [], []
-    for w, k0 in enumerate(range(0, K, T)):
-        k1 = min(k0 + T, K)
-        resets = None
-        if done is not None and k1 - k0 > 1:
-            resets = torch.cat([torch.zeros_like(done[:1]), done[k0:k1 - 1]]).to(torch.bool)
-        lg, v, m, _ = policy.forward_sequence(obs[k0:k1], prev_actions[k0:k1], state[w].detach().to(dt), resets)
-        logits.append(lg)
-        value.append(v)
-        moa.append(m)
-    return torch.cat(logits), torch.cat(value), torch.cat(moa)
+    return _forward_windows(policy, obs, prev_actions, state, done, seq_len)[:3]
 
 
 def ppo_loss_moa(policy, batch, *, seq_len, moa_weight, clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff,
@@ -1003,46 +916,13 @@ def ppo_loss_moa(policy, batch, *, seq_len, moa_weight, clip_param, vf_clip_para
     on the policy); CPU tensors run forward_sequence per window, ppo_terms and moa_loss per set under autograd."""
     if not isinstance(policy, ConvMOAPolicy):
         raise ValueError("ppo_loss_moa is for a ConvMOAPolicy (ppo_loss and ppo_loss_recurrent are the other policies')")
-    if not isinstance(batch, dict):
-        raise ValueError("batch must be the dict sample() returns")
-    if isinstance(seq_len, bool) or int(seq_len) != seq_len or int(seq_len) < 1:
-        raise ValueError("seq_len must be an integer >= 1")
-    seq_len = int(seq_len)
-    hyper = tuple(float(x) for x in (clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff, moa_weight))
-    if not all(np.isfinite(hyper)) or hyper[0] < 0 or hyper[1] < 0:
-        raise ValueError("the hyper-parameters must be finite, clip_param and vf_clip_param >= 0")
-    if hyper[5] < 0:
-        raise ValueError("moa_weight must be >= 0")
-    t, (K, E, N) = _ppo_tensors(policy, batch, obs_first, hyper[4])
-    if N != policy.num_agents:
-        raise ValueError("the policy is for %d agents, the batch has %d" % (policy.num_agents, N))
-    dev, P = t["actions"].device, policy.num_sets
-    if policy.conv_w.device != dev:
-        raise ValueError("the policy is on %s, the batch on %s" % (policy.conv_w.device, dev))
-    state, done, prev = _moa_tensors(policy, batch, K, E, N, seq_len, dev)
-    t["state"], t["done"], t["prev_actions"] = state, done, prev
+    hyper = (clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff, moa_weight)
+    t, (K, E, N), seq_len, hyper, dev = _ppo_prepare(policy, batch, obs_first, seq_len, hyper)
     if dev.type == "cuda":
-        if policy.conv_w.dtype != torch.float32:
-            raise ValueError("the device path needs a float32 policy")
-        params = tuple(getattr(policy, name) for name, _, _ in policy.layout())
-        loss, stats = _MOAPPOLossFunction.apply(policy, t, (K, E, N), seq_len, hyper, *params)
-        return loss, {name: stats[:, k] for k, name in enumerate(MOA_PPO_STATS)}
-    if dev.type != "cpu":
-        raise ValueError("the tensors must be on the CPU or on a GPU, not on %s" % (dev,))
-    logits, value, moa = moa_forward(policy, _ppo_obs(t, K), prev, state, done, seq_len)
-    terms = ppo_terms(logits, value, t, *hyper[:5])
-    A = policy.num_actions
-    acts = t["actions"].clamp(0, A - 1)
-    if P == 1:
-        ce = policy.moa_loss(moa, acts).reshape(1)
-    else:                                                             # set p's rows are agent p's: its N - 1 predictions
-        others = acts.long()[..., policy._others.to(dev)]             # [K, E, N, N-1]
-        ce = torch.stack([torch.nn.functional.cross_entropy(moa[:, :, p].reshape(-1, A), others[:, :, p].reshape(-1))
-                          for p in range(P)])
-    means = [_set_means(x, P) for x in terms]
-    means[0] = means[0] + hyper[5] * ce
-    means.append(ce)
-    return means[0].sum(), {name: m.detach() for name, m in zip(MOA_PPO_STATS, means)}
+        return _device_loss(policy, (ConvMOAPolicy, "ppo"), t, (K, E, N), seq_len, hyper)
+    logits, value, moa = moa_forward(policy, _ppo_obs(t, K), t["prev_actions"], t["state"], t["done"], seq_len)
+    means = [_set_means(x, policy.num_sets) for x in ppo_terms(logits, value, t, *hyper[:5])]
+    return _cpu_result(means, MOA_PPO_STATS, _moa_set_ce(policy, moa, t["actions"]), hyper[5])
 
 
 # ---- the A3C loss of the three policies (include/ssd.h, A3C LOSS AND GRADIENTS; DESIGN.md section 19) ----
@@ -1069,76 +949,26 @@ def _set_sums(x, P):
     return x.sum().reshape(1) if P == 1 else x.reshape(-1, P).sum(0)
 
 
-class _A3CLossFunction(torch.autograd.Function):
-    """ssd_policy_ac_grad, ssd_policy_lstm_ac_grad or ssd_policy_moa_ac_grad (by the policy's class) as a torch function of the
-    policy's parameters, as _PPOLossFunction: the same scratch kept on the policy, the same unpacking."""
-
-    @staticmethod
-    def forward(ctx, policy, t, dims, seq_len, hyper, *params):
-        import ctypes as C
-        K, E, N = dims
-        P, A = policy.num_sets, policy.num_actions
-        dev = t["actions"].device
-        weights = policy.packed()
-        moa, conv_fc = isinstance(policy, ConvMOAPolicy), isinstance(policy, ConvFCPolicy)
-        need = policy.ppo_scratch_shape(K * E * N // P)[0] if conv_fc else policy.ppo_scratch_shape(K, E, N, seq_len)[0]
-        scratch = getattr(policy, "_ppo_scratch", None)          # one buffer serves the policy's PPO and A3C calls
-        if scratch is None or scratch.device != dev or scratch.numel() < need:
-            scratch = policy._ppo_scratch = torch.empty(need, dtype=torch.float32, device=dev)
-        grads = torch.empty((P, policy.set_floats), dtype=torch.float32, device=dev)
-        stats = torch.empty((P, len(MOA_A3C_STATS if moa else A3C_STATS)), dtype=torch.float64, device=dev)
-        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())   # noqa: E731
-        index = dev.index if dev.index is not None else torch.cuda.current_device()
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        rows = (ptr(t["actions"]), ptr(t["advantages"]), ptr(t["value_targets"]), K, E, N)
-        tail = (ptr(scratch), ptr(grads), ptr(stats), index, 0, stream)
-        L = _capi.lib()
-        if conv_fc:
-            rc = L.ssd_policy_ac_grad(ptr(weights), P, A, ptr(t["obs_first"]), ptr(t["obs"]), *rows, *hyper, *tail)
-        elif moa:
-            rc = L.ssd_policy_moa_ac_grad(ptr(weights), P, A, policy.cell_size, seq_len, ptr(t["obs_first"]), ptr(t["obs"]),
-                                          ptr(t["state"]), ptr(t["prev_actions"]), ptr(t["done"]), *rows, *hyper, *tail)
-        else:
-            rc = L.ssd_policy_lstm_ac_grad(ptr(weights), P, A, policy.cell_size, seq_len, ptr(t["obs_first"]), ptr(t["obs"]),
-                                           ptr(t["state"]), ptr(t["done"]), *rows, *hyper, *tail)
-        _capi.policy_check(rc)
-        ctx.policy = policy
-        ctx.save_for_backward(grads)
-        ctx.mark_non_differentiable(stats)
-        return stats[:, 0].sum().to(torch.float32), stats
-
-    @staticmethod
-    def backward(ctx, g_loss, g_stats):
-        (grads,) = ctx.saved_tensors
-        out = unpack_gradient(ctx.policy, grads, g_loss)
-        return (None, None, None, None, None) + tuple(g if needs else None for g, needs in zip(out, ctx.needs_input_grad[5:]))
-
-
 def _a3c_prepare(policy, batch, obs_first, seq_len, hyper):
-    """The checks the three A3C functions share -> (t, (K, E, N), seq_len, dev)."""
+    """The checks the three A3C functions share -> (t, (K, E, N), seq_len, dev).  seq_len None: the conv-FC policy's call; hyper:
+    (vf_loss_coeff, entropy_coeff) and, for the MOA policy, moa_weight."""
     if seq_len is not None:
         if not isinstance(batch, dict):
             raise ValueError("batch must be the dict sample() returns")
-        if isinstance(seq_len, bool) or int(seq_len) != seq_len or int(seq_len) < 1:
-            raise ValueError("seq_len must be an integer >= 1")
-        seq_len = int(seq_len)
-    if not all(np.isfinite(hyper)):
-        raise ValueError("the hyper-parameters must be finite")
-    t, dims = _ppo_tensors(policy, batch, obs_first, 0.0, a3c=True)
+        seq_len = _check_seq_len(seq_len)
+    _check_hyper(hyper, clips=False)
+    t, (K, E, N) = _ppo_tensors(policy, batch, obs_first, 0.0, a3c=True)
     dev = t["actions"].device
-    if policy.conv_w.device != dev:
-        raise ValueError("the policy is on %s, the batch on %s" % (policy.conv_w.device, dev))
-    if dev.type not in ("cuda", "cpu"):
-        raise ValueError("the tensors must be on the CPU or on a GPU, not on %s" % (dev,))
-    if dev.type == "cuda" and policy.conv_w.dtype != torch.float32:
-        raise ValueError("the device path needs a float32 policy")
-    return t, dims, seq_len, dev
-
-
-def _a3c_device(policy, t, dims, seq_len, hyper, names):
-    params = tuple(getattr(policy, name) for name, _, _ in policy.layout())
-    loss, stats = _A3CLossFunction.apply(policy, t, dims, seq_len, hyper, *params)
-    return loss, {name: stats[:, k] for k, name in enumerate(names)}
+    _check_same_device(policy, dev)
+    _check_device_type(dev)
+    _check_float32(policy, dev)
+    if len(hyper) > 2 and hyper[2] < 0:
+        raise ValueError("moa_weight must be >= 0")
+    if isinstance(policy, ConvMOAPolicy) and N != policy.num_agents:
+        raise ValueError("the policy is for %d agents, the batch has %d" % (policy.num_agents, N))
+    if seq_len is not None:
+        t["state"], t["done"], t["prev_actions"] = _state_tensors(policy, batch, K, E, N, seq_len, dev)
+    return t, (K, E, N), seq_len, dev
 
 
 def a3c_loss(policy, batch, *, vf_loss_coeff, entropy_coeff, obs_first=None):
@@ -1162,10 +992,9 @@ def a3c_loss(policy, batch, *, vf_loss_coeff, entropy_coeff, obs_first=None):
     hyper = (float(vf_loss_coeff), float(entropy_coeff))
     t, (K, E, N), _, dev = _a3c_prepare(policy, batch, obs_first, None, hyper)
     if dev.type == "cuda":
-        return _a3c_device(policy, t, (K, E, N), 0, hyper, A3C_STATS)
+        return _device_loss(policy, (ConvFCPolicy, "a3c"), t, (K, E, N), 0, hyper)
     logits, value = policy(_ppo_obs(t, K))
-    sums = [_set_sums(x, policy.num_sets) for x in a3c_terms(logits, value, t, *hyper)]
-    return sums[0].sum(), {name: m.detach() for name, m in zip(A3C_STATS, sums)}
+    return _cpu_result([_set_sums(x, policy.num_sets) for x in a3c_terms(logits, value, t, *hyper)], A3C_STATS)
 
 
 def a3c_loss_recurrent(policy, batch, *, seq_len, vf_loss_coeff, entropy_coeff, obs_first=None):
@@ -1181,12 +1010,10 @@ def a3c_loss_recurrent(policy, batch, *, seq_len, vf_loss_coeff, entropy_coeff, 
         raise ValueError("a3c_loss_recurrent is for a ConvLSTMPolicy (a3c_loss is the ConvFCPolicy's)")
     hyper = (float(vf_loss_coeff), float(entropy_coeff))
     t, (K, E, N), seq_len, dev = _a3c_prepare(policy, batch, obs_first, seq_len, hyper)
-    t["state"], t["done"] = _recurrent_tensors(policy, batch, K, E, N, seq_len, dev)
     if dev.type == "cuda":
-        return _a3c_device(policy, t, (K, E, N), seq_len, hyper, A3C_STATS)
+        return _device_loss(policy, (ConvLSTMPolicy, "a3c"), t, (K, E, N), seq_len, hyper)
     logits, value = recurrent_forward(policy, _ppo_obs(t, K), t["state"], t["done"], seq_len)
-    sums = [_set_sums(x, policy.num_sets) for x in a3c_terms(logits, value, t, *hyper)]
-    return sums[0].sum(), {name: m.detach() for name, m in zip(A3C_STATS, sums)}
+    return _cpu_result([_set_sums(x, policy.num_sets) for x in a3c_terms(logits, value, t, *hyper)], A3C_STATS)
 
 
 def a3c_loss_moa(policy, batch, *, seq_len, moa_weight, vf_loss_coeff, entropy_coeff, obs_first=None):
@@ -1205,26 +1032,11 @@ def a3c_loss_moa(policy, batch, *, seq_len, moa_weight, vf_loss_coeff, entropy_c
         raise ValueError("a3c_loss_moa is for a ConvMOAPolicy (a3c_loss and a3c_loss_recurrent are the other policies')")
     hyper = (float(vf_loss_coeff), float(entropy_coeff), float(moa_weight))
     t, (K, E, N), seq_len, dev = _a3c_prepare(policy, batch, obs_first, seq_len, hyper)
-    if hyper[2] < 0:
-        raise ValueError("moa_weight must be >= 0")
-    if N != policy.num_agents:
-        raise ValueError("the policy is for %d agents, the batch has %d" % (policy.num_agents, N))
-    t["state"], t["done"], t["prev_actions"] = _moa_tensors(policy, batch, K, E, N, seq_len, dev)
-    P, A = policy.num_sets, policy.num_actions
     if dev.type == "cuda":
-        return _a3c_device(policy, t, (K, E, N), seq_len, hyper, MOA_A3C_STATS)
+        return _device_loss(policy, (ConvMOAPolicy, "a3c"), t, (K, E, N), seq_len, hyper)
     logits, value, moa = moa_forward(policy, _ppo_obs(t, K), t["prev_actions"], t["state"], t["done"], seq_len)
-    sums = [_set_sums(x, P) for x in a3c_terms(logits, value, t, *hyper[:2])]
-    acts = t["actions"].clamp(0, A - 1)
-    if P == 1:
-        ce = policy.moa_loss(moa, acts).reshape(1)
-    else:                                                             # set p's rows are agent p's: its N - 1 predictions
-        others = acts.long()[..., policy._others.to(dev)]             # [K, E, N, N-1]
-        ce = torch.stack([torch.nn.functional.cross_entropy(moa[:, :, p].reshape(-1, A), others[:, :, p].reshape(-1))
-                          for p in range(P)])
-    sums[0] = sums[0] + hyper[2] * ce
-    sums.append(ce)
-    return sums[0].sum(), {name: m.detach() for name, m in zip(MOA_A3C_STATS, sums)}
+    sums = [_set_sums(x, policy.num_sets) for x in a3c_terms(logits, value, t, *hyper[:2])]
+    return _cpu_result(sums, MOA_A3C_STATS, _moa_set_ce(policy, moa, t["actions"]), hyper[2])
 
 
 # ---- the IMPALA loss of the three policies: V-trace targets under the current weights, then the A3C loss's path
@@ -1255,39 +1067,30 @@ def _fragment_tensors(policy, batch, obs_first, seq_len):
         if (not isinstance(obs_first, torch.Tensor) or obs_first.dtype != torch.uint8 or obs_first.device != dev
                 or tuple(obs_first.shape) != (E, N, VIEW, VIEW, 3) or not obs_first.is_contiguous()):
             raise ValueError("obs_first must be a contiguous uint8 tensor of shape %s on %s" % ((E, N, VIEW, VIEW, 3), dev))
-    if policy.conv_w.device != dev:
-        raise ValueError("the policy is on %s, the batch on %s" % (policy.conv_w.device, dev))
-    if dev.type not in ("cuda", "cpu"):
-        raise ValueError("the tensors must be on the CPU or on a GPU, not on %s" % (dev,))
-    if dev.type == "cuda" and policy.conv_w.dtype != torch.float32:
-        raise ValueError("the device path needs a float32 policy")
+    _check_same_device(policy, dev)
+    _check_device_type(dev)
+    _check_float32(policy, dev)
     t = {"actions": acts, "obs": obs, "obs_first": obs_first}
     if isinstance(policy, ConvFCPolicy):
         return t, (K, E, N), None
-    if seq_len is None or isinstance(seq_len, bool) or int(seq_len) != seq_len or int(seq_len) < 1:
+    if seq_len is None:
         raise ValueError("seq_len must be an integer >= 1")
-    seq_len = int(seq_len)
-    if isinstance(policy, ConvMOAPolicy):
-        if N != policy.num_agents:
-            raise ValueError("the policy is for %d agents, the batch has %d" % (policy.num_agents, N))
-        t["state"], t["done"], t["prev_actions"] = _moa_tensors(policy, batch, K, E, N, seq_len, dev)
-    else:
-        t["state"], t["done"] = _recurrent_tensors(policy, batch, K, E, N, seq_len, dev)
+    seq_len = _check_seq_len(seq_len)
+    if isinstance(policy, ConvMOAPolicy) and N != policy.num_agents:
+        raise ValueError("the policy is for %d agents, the batch has %d" % (policy.num_agents, N))
+    t["state"], t["done"], t["prev_actions"] = _state_tensors(policy, batch, K, E, N, seq_len, dev)
     return t, (K, E, N), seq_len
 
 
 def _evaluate_device(policy, t, dims, T):
     """evaluate_fragment through the library's forward entry points on torch's current stream, rows 0 .. K - 1 and the
     bootstrap as row K of one allocation."""
-    import ctypes as C
     K, E, N = dims
     A, P, dev = policy.num_actions, policy.num_sets, t["actions"].device
     weights = policy.packed()
     logits = torch.empty((K + 1, E, N, A), dtype=torch.float32, device=dev)
     value = torch.empty((K + 1, E, N), dtype=torch.float32, device=dev)
-    ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())   # noqa: E731
-    index = dev.index if dev.index is not None else torch.cuda.current_device()
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    ptr, index, stream = _device_handles(dev)
     L = _capi.lib()
     obs, first = t["obs"], t["obs_first"]
     if isinstance(policy, ConvFCPolicy):                          # one launch, or two: obs_first's row, then obs[0 .. K - 1]
@@ -1327,27 +1130,17 @@ def _evaluate_device(policy, t, dims, T):
 def _evaluate_host(policy, t, dims, T):
     """evaluate_fragment in plain torch: the loss calls' forwards window by window, and one more step for the bootstrap."""
     K, E, N = dims
-    obs, first, dt = t["obs"], t["obs_first"], policy.conv_w.dtype
+    obs, first = t["obs"], t["obs_first"]
     rows = obs[:K] if first is None else _ppo_obs(t, K)
     last = obs[K] if first is None else obs[K - 1]
     if isinstance(policy, ConvFCPolicy):
         logits, value = policy(rows)
         return logits, value, policy(last)[1]
-    moa = isinstance(policy, ConvMOAPolicy)
-    done, logits, value, st = t["done"], [], [], None
-    for w, k0 in enumerate(range(0, K, T)):
-        k1 = min(k0 + T, K)
-        resets = None
-        if done is not None and k1 - k0 > 1:
-            resets = torch.cat([torch.zeros_like(done[:1]), done[k0:k1 - 1]]).to(torch.bool)
-        args = (rows[k0:k1], t["prev_actions"][k0:k1]) if moa else (rows[k0:k1],)
-        out = policy.forward_sequence(*args, t["state"][w].to(dt), resets)
-        logits.append(out[0])
-        value.append(out[1])
-        st = out[-1]
+    moa, done = isinstance(policy, ConvMOAPolicy), t["done"]
+    logits, value, *_, st = _forward_windows(policy, rows, t["prev_actions"], t["state"], done, T)
     starts = None if done is None else done[K - 1].to(torch.bool)
     boot = policy(last, t["actions"][K - 1], st, starts)[1] if moa else policy(last, st, starts)[1]
-    return torch.cat(logits), torch.cat(value), boot
+    return logits, value, boot
 
 
 def evaluate_fragment(policy, batch, obs_first=None, seq_len=None):
@@ -1712,24 +1505,20 @@ def _ws_ppo_tensors(policy, seq, seq_len, kl_coeff):
         t["behaviour_dist"] = None                           # not part of the loss
     elif t["behaviour_dist"] is None:
         raise ValueError("kl_coeff != 0 needs dist (the dist the actions were sampled from)")
-
-    def check(x, dtype, shape, name):
-        if not isinstance(x, torch.Tensor) or x.dtype != dtype or tuple(x.shape) != shape or x.device != dev or not x.is_contiguous():
-            raise ValueError("%s must be a contiguous %s tensor of shape %s on %s" % (name, dtype, shape, dev))
     for name in ("actions", "logp_old", "advantages", "value_targets", "vf_pred"):
-        check(t[name], torch.float32, (M, Q), name)
-    check(t["obs"], torch.float32, (M, Q, WS_OBS), "obs")
+        _check_tensor(t[name], torch.float32, (M, Q), name, dev)
+    _check_tensor(t["obs"], torch.float32, (M, Q, WS_OBS), "obs", dev)
     if t["behaviour_dist"] is not None:
-        check(t["behaviour_dist"], torch.float32, (M, Q, WS_OUT), "dist")
+        _check_tensor(t["behaviour_dist"], torch.float32, (M, Q, WS_OUT), "dist", dev)
     if t["starts"] is not None:
         if t["starts"].dtype == torch.bool:
             t["starts"] = t["starts"].to(torch.uint8)
-        check(t["starts"], torch.uint8, (M, Q), "starts")
+        _check_tensor(t["starts"], torch.uint8, (M, Q), "starts", dev)
     S = -(-M // T)
     st = t["state"]
     if not isinstance(st, torch.Tensor) or st.dim() != 4 or st.shape[0] < S or tuple(st.shape[1:]) != (Q, 2, C):
         raise ValueError("state must be [S, %d, 2, %d] with S >= ceil(M / seq_len) = %d" % (Q, C, S))
-    check(st, torch.float32, tuple(st.shape), "state")
+    _check_tensor(st, torch.float32, tuple(st.shape), "state", dev)
     return t, (M, Q)
 
 
@@ -1749,41 +1538,6 @@ def ws_forward_windows(policy, agent_id, obs, state, starts, seq_len):
         dists.append(d)
         values.append(v)
     return torch.cat(dists), torch.cat(values)
-
-
-class _WatershedPPOLossFunction(torch.autograd.Function):
-    """ssd_ws_policy_ppo_grad as a torch function of the policy's parameters, as _RecurrentPPOLossFunction: the packed
-    gradient of set agent_id goes to entry agent_id of every parameter (a shared dense1: entry agent_id % 4)."""
-
-    @staticmethod
-    def forward(ctx, policy, agent_id, t, dims, seq_len, hyper, *params):
-        import ctypes as C
-        M, Q = dims
-        dev = t["actions"].device
-        weights = policy.packed()
-        need = _capi.SSD_WSPPO_SCRATCH_FLOATS(M, Q, policy.cell_size, seq_len)
-        scratch = getattr(policy, "_ppo_scratch", None)          # kept between calls, as packed()'s buffer is
-        if scratch is None or scratch.device != dev or scratch.numel() < need:
-            scratch = policy._ppo_scratch = torch.empty(need, dtype=torch.float32, device=dev)
-        grads = torch.empty((policy.set_floats,), dtype=torch.float32, device=dev)
-        stats = torch.empty((len(PPO_STATS),), dtype=torch.float64, device=dev)
-        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())   # noqa: E731
-        index = dev.index if dev.index is not None else torch.cuda.current_device()
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _capi.policy_check(_capi.lib().ssd_ws_policy_ppo_grad(
-            ptr(weights), policy.num_sets, policy.cell_size, policy.variant, agent_id, seq_len, ptr(t["obs"]), ptr(t["state"]),
-            ptr(t["starts"]), ptr(t["actions"]), ptr(t["logp_old"]), ptr(t["advantages"]), ptr(t["value_targets"]),
-            ptr(t["vf_pred"]), ptr(t["behaviour_dist"]), M, Q, *hyper, ptr(scratch), ptr(grads), ptr(stats), index, 0, stream))
-        ctx.policy, ctx.agent_id = policy, agent_id
-        ctx.save_for_backward(grads)
-        ctx.mark_non_differentiable(stats)
-        return stats[0].to(torch.float32), stats
-
-    @staticmethod
-    def backward(ctx, g_loss, g_stats):
-        (grads,) = ctx.saved_tensors
-        out = unpack_gradient(ctx.policy, grads, g_loss, only_set=ctx.agent_id)
-        return (None,) * 6 + tuple(g if needs else None for g, needs in zip(out, ctx.needs_input_grad[6:]))
 
 
 def ppo_loss_watershed(policy, agent_id, seq, *, seq_len, clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff):
@@ -1811,25 +1565,135 @@ def ppo_loss_watershed(policy, agent_id, seq, *, seq_len, clip_param, vf_clip_pa
     if isinstance(agent_id, bool) or int(agent_id) != agent_id or not 0 <= int(agent_id) < policy.num_sets:
         raise ValueError("agent_id must be 0..%d" % (policy.num_sets - 1))
     agent_id = int(agent_id)
-    if isinstance(seq_len, bool) or int(seq_len) != seq_len or int(seq_len) < 1:
-        raise ValueError("seq_len must be an integer >= 1")
-    seq_len = int(seq_len)
+    seq_len = _check_seq_len(seq_len)
     hyper = tuple(float(x) for x in (clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff))
-    if not all(np.isfinite(hyper)) or hyper[0] < 0 or hyper[1] < 0:
-        raise ValueError("the hyper-parameters must be finite, clip_param and vf_clip_param >= 0")
+    _check_hyper(hyper, clips=True)
     t, (M, Q) = _ws_ppo_tensors(policy, seq, seq_len, hyper[4])
     dev = t["actions"].device
-    if policy.dense0_w.device != dev:
-        raise ValueError("the policy is on %s, the sequences on %s" % (policy.dense0_w.device, dev))
+    _check_same_device(policy, dev, "sequences")
+    _check_float32(policy, dev)
     if dev.type == "cuda":
-        if policy.dense0_w.dtype != torch.float32:
-            raise ValueError("the device path needs a float32 policy")
-        params = tuple(getattr(policy, name) for name, _, _ in policy.layout())
-        loss, stats = _WatershedPPOLossFunction.apply(policy, agent_id, t, (M, Q), seq_len, hyper, *params)
-        return loss, {name: stats[k] for k, name in enumerate(PPO_STATS)}
-    if dev.type != "cpu":
-        raise ValueError("the tensors must be on the CPU or on a GPU, not on %s" % (dev,))
+        return _device_loss(policy, (WatershedLSTMPolicy, "ppo"), t, (M, Q), seq_len, hyper, only_set=agent_id)
+    _check_device_type(dev)
     dist, value = ws_forward_windows(policy, agent_id, t["obs"], t["state"], t["starts"], seq_len)
     terms = ws_ppo_terms(dist, value, t, bool(ws_is_comm(policy.variant, agent_id)), *hyper)
     means = [x.mean() for x in terms]
     return means[0], {name: m.detach() for name, m in zip(PPO_STATS, means)}
+
+
+# ---- the device path of the ten loss calls and of evaluate_fragment: one record of what to call, one torch function ----
+
+def _device_handles(dev):
+    """What a library call on torch's current stream of `dev` needs besides its own arguments: (ptr: the address of a tensor,
+    or NULL for None; the device index; the stream handle)."""
+    import ctypes as C
+    ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())   # noqa: E731
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    return ptr, index, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+# (policy class, loss) -> (the entry point, its arguments up to `scratch` in the order and by the names of include/ssd.h -- but
+# vf_pred, the contract name, for vf_preds --, broken into lines where the header breaks them; the columns of its stats).  After
+# them every entry point takes scratch, grads, stats, device_id, flags and stream.  A name stands for the call's tensor or number
+# of that name, else for the policy's attribute.
+_LOSS_CALLS = {
+    (ConvFCPolicy, "ppo"): ("ssd_policy_ppo_grad",
+                            "weights num_sets num_actions obs_first obs "
+                            "actions logp_old advantages value_targets "
+                            "vf_pred behaviour_logits n_steps num_envs "
+                            "num_agents clip_param vf_clip_param vf_loss_coeff entropy_coeff "
+                            "kl_coeff", PPO_STATS),
+    (ConvLSTMPolicy, "ppo"): ("ssd_policy_lstm_ppo_grad",
+                              "weights num_sets num_actions cell_size seq_len "
+                              "obs_first obs state done "
+                              "actions logp_old advantages value_targets "
+                              "vf_pred behaviour_logits n_steps num_envs "
+                              "num_agents clip_param vf_clip_param vf_loss_coeff "
+                              "entropy_coeff kl_coeff", PPO_STATS),
+    (ConvMOAPolicy, "ppo"): ("ssd_policy_moa_ppo_grad",
+                             "weights num_sets num_actions cell_size seq_len "
+                             "obs_first obs state prev_actions "
+                             "done actions logp_old advantages "
+                             "value_targets vf_pred behaviour_logits n_steps "
+                             "num_envs num_agents clip_param vf_clip_param vf_loss_coeff "
+                             "entropy_coeff kl_coeff moa_weight", MOA_PPO_STATS),
+    (ConvFCPolicy, "a3c"): ("ssd_policy_ac_grad",
+                            "weights num_sets num_actions obs_first obs "
+                            "actions advantages value_targets n_steps "
+                            "num_envs num_agents vf_loss_coeff entropy_coeff", A3C_STATS),
+    (ConvLSTMPolicy, "a3c"): ("ssd_policy_lstm_ac_grad",
+                              "weights num_sets num_actions cell_size seq_len "
+                              "obs_first obs state done "
+                              "actions advantages value_targets n_steps "
+                              "num_envs num_agents vf_loss_coeff entropy_coeff", A3C_STATS),
+    (ConvMOAPolicy, "a3c"): ("ssd_policy_moa_ac_grad",
+                             "weights num_sets num_actions cell_size seq_len "
+                             "obs_first obs state prev_actions "
+                             "done actions advantages value_targets "
+                             "n_steps num_envs num_agents vf_loss_coeff entropy_coeff "
+                             "moa_weight", MOA_A3C_STATS),
+    (WatershedLSTMPolicy, "ppo"): ("ssd_ws_policy_ppo_grad",
+                                   "weights num_sets cell_size variant agent_id "
+                                   "seq_len obs state starts actions "
+                                   "logp_old advantages value_targets vf_pred "
+                                   "behaviour_dist n_steps num_seqs clip_param "
+                                   "vf_clip_param vf_loss_coeff entropy_coeff kl_coeff", PPO_STATS)}
+_LOSS_CALLS = {key: (symbol, tuple(names.split()), stats) for key, (symbol, names, stats) in _LOSS_CALLS.items()}
+_HYPER = {"ppo": ("clip_param", "vf_clip_param", "vf_loss_coeff", "entropy_coeff", "kl_coeff", "moa_weight"),
+          "a3c": ("vf_loss_coeff", "entropy_coeff", "moa_weight")}
+
+
+# One call of a loss-and-gradient entry point: its symbol, its arguments up to `scratch` (tensors and numbers, in the entry
+# point's order), the float32 scratch it needs, the shapes of its grads and stats, and only_set: the one weight set whose
+# gradient grads [set_floats] is (the Watershed call's agent id), or None for grads [P, set_floats].
+_LossCall = collections.namedtuple("_LossCall", "symbol args scratch_floats grads_shape stats_shape only_set")
+
+
+class _LossFunction(torch.autograd.Function):
+    """A loss-and-gradient entry point as a torch function of the policy's parameters: forward enqueues the library's launches
+    on the current stream and keeps the packed gradient, backward scatters it into the parameters' shapes by layout()."""
+
+    @staticmethod
+    def forward(ctx, policy, call, *params):
+        dev = call.args[0].device
+        scratch = getattr(policy, "_ppo_scratch", None)          # kept between calls, as packed()'s buffer is: one buffer
+        if scratch is None or scratch.device != dev or scratch.numel() < call.scratch_floats:      # serves every loss call
+            scratch = policy._ppo_scratch = torch.empty(call.scratch_floats, dtype=torch.float32, device=dev)
+        grads = torch.empty(call.grads_shape, dtype=torch.float32, device=dev)
+        stats = torch.empty(call.stats_shape, dtype=torch.float64, device=dev)
+        ptr, index, stream = _device_handles(dev)
+        args = [ptr(a) if isinstance(a, torch.Tensor) else a for a in call.args]      # numbers and None as they are
+        _capi.policy_check(getattr(_capi.lib(), call.symbol)(*args, ptr(scratch), ptr(grads), ptr(stats), index, 0, stream))
+        ctx.policy, ctx.only_set = policy, call.only_set
+        ctx.save_for_backward(grads)
+        ctx.mark_non_differentiable(stats)
+        loss = stats[:, 0].sum() if call.only_set is None else stats[0]     # the sum over the weight sets; the one set's
+        return loss.to(torch.float32), stats
+
+    @staticmethod
+    def backward(ctx, g_loss, g_stats):
+        (grads,) = ctx.saved_tensors
+        out = unpack_gradient(ctx.policy, grads, g_loss, only_set=ctx.only_set)
+        return (None, None) + tuple(g if needs else None for g, needs in zip(out, ctx.needs_input_grad[2:]))
+
+
+def _device_loss(policy, key, t, dims, seq_len, hyper, only_set=None):
+    """The loss call `key` of _LOSS_CALLS on the checked tensors t -> (loss, stats by name).  dims: (K, E, N), or (M, Q) of the
+    Watershed call, whose agent id is only_set."""
+    symbol, names, stat_names = _LOSS_CALLS[key]
+    P = policy.num_sets
+    values = dict(t, weights=policy.packed(), seq_len=seq_len, agent_id=only_set)
+    values.update(zip(("n_steps", "num_seqs") if only_set is not None else ("n_steps", "num_envs", "num_agents"), dims))
+    values.update(zip(_HYPER[key[1]], hyper))
+    args = tuple(values[name] if name in values else getattr(policy, name) for name in names)
+    if only_set is not None:
+        scratch_floats = _capi.SSD_WSPPO_SCRATCH_FLOATS(*dims, policy.cell_size, seq_len)
+    elif isinstance(policy, ConvFCPolicy):
+        scratch_floats = policy.ppo_scratch_shape(dims[0] * dims[1] * dims[2] // P)[0]
+    else:
+        scratch_floats = policy.ppo_scratch_shape(*dims, seq_len)[0]
+    lead = () if only_set is not None else (P,)
+    call = _LossCall(symbol, args, scratch_floats, lead + (policy.set_floats,), lead + (len(stat_names),), only_set)
+    params = tuple(getattr(policy, name) for name, _, _ in policy.layout())
+    loss, stats = _LossFunction.apply(policy, call, *params)
+    return loss, dict(zip(stat_names, stats.unbind(-1)))             # the columns: [P] each, scalars for the Watershed call
