@@ -1140,6 +1140,89 @@ int ssd_ws_policy_ppo_grad(const float *weights, int32_t num_sets, int32_t cell_
                            double vf_clip_param, double vf_loss_coeff, double entropy_coeff, double kl_coeff, float *scratch,
                            float *grads, double *stats, int32_t device_id, uint32_t flags, void *stream);
 
+/* ======================================================================================================================
+ * WATERSHED A3C LOSS AND GRADIENTS -- ssd_ws_policy_ac_grad, the A3C twin of ssd_ws_policy_ppo_grad: the reference's A3C loss
+ * (algorithms/a3c_causal.py:28-46), which every Watershed launcher offers next to PPO (run_scripts/
+ * train_watershed_baseline.py:173-187), on one agent id's sequences with truncated backpropagation through time.  It is the
+ * call above with another row loss and another last step, exactly as A3C LOSS AND GRADIENTS is to the other policies' PPO
+ * calls: the same kernels compiled with the A3C row terms, the same host code (csrc/ssd_ws_policy_grad.hip; DESIGN.md
+ * section 22).  Added after ABI 6 without a version bump: the call is additive.  With advantages = V-trace's pg_advantages
+ * and value_targets = vs it is the IMPALA loss (V-TRACE TARGETS; ssd_ws_policy_forward_seq below gives the target policy's
+ * values and log-probabilities).
+ *
+ * Network, rows [M, Q], the gathered obs, the state rule with starts, windows of seq_len, tiles, groups, chunks and splits,
+ * the order of every sum, the scratch (SSD_WSPPO_SCRATCH_FLOATS: one buffer serves both calls) and its alignment, and the
+ * 1 + 3 per window + 1 launches: exactly those of WATERSHED PPO LOSS AND GRADIENTS.  logp_old, vf_preds and behaviour_dist
+ * are not inputs, and there are no clip or KL hyper-parameters.
+ *
+ * Row loss, in float32 in this order.
+ *   comm agent:   exactly the row terms of A3C LOSS AND GRADIENTS with A = 5 (the same device code), a = actions[row] clamped
+ *     to 0 .. 4.
+ *   action agent: with a = actions[row] (the unclipped sample), (mean, log_std) = dist[0:2]:
+ *       sd = expf(log_std)            z = (a - mean) / sd
+ *       logp = ((-0.5f * (z * z)) - log_std) - 0.9189385f        ent = log_std + 1.4189385f
+ *       pi = -(logp * adv)            d1 = value - vt            vf = 0.5f * (d1 * d1)
+ *       row_loss = (pi + vf_loss_coeff * vf) - entropy_coeff * ent
+ *       d row_loss / d mean = -adv * (z / sd)        d row_loss / d log_std = (-adv * (z * z - 1.f)) - entropy_coeff
+ *       d row_loss / d dist[2:5] = 0 exactly         d row_loss / d value = vf_loss_coeff * d1
+ * The loss is the SUM of row_loss over the M Q rows (the reference reduces with reduce_sum).  No clip kinks; ReLU's
+ * derivative at 0 is 0.
+ *
+ * Arithmetic and order: the PPO call's.  The one difference is the last step: the float64 total of an entry is rounded to
+ * float32 as it is, without the division by the rows.  No atomics: the same inputs give the same bits.
+ *
+ * Outputs.  grads f32 [SSD_WSP_SET_FLOATS(C)], padding floats zero.  stats f64 [4]: the SUMS of row_loss, pi, vf and ent (the
+ * reference's total_loss, policy_loss, vf_loss and policy_entropy).
+ *
+ * SSD_E_INVALID before anything is launched (ssd_policy_last_error says why) for everything ssd_ws_policy_ppo_grad refuses,
+ * less the arguments that are gone: the required per-row pointers are obs, state, actions, advantages and value_targets, the
+ * hyper-parameters that must be finite are vf_loss_coeff and entropy_coeff.
+ * ====================================================================================================================== */
+int ssd_ws_policy_ac_grad(const float *weights, int32_t num_sets, int32_t cell_size, int32_t variant, int32_t agent_id,
+                          int32_t seq_len, const float *obs, const float *state, const uint8_t *starts, const float *actions,
+                          const float *advantages, const float *value_targets, int32_t n_steps, int32_t num_seqs,
+                          double vf_loss_coeff, double entropy_coeff, float *scratch, float *grads, double *stats,
+                          int32_t device_id, uint32_t flags, void *stream);
+
+/* ======================================================================================================================
+ * WATERSHED SEQUENCE FORWARD -- ssd_ws_policy_forward_seq: one agent id's sequences under the CURRENT weights, without
+ * gradient, in ONE launch: what V-trace needs of the target policy (dist, value, the log-probability of the taken action and
+ * the bootstrap value) when the weights have moved since the rollout ran (csrc/ssd_ws_policy_seq.hip).
+ * It replaces M + 1 chained launches of ssd_ws_policy_forward, each of which reads and writes the state through memory.
+ * Added after ABI 6 without a version bump: the call is additive.
+ *
+ * Network, weight layout, (variant, agent_id) and the heads: WATERSHED POLICY ROLLOUTS.  Rows: M = n_steps own steps of
+ * Q = num_seqs sequences, as WATERSHED PPO LOSS AND GRADIENTS.  Inputs: obs f32 [M, Q, 12], state f32 [ceil(M / T), Q, 2, C]
+ * (T = seq_len), starts u8 [M, Q] or NULL, actions f32 [M, Q] or NULL, obs_next f32 [Q, 12] or NULL (the observation after
+ * the last own step), start_next u8 [Q] or NULL.  Outputs, each may be NULL: dist f32 [M, Q, 5], value f32 [M, Q], logp f32
+ * [M, Q] (needs actions), bootstrap_value f32 [Q] (needs obs_next), state_out f32 [Q, 2, C].  A NULL output is not written.
+ *
+ * State rule: that of the loss calls.  Step m of sequence q uses state[m / T] as stored when m % T == 0 (starts[m] is NOT
+ * looked at there), zero when m % T != 0 and starts[m, q] != 0, otherwise the (h', c') this call computed for step m - 1.
+ * The bootstrap row runs one more step on obs_next with the state step M - 1 computed, zero where start_next[q] != 0, and
+ * never a state entry (not even when M % T == 0).  state_out is the state after step M - 1; the bootstrap step changes nothing.
+ *
+ * logp: the rollouts' expression of the taken action under the current dist.  A comm agent: l_a - (m + logf(s)) with
+ * a = (int)actions[row] clamped to 0 .. 4, m the maximal logit and s the float32 sum of expf(l_k - m) over k ascending.  An
+ * action agent: ((-0.5f * (z * z)) - log_std) - 0.9189385f with z = (a - mean) / expf(log_std) on the unclipped sample.
+ *
+ * Arithmetic: the header's exact float32, every fmaf chain in ascending k.  dist, value and the state equal, bit for bit,
+ * what ssd_ws_policy_forward gives when it is chained step by step under the same rule; with unchanged weights on a fresh
+ * rollout's rows of one id, dist, value and logp give back what the rollout recorded.
+ *
+ * One workgroup of 4 C threads per tile of SSD_WSPPO_TILE sequences, persistent over tiles g, g + G, ... with
+ * G = SSD_WSPPO_GROUPS(Q); h stays in LDS and c in registers across all steps.  One launch on `stream`, no scratch, no
+ * allocation, no synchronisation.  SSD_E_INVALID before anything is launched (ssd_policy_last_error says why) for an unknown
+ * variant, a num_sets that is not the variant's, an agent_id outside 0 .. num_sets - 1, a cell_size other than 64, 128 or 256,
+ * seq_len, n_steps or num_seqs < 1, more than 2^31 - 17 rows with the bootstrap's, a NULL weights, obs or state, logp without
+ * actions, bootstrap_value without obs_next, a misaligned float buffer, flags other than 0.
+ * ====================================================================================================================== */
+int ssd_ws_policy_forward_seq(const float *weights, int32_t num_sets, int32_t cell_size, int32_t variant, int32_t agent_id,
+                              int32_t seq_len, const float *obs, const float *state, const uint8_t *starts,
+                              const float *actions, const float *obs_next, const uint8_t *start_next, int32_t n_steps,
+                              int32_t num_seqs, float *dist, float *value, float *logp, float *bootstrap_value,
+                              float *state_out, int32_t device_id, uint32_t flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

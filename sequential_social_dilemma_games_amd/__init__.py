@@ -17,6 +17,8 @@
     from sequential_social_dilemma_games_amd import clip_grad_by_set_norm       # A3C's gradient clip, per weight set
     from sequential_social_dilemma_games_amd import vtrace, evaluate_fragment   # IMPALA's V-trace targets of a fragment
     from sequential_social_dilemma_games_amd import impala_loss, impala_loss_recurrent, impala_loss_moa   # the IMPALA loss
+    from sequential_social_dilemma_games_amd import a3c_loss_watershed, impala_loss_watershed   # both for the Watershed policy
+    from sequential_social_dilemma_games_amd import evaluate_sequences, ws_a3c_terms   # its sequences under the current weights
 
 Everything that steps an env goes through libssd_hip.so (include/ssd.h); importing this package does
 not load it, constructing an env does -- and fails loudly if it is missing.
@@ -42,7 +44,8 @@ def __getattr__(name):
         return EpisodeStats
     if name in ("ConvFCPolicy", "ConvLSTMPolicy", "ConvMOAPolicy", "WatershedLSTMPolicy", "ppo_loss", "ppo_loss_recurrent",
                 "ppo_loss_moa", "ppo_loss_watershed", "ws_ppo_terms", "a3c_loss", "a3c_loss_recurrent", "a3c_loss_moa", "clip_grad_by_set_norm", "A3C_STATS",
-                "MOA_A3C_STATS", "evaluate_fragment", "impala_loss", "impala_loss_recurrent", "impala_loss_moa"):
+                "MOA_A3C_STATS", "evaluate_fragment", "impala_loss", "impala_loss_recurrent", "impala_loss_moa",
+                "ws_a3c_terms", "a3c_loss_watershed", "evaluate_sequences", "impala_loss_watershed"):
         from . import policy
         return getattr(policy, name)
     if name in ("compute_advantages", "vtrace"):

@@ -2,6 +2,9 @@
 // 5-wide distribution head and a value head) on the sequences of ONE agent id, with truncated backpropagation through time,
 // its statistics and the gradient of every parameter of that id's weight set: ssd_ws_policy_ppo_grad.  include/ssd.h
 // (WATERSHED PPO LOSS AND GRADIENTS) states the contract; DESIGN.md section 21 the shape, the resources and the measurements.
+// ssd_ws_policy_ac_grad is the same call with the reference's A3C row terms (include/ssd.h, WATERSHED A3C LOSS AND GRADIENTS;
+// DESIGN.md section 22): the sequence kernel and the reduce compiled once more with ssd::kLossAc -- a3c_row / ws_gauss_ac_row
+// for ppo_row / ws_gauss_row, and the float64 totals rounded as they are, without the division by the rows.
 //
 // The kernels are this file's own (the shared BPTT kernels of ssd_bptt_device.hpp are built around 32 trunk features a row and
 // an integer action; this net has 16 and two kinds of head), put together from the inline pieces the headers define once:
@@ -113,8 +116,31 @@ __device__ __forceinline__ void ws_gauss_row(const float *l, float *d, float act
     d[kOut] = a.vf_coeff * dvf;
 }
 
+// The A3C terms of an action agent's row (include/ssd.h, WATERSHED A3C LOSS AND GRADIENTS): a3c_row with ws_gauss_row's logp and
+// entropy in the place of the Categorical's.  Only vf_coeff and ent_coeff of the hyper-parameters are read; st receives total,
+// policy, vf, entropy in 0..3 (st[4] is left alone).  No kinks; d[2..4] = 0 exactly.
+__device__ __forceinline__ void ws_gauss_ac_row(const float *l, float *d, float act, float adv, float vt, const PpoHyper &a,
+                                                double (&st)[5]) {
+    const float mean = l[0], log_std = l[1], value = l[kOut];
+    const float sd = expf(log_std);
+    const float z = (act - mean) / sd;
+    const float logp = ((-0.5f * (z * z)) - log_std) - 0.9189385f;
+    const float ent = log_std + 1.4189385f;
+    const float pi = -(logp * adv);
+    const float d1 = value - vt;
+    const float vf = 0.5f * (d1 * d1);
+    const float row_loss = (pi + a.vf_coeff * vf) - a.ent_coeff * ent;
+    st[0] += (double)row_loss; st[1] += (double)pi; st[2] += (double)vf; st[3] += (double)ent;
+    d[0] = -adv * (z / sd);
+    d[1] = (-adv * (z * z - 1.f)) - a.ent_coeff;
+    d[2] = 0.f; d[3] = 0.f; d[4] = 0.f;
+    d[kOut] = a.vf_coeff * d1;
+}
+
 // ------------------------------------------------------------------------------------------------- the sequence kernel
-template <int C>
+// kLoss: the row loss, ssd::kLossPpo (ppo_row / ws_gauss_row) or ssd::kLossAc (a3c_row / ws_gauss_ac_row, which do not read
+// logp_old, vf_pred or beh).
+template <int C, int kLoss>
 __global__ void __launch_bounds__(4 * C) ssd_ws_seq_kernel(WsGradArgs a) {
     constexpr int kThreads = 4 * C, kK = kX + C, kPitch = kK + 52, kZP = 4 * C + 4;   // both pitches = 4 (mod 64)
     static_assert(kThreads >= kTile * kX, "tile");
@@ -221,13 +247,19 @@ __global__ void __launch_bounds__(4 * C) ssd_ws_seq_kernel(WsGradArgs a) {
                 double st[5];
 #pragma unroll
                 for (int k = 0; k < 5; ++k) st[k] = s_stat[tid * 5 + k];
-                const float *bl = a.beh ? a.beh + r * kOut : nullptr;
+                [[maybe_unused]] const float *bl = a.beh ? a.beh + r * kOut : nullptr;
                 if (a.comm) {
                     int act = (int)a.actions[r];
                     act = act < 0 ? 0 : (act >= kOut ? kOut - 1 : act);
-                    ssd::ppo_row(s_out + tid * kHd, d, kOut, act, a.adv[r], a.vt[r], a.vf_pred[r], a.logp_old[r], bl, a.h, st);
+                    if constexpr (kLoss == ssd::kLossAc)
+                        ssd::a3c_row(s_out + tid * kHd, d, kOut, act, a.adv[r], a.vt[r], a.h, st);
+                    else
+                        ssd::ppo_row(s_out + tid * kHd, d, kOut, act, a.adv[r], a.vt[r], a.vf_pred[r], a.logp_old[r], bl, a.h, st);
                 } else {
-                    ws_gauss_row(s_out + tid * kHd, d, a.actions[r], a.adv[r], a.vt[r], a.vf_pred[r], a.logp_old[r], bl, a.h, st);
+                    if constexpr (kLoss == ssd::kLossAc)
+                        ws_gauss_ac_row(s_out + tid * kHd, d, a.actions[r], a.adv[r], a.vt[r], a.h, st);
+                    else
+                        ws_gauss_row(s_out + tid * kHd, d, a.actions[r], a.adv[r], a.vt[r], a.vf_pred[r], a.logp_old[r], bl, a.h, st);
                 }
 #pragma unroll
                 for (int j = 0; j < kHd; ++j) a.dx[r * kX + j] = d[j];
@@ -468,11 +500,14 @@ struct WsReduceArgs {
     int32_t C, set_floats, rows, TG, G, S;
     const float *part_trunk, *part_seq, *part_w;
     float *grads;                  // [set_floats]
-    double *stats;                 // [5]
+    double *stats;                 // [5], or [4] of the A3C call
 };
 
 // The partials of every entry added in order in float64, times 1 / rows, rounded once; the padding floats are zero.
+// kLossAc: the sums as they are (the A3C loss is a sum over rows), and the four statistics of the A3C row terms to stats [4].
+template <int kLoss>
 __global__ void __launch_bounds__(256) ssd_ws_reduce_kernel(WsReduceArgs a) {
+    constexpr bool kSum = kLoss == ssd::kLossAc;
     const int idx = blockIdx.x * 256 + threadIdx.x, C = a.C;
     const int seq_pitch = kHd * C + kHd + kStatFloats, w_floats = (kX + C) * 4 * C, w_pitch = w_floats + 4 * C;
     if (idx < a.set_floats) {
@@ -497,19 +532,20 @@ __global__ void __launch_bounds__(256) ssd_ws_reduce_kernel(WsReduceArgs a) {
         }
         double sum = 0.0;
         for (int g = 0; g < n; ++g) sum += (double)src[g * pitch];
-        a.grads[idx] = (float)(sum / (double)a.rows);
+        a.grads[idx] = kSum ? (float)sum : (float)(sum / (double)a.rows);
     }
-    if (blockIdx.x == 0 && threadIdx.x < 5) {
+    if (blockIdx.x == 0 && threadIdx.x < (kSum ? 4 : 5)) {
         double sum = 0.0;
         for (int g = 0; g < a.G; ++g)
             sum += reinterpret_cast<const double *>(a.part_seq + (size_t)g * seq_pitch + kHd * C + kHd)[threadIdx.x];
-        a.stats[threadIdx.x] = sum / (double)a.rows;
+        a.stats[threadIdx.x] = kSum ? sum : sum / (double)a.rows;
     }
 }
 
 template <int C>
-hipError_t launch_window(const WsGradArgs &a, hipStream_t stream) {
-    hipLaunchKernelGGL((ssd_ws_seq_kernel<C>), dim3((unsigned)a.G), dim3(4 * C), 0, stream, a);
+hipError_t launch_window(int loss, const WsGradArgs &a, hipStream_t stream) {
+    if (loss == ssd::kLossPpo) hipLaunchKernelGGL((ssd_ws_seq_kernel<C, ssd::kLossPpo>), dim3((unsigned)a.G), dim3(4 * C), 0, stream, a);
+    else hipLaunchKernelGGL((ssd_ws_seq_kernel<C, ssd::kLossAc>), dim3((unsigned)a.G), dim3(4 * C), 0, stream, a);
     if (const hipError_t e = hipGetLastError()) return e;
     hipLaunchKernelGGL((ssd_ws_dw_kernel<C>), dim3(4 * C / 64, (unsigned)a.S), dim3(256), 0, stream, a);
     if (const hipError_t e = hipGetLastError()) return e;
@@ -519,16 +555,15 @@ hipError_t launch_window(const WsGradArgs &a, hipStream_t stream) {
 
 bool misaligned(const void *p, unsigned n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1u)) != 0; }
 
-}  // namespace
-
-extern "C" int ssd_ws_policy_ppo_grad(const float *weights, int32_t num_sets, int32_t cell_size, int32_t variant, int32_t agent_id,
-                                      int32_t seq_len, const float *obs, const float *state, const uint8_t *starts,
-                                      const float *actions, const float *logp_old, const float *advantages,
-                                      const float *value_targets, const float *vf_preds, const float *behaviour_dist,
-                                      int32_t n_steps, int32_t num_seqs, double clip_param, double vf_clip_param,
-                                      double vf_loss_coeff, double entropy_coeff, double kl_coeff, float *scratch, float *grads,
-                                      double *stats, int32_t device_id, uint32_t flags, void *stream_) {
+// Both entry points.  loss: ssd::kLossPpo or ssd::kLossAc; the A3C call passes null for logp_old, vf_preds and behaviour_dist
+// and 0 for the hyper-parameters it does not have.
+int ws_grad(int loss, const float *weights, int32_t num_sets, int32_t cell_size, int32_t variant, int32_t agent_id, int32_t seq_len,
+            const float *obs, const float *state, const uint8_t *starts, const float *actions, const float *logp_old,
+            const float *advantages, const float *value_targets, const float *vf_preds, const float *behaviour_dist, int32_t n_steps,
+            int32_t num_seqs, double clip_param, double vf_clip_param, double vf_loss_coeff, double entropy_coeff, double kl_coeff,
+            float *scratch, float *grads, double *stats, int32_t device_id, uint32_t flags, void *stream_) {
     using ssd::policy_fail;
+    const bool ac = loss == ssd::kLossAc;
     if (!weights) return policy_fail("weights are required");
     if (variant != SSD_WS_SEQ && variant != SSD_WS_SEQ_COMM) return policy_fail("unknown variant");
     if (num_sets != (variant == SSD_WS_SEQ ? 4 : 8)) return policy_fail("num_sets must be 4 (Seq) or 8 (SeqComm): one set per agent id");
@@ -537,8 +572,12 @@ extern "C" int ssd_ws_policy_ppo_grad(const float *weights, int32_t num_sets, in
     if (seq_len < 1) return policy_fail("seq_len must be >= 1");
     if (n_steps < 1 || num_seqs < 1) return policy_fail("n_steps and num_seqs must be >= 1");
     if ((int64_t)n_steps * num_seqs > (int64_t)INT32_MAX - 16) return policy_fail("at most 2^31 - 17 rows");
-    if (!obs || !state || !actions || !logp_old || !advantages || !value_targets || !vf_preds)
+    if (ac) {
+        if (!obs || !state || !actions || !advantages || !value_targets)
+            return policy_fail("obs, state, actions, advantages and value_targets are required");
+    } else if (!obs || !state || !actions || !logp_old || !advantages || !value_targets || !vf_preds) {
         return policy_fail("obs, state, actions, logp_old, advantages, value_targets and vf_preds are required");
+    }
     if (!scratch || !grads || !stats) return policy_fail("scratch, grads and stats are required");
     const double hyper[5] = {clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff};
     for (const double x : hyper)
@@ -590,20 +629,47 @@ extern "C" int ssd_ws_policy_ppo_grad(const float *weights, int32_t num_sets, in
         a.obs = obs + r0 * kObs;
         a.ring = state + (size_t)(m0 / T) * Q * 2 * C;
         a.starts = starts ? starts + r0 : nullptr;                   // row t > 0 of the window looks at starts[m0 + t]
-        a.actions = actions + r0; a.logp_old = logp_old + r0; a.adv = advantages + r0; a.vt = value_targets + r0;
-        a.vf_pred = vf_preds + r0;
+        a.actions = actions + r0; a.adv = advantages + r0; a.vt = value_targets + r0;
+        a.logp_old = ac ? nullptr : logp_old + r0;
+        a.vf_pred = ac ? nullptr : vf_preds + r0;
         a.beh = kl_coeff != 0.0 ? behaviour_dist + r0 * kOut : nullptr;
         hipError_t e;
         switch (C) {
-        case 64: e = launch_window<64>(a, stream); break;
-        case 128: e = launch_window<128>(a, stream); break;
-        default: e = launch_window<256>(a, stream); break;
+        case 64: e = launch_window<64>(loss, a, stream); break;
+        case 128: e = launch_window<128>(loss, a, stream); break;
+        default: e = launch_window<256>(loss, a, stream); break;
         }
         if (e != hipSuccess) return ssd::policy_launched(e);
     }
     WsReduceArgs r{};
     r.C = C; r.set_floats = set_floats; r.rows = (int32_t)((int64_t)M * Q); r.TG = a.TG; r.G = a.G; r.S = a.S;
     r.part_trunk = a.part_trunk; r.part_seq = a.part_seq; r.part_w = a.part_w; r.grads = grads; r.stats = stats;
-    hipLaunchKernelGGL(ssd_ws_reduce_kernel, dim3((unsigned)((set_floats + 255) / 256)), dim3(256), 0, stream, r);
+    const dim3 reduce_grid((unsigned)((set_floats + 255) / 256));
+    if (ac) hipLaunchKernelGGL(ssd_ws_reduce_kernel<ssd::kLossAc>, reduce_grid, dim3(256), 0, stream, r);
+    else hipLaunchKernelGGL(ssd_ws_reduce_kernel<ssd::kLossPpo>, reduce_grid, dim3(256), 0, stream, r);
     return ssd::policy_launched(hipGetLastError());
+}
+
+}  // namespace
+
+extern "C" int ssd_ws_policy_ppo_grad(const float *weights, int32_t num_sets, int32_t cell_size, int32_t variant, int32_t agent_id,
+                                      int32_t seq_len, const float *obs, const float *state, const uint8_t *starts,
+                                      const float *actions, const float *logp_old, const float *advantages,
+                                      const float *value_targets, const float *vf_preds, const float *behaviour_dist,
+                                      int32_t n_steps, int32_t num_seqs, double clip_param, double vf_clip_param,
+                                      double vf_loss_coeff, double entropy_coeff, double kl_coeff, float *scratch, float *grads,
+                                      double *stats, int32_t device_id, uint32_t flags, void *stream_) {
+    return ws_grad(ssd::kLossPpo, weights, num_sets, cell_size, variant, agent_id, seq_len, obs, state, starts, actions, logp_old,
+                   advantages, value_targets, vf_preds, behaviour_dist, n_steps, num_seqs, clip_param, vf_clip_param, vf_loss_coeff,
+                   entropy_coeff, kl_coeff, scratch, grads, stats, device_id, flags, stream_);
+}
+
+extern "C" int ssd_ws_policy_ac_grad(const float *weights, int32_t num_sets, int32_t cell_size, int32_t variant, int32_t agent_id,
+                                     int32_t seq_len, const float *obs, const float *state, const uint8_t *starts,
+                                     const float *actions, const float *advantages, const float *value_targets, int32_t n_steps,
+                                     int32_t num_seqs, double vf_loss_coeff, double entropy_coeff, float *scratch, float *grads,
+                                     double *stats, int32_t device_id, uint32_t flags, void *stream_) {
+    return ws_grad(ssd::kLossAc, weights, num_sets, cell_size, variant, agent_id, seq_len, obs, state, starts, actions, nullptr,
+                   advantages, value_targets, nullptr, nullptr, n_steps, num_seqs, 0.0, 0.0, vf_loss_coeff, entropy_coeff, 0.0,
+                   scratch, grads, stats, device_id, flags, stream_);
 }

@@ -1489,11 +1489,14 @@ _WS_PPO_KEYS = (("obs", ("obs",)), ("actions", ("actions",)), ("logp_old", ("log
                 ("behaviour_dist", ("behaviour_dist", "dist")), ("starts", ("starts",)), ("state", ("state",)))
 
 
-def _ws_ppo_tensors(policy, seq, seq_len, kl_coeff):
-    """The Watershed loss's inputs by their contract names from a dict of [M, Q, ...] tensors, checked against each other."""
+def _ws_ppo_tensors(policy, seq, seq_len, kl_coeff, a3c=False):
+    """The Watershed loss's inputs by their contract names from a dict of [M, Q, ...] tensors, checked against each other.
+    a3c: the A3C loss's inputs -- logp_old, vf_pred and behaviour_dist are not looked at (None)."""
     if not isinstance(seq, dict):
         raise ValueError("seq must be a dict of [M, Q, ...] tensors")
     t = {name: next((seq[k] for k in keys if seq.get(k) is not None), None) for name, keys in _WS_PPO_KEYS}
+    if a3c:
+        t["logp_old"] = t["vf_pred"] = t["behaviour_dist"] = None
     acts = t["actions"]
     if not isinstance(acts, torch.Tensor) or acts.dim() != 2 or acts.numel() == 0:
         raise ValueError("actions must be a float32 tensor [M, Q]")
@@ -1505,7 +1508,7 @@ def _ws_ppo_tensors(policy, seq, seq_len, kl_coeff):
         t["behaviour_dist"] = None                           # not part of the loss
     elif t["behaviour_dist"] is None:
         raise ValueError("kl_coeff != 0 needs dist (the dist the actions were sampled from)")
-    for name in ("actions", "logp_old", "advantages", "value_targets", "vf_pred"):
+    for name in ("actions",) + (_A3C_ROWS if a3c else ("logp_old", "advantages", "value_targets", "vf_pred")):
         _check_tensor(t[name], torch.float32, (M, Q), name, dev)
     _check_tensor(t["obs"], torch.float32, (M, Q, WS_OBS), "obs", dev)
     if t["behaviour_dist"] is not None:
@@ -1522,10 +1525,11 @@ def _ws_ppo_tensors(policy, seq, seq_len, kl_coeff):
     return t, (M, Q)
 
 
-def ws_forward_windows(policy, agent_id, obs, state, starts, seq_len):
+def ws_forward_windows(policy, agent_id, obs, state, starts, seq_len, return_state=False):
     """The learner's forward of a WatershedLSTMPolicy over one agent's sequences, in plain torch under autograd, by the state
     rule of include/ssd.h: obs [M, Q, 12], state [S, Q, 2, C] (detached: data), starts u8/bool [M, Q] or None -> (dist [M, Q, 5],
-    value [M, Q]).  Window by window through forward_sequence; starts at a window's first step are not looked at."""
+    value [M, Q]), and with return_state the state [Q, 2, C] after step M - 1.  Window by window through forward_sequence;
+    starts at a window's first step are not looked at."""
     M, T = int(obs.shape[0]), int(seq_len)
     dt = policy.dense0_w.dtype
     dists, values = [], []
@@ -1534,10 +1538,35 @@ def ws_forward_windows(policy, agent_id, obs, state, starts, seq_len):
         resets = None
         if starts is not None and m1 - m0 > 1:
             resets = torch.cat([torch.zeros_like(starts[:1]), starts[m0 + 1:m1]]).to(torch.bool)
-        d, v, _ = policy.forward_sequence(agent_id, obs[m0:m1], state[w].detach().to(dt), resets)
+        d, v, last = policy.forward_sequence(agent_id, obs[m0:m1], state[w].detach().to(dt), resets)
         dists.append(d)
         values.append(v)
+    if return_state:
+        return torch.cat(dists), torch.cat(values), last
     return torch.cat(dists), torch.cat(values)
+
+
+def _ws_agent(name, policy, agent_id):
+    """The policy and the agent id of a Watershed call `name`, checked -> the id as an int."""
+    if not isinstance(policy, WatershedLSTMPolicy):
+        raise ValueError("%s is for a WatershedLSTMPolicy" % name)
+    if isinstance(agent_id, bool) or int(agent_id) != agent_id or not 0 <= int(agent_id) < policy.num_sets:
+        raise ValueError("agent_id must be 0..%d" % (policy.num_sets - 1))
+    return int(agent_id)
+
+
+def _ws_loss_prepare(name, policy, agent_id, seq, seq_len, hyper, a3c):
+    """The checks the Watershed loss functions share, in the PPO call's order -> (agent_id, seq_len, hyper, t, (M, Q), dev).
+    hyper: the PPO call's five, or (vf_loss_coeff, entropy_coeff) of the A3C call."""
+    agent_id = _ws_agent(name, policy, agent_id)
+    seq_len = _check_seq_len(seq_len)
+    hyper = tuple(float(x) for x in hyper)
+    _check_hyper(hyper, clips=not a3c)
+    t, dims = _ws_ppo_tensors(policy, seq, seq_len, 0.0 if a3c else hyper[4], a3c=a3c)
+    dev = t["actions"].device
+    _check_same_device(policy, dev, "sequences")
+    _check_float32(policy, dev)
+    return agent_id, seq_len, hyper, t, dims, dev
 
 
 def ppo_loss_watershed(policy, agent_id, seq, *, seq_len, clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff):
@@ -1560,18 +1589,8 @@ def ppo_loss_watershed(policy, agent_id, seq, *, seq_len, clip_param, vf_clip_pa
     caller's choice: advantages and value_targets are inputs (compute_advantages accepts any [R, L] tensors).
     CUDA tensors go to the library (ssd_ws_policy_ppo_grad on torch's current stream, no synchronisation; the scratch is kept
     on the policy); CPU tensors run forward_sequence per window and ws_ppo_terms under autograd."""
-    if not isinstance(policy, WatershedLSTMPolicy):
-        raise ValueError("ppo_loss_watershed is for a WatershedLSTMPolicy")
-    if isinstance(agent_id, bool) or int(agent_id) != agent_id or not 0 <= int(agent_id) < policy.num_sets:
-        raise ValueError("agent_id must be 0..%d" % (policy.num_sets - 1))
-    agent_id = int(agent_id)
-    seq_len = _check_seq_len(seq_len)
-    hyper = tuple(float(x) for x in (clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff))
-    _check_hyper(hyper, clips=True)
-    t, (M, Q) = _ws_ppo_tensors(policy, seq, seq_len, hyper[4])
-    dev = t["actions"].device
-    _check_same_device(policy, dev, "sequences")
-    _check_float32(policy, dev)
+    hyper = (clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff)
+    agent_id, seq_len, hyper, t, (M, Q), dev = _ws_loss_prepare("ppo_loss_watershed", policy, agent_id, seq, seq_len, hyper, False)
     if dev.type == "cuda":
         return _device_loss(policy, (WatershedLSTMPolicy, "ppo"), t, (M, Q), seq_len, hyper, only_set=agent_id)
     _check_device_type(dev)
@@ -1581,7 +1600,186 @@ def ppo_loss_watershed(policy, agent_id, seq, *, seq_len, clip_param, vf_clip_pa
     return means[0], {name: m.detach() for name, m in zip(PPO_STATS, means)}
 
 
-# ---- the device path of the ten loss calls and of evaluate_fragment: one record of what to call, one torch function ----
+# ---- the A3C and the IMPALA loss for the Watershed policy (include/ssd.h, WATERSHED A3C LOSS AND GRADIENTS and WATERSHED
+# ---- SEQUENCE FORWARD) ----
+
+def ws_logp(dist, actions, is_comm):
+    """The log-probability of the taken actions under dist [..., 5] in plain torch, in the dtype of dist: the Categorical's
+    log_softmax(dist)[a] with the message index clamped to 0 .. 4 for a comm agent, else the Gaussian's
+    -0.5 z^2 - log_std - 0.9189385 with z = (a - mean) / exp(log_std) on the unclipped sample."""
+    dt = dist.dtype
+    if is_comm:
+        a = actions.to(torch.int64).clamp(0, WS_OUT - 1).unsqueeze(-1)
+        return torch.log_softmax(dist, dim=-1).gather(-1, a).squeeze(-1)
+    mean, log_std = dist[..., 0], dist[..., 1]
+    z = (actions.to(dt) - mean) / torch.exp(log_std)
+    return -0.5 * (z * z) - log_std - torch.tensor(np.float32(0.9189385), dtype=dt)
+
+
+def ws_a3c_terms(dist, value, t, is_comm, vf_loss_coeff, entropy_coeff):
+    """The reference's A3C loss (algorithms/a3c_causal.py:28-46) per row for a Watershed head in plain torch, in the dtype of
+    dist: (row_loss, pi, vf, ent), each of actions' shape.  dist [..., 5], value [...]; t: actions, advantages and value_targets.
+    is_comm: Categorical over the 5 outputs (a3c_terms with A = 5; actions hold the message index), else the one-dimensional
+    DiagGaussian of ws_ppo_terms: logp as ws_logp, entropy = log_std + 1.4189385."""
+    if is_comm:
+        return a3c_terms(dist, value, t, vf_loss_coeff, entropy_coeff)
+    dt = dist.dtype
+    logp = ws_logp(dist, t["actions"], False)
+    ent = dist[..., 1] + torch.tensor(np.float32(1.4189385), dtype=dt)
+    pi = -(logp * t["advantages"].to(dt))
+    vf = 0.5 * (value - t["value_targets"].to(dt)).square()
+    return (pi + vf_loss_coeff * vf) - entropy_coeff * ent, pi, vf, ent
+
+
+def a3c_loss_watershed(policy, agent_id, seq, *, seq_len, vf_loss_coeff, entropy_coeff):
+    """The reference's A3C loss (algorithms/a3c_causal.py:28-46; every Watershed launcher offers it next to PPO) of ONE agent id
+    of a WatershedLSTMPolicy on that agent's own steps, with truncated backpropagation through time over windows of seq_len
+    steps -> (loss, stats), as ppo_loss_watershed: loss a scalar tensor that backpropagates into row agent_id of every
+    parameter, stats a dict of scalar tensors (A3C_STATS: the SUMS over the M Q rows of the total, policy, value-function and
+    entropy terms).  Per row -logp * adv + vf_loss_coeff * 0.5 (value - vt)^2 - entropy_coeff * ent, summed, not averaged
+    (include/ssd.h, WATERSHED A3C LOSS AND GRADIENTS).
+
+        adv, vt = compute_advantages(rew, value, last_value, done, gamma=0.99, use_gae=False, bonus=...)
+        loss, stats = a3c_loss_watershed(policy, 5, dict(seq, advantages=adv, value_targets=vt), seq_len=16,
+                                         vf_loss_coeff=0.5, entropy_coeff=0.01)
+        loss.backward(); clip_grad_by_set_norm(policy, 40.0); optimiser.step()
+
+    seq: ppo_loss_watershed's dict, of which obs, actions, advantages, value_targets, state and, where present, starts are
+    read; logp, value and dist are ignored.  The state rule and the argument checks are ppo_loss_watershed's.
+    CUDA tensors go to the library (ssd_ws_policy_ac_grad on torch's current stream, no synchronisation; the scratch is the
+    PPO call's); CPU tensors run forward_sequence per window and ws_a3c_terms under autograd."""
+    agent_id, seq_len, hyper, t, (M, Q), dev = _ws_loss_prepare("a3c_loss_watershed", policy, agent_id, seq, seq_len,
+                                                                (vf_loss_coeff, entropy_coeff), True)
+    if dev.type == "cuda":
+        return _device_loss(policy, (WatershedLSTMPolicy, "a3c"), t, (M, Q), seq_len, hyper, only_set=agent_id)
+    _check_device_type(dev)
+    dist, value = ws_forward_windows(policy, agent_id, t["obs"], t["state"], t["starts"], seq_len)
+    sums = [x.sum() for x in ws_a3c_terms(dist, value, t, bool(ws_is_comm(policy.variant, agent_id)), *hyper)]
+    return sums[0], {name: x.detach() for name, x in zip(A3C_STATS, sums)}
+
+
+def _ws_eval_tensors(policy, seq, seq_len):
+    """What evaluate_sequences reads of a dict of [M, Q, ...] tensors, checked against each other -> (t, (M, Q))."""
+    if not isinstance(seq, dict):
+        raise ValueError("seq must be a dict of [M, Q, ...] tensors")
+    t = {name: seq.get(name) for name in ("obs", "actions", "state", "starts", "obs_next", "start_next")}
+    acts = t["actions"]
+    if not isinstance(acts, torch.Tensor) or acts.dim() != 2 or acts.numel() == 0:
+        raise ValueError("actions must be a float32 tensor [M, Q]")
+    M, Q = (int(n) for n in acts.shape)
+    C, T, dev = policy.cell_size, int(seq_len), acts.device
+    if (M + 1) * Q > 2 ** 31 - 17:
+        raise ValueError("the sequences must have at most 2^31 - 17 rows, the bootstrap's included")
+    _check_tensor(acts, torch.float32, (M, Q), "actions", dev)
+    _check_tensor(t["obs"], torch.float32, (M, Q, WS_OBS), "obs", dev)
+    for name, shape in (("starts", (M, Q)), ("start_next", (Q,))):
+        if t[name] is not None:
+            if isinstance(t[name], torch.Tensor) and t[name].dtype == torch.bool:
+                t[name] = t[name].to(torch.uint8)
+            _check_tensor(t[name], torch.uint8, shape, name, dev)
+    if t["obs_next"] is not None:
+        _check_tensor(t["obs_next"], torch.float32, (Q, WS_OBS), "obs_next", dev)
+    elif t["start_next"] is not None:
+        raise ValueError("start_next needs obs_next")
+    S = -(-M // T)
+    st = t["state"]
+    if not isinstance(st, torch.Tensor) or st.dim() != 4 or st.shape[0] < S or tuple(st.shape[1:]) != (Q, 2, C):
+        raise ValueError("state must be [S, %d, 2, %d] with S >= ceil(M / seq_len) = %d" % (Q, C, S))
+    _check_tensor(st, torch.float32, tuple(st.shape), "state", dev)
+    return t, (M, Q)
+
+
+def evaluate_sequences(policy, agent_id, seq, seq_len):
+    """One agent id's sequences under the policy's CURRENT weights -> (dist [M,Q,5], value [M,Q], logp [M,Q], bootstrap_value
+    [Q] or None), without gradient: what V-trace needs of the target policy (postprocessing.vtrace) when the weights have moved
+    since sample() ran.  The Watershed counterpart of evaluate_fragment, on the rows ppo_loss_watershed takes.
+
+    seq: obs f32 [M,Q,12], actions f32 [M,Q], state f32 [ceil(M / seq_len),Q,2,C], optionally starts u8 or bool [M,Q] (the loss
+    calls' state rule), obs_next f32 [Q,12] (the observation after the last own step) and start_next u8 or bool [Q].  logp is
+    the log-probability of actions under dist (ws_logp's expressions).  bootstrap_value is the value of obs_next under the state
+    step M - 1 computed, zero where start_next, never a state entry; without obs_next it is None.
+    CUDA tensors go to the library: ssd_ws_policy_forward_seq, ONE launch on torch's current stream for all M steps and the
+    bootstrap, no scratch and no synchronisation; with unchanged weights on a fresh sample()'s rows of the id it gives back
+    the recorded dist, value and logp to the bit.  CPU tensors run ws_forward_windows and one forward step under no_grad."""
+    agent_id = _ws_agent("evaluate_sequences", policy, agent_id)
+    seq_len = _check_seq_len(seq_len)
+    t, (M, Q) = _ws_eval_tensors(policy, seq, seq_len)
+    dev = t["actions"].device
+    _check_same_device(policy, dev, "sequences")
+    _check_device_type(dev)
+    _check_float32(policy, dev)
+    is_comm = bool(ws_is_comm(policy.variant, agent_id))
+    with torch.no_grad():
+        if dev.type == "cuda":
+            dist = torch.empty((M, Q, WS_OUT), dtype=torch.float32, device=dev)
+            value, logp = (torch.empty((M, Q), dtype=torch.float32, device=dev) for _ in range(2))
+            boot = None if t["obs_next"] is None else torch.empty((Q,), dtype=torch.float32, device=dev)
+            ptr, index, stream = _device_handles(dev)
+            rc = _capi.lib().ssd_ws_policy_forward_seq(ptr(policy.packed()), policy.num_sets, policy.cell_size, policy.variant,
+                                                       agent_id, seq_len, ptr(t["obs"]), ptr(t["state"]), ptr(t["starts"]),
+                                                       ptr(t["actions"]), ptr(t["obs_next"]), ptr(t["start_next"]), M, Q,
+                                                       ptr(dist), ptr(value), ptr(logp), ptr(boot), None, index, 0, stream)
+            _capi.policy_check(rc)
+            return dist, value, logp, boot
+        dist, value, last = ws_forward_windows(policy, agent_id, t["obs"], t["state"], t["starts"], seq_len, return_state=True)
+        boot = None
+        if t["obs_next"] is not None:
+            agent = torch.full((Q,), agent_id, dtype=torch.int64)
+            starts = None if t["start_next"] is None else t["start_next"].to(torch.bool)
+            boot = policy(t["obs_next"], agent, last, starts)[1]
+        return dist, value, ws_logp(dist, t["actions"], is_comm), boot
+
+
+def impala_loss_watershed(policy, agent_id, seq, *, seq_len, gamma=0.99, vf_loss_coeff=0.5, entropy_coeff=0.01,
+                          clip_rho_threshold=1.0, clip_pg_rho_threshold=1.0):
+    """The reference's IMPALA loss (algorithms/impala_causal.py:79-143; RLlib 0.7.6's VTraceLoss, which takes
+    action_dist.logp(actions) and the recorded behaviour_action_logp and so serves the Box actions of the action agents as well
+    as the comm agents' messages) of ONE agent id of a WatershedLSTMPolicy -> (loss, stats), as a3c_loss_watershed:
+    -sum logp * pg_advantages + vf_loss_coeff * 0.5 sum (value - vs)^2 - entropy_coeff * sum entropy, where vs and
+    pg_advantages are the V-trace targets (stop-gradient data) of the sequences under the policy's CURRENT weights.
+
+        for _ in range(passes):
+            loss, stats = impala_loss_watershed(policy, 5, seq, seq_len=16, gamma=0.99, vf_loss_coeff=0.5, entropy_coeff=0.01)
+            optimiser.zero_grad(); loss.backward(); clip_grad_by_set_norm(policy, 40.0); optimiser.step()
+
+    The call is (1) evaluate_sequences, (2) rhos = exp(logp - seq["logp"]) in float32 torch, (3) postprocessing.vtrace(zero
+    int32 rewards, value, rhos, bootstrap_value, seq["done"], bonus=seq["rew"], bonus_weight=1.0, ...): the float rewards go
+    through vtrace's bonus input, the one examples/ppo_train_watershed.py gives compute_advantages, (4) a3c_loss_watershed
+    with advantages = pg_advantages and value_targets = vs; stats are A3C_STATS.
+    seq: a3c_loss_watershed's dict (advantages and value_targets are not read) and logp f32 [M,Q] (the behaviour policy's, as
+    sample() records it), rew f32 [M,Q] (the reward credited to own step m: the caller's choice), done u8 [M,Q] (the episode
+    ended after own step m), obs_next f32 [Q,12] and optionally start_next u8 [Q] (default done[M - 1]).
+    One difference from the reference, as with the other IMPALA calls: RLlib cuts the batch into sequences of T rows, drops
+    each sequence's last row from the loss (drop_last) and bootstraps from its value; here every row is a loss row and the
+    bootstrap is the current value of obs_next (include/ssd.h, V-TRACE TARGETS).  There is no row mask.
+    CUDA tensors stay on the device, on torch's current stream without a host synchronisation."""
+    from .postprocessing import vtrace
+    _ws_agent("impala_loss_watershed", policy, agent_id)
+    if not isinstance(seq, dict):
+        raise ValueError("seq must be a dict of [M, Q, ...] tensors")
+    for key in ("logp", "rew", "done", "obs_next"):
+        if not isinstance(seq.get(key), torch.Tensor):
+            raise ValueError("%s is required" % key)
+    done = seq["done"].to(torch.uint8) if seq["done"].dtype == torch.bool else seq["done"]
+    acts = seq.get("actions")
+    if seq.get("start_next") is None and isinstance(acts, torch.Tensor) and tuple(done.shape) == tuple(acts.shape) and acts.dim() == 2 \
+            and acts.numel() and done.dtype == torch.uint8:
+        seq = dict(seq, start_next=done[-1].contiguous())     # (a done of another shape is refused below, by its name)
+    dist, value, logp, boot = evaluate_sequences(policy, agent_id, seq, seq_len)
+    shape, dev = tuple(value.shape), value.device
+    _check_tensor(seq["logp"], torch.float32, shape, "logp", dev)
+    _check_tensor(seq["rew"], torch.float32, shape, "rew", dev)
+    _check_tensor(done, torch.uint8, shape, "done", dev)
+    with torch.no_grad():
+        rhos = torch.exp(logp.float() - seq["logp"])                  # float32 torch for a float32 policy
+        vs, pg = vtrace(torch.zeros(shape, dtype=torch.int32, device=dev), value.float().contiguous(), rhos,
+                        boot.float().contiguous(), done, gamma=gamma, clip_rho_threshold=clip_rho_threshold,
+                        clip_pg_rho_threshold=clip_pg_rho_threshold, bonus=seq["rew"], bonus_weight=1.0)
+    return a3c_loss_watershed(policy, agent_id, dict(seq, advantages=pg, value_targets=vs), seq_len=seq_len,
+                              vf_loss_coeff=vf_loss_coeff, entropy_coeff=entropy_coeff)
+
+
+# ---- the device path of the eleven loss calls and of evaluate_fragment: one record of what to call, one torch function ----
 
 def _device_handles(dev):
     """What a library call on torch's current stream of `dev` needs besides its own arguments: (ptr: the address of a tensor,
@@ -1637,7 +1835,12 @@ _LOSS_CALLS = {
                                    "seq_len obs state starts actions "
                                    "logp_old advantages value_targets vf_pred "
                                    "behaviour_dist n_steps num_seqs clip_param "
-                                   "vf_clip_param vf_loss_coeff entropy_coeff kl_coeff", PPO_STATS)}
+                                   "vf_clip_param vf_loss_coeff entropy_coeff kl_coeff", PPO_STATS),
+    (WatershedLSTMPolicy, "a3c"): ("ssd_ws_policy_ac_grad",
+                                   "weights num_sets cell_size variant agent_id "
+                                   "seq_len obs state starts actions "
+                                   "advantages value_targets n_steps num_seqs "
+                                   "vf_loss_coeff entropy_coeff", A3C_STATS)}
 _LOSS_CALLS = {key: (symbol, tuple(names.split()), stats) for key, (symbol, names, stats) in _LOSS_CALLS.items()}
 _HYPER = {"ppo": ("clip_param", "vf_clip_param", "vf_loss_coeff", "entropy_coeff", "kl_coeff", "moa_weight"),
           "a3c": ("vf_loss_coeff", "entropy_coeff", "moa_weight")}
