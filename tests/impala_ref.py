@@ -13,6 +13,7 @@ import a3c_ref
 import ppo_moa_ref
 import ppo_ref
 from gae_ref import rewards
+from ppo_lstm_ref import make_done
 from sequential_social_dilemma_games_amd.policy import A3C_STATS, MOA_A3C_STATS
 
 HYPER = dict(gamma=0.99, vf_loss_coeff=0.5, entropy_coeff=0.01, clip_rho_threshold=1.0, clip_pg_rho_threshold=1.0)
@@ -20,22 +21,55 @@ MOA_WEIGHT, INFLUENCE_WEIGHT = 10.0, 0.25
 # "grad_vs": the gradient flows through vs into the value head; "no_clip": rho left unclipped in delta and pg;
 # "stale_bootstrap": the bootstrap is batch["last_value"], the behaviour policy's; "ignore_done": the discount is gamma everywhere
 VARIANTS = ("grad_vs", "no_clip", "stale_bootstrap", "ignore_done")
+# wrong rules of the EVALUATION (evaluate's variant).  "no_shift": rows read obs[k] although obs_first is given; "boot_prev_row":
+# the bootstrap reads the observation row K - 1 acted on; "boot_from_ring": when K % T == 0 the bootstrap row takes state[K // T]
+# as stored, with no start rule; "boot_ignores_done": the bootstrap row gets starts = None; "carry_ignores_done": the loss rows
+# that read the carried state get starts = None.  The last three do not apply to the conv-FC policy (eval_variants_of).
+EVAL_VARIANTS = ("no_shift", "boot_prev_row", "boot_from_ring", "boot_ignores_done", "carry_ignores_done")
 
 
-def evaluate(kind, pol, t, first, T):
-    """(logits [K,E,N,A], value [K,E,N], pred or None, bootstrap [E,N]) with gradient: K + 1 steps, one after the other."""
+def eval_variants_of(kind):
+    return EVAL_VARIANTS[:2] if kind == "fc" else EVAL_VARIANTS
+
+
+def eval_variant_applies(kind, variant, t, first, T):
+    """True where the wrong rule `variant` reads something else than the right one on this fragment: done is present and set
+    where the rule looks; "boot_from_ring" needs K % T == 0 (and a ring entry state[K // T] to take, make_batch's ring_extra)."""
+    K, done = t["actions"].shape[0], t.get("done")
+    if variant == "boot_prev_row":
+        return True
+    if variant == "no_shift":
+        return first is not None
+    if kind == "fc":
+        return False
+    if variant == "boot_from_ring":
+        return K % T == 0
+    if done is None:
+        return False
+    if variant == "boot_ignores_done":
+        return bool(done[K - 1].any())
+    return any(bool(done[k - 1].any()) for k in range(1, K) if k % T)           # "carry_ignores_done"
+
+
+def evaluate(kind, pol, t, first, T, variant=None):
+    """(logits [K,E,N,A], value [K,E,N], pred or None, bootstrap [E,N]) with gradient: K + 1 steps, one after the other.
+    variant: None (the contract) or one of EVAL_VARIANTS."""
     K = t["actions"].shape[0]
-    obs = torch.cat([ppo_ref.shifted_obs(t["obs"], first, K), t["obs"][K - 1:K] if first is not None else t["obs"][K:K + 1]])
+    rows = t["obs"][:K] if variant == "no_shift" else ppo_ref.shifted_obs(t["obs"], first, K)
+    last = rows[K - 1:K] if variant == "boot_prev_row" else (t["obs"][K - 1:K] if first is not None else t["obs"][K:K + 1])
+    obs = torch.cat([rows, last])
     if kind == "fc":
         logits, value = pol(obs)
         return logits[:K], value[:K], None, value[K]
     done, dt = t.get("done"), pol.conv_w.dtype
     outs, st = ([], [], []), None
     for k in range(K + 1):
-        if k < K and k % T == 0:
+        if k % T == 0 and (k < K or variant == "boot_from_ring"):
             st, starts = t["state"][k // T].detach().to(dt), None
         else:
             starts = None if done is None else done[k - 1].to(torch.bool)
+            if variant == ("boot_ignores_done" if k == K else "carry_ignores_done"):
+                starts = None
         if kind == "lstm":
             lg, v, nxt = pol(obs[k], st, starts)
             pr = None
@@ -88,12 +122,13 @@ def targets(kind, t, logits, value, boot, h, variant=None):
     return rnd(vs), rnd(pg), rhos
 
 
-def autograd_loss(kind, policy, t, h, first, T=None, moa_weight=MOA_WEIGHT, variant=None):
-    """The restatement under torch autograd on a float64 copy of `policy` -> (loss, {stat: [P]}, {param: grad}, rhos)."""
+def autograd_loss(kind, policy, t, h, first, T=None, moa_weight=MOA_WEIGHT, variant=None, eval_variant=None):
+    """The restatement under torch autograd on a float64 copy of `policy` -> (loss, {stat: [P]}, {param: grad}, rhos).
+    variant: one of VARIANTS (a wrong loss); eval_variant: one of EVAL_VARIANTS (a wrong evaluation under a right loss)."""
     pol = copy.deepcopy(policy).to(dtype=torch.float64)
     pol.zero_grad()
     P = pol.num_sets
-    logits, value, pred, boot = evaluate(kind, pol, t, first, T)
+    logits, value, pred, boot = evaluate(kind, pol, t, first, T, eval_variant)
     vs, pg, rhos = targets(kind, t, logits, value, boot, h, variant)
     terms = a3c_ref.row_terms(logits, value, t["actions"], pg, vs, h)
     rows = t["actions"].numel() // P
@@ -113,18 +148,26 @@ def autograd_loss(kind, policy, t, h, first, T=None, moa_weight=MOA_WEIGHT, vari
     return loss.detach(), {k: m.detach() for k, m in zip(names, sums)}, grads, rhos
 
 
-def make_batch(kind, A, N, P, K, E, T, seed, C=64, done_mode="per_env", last_done=True):
+def make_batch(kind, A, N, P, K, E, T, seed, C=64, done_mode="per_env", last_done=True, ring_extra=0):
     """(the target policy, batch, obs_first): a3c_ref.make_inputs' fragment for the policy of `seed`, and besides rew (as the
-    games pay it), done for the conv-FC policy too, done on the last row of env 0 (last_done), influence for the MOA policy,
-    and logp and last_value from a BEHAVIOUR policy -- the policy of another seed, in float64 by the same state rule -- so that
-    the importance weights spread on both sides of 1."""
+    games pay it), done for the conv-FC policy too (at rate 0.25 for "per_env", ppo_lstm_ref.make_done's otherwise), influence
+    for the MOA policy, and logp and last_value from a BEHAVIOUR policy -- the policy of another seed, in float64 by the same
+    state rule -- so that the importance weights spread on both sides of 1.  last_done: True ends env 0 on the last row as well;
+    "alternate" makes the last row of done 1 for every other env (0, 2, ...) and 0 for the rest, so that the bootstrap row's
+    start rule has lanes of both kinds (no ring entry and no prev_actions depend on the last row).  ring_extra: that many more
+    entries on the state ring than ceil(K / T), random as a stale entry would be; nothing may read them."""
     pol = a3c_ref.make_policy(kind, A, N, P, C=C, seed=seed)
     t, first = a3c_ref.make_inputs(kind, pol, K, E, N, T, seed=500 + seed, obs_first=True, done_mode=done_mode)
     g = torch.Generator().manual_seed(900 + seed)
     rng = np.random.default_rng(900 + seed)
-    if t.get("done") is None and done_mode != "none":
+    if t.get("done") is None and done_mode == "per_env":
         t["done"] = (torch.rand((K, E, N), generator=g) < 0.25).to(torch.uint8)
-    if last_done and t.get("done") is not None:
+    elif t.get("done") is None and done_mode != "none":
+        t["done"] = make_done(done_mode, K, E, N, min(T or K, K), g)
+    if t.get("done") is not None and last_done == "alternate":
+        t["done"][K - 1] = 0
+        t["done"][K - 1, ::2] = 1
+    elif t.get("done") is not None and last_done:
         t["done"][K - 1, 0] = 1
     t["rew"] = torch.from_numpy(rewards(rng, (K, E, N)))
     if kind == "moa":
@@ -134,4 +177,36 @@ def make_batch(kind, A, N, P, K, E, T, seed, C=64, done_mode="per_env", last_don
         logits, _, _, boot = evaluate(kind, beh, t, first, T)
         t["logp"] = torch.log_softmax(logits, -1).gather(-1, t["actions"].long().unsqueeze(-1)).squeeze(-1).float()
         t["last_value"] = boot.float()
+    if ring_extra and kind != "fc":
+        stale = 0.5 * torch.randn((ring_extra,) + tuple(t["state"].shape[1:]), generator=torch.Generator().manual_seed(1300 + seed))
+        t["state"] = torch.cat([t["state"], stale]).contiguous()
     return pol, t, first
+
+
+# ---- the edge matrix of evaluate_fragment and the IMPALA calls (test_impala_loss_cpu.py, test_evaluate_fragment_gpu.py,
+# ---- test_impala_loss_gpu.py): E = 17, N = 5 is two 16-row tiles per weight set at P = N, the second with one row ----
+EDGE_E, EDGE_N = 17, 5
+
+
+def edge(K, T, done, P=5, A=8, C=64, seed=1):
+    return (K, T, done, P, A, C, seed)
+
+
+# (K, T): whole windows only (4, 2) and (6, 3); K = 1 < T; T = 1; the ragged (5, 2); one window with T > K.  done: "none"
+# (absent), "per_env" with the alternating last row, "window_end", "all".  P, A and C rotate.
+EDGE_CASES = [edge(4, 2, "per_env", seed=1), edge(4, 2, "none", P=1, A=9, seed=2), edge(6, 3, "none", seed=3),
+              edge(6, 3, "all", P=1, seed=4), edge(6, 3, "window_end", A=9, seed=5), edge(1, 2, "per_env", seed=6),
+              edge(1, 2, "none", P=1, A=9, seed=7), edge(3, 1, "per_env", A=9, seed=8), edge(3, 1, "all", P=1, seed=9),
+              edge(5, 2, "window_end", seed=10), edge(5, 2, "per_env", P=1, A=9, seed=11), edge(4, 8, "window_end", seed=12),
+              edge(4, 8, "all", P=1, A=9, seed=13), edge(4, 2, "all", C=128, seed=14)]
+
+
+def edge_id(case):
+    return "K%d-T%d-%s-P%d-A%d-C%d" % case[:6]
+
+
+def edge_batch(kind, case, E=EDGE_E, ring_extra=0):
+    """make_batch for a case of EDGE_CASES; "per_env" gets the alternating last row."""
+    K, T, done, P, A, C, seed = case
+    return make_batch(kind, A, EDGE_N, P, K, E, T, seed=seed, C=C, done_mode=done, last_done="alternate" if done == "per_env" else True,
+                      ring_extra=ring_extra)
