@@ -93,9 +93,11 @@ struct AqlState {
     struct Set {
         bool valid = false;
         Key key;
-        uint8_t *dev = nullptr;                     // [chains][slots][kKinds] blocks of kBlock bytes
+        uint8_t *dev = nullptr;                     // [chains][slots][n_dense] blocks of kBlock bytes
         size_t cap = 0;
-        Geo geo[8][22];                             // per chain and kind (kKinds: asserted below)
+        Geo geo[8][62];                             // per chain and kind (kKinds: asserted below)
+        int8_t dense[62] = {};                      // the kind's place among the blocks of one (chain, slot): only the kinds the key's
+        int n_dense = 0;                            // calls can use have a block (-1: none)
         uint64_t last_use[8] = {};                  // index of the last join packet after a use, per chain (+1)
         uint64_t stamp = 0;
     };
@@ -105,22 +107,35 @@ struct AqlState {
     //   kRn  reset that renders nothing (inside a split rollout), in place
     //   kA   the first step of a split rollout: env waves only                        kAB  env waves + renderer workgroups for the step before
     //   kB   renderer workgroups only, for the step that produced buffer o (ends a split rollout, and precedes a reset inside one)
-    // Step pairs (key.pairs; the step-pair kernel, ssd::kModeStepPair): a launch whose env waves take two steps -- block i then
-    // serves steps i and i + 1 -- and the launches that follow one, whose renderer workgroups deliver both steps' observations:
-    //   kP   pair, env waves only             kPB  pair + renderers for the single step before      kPBB  pair + renderers for the pair before
-    //   kABB single step + renderers for the pair before (an odd remainder, the step ahead of a reset)
-    //   kBB  renderer workgroups only, for the pair that produced buffer o
-    enum Kind { kS = 0, kR = 1, kRn = 2, kA = 3, kAB = 4, kB = 5, kP = 6, kPB = 7, kPBB = 8, kABB = 9, kBB = 10, kKindsPerO = 11, kKinds = 22 };
-    static_assert(sizeof(Set::geo[0]) / sizeof(Geo) == kKinds, "Set::geo holds one entry per kind");
+    // Step runs (key.pairs = the longest run, 2 .. kMaxRun; the step-pair kernel, ssd::kModeStepPair): a launch whose env waves take n
+    // steps -- block i then serves steps i .. i + n - 1 -- and the launches that follow one, whose renderer workgroups deliver all of
+    // its steps' observations:
+    //   run_kind(n, rendered)   n = 1 .. kMaxRun steps + renderers for the `rendered` = 0 .. kMaxRun steps of the launch before
+    //   run_kind(0, rendered)   renderer workgroups only, for the run that produced buffer o
+    // (a single step behind nothing or behind a single step is kA / kAB, the renderers for a single step kB, as without runs)
+    enum Kind { kS = 0, kR = 1, kRn = 2, kA = 3, kAB = 4, kB = 5, kRun = 6, kKindsPerO = kRun + (ssd::kMaxRun + 1) * (ssd::kMaxRun + 1), kKinds = 2 * kKindsPerO };
+    static constexpr int run_kind(int n, int rendered) { return kRun + n * (ssd::kMaxRun + 1) + rendered; }
+    // the step counts a launch takes under a run cap (0: no runs): 1, 2 and the cap itself -- 4 in the product, 3 under the test hook
+    static constexpr bool run_len(int n, int cap) { return n == 1 || (n == 2 && cap >= 2) || (n > 2 && n == cap); }
+    // whether a key with this run cap has a block for kind `base` (of either orientation)
+    static constexpr bool run_kind_used(int base, int cap) {
+        const int n = (base - kRun) / (ssd::kMaxRun + 1), rd = (base - kRun) % (ssd::kMaxRun + 1);
+        if (n > 0 ? !run_len(n, cap) : rd == 0) return false;
+        if (rd > 0 && !run_len(rd, cap)) return false;
+        return n >= 2 || rd >= 2;
+    }
+    static_assert(sizeof(Set::geo[0]) / sizeof(Geo) == kKinds && sizeof(Set::dense) == kKinds, "Set::geo and Set::dense hold one entry per kind");
     uint8_t *world_buf[2] = {};                     // split rollouts: the pair of state buffers ([0]: the handle's original ones)
     uint32_t *agents_buf[2] = {};
     uint32_t *beam_list[2] = {};                    // [2][E][64] beam marks left by a launch of orientation o (second half: a second pass's)
     uint8_t *snap_grid[2] = {};                     // [E][S] overlay snapshot left by a launch of orientation o (rare steps)
-    // the same four for what the FIRST step of a pair launch of orientation o left (read by the next launch's renderers alone)
-    uint8_t *mid_world[2] = {}, *mid_snap[2] = {};
-    uint32_t *mid_agents[2] = {}, *mid_list[2] = {};
+    // the same four for what pass k of a run launch of orientation o left, for every pass but the run's last: [k][o] (read by the next
+    // launch's renderers alone)
+    static constexpr int kMids = ssd::kMaxRun - 1;
+    uint8_t *mid_world[kMids][2] = {}, *mid_snap[kMids][2] = {};
+    uint32_t *mid_agents[kMids][2] = {}, *mid_list[kMids][2] = {};
     static constexpr int kSets = 4;
-    static constexpr size_t kBlock = 640;           // >= sizeof(ssd::PairKernArgs), a multiple of 64
+    static constexpr size_t kBlock = 896;           // >= sizeof(ssd::PairKernArgs), a multiple of 64
     Set sets[kSets];
     uint64_t clock = 0;
 };
@@ -742,8 +757,9 @@ static void aql_teardown(ssd_env *env) {
     for (int i = 0; i < 2; ++i) { if (A.snap_grid[i]) (void)hipFree(A.snap_grid[i]); if (A.beam_list[i]) (void)hipFree(A.beam_list[i]); }
     if (A.world_buf[1]) (void)hipFree(A.world_buf[1]);
     if (A.agents_buf[1]) (void)hipFree(A.agents_buf[1]);
-    for (int i = 0; i < 2; ++i)
-        for (void *m : {(void *)A.mid_world[i], (void *)A.mid_snap[i], (void *)A.mid_agents[i], (void *)A.mid_list[i]}) if (m) (void)hipFree(m);
+    for (int k = 0; k < AqlState::kMids; ++k)
+        for (int i = 0; i < 2; ++i)
+            for (void *m : {(void *)A.mid_world[k][i], (void *)A.mid_snap[k][i], (void *)A.mid_agents[k][i], (void *)A.mid_list[k][i]}) if (m) (void)hipFree(m);
     env->aql.reset();
 }
 
@@ -807,16 +823,21 @@ static inline void aql_wait_consumed(ssd::aql::Queue *q, uint64_t idx_plus_1) {
     while (idx_plus_1 && ssd::aql::read_index(q) < idx_plus_1 && !ssd::aql::queue_failed(q)) __builtin_ia32_pause();
 }
 
-// The second state buffers, the render side buffers of split rollouts and the two `mid` sets of step pairs, once per handle: all
-// fourteen or none.
+// The second state buffers, the render side buffers of split rollouts and the `mid` sets of step runs (one per pass before a run's
+// last and orientation), once per handle: all thirty or none.
 static bool aql_split_buffers(ssd_env *env) {
     AqlState &A = *env->aql;
     if (A.world_buf[1]) return true;                                // (set last, below)
     const size_t grid = (size_t)env->E * env->S, agents = (size_t)env->E * (env->N ? env->N : 1) * 4;
     const size_t lists = (size_t)env->E * 128 * 4;                  // (beam lists: [E][64] + a second [E][64] for steps whose beams took two passes)
-    const size_t sizes[14] = {grid, agents, grid, grid, lists, lists, grid, grid, grid, grid, agents, agents, lists, lists};
-    void *buf[14] = {};
-    for (int i = 0; i < 14; ++i)
+    constexpr int kBufs = 6 + 8 * AqlState::kMids;
+    size_t sizes[kBufs] = {grid, agents, grid, grid, lists, lists};
+    for (int k = 0; k < AqlState::kMids; ++k) {
+        const size_t mids[8] = {grid, grid, grid, grid, agents, agents, lists, lists};
+        for (int j = 0; j < 8; ++j) sizes[6 + 8 * k + j] = mids[j];
+    }
+    void *buf[kBufs] = {};
+    for (int i = 0; i < kBufs; ++i)
         if (hipMalloc(&buf[i], sizes[i]) != hipSuccess) {
             (void)hipGetLastError();
             for (int j = 0; j < i; ++j) (void)hipFree(buf[j]);
@@ -826,10 +847,12 @@ static bool aql_split_buffers(ssd_env *env) {
     A.agents_buf[1] = static_cast<uint32_t *>(buf[1]);
     A.snap_grid[0] = static_cast<uint8_t *>(buf[2]); A.snap_grid[1] = static_cast<uint8_t *>(buf[3]);
     A.beam_list[0] = static_cast<uint32_t *>(buf[4]); A.beam_list[1] = static_cast<uint32_t *>(buf[5]);
-    for (int i = 0; i < 2; ++i) {
-        A.mid_world[i] = static_cast<uint8_t *>(buf[6 + i]); A.mid_snap[i] = static_cast<uint8_t *>(buf[8 + i]);
-        A.mid_agents[i] = static_cast<uint32_t *>(buf[10 + i]); A.mid_list[i] = static_cast<uint32_t *>(buf[12 + i]);
-    }
+    for (int k = 0; k < AqlState::kMids; ++k)
+        for (int i = 0; i < 2; ++i) {
+            void **b = buf + 6 + 8 * k;
+            A.mid_world[k][i] = static_cast<uint8_t *>(b[i]); A.mid_snap[k][i] = static_cast<uint8_t *>(b[2 + i]);
+            A.mid_agents[k][i] = static_cast<uint32_t *>(b[4 + i]); A.mid_list[k][i] = static_cast<uint32_t *>(b[6 + i]);
+        }
     A.world_buf[1] = static_cast<uint8_t *>(buf[0]);
     return true;
 }
@@ -847,7 +870,16 @@ static AqlState::Set *aql_set(ssd_env *env, const AqlState::Key &key, int chains
     if (st.valid) for (int c = 0; c < 8 && c < A.nq; ++c) aql_wait_consumed(A.q[c], st.last_use[c]);   // nobody reads the old blocks any more
     st.valid = false;
     constexpr int kKinds = AqlState::kKinds;
-    const size_t need = (size_t)chains * key.slots * kKinds * AqlState::kBlock;
+    // (the kinds this key's calls can use, and their places among the blocks of one chain and slot)
+    st.n_dense = 0;
+    for (int kind = 0; kind < kKinds; ++kind) {
+        const int o = kind / AqlState::kKindsPerO, base = kind % AqlState::kKindsPerO;
+        const bool split_kind = base >= AqlState::kRn, run_kind = base >= AqlState::kRun;
+        const bool used = !(split_kind && !key.split) && !(run_kind && !AqlState::run_kind_used(base, key.pairs)) && !(!key.split && o == 1);
+        st.dense[kind] = used ? (int8_t)st.n_dense++ : (int8_t)-1;
+    }
+    const int n_dense = st.n_dense;
+    const size_t need = (size_t)chains * key.slots * n_dense * AqlState::kBlock;
     if (need > st.cap) {
         if (st.dev) (void)hipFree(st.dev);
         st.dev = nullptr; st.cap = 0;
@@ -863,10 +895,8 @@ static AqlState::Set *aql_set(ssd_env *env, const AqlState::Key &key, int chains
             const int r = i % key.ring;
             for (int kind = 0; kind < kKinds; ++kind) {
                 const int o = kind / AqlState::kKindsPerO, base = kind % AqlState::kKindsPerO;
-                const bool split_kind = base >= AqlState::kRn, pair_kind = base >= AqlState::kP;
-                if (split_kind && !key.split) continue;
-                if (pair_kind && !key.pairs) continue;
-                if (!key.split && o == 1) continue;              // (without the pair there is one orientation)
+                const bool pair_kind = base >= AqlState::kRun;
+                if (st.dense[kind] < 0) continue;                // (no call of this key uses the kind; without the pair there is one orientation)
                 Params p = cur.p;
                 ssd::PairParams q{};
                 if (key.split) { p.world = A.world_buf[o]; p.agents = A.agents_buf[o]; }     // the launch reads buffer o
@@ -882,37 +912,44 @@ static AqlState::Set *aql_set(ssd_env *env, const AqlState::Key &key, int chains
                     cursor_actions(cur, p, (size_t)i);
                     p.rew = cur.rew ? cur.rew + (size_t)r * cur.en : nullptr; p.done = cur.done ? cur.done + (size_t)r * cur.en : nullptr;
                     if (pair_kind) {
-                        // Block i serves steps i and i + 1 (output slots r and r1, action slots likewise).  The env waves read buffer o,
-                        // leave their first step in mid set o and their second in buffer 1 - o with its marks in list o, as a single
-                        // step's.  The renderer workgroups deliver the launch before (orientation 1 - o): a pair's first step from mid
-                        // set 1 - o, its second -- or a single step -- from buffer o and list 1 - o; into the slots before r (kBB: the
-                        // pair is this block's own: slots r and r1).
-                        const int r1 = (r + 1) % key.ring, rm1 = (r + key.ring - 1) % key.ring, rm2 = (r + 2 * key.ring - 2) % key.ring;
+                        // Block i serves steps i .. i + n - 1 (output slots r .. r + n - 1, action slots likewise).  The env waves read
+                        // buffer o, leave pass k of their first n - 1 in mid set [k][o] and their last in buffer 1 - o with its marks in
+                        // list o, as a single step's.  The renderer workgroups deliver the `rd` steps of the launch before (orientation
+                        // 1 - o): its last step -- or a single step -- from buffer o and list 1 - o, the steps before it from mid sets
+                        // [.][1 - o]; into the rd slots before r (renderer workgroups only: the run is this block's own, slots r ..
+                        // r + rd - 1).
+                        constexpr int kMax = ssd::kMaxRun;
+                        const int n = (base - AqlState::kRun) / (kMax + 1), rd = (base - AqlState::kRun) % (kMax + 1);
+                        auto ring_slot = [&](int d) { return ((r + d) % key.ring + key.ring) % key.ring; };
                         auto slot_obs = [&](int sl) { return cur.obs ? cur.obs + (size_t)sl * cur.ob : nullptr; };
-                        const bool env_two = base == AqlState::kP || base == AqlState::kPB || base == AqlState::kPBB;
-                        const bool render_two = base == AqlState::kPBB || base == AqlState::kABB || base == AqlState::kBB;
                         p.mode = ssd::kModeStepPair;
                         p.obs = nullptr;
-                        p.snap_mode = (base == AqlState::kBB ? 4 : 1) | (base != AqlState::kP ? 2 : 0) | (render_two ? 8 : 0) | (env_two ? 0 : 16);
+                        p.snap_mode = (n == 0 ? 4 : 1) | (rd > 0 ? 2 : 0);
                         p.world_out = A.world_buf[1 - o]; p.agents_out = A.agents_buf[1 - o];
                         p.beam_list = A.beam_list[o]; p.snap = A.snap_grid[o];
                         p.beam_list_in = A.beam_list[1 - o]; p.snap_in = A.snap_grid[1 - o];
-                        // (the env waves' records, one per pass of the launch: a first step of two into mid set o, the launch's last
-                        // step as a single step's -- each with the ring slots of its own step)
-                        const ssd::PassRec last_rec{p.world_out, p.agents_out, p.beam_list, p.snap,
-                                                    cur.rew ? cur.rew + (size_t)(env_two ? r1 : r) * cur.en : nullptr,
-                                                    cur.done ? cur.done + (size_t)(env_two ? r1 : r) * cur.en : nullptr};
-                        if (env_two) {
-                            q.pass[0] = ssd::PassRec{A.mid_world[o], A.mid_agents[o], A.mid_list[o], A.mid_snap[o], p.rew, p.done};
-                            q.pass[1] = last_rec;
-                            q.actions2 = cur.actions ? cur.actions + ((size_t)(i + 1) % (size_t)cur.action_ring) * cur.en : nullptr;
-                        } else {
-                            q.pass[0] = last_rec;
+                        // (the env waves' records, one per pass of the launch: every pass but the last into its mid set of orientation
+                        // o, the launch's last step as a single step's -- each with the ring and action slots of its own step)
+                        q.n_pass = n; q.n_render = rd;
+                        for (int k = 0; k < n; ++k) {
+                            const int rk = ring_slot(k);
+                            ssd::PassRec &rec = q.pass[k];
+                            if (k + 1 < n) rec = ssd::PassRec{A.mid_world[k][o], A.mid_agents[k][o], A.mid_list[k][o], A.mid_snap[k][o], nullptr, nullptr, nullptr};
+                            else rec = ssd::PassRec{p.world_out, p.agents_out, p.beam_list, p.snap, nullptr, nullptr, nullptr};
+                            rec.rew = cur.rew ? cur.rew + (size_t)rk * cur.en : nullptr;
+                            rec.done = cur.done ? cur.done + (size_t)rk * cur.en : nullptr;
+                            rec.actions = cur.actions ? cur.actions + ((size_t)(i + k) % (size_t)cur.action_ring) * cur.en : nullptr;
                         }
-                        q.world_mid_in = A.mid_world[1 - o]; q.agents_mid_in = A.mid_agents[1 - o]; q.beam_list_mid_in = A.mid_list[1 - o];
-                        q.snap_mid_in = A.mid_snap[1 - o];
-                        p.obs_b = slot_obs(base == AqlState::kBB ? r1 : rm1);
-                        q.obs_b0 = slot_obs(base == AqlState::kBB ? r : rm2);
+                        // (the renderers' inputs, laid out from the run's end: slot kMax - 1 is its last step -- p.beam_list_in, p.snap_in,
+                        // p.obs_b -- and slot t the step kMax - 1 - t before it, which is step j = t - (kMax - rd) of the run)
+                        const int first = n == 0 ? 0 : -rd;      // (ring slot of the run's first step, relative to r)
+                        for (int t = kMax - rd; t < kMax - 1; ++t) {
+                            if (t < 0) continue;
+                            const int j = t - (kMax - rd);
+                            q.mid_in[t] = ssd::MidIn{A.mid_world[j][1 - o], A.mid_agents[j][1 - o], A.mid_list[j][1 - o], A.mid_snap[j][1 - o]};
+                            q.obs_b0[t] = slot_obs(ring_slot(first + j));
+                        }
+                        p.obs_b = slot_obs(ring_slot(first + rd - 1));
                     } else if (base >= AqlState::kA) {
                         // env waves: read buffer o, write buffer 1 - o, leave their beam marks in list o.  Renderer workgroups of
                         // a kAB launch: the step before produced buffer o (a launch of orientation 1 - o: its marks are in list
@@ -937,7 +974,7 @@ static AqlState::Set *aql_set(ssd_env *env, const AqlState::Key &key, int chains
                     if (!ssd::aql::lookup(env->device, L.fn, &g.k) || g.k.kernarg_size > AqlState::kBlock || g.k.kernarg_size < sizeof(ssd::KernArgs)) return nullptr;
                     g.grid_x = L.grid_x; g.block_x = L.block_x; g.lds = L.lds;
                 }
-                std::memcpy(host.data() + (((size_t)c * key.slots + i) * kKinds + kind) * AqlState::kBlock, &L.args, L.args_bytes());
+                std::memcpy(host.data() + (((size_t)c * key.slots + i) * n_dense + st.dense[kind]) * AqlState::kBlock, &L.args, L.args_bytes());
             }
         }
     }
@@ -962,7 +999,7 @@ static int rollout_aql(ssd_env *env, int chains, const ChainJob *jobs, hipStream
     {   // one argument block per chain, kind and residue of the step index modulo lcm(output ring, action ring)
         const long long ar = key.action_ring > 0 ? key.action_ring : 1;
         const long long l = (long long)key.ring / gcd_i(key.ring, (int)ar) * ar;
-        if (l * chains > 2048) return 1;                            // (22 x 640 B per chain and block index)
+        if (l * chains > 2048) return 1;                            // (up to 36 x 896 B per chain and block index)
         key.slots = (int32_t)l;
     }
     key.stamps = env->p.stamps; key.dbg_skip = env->p.dbg_skip;
@@ -996,14 +1033,21 @@ static int rollout_aql(ssd_env *env, int chains, const ChainJob *jobs, hipStream
     const int split_cap = chains == 1 ? 3072 : 2304;
     key.split = (coherent && env_split != 0 && j0.obs != nullptr && per_launch <= split_cap) ? 1 : 0;   // (the argument set holds both forms' launches)
     const bool split = key.split && j0.n_steps >= 4;
-    // Step pairs: a split chain's launches advance their envs by TWO steps each wherever two steps remain before the call's end
-    // and before the next reset -- half the dependent launches, and the second step starts from the env as it stands in LDS and
-    // registers, without a prologue.  Every step still lands in its ring slot and is rendered by the next launch's extra workgroups,
-    // two steps per renderer wave.  Where a step-pair kernel exists (ssd_kernels.hip, pair_profile); the argument set then holds
-    // both forms' launches.  (Test-hook build: SSD_AQL_PAIRS=0 keeps single steps -- same results.)
+    // Step runs: a split chain's launches advance their envs by a RUN of steps each -- four wherever four steps remain before the
+    // call's end and before the next reset, else two where two remain, else one -- a quarter of the dependent launches, and every
+    // step behind a launch's first starts from the env as it stands in LDS and registers, without a prologue.  Every step still
+    // lands in its ring slot and is rendered by the next launch's extra workgroups, a whole run per renderer wave.  As long as the
+    // form's step-pair kernel is built for (ssd_kernels.hip, pair_profile: four, two, or no runs at all); the argument set then holds
+    // all forms' launches.  (Test-hook build: SSD_AQL_PAIRS=0 keeps single steps, SSD_AQL_RUN=1 .. 4 caps the run -- at 3 the launches
+    // take three steps, two and one, which no product call does -- same results.)
     static const int env_pairs = SSD_HOOK("SSD_AQL_PAIRS", 1);
-    key.pairs = (key.split && env_pairs != 0 && ssd::pair_profile(env->p, env->game)) ? 1 : 0;
-    const bool pairs = split && key.pairs;
+    static const int env_run = SSD_HOOK("SSD_AQL_RUN", ssd::kMaxRun);
+    {
+        int cap = (key.split && env_pairs != 0) ? ssd::pair_profile(env->p, env->game) : 1;
+        if (env_run >= 1 && env_run < cap) cap = env_run;
+        key.pairs = cap >= 2 ? cap : 0;
+    }
+    const int run_cap = split ? key.pairs : 0;
     // (a split set holds its launches for both orientations of the state pair; any other set names the buffer that is current now)
     key.world = key.split ? nullptr : env->p.world;
     AqlState::Set *st = aql_set(env, key, chains, jobs);
@@ -1075,10 +1119,9 @@ static int rollout_aql(ssd_env *env, int chains, const ChainJob *jobs, hipStream
     const int kAcq = env_acq >= 0 ? env_acq : (coherent ? 0 : 1), kRel = env_rel >= 0 ? env_rel : (coherent ? 0 : 1);
     const int32_t reset_every = j0.reset_every, step0 = j0.step0, slots = key.slots;
     const bool obs_wb = j0.obs && !key.f32 && (size_t)j0.ring * obs_bytes(env, false) > ((size_t)232 << 20);   // (chain_cursor's obs_nt)
-    constexpr int kKinds = AqlState::kKinds;
     auto put = [&](int c, size_t i, int kind, bool barrier, int acq, int rel) {
         const AqlState::Geo &g = st->geo[c][kind];
-        ssd::aql::dispatch(A.q[c], g.k, g.grid_x, g.block_x, g.lds, st->dev + (((size_t)c * slots + i) * kKinds + kind) * AqlState::kBlock,
+        ssd::aql::dispatch(A.q[c], g.k, g.grid_x, g.block_x, g.lds, st->dev + (((size_t)c * slots + i) * st->n_dense + st->dense[kind]) * AqlState::kBlock,
                            barrier, acq, rel);
     };
     // orientation: which buffer of the pair holds the current state (always 0 until the first split rollout of the handle)
@@ -1087,47 +1130,53 @@ static int rollout_aql(ssd_env *env, int chains, const ChainJob *jobs, hipStream
     int pending = 0;                                      // steps of the launch before whose observations are still to be rendered (split rollouts)
     size_t i_prev = 0;
     int launches = 0;                                     // step launches so far, per chain
-    bool any_pair = false;
+    int longest = 0;                                      // the longest run one launch took
+    // (the renderer workgroups that deliver a run of `rendered` steps, alone: a single step's are kB)
+    auto render_only = [&](int rendered) { return rendered == 1 ? (int)AqlState::kB : AqlState::run_kind(0, rendered); };
     for (int k = 0; k < j0.n_steps;) {
         const size_t i = (size_t)((step0 + k) % slots);   // argument block of this step (output slot i % ring, action slot i % action_ring)
         const bool reset = reset_every > 0 && (step0 + k) % reset_every == 0;
-        // (a pair never spans a reset or the call's end: odd remainders and the step ahead of a reset are single launches)
-        const bool two = pairs && k + 1 < j0.n_steps && !(reset_every > 0 && (step0 + k + 1) % reset_every == 0);
-        const int n = two ? 2 : 1;
+        // (a run never spans a reset or the call's end: the steps left before either go as shorter runs and single launches)
+        int avail = j0.n_steps - k;
+        if (reset_every > 0) avail = std::min(avail, reset_every - (step0 + k) % reset_every);
+        const int n = (run_cap > 2 && avail >= run_cap) ? run_cap : (run_cap >= 2 && avail >= 2) ? 2 : 1;
         const bool last = k + n >= j0.n_steps;
         for (int c = 0; c < chains; ++c) {
             const int acq = k == 0 ? 1 : kAcq;                                 // (the call's first launch of the chain)
             if (reset) {
                 // (a reset works in place: the launch before it must have been rendered from that buffer first)
-                if (split && pending) put(c, i_prev, o * KO + (pending == 2 ? AqlState::kBB : AqlState::kB), true, kAcq, kRel);
+                if (split && pending) put(c, i_prev, o * KO + render_only(pending), true, kAcq, kRel);
                 put(c, i, o * KO + (split ? AqlState::kRn : AqlState::kR), true, acq, kRel);
             }
             const int rendered = reset ? 0 : pending;
-            const int base = !split ? AqlState::kS
-                             : two  ? (rendered == 2 ? AqlState::kPBB : rendered == 1 ? AqlState::kPB : AqlState::kP)
-                                    : (rendered == 2 ? AqlState::kABB : rendered == 1 ? AqlState::kAB : AqlState::kA);
+            const int base = !split ? (int)AqlState::kS
+                             : (n == 1 && rendered <= 1) ? (rendered == 1 ? (int)AqlState::kAB : (int)AqlState::kA)
+                                                         : AqlState::run_kind(n, rendered);
             // (an output ring past the memory-side cache is written with write-back stores, ssd_kernels.hip select(): one launch per
             // round of the ring releases at agent scope, so that whatever of a slot still sits dirty in an L2 is in memory before
-            // the slot's bytes are written again -- possibly through another XCD's L2; a pair releases for either of its steps)
-            const bool round = (step0 + k) % j0.ring == 0 || (two && (step0 + k + 1) % j0.ring == 0);
+            // the slot's bytes are written again -- possibly through another XCD's L2; a run releases for any of its steps)
+            bool round = false;
+            for (int j = 0; j < n; ++j) round = round || (step0 + k + j) % j0.ring == 0;
             const int rel = (obs_wb && round) ? 1 : kRel;
             put(c, i, o * KO + base, true, reset ? kAcq : acq, rel);
-            if (split && last) put(c, i, (1 - o) * KO + (two ? AqlState::kBB : AqlState::kB), true, kAcq, kRel);   // (renders the buffer this launch wrote)
+            if (split && last) put(c, i, (1 - o) * KO + render_only(n), true, kAcq, kRel);   // (renders the buffer this launch wrote)
             // (the doorbell -- an uncached write across the bus, 0.3 - 0.5 us -- after the first two launches, so that the device starts
             // at once, and then after every fourth: the device needs 5 us per step, the host under 1, it never runs dry; the join
-            // rings for the rest)
+            // rings for the rest.  Runs longer than two: after every launch -- one lasts some 14 us, and four of them unannounced
+            // would leave the device with nothing to start on after the first two)
 #if SSD_RING_EVERY > 1
-            if (!coherent || launches < 2 || (launches % SSD_RING_EVERY) == SSD_RING_EVERY - 1) ssd::aql::ring(A.q[c]);   // (large launches: every step, as ever)
+            if (!coherent || launches < 2 || run_cap > 2 || (launches % SSD_RING_EVERY) == SSD_RING_EVERY - 1) ssd::aql::ring(A.q[c]);   // (large launches: every step, as ever)
 #else
             ssd::aql::ring(A.q[c]);
 #endif
         }
         if (split) { o = 1 - o; pending = n; i_prev = i; }
-        any_pair = any_pair || two;
+        longest = std::max(longest, n);
         launches++;
         k += n;
     }
-    if (any_pair) env->last_path |= SSD_PATH_PAIRS;
+    if (longest > 1) env->last_path |= SSD_PATH_PAIRS;
+    env->last_path = (env->last_path & ~(7 << SSD_PATH_RUN_SHIFT)) | (longest << SSD_PATH_RUN_SHIFT);
     if (split) {                                          // the current state now sits in buffer o
         env->p.world = A.world_buf[o]; env->p.agents = A.agents_buf[o];
     }
@@ -1228,7 +1277,7 @@ static int rollout(ssd_env *env, const int32_t *actions, const uint8_t *order, i
             const int rc = rollout_aql(env, chains, jobs, s);
             env->last_path |= ssd::aql::pool_report(env->device);
             if (rc <= 0) return rc;
-            env->last_path &= ~(SSD_PATH_AQL | SSD_PATH_COHERENT | SSD_PATH_SPLIT | SSD_PATH_PAIRS | SSD_PATH_SYNC | SSD_PATH_FORKED);
+            env->last_path &= ~(SSD_PATH_AQL | SSD_PATH_COHERENT | SSD_PATH_SPLIT | SSD_PATH_PAIRS | SSD_PATH_SYNC | SSD_PATH_FORKED | (7 << SSD_PATH_RUN_SHIFT));
             // (this call created a queue that failed its probe: an automatic chain count is chosen again for the pool that is left)
             if (!automatic || ssd::aql::pool_size(env->device) >= pool_before) break;
             chains = by_size();

@@ -31,8 +31,8 @@ enum Mode : int32_t {
     kModeStep = 0, kModeReset = 1, kModeObserve = 2,
     kModeRollout = 3,      // n_steps random-action steps in ONE launch
     kModeStepAuto = 4,     // a step that also resets, in the same launch, the envs that reach the horizon (SSD_AUTO_RESET)
-    kModeStepPair = 5      // split rollouts: the env waves take TWO consecutive steps per launch, the env resident in LDS and registers
-                           // between them (the map-specific coherent kernels only; ssd_capi.hip, rollout_aql)
+    kModeStepPair = 5      // split rollouts: the env waves take a RUN of 1 .. kMaxRun consecutive steps per launch, the env resident in LDS
+                           // and registers between them (the map-specific coherent kernels only; ssd_capi.hip, rollout_aql)
 };
 
 // PRNG streams (sequential_social_dilemma_games_amd/prng.py)
@@ -110,28 +110,31 @@ struct Params {
     uint8_t *obs_b;                // [E][N][V][V][3]  where the renderer workgroups write
 };
 
-// What a step-pair launch (kModeStepPair, ssd_env_pair_kernel) names beside Params.  Further Params::snap_mode bits there: 8 = the
-// launch before was a pair -- the renderer workgroups render its two steps, the first from the `*_mid_in` set into `obs_b0`, then the
-// second as a single step's; 16 = the env waves take one step only (a single step behind a pair: its renderers need this kernel).
+// What a step-run launch (kModeStepPair, the step-pair kernels) names beside Params: the env waves take `n_pass` (1 .. kMaxRun)
+// consecutive steps, the renderer workgroups deliver the `n_render` (0 .. kMaxRun) steps of the launch before.
 // The env waves read ONE RECORD PER PASS (PassRec), pass[k] for the launch's k-th pass, with scalar loads a phase ahead of the pass
-// that needs it: a pass then holds one set of output pointers in registers and selects nothing at its uses.  The FIRST step of two
-// leaves grid and agents in the `mid` set, its beam marks and rare overlay snapshot in the mid list / mid snapshot; the launch's LAST
-// step -- the second of two, or the only one (bit 16: then it is pass[0]) -- writes the other state buffer, the list and the snapshot
-// as a single step's launch does, and the header behind them.  Either step's rewards and dones are those of its own ring slot.  A
-// run of more steps per launch would be more records of the first kind, nothing else.
-// Caller-supplied actions are not in the records: both steps' are loaded in the prologue, the first step's from Params::actions,
-// the second step's from `actions2`.
-// The renderer workgroups read their five inputs (`*_mid_in`, `obs_b0`) inside their own branch.
+// that needs it: a pass then holds one set of output pointers in registers and selects nothing at its uses.  Passes 0 .. n_pass - 2
+// leave grid and agents in `mid` set k, their beam marks and rare overlay snapshot in that set's list / snapshot; the launch's LAST
+// pass -- pass[n_pass - 1] -- writes the other state buffer, the list and the snapshot as a single step's launch does, and the header
+// behind them.  Every step's rewards and dones are those of its own ring slot.
+// Caller-supplied actions: every record names its own step's slot of the action ring.  The first two passes' are loaded in the
+// prologue (the first from Params::actions, the same pointer), pass k + 1's at the top of pass k.
+// The renderer workgroups read their inputs inside their own branch.  They are laid out FROM THE END of the run they render: slot
+// kMaxRun - 1 is the run's last step (the state this launch steps from: Params::beam_list_in / snap_in / obs_b), slot t < kMaxRun - 1
+// the step kMaxRun - 1 - t before it (`mid_in[t]`, into `obs_b0[t]`); slots below kMaxRun - n_render are not used.
+constexpr int kMaxRun = 4;
 struct PassRec {
     uint8_t *world; uint32_t *agents;      // [E][S], [E][N]: where the pass leaves the env
     uint32_t *beam_list; uint8_t *snap;    // [2][E][64], [E][S]
     int32_t *rew; uint8_t *done;           // [E][N] of the step's ring slot (null: not wanted)
+    const int32_t *actions;                // [E][N] the step's slot of the action ring (null: drawn actions)
 };
+struct MidIn { const uint8_t *world; const uint32_t *agents; const uint32_t *beam_list; const uint8_t *snap; };
 struct PairParams {
-    PassRec pass[2];
-    const int32_t *actions2;               // [E][N] the second step's slot of the action ring (null: drawn actions)
-    const uint8_t *world_mid_in; const uint32_t *agents_mid_in; const uint32_t *beam_list_mid_in; const uint8_t *snap_mid_in;
-    uint8_t *obs_b0;
+    PassRec pass[kMaxRun];
+    int32_t n_pass, n_render;
+    MidIn mid_in[kMaxRun - 1];
+    uint8_t *obs_b0[kMaxRun - 1];
 };
 
 // The kernarg segment of ssd_env_kernel: its nine leading arguments (repeated Params fields, 56 bytes: preloaded into SGPRs
@@ -166,7 +169,7 @@ void launch_agent_action_obs(const int32_t *actions, const uint8_t *done_mask, l
 size_t lds_bytes(const Params &p, int envs_per_block, bool f32);
 int envs_per_block(const Params &p, bool f32);
 int fast_profile(const Params &p, int game);    // which map-specific step kernel a launch gets (0: the general ones)
-bool pair_profile(const Params &p, int game);   // whether a coherent step launch of this form has a two-steps-per-launch kernel
+int pair_profile(const Params &p, int game);    // the longest run of steps a coherent step launch of this form has a kernel for (1: single steps only)
 bool select(const Params &p, int game, Launch *out, const PairParams *pair = nullptr);   // resolve a launch without issuing it (kModeStepPair: with its block)
 void launch(const Launch &L, void *stream);            // hipLaunchKernel of a resolved launch
 void launch(const Params &p, int game, void *stream);

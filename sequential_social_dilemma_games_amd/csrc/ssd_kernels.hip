@@ -357,6 +357,15 @@ constexpr FastMap kFastMap[2][3] = {
     {{0, 0, 0, 0, 0, 0, 0, 0}, {16, 38, 45, 720, 336, 320, 155, 0}, {25, 38, 45, 1136, 336, 320, 252, 0}},
     {{0, 0, 0, 0, 0, 0, 0, 0}, {25, 18, 25, 640, 192, 176, 103, 119}, {48, 36, 43, 2064, 320, 304, 412, 476}}};
 
+// The longest run of steps per launch a step-pair kernel is built for (pair_profile() tells the host the same).  The env role is one
+// loop over the launch's passes whatever their number; what grows with the run is the renderer role, which holds every step of the run
+// before in registers at once.  A kernel gets runs of kMaxRun only if it then still compiles to eight waves per SIMD without scratch
+// memory and without a spilled vector register; otherwise it stays at pairs.
+// Harvest's three do, and so does Cleanup 25 x 18's with 5 agents (64 vector registers).  Cleanup 25 x 18's with 10 agents does not:
+// built for runs of four it spills two vector registers (12 bytes of scratch memory per lane).
+template <int GAME, int NA, int FAST>
+constexpr int run_max() { return (GAME == 0 || NA == 5) ? kMaxRun : 2; }
+
 // COH ("coherent"): the env's state, rewards, dones and observations move with agent-scope (sc1) accesses only: nothing of a
 // launch stays dirty in an XCD's L2 and nothing is read through a CU's L1, so consecutive launches of a chain need no cache
 // write-back / invalidate between them -- the library's own dispatch queues (ssd_aql.hip) then order them with the packet's
@@ -518,10 +527,13 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
             return;
         }
     }
-    // ---- the same role in the step-pair kernels: the launch before took one step (as above) or two (snap_mode bit 8): then both are
-    //      rendered here, in order -- the first from the `mid` set that launch's env waves left (state + list / snapshot), the second
-    //      from the buffer this launch steps from.  Both steps' loads go out before the first use, each step has an LDS layer of its own.
-    //      With a ring of one slot both passes store the same bytes from the same lanes with the same policy, in program order. ----
+    // ---- the same role in the step-pair kernels: the launch before took a run of n_render steps (1 .. kRun), and all of them are
+    //      rendered here, strictly in step order -- the run's last step from the buffer this launch steps from, as above, the steps before
+    //      it from the `mid` sets that launch's env waves left (state + list / snapshot).  The block names them from the run's END
+    //      (PairParams): slot kMaxRun - 1 is the last step, slot t the step kMaxRun - 1 - t before it.  Every step's loads go out before
+    //      the first use; the wave's LDS region holds two layers with aprons, so the steps are filled and rendered in rounds of two:
+    //      slots 0 and 1, then slots 2 and 3.  With a ring of one slot all steps store the same bytes from the same lanes with the
+    //      same policy, in program order: the last step's stay. ----
     if constexpr (pair && COH && STD && NA > 0 && NA % 5 == 0 && !F32 && FAST != 0) {
         if ((p.snap_mode & 2) && blk >= p.blocks_a) {
             const int eb = a_e_begin + (blk - p.blocks_a) * a_epb + wv;
@@ -529,13 +541,21 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
                 typedef __attribute__((address_space(3))) const uint8_t lds_u8;
                 constexpr int kGridLoads = (fm.S + 1023) / 1024;
                 constexpr bool kTwoLists = GAME == 1 && NA > 5;
-                const bool two = (p.snap_mode & 8) != 0;               // (wave-uniform: a kernel argument)
-                // (the role's own part of the pair's block, requested with the role's first kernel arguments)
-                const uint8_t *const q_world_mid_in = qptr(offsetof(PairParams, world_mid_in), (const uint8_t *)nullptr);
-                const uint32_t *const q_agents_mid_in = qptr(offsetof(PairParams, agents_mid_in), (const uint32_t *)nullptr);
-                const uint32_t *const q_beam_list_mid_in = qptr(offsetof(PairParams, beam_list_mid_in), (const uint32_t *)nullptr);
-                const uint8_t *const q_snap_mid_in = qptr(offsetof(PairParams, snap_mid_in), (const uint8_t *)nullptr);
-                uint8_t *const q_obs_b0 = qptr(offsetof(PairParams, obs_b0), (uint8_t *)nullptr);
+                constexpr int kRun = run_max<GAME, NA, FAST>();
+                static_assert(kMaxRun == 4 && (kRun == 2 || kRun == 4), "two rounds of two layers");
+                // (wave-uniform: a kernel argument, requested with the role's first kernel arguments)
+                const int n_render = (int)(uint32_t)(qargs[offsetof(PairParams, n_pass) / 8] >> 32);
+                // slot t is in use (wave-uniform)
+                auto used = [&](int t) { return t >= kMaxRun - n_render; };
+                struct MidPtr { const uint8_t *world; const uint32_t *agents; const uint32_t *list; const uint8_t *snap; uint8_t *obs; };
+                auto mid_ptr = [&](int t) {
+                    const size_t at = offsetof(PairParams, mid_in) + (size_t)t * sizeof(MidIn);
+                    MidPtr m;
+                    m.world = qptr(at + offsetof(MidIn, world), m.world); m.agents = qptr(at + offsetof(MidIn, agents), m.agents);
+                    m.list = qptr(at + offsetof(MidIn, beam_list), m.list); m.snap = qptr(at + offsetof(MidIn, snap), m.snap);
+                    m.obs = qptr(offsetof(PairParams, obs_b0) + (size_t)t * sizeof(uint8_t *), m.obs);
+                    return m;
+                };
                 struct StepIn { u32x4_t g[kGridLoads]; uint32_t areg, entry, entry2; };
                 // one step's state as its env wave left it: grid, agents (flags in agent 0's bits 20..22), first beam list
                 auto fetch = [&](const uint8_t *world, const uint32_t *agents, const uint32_t *list) {
@@ -560,25 +580,34 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
                 };
                 const uint32_t lut_a = a_lut[lane], lut_b = a_lut[lane + 64];
                 const uint4 vt0 = reinterpret_cast<const uint4 *>(p.view_tab)[2 * lane], vt1 = reinterpret_cast<const uint4 *>(p.view_tab)[2 * lane + 1];
-                // (two layers with aprons in the wave's LDS region, one per step: the second lies over the beam and occupancy layers,
-                // which a renderer wave does not use -- so both steps' loads can leave their registers before the first view is rendered)
+                // (two layers with aprons in the wave's LDS region: the second lies over the beam and occupancy layers, which a
+                // renderer wave does not use -- so a round's two steps can leave their registers before its first view is rendered)
                 static_assert(fm.S >= fm.A0 + fm.A1, "the renderer's second layer fits the beam and occupancy layers");
                 uint8_t *const s_world2 = s_world + S + A1 + A0;
+                // (the steps before the run's last: slot kFirst .. kMaxRun - 2 of the block; a kernel held to pairs has one)
+                constexpr int kFirst = kMaxRun - kRun;
+                StepIn sm[kMaxRun - 1];
+                MidPtr mp[kMaxRun - 1];
                 StepIn sb = fetch(a_world, a_agents, p.beam_list_in);
-                StepIn sa = sb;
-                if (two) sa = fetch(q_world_mid_in, q_agents_mid_in, q_beam_list_mid_in);
-                {   // the aprons of the layers: '0' (void) cells
+#pragma unroll
+                for (int t = kMaxRun - 2; t >= kFirst; --t) {
+                    sm[t] = sb; mp[t] = MidPtr{};
+                    if (used(t)) { mp[t] = mid_ptr(t); sm[t] = fetch(mp[t].world, mp[t].agents, mp[t].list); }
+                }
+                {   // the aprons of the layers: '0' (void) cells, written once for all rounds
                     const uint4 z = make_uint4(0x30303030u, 0x30303030u, 0x30303030u, 0x30303030u);
                     const int n0 = A0 >> 4, n1 = A1 >> 4;
                     for (int i = lane; i < n0 + n1; i += 64) {
                         const int at = i < n0 ? i * 16 - A0 : S + (i - n0) * 16;
                         *reinterpret_cast<uint4 *>(s_world + at) = z;
-                        if (two) *reinterpret_cast<uint4 *>(s_world2 + at) = z;
+                        if (used(kMaxRun - 2)) *reinterpret_cast<uint4 *>(s_world2 + at) = z;
                     }
                 }
                 s_lut[lane] = lut_a; s_lut[lane + 64] = lut_b;
                 fetch_rare(sb, p.beam_list_in, p.snap_in);
-                if (two) fetch_rare(sa, q_beam_list_mid_in, q_snap_mid_in);
+#pragma unroll
+                for (int t = kMaxRun - 2; t >= kFirst; --t)
+                    if (used(t)) fetch_rare(sm[t], mp[t].list, mp[t].snap);
                 // layer <- state <- agents <- beam marks (or the snapshot as it is)
                 auto fill = [&](const StepIn &s, uint8_t *layer) {
                     const uint32_t flags = rfl(s.areg) >> 20;
@@ -600,8 +629,6 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
                         }
                     }
                 };
-                fill(sb, s_world);
-                if (two) fill(sa, s_world2);
                 // the N views of a layer (lane = agent: its cell and orientation)
                 auto views = [&](const uint32_t areg, const uint8_t *layer, uint8_t *obs_to) {
                     const uint32_t cellb = areg & 0xFFFFu, orientb = (areg >> 16) & 3u;
@@ -610,7 +637,18 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
                     render_views_std<NA, true>(lane, WP, kq, s0, (uint32_t)(uintptr_t)(lds_u8 *)layer, s_lut, obs_to + (size_t)eb * N * SSD_OBS_STRIDE, p.obs_wt,
                                                vt0, vt1);
                 };
-                if (two) views(sa.areg, s_world2, q_obs_b0);
+                if constexpr (kRun > 2) {
+                    if (used(1)) {                                       // the first round: slots 0 and 1 (a run of three or four)
+                        fill(sm[1], s_world);
+                        if (used(0)) { fill(sm[0], s_world2); views(sm[0].areg, s_world2, mp[0].obs); }
+                        views(sm[1].areg, s_world, mp[1].obs);
+                        // (the round's LDS reads are issued ahead of the next round's writes to the same layers: one wave's LDS
+                        // accesses are served in order)
+                        wave_sync();
+                    }
+                }
+                fill(sb, s_world);
+                if (used(kMaxRun - 2)) { fill(sm[kMaxRun - 2], s_world2); views(sm[kMaxRun - 2].areg, s_world2, mp[kMaxRun - 2].obs); }
                 views(sb.areg, s_world, p.obs_b);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
@@ -654,17 +692,22 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
         // serves both passes.  It is centred one count higher -- lane l holds the entries of (count in the header + 1 - l) -- because
         // the first pass may have spawned a waste cell; a pass reads lane (count in the header + 1 - its own count), whatever both
         // passes cleaned and spawned so far.  Cleanup 25 x 18 x 4096, alternating fresh processes: 5.01 -> 4.74 us per step.
+        // Runs of up to kMaxRun passes: every pass before the one under way may have spawned a waste cell, so the window is centred
+        // kMaxRun - 1 counts higher -- lane l holds the entries of (count in the header + kPreUp - l), a pass reads lane (count in the
+        // header + kPreUp - its own count).
         constexpr bool kPre = GAME == 1 && (MODE == kModeStep || pair) && COH && FAST != 0;
-        constexpr int kPreUp = pair ? 1 : 0;
+        constexpr int kPreUp = pair ? kMaxRun - 1 : 0;
         uint4 hdr;
         // (a step-pair launch: where the pass under way leaves its state and outputs -- the record of the launch's first pass comes
         // with the prologue's other argument fetches, the second pass's at the top of that pass)
         [[maybe_unused]] PassRec rec{};
+        [[maybe_unused]] int n_pass = 1;                       // (a step-pair launch: the passes of its run, 1 .. kMaxRun)
         if (kCoh) {
             const uint32_t hv = cload(reinterpret_cast<const uint32_t *>(a_hdr + e) + (lane & 3));
             if constexpr (pair) {
                 rec = load_rec(0);
-                asm volatile("" ::"s"(rec.world), "s"(rec.agents), "s"(rec.beam_list), "s"(rec.snap), "s"(rec.rew), "s"(rec.done));
+                n_pass = (int)(uint32_t)qargs[offsetof(PairParams, n_pass) / 8];
+                asm volatile("" ::"s"(rec.world), "s"(rec.agents), "s"(rec.beam_list), "s"(rec.snap), "s"(rec.rew), "s"(rec.done), "s"(n_pass));
             }
             // (these kernel arguments are fetched while the header is on its way)
             if constexpr (kPre) asm volatile("" ::"s"(p.waste_cells), "s"(p.thr_ca), "s"(p.thr_cw), "s"(p.n_thr));
@@ -679,13 +722,17 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
         }
         uint32_t areg = 0;
         int act_in = -1;
-        [[maybe_unused]] int act_in2 = -1;
+        int act_next = -1;                                     // (the actions of the pass or step after the one under way, where fetched ahead)
+        // (a step-pair launch: pass k's slot of the caller's action ring, out of its record)
+        [[maybe_unused]] auto next_actions = [&](int k) {
+            return qptr(offsetof(PairParams, pass) + (size_t)k * sizeof(PassRec) + offsetof(PassRec, actions), (const uint32_t *)nullptr);
+        };
         uint32_t ord_in = 0xFFu;
         // (the env's offset in every [E][N] array -- agents, actions, rewards, dones -- computed ONCE and kept in a scalar register: left
         // to the compiler it is re-derived inside every predicated block that uses it, a 64-bit multiply each)
         uint32_t eN32 = rfl((uint32_t)e * (uint32_t)N);
         asm volatile("" : "+s"(eN32));
-        const size_t eN = eN32;
+        size_t eN = eN32;
         if (mode != kModeReset && is_agent) areg = cload(a_agents + eN + lane);
         const uint8_t *gsrc = mode == kModeReset ? p.reset_world : a_world + (size_t)e * S;
         // (a known map's grid is kGridLoads pieces of 1 KiB, 16 bytes per lane each: ALL of them go out here -- fetched one after
@@ -737,10 +784,10 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
             // invalidates a CU's L1, and the same action buffer may have held another call's actions a moment ago)
             if (p.num_actions_random <= 0) act_in = (int)cload(reinterpret_cast<const uint32_t *>(p.actions) + eN + lane);
             if (has_order) ord_in = p.order[eN + lane];
-            // (a pair's second step: its slot of the caller's action ring, fetched with the first)
+            // (a run's second pass: its slot of the caller's action ring, fetched with the first; later passes': at the top of the
+            // pass before)
             if constexpr (pair)
-                if (p.num_actions_random <= 0 && !(p.snap_mode & 16))
-                    act_in2 = (int)cload(qptr(offsetof(PairParams, actions2), (const uint32_t *)nullptr) + eN + lane);
+                if (p.num_actions_random <= 0 && n_pass > 1) act_next = (int)cload(next_actions(1) + eN + lane);
         }
 #pragma unroll
         for (int j = 0; j < kLR; ++j) {
@@ -806,9 +853,9 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
         // (`top_bit`, per lane: bit 19 of the agent's word = "the highest index on its cell" -- what shows on the cell,
         // map_env.py:289-297 -- for the renderer workgroups of the next launch: they then need not compare the agents' cells pair by
         // pair again)
-        // (a step-pair launch: the pass under way is the pair's first -- its state goes to the `mid` set, for the renderers alone)
-        [[maybe_unused]] bool mid_pass = false;
-        if constexpr (pair) mid_pass = !(p.snap_mode & 16);
+        // (a step-pair launch: the pass under way, counted; before the run's last pass the state goes to a `mid` set, for the
+        // renderers alone)
+        [[maybe_unused]] int pass_k = 0;
         auto write_state = [&](const uint32_t render_flags, const uint32_t top_bit = 0u) {
             uint8_t *gw = a_world + (size_t)e * S;
             if constexpr (kCoh) {
@@ -843,7 +890,7 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
                     store16_sc1(out_r, (uint32_t)i, v);                 // one 16-byte write-through store
                 }
                 if (is_agent) cstore(ga + eN + lane, cell | (orient << 16) | top_bit | (lane == 0 ? render_flags : 0u));
-                if (!pair || !mid_pass)                                  // (a pair writes the header once, after its second step)
+                if (!pair || pass_k + 1 >= n_pass)                       // (a run writes the header once, after its last step)
                 {   // the header's four words, one per lane: three v_writelane into a register that holds the fourth everywhere (as a
                     // chain of selects on the lane index the compiler made ~20 instructions of nested exec-mask branches of it)
                     uint32_t hw = waste_last | (waste_cur << 16) | (share ? 1u << 31 : 0u);
@@ -867,7 +914,6 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
         // ---- One pass = one reset or one step of the env.  A step / reset / observe launch makes one pass.  A rollout
         //      launch (rollout.py:58-70) loops: [reset pass when one is due,] step pass, ... with the env resident in LDS
         //      and registers; every step pass writes its observations / rewards / dones to its slot of the output ring. ----
-        [[maybe_unused]] bool pass_b = false;                 // the second step of a step-pair launch is under way
         int k_step = 0;                                       // steps done so far (rollout)
         int to_reset = -1;                                    // steps until the next reset is due (rollout; < 0: never)
         uint32_t slot = 0;                                    // output ring slot of the current step (rollout)
@@ -883,7 +929,6 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
         // the rollout kernels are short of them: carried by the random-action kernel as well they cost it 8 %, 3.7 -> 4.0 us per step)
         constexpr bool roll_acts = roll && ACTS;
         uint32_t aslot = 0;
-        int act_next = -1;
         uint32_t ord_next = 0xFFu;
         auto fetch_action = [&]() {
             if (is_agent) {
@@ -899,17 +944,21 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
         const size_t en_stride = (size_t)p.E_total * N;
         size_t slot_en_run = roll ? (size_t)slot * en_stride : 0;
         for (;;) {
+            // (a run's passes: the offset is made opaque again at the top of every pass, at no instruction's cost -- or the compiler
+            // builds the per-lane addresses of the pass's loop-invariant stores ahead of the loop and carries them through it, in
+            // vector registers that Cleanup's kernels do not have: two of them went to scratch memory)
+            if constexpr (pair) { asm volatile("" : "+s"(eN32)); eN = eN32; }
             const bool is_reset = (roll || auto_mode) ? in_reset : (mode == kModeReset);
             const bool is_step = (roll || auto_mode) ? !in_reset : (mode == kModeStep);
             const size_t slot_en = roll ? slot_en_run : 0;   // element offset of the slot in rew / done (rollout: a running sum, below)
-            if (roll || (auto_mode && in_reset) || (pair && pass_b)) {
+            if (roll || (auto_mode && in_reset) || (pair && pass_k > 0)) {
                 // a fresh pass over the resident env: default priority, empty beam / occupancy layers, and on a reset
                 // the grid of reset_map() (:560-564) + custom_reset
                 __builtin_amdgcn_s_setprio(0);
                 rew = 0;
-                // (a pair's second pass: its record is requested here, ahead of the layer clears, and is in registers when their wait
-                // is over -- the first pass's pointers end with that pass)
-                if constexpr (pair) rec = load_rec(1);
+                // (a run's further passes: the pass's record is requested here, ahead of the layer clears, and is in registers when
+                // their wait is over -- the pass before's pointers end with that pass; its actions were fetched a pass ago)
+                if constexpr (pair) { rec = load_rec(pass_k); act_in = act_next; }
                 for (int i = lane * 16; i < S; i += 64 * 16) {
                     if (is_reset) *reinterpret_cast<uint4 *>(s_world + i) = *reinterpret_cast<const uint4 *>(p.reset_world + i);
                     *reinterpret_cast<uint4 *>(s_beam + i) = make_uint4(0, 0, 0, 0);
@@ -918,7 +967,14 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
                 wave_sync();
                 if constexpr (pair) asm volatile("" ::"s"(rec.world), "s"(rec.agents), "s"(rec.beam_list), "s"(rec.snap), "s"(rec.rew), "s"(rec.done));
             }
-            uint32_t cleaned = 0;                                 // 'H' cells turned into 'R' by this pass's CLEAN beams
+            // (a run with caller-supplied actions: the NEXT pass's slot of the action ring is fetched here, a pass ahead, as the rollout
+            // kernel's fetch_action() does -- its pointer only now, so that no register carries it through the prologue or for a launch
+            // that draws its actions, which loads nothing; the first two passes' are the prologue's)
+            if constexpr (pair && run_max<GAME, NA, FAST>() > 2) {
+                if (pass_k > 0 && p.num_actions_random <= 0 && pass_k + 1 < n_pass && is_agent)
+                    act_next = (int)cload(next_actions(pass_k + 1) + eN + lane);
+            }
+            uint32_t cleaned = 0;                                // 'H' cells turned into 'R' by this pass's CLEAN beams
             if (is_reset) {
                 // ---- MapEnv.reset (map_env.py:214-249) ----
                 episode += 1; t = 0;
@@ -980,11 +1036,16 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
                     const uint32_t pk = stream_key_of(kAction);
                     if (is_agent) {
                         act = (int)randint(draw(pk, (uint32_t)lane), (uint32_t)p.num_actions_random);
-                        if (!roll && p.actions_out) p.actions_out[eN + lane] = act;
+                        if (!roll && p.actions_out) {
+                            // (a run's passes in Cleanup's kernels, which have no vector register to spare: the pointer is opaque here, for
+                            // the same reason as the env's offset at the top of the pass; Harvest's kernels spill three scalars more with it)
+                            int32_t *actions_out = p.actions_out;
+                            if constexpr (pair && GAME == 1) asm volatile("" : "+s"(actions_out));
+                            actions_out[eN + lane] = act;
+                        }
                     }
                 } else {                                         // (drawn actions are valid by construction: ssd_step_random checks n)
                     act = act_in;
-                    if constexpr (pair) act = pass_b ? act_in2 : act_in;
                     const bool bad = is_agent && (act < -1 || act >= kNumActions);
                     if (ballot(bad)) { status |= kStBadAction; if (bad) act = -1; }
                 }
@@ -1603,7 +1664,7 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
                     uint64_t thr_a = 0, thr_w = 0;
                     bool thr_have = false;                                              // (wave-uniform) the prologue's window serves
                     if constexpr (kPre) {
-                        const uint32_t back = pair ? rfl(waste0 + 1u - nh) : rfl(cleaned); // the window's lane: cells cleaned this step (a pair: see kPre)
+                        const uint32_t back = pair ? rfl(waste0 + (uint32_t)kPreUp - nh) : rfl(cleaned); // the window's lane: cells cleaned this step (a pair: see kPre)
                         if (back < 64u) {
                             thr_a = (uint64_t)rl((uint32_t)thr_pa, back) | ((uint64_t)rl((uint32_t)(thr_pa >> 32), back) << 32);
                             thr_w = (uint64_t)rl((uint32_t)thr_pw, back) | ((uint64_t)rl((uint32_t)(thr_pw >> 32), back) << 32);
@@ -1670,6 +1731,11 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
                 // ---- write the env back (grid, agents, header: a rollout does that once, after its last step) and
                 //      this step's rewards and dones ----
                 waste_last = waste_count;
+                // (a run with caller-supplied actions: the next pass's actions, requested at this pass's top, are taken out of the
+                // memory pipeline HERE, ahead of the pass's stores -- where they have long arrived -- and not at the top of the next pass,
+                // where the wait for them would be a wait for this pass's write-through stores as well.  Unconditionally: the compiler
+                // places its waits by program point, not by path, and a launch that draws its actions has nothing in flight here either)
+                if constexpr (pair) asm volatile("" : "+v"(act_next));
                 if (!roll) {
                     uint32_t render_flags = 0;
                     if constexpr (stepping && COH) {
@@ -1943,9 +2009,8 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
                 if (is_step && p.horizon > 0 && t >= (uint32_t)p.horizon) { in_reset = true; continue; }
                 break;
             }
-            if constexpr (pair) {                             // the second step, from the env as it stands in LDS and registers
-                if (!mid_pass) break;
-                mid_pass = false; pass_b = true;
+            if constexpr (pair) {                             // the run's next step, from the env as it stands in LDS and registers
+                if (++pass_k >= n_pass) break;
                 continue;
             }
             if (!roll) break;
@@ -2034,10 +2099,13 @@ int fast_profile(const Params &p, int game) {
     return fast;
 }
 
-// Whether launches with these parameters have a step-pair kernel (kModeStepPair).
-bool pair_profile(const Params &p, int game) {
+// The longest run of steps one launch with these parameters has a step-pair kernel for (kModeStepPair); 1: single steps only.
+int pair_profile(const Params &p, int game) {
     const int fast = fast_profile(p, game);
-    return !p.obs_f32 && fast > 0 && (game == 0 || fast == 1);
+    if (p.obs_f32 || fast <= 0 || !(game == 0 || fast == 1)) return 1;
+    // (the instantiations of select_step(): Harvest 16 x 38 and 25 x 38 with 5 agents, 16 x 38 with 10; Cleanup 25 x 18 with 5 and 10)
+    if (game == 0) return p.N == 5 ? (fast == 1 ? run_max<0, 5, 1>() : run_max<0, 5, 2>()) : run_max<0, 10, 1>();
+    return p.N == 5 ? run_max<1, 5, 1>() : run_max<1, 10, 1>();
 }
 
 template <int GAME, bool F32>
