@@ -1,4 +1,4 @@
-// csrc/ssd_internal.hpp -- kernel parameter block shared by ssd_kernels.hip and ssd_capi.hip.
+// csrc/ssd_internal.hpp -- kernel parameter block shared by ssd_kernels.hip, ssd_capi.hip, ssd_rollout.hip and ssd_rollout_plan.hpp (plain C++ once the includer defines uint4).
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
@@ -32,7 +32,7 @@ enum Mode : int32_t {
     kModeRollout = 3,      // n_steps random-action steps in ONE launch
     kModeStepAuto = 4,     // a step that also resets, in the same launch, the envs that reach the horizon (SSD_AUTO_RESET)
     kModeStepPair = 5      // split rollouts: the env waves take a RUN of 1 .. kMaxRun consecutive steps per launch, the env resident in LDS
-                           // and registers between them (the map-specific coherent kernels only; ssd_capi.hip, rollout_aql)
+                           // and registers between them (the map-specific coherent kernels only; ssd_rollout_plan.hpp, Schedule)
 };
 
 // PRNG streams (sequential_social_dilemma_games_amd/prng.py)

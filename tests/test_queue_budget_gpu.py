@@ -63,7 +63,7 @@ def test_hip_default_queue_count_keeps_the_two_chain_split_path():
 
 @pytest.mark.parametrize("ring", [1, 3])
 def test_one_queue_pool_splits_a_single_chain_up_to_3072_envs(ring):
-    """SSD_AQL_QUEUES=1: one chain.  3072 envs in that chain take split rendering (the single-chain cap, csrc/ssd_capi.hip), 12
+    """SSD_AQL_QUEUES=1: one chain.  3072 envs in that chain take split rendering (the single-chain cap, csrc/ssd_rollout_plan.hpp, choose_form), 12
     steps across resets at steps 0, 5 and 10 -- the call ends in the renderer-only launch -- and the last ring slots equal the
     oracle's."""
     out = _child({"GPU_MAX_HW_QUEUES": "4", "SSD_AQL_QUEUES": "1"}, envs=3072, ring=ring, steps=12, every=5)

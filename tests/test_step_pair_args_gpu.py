@@ -1,5 +1,5 @@
 """Step pairs, the argument side: a step-pair launch's env waves take where each of their two passes leaves its state and outputs
-from one record per pass behind the kernel's declared arguments (ssd_internal.hpp, PassRec; filled by ssd_capi.hip, aql_set).
+from one record per pass behind the kernel's declared arguments (ssd_internal.hpp, PassRec; filled by ssd_rollout_plan.hpp, fill_block, for ssd_rollout.hip, aql_set).
 What such a record can get wrong and tests/test_step_pairs_gpu.py does not run: a pair whose second step's ring and action slots
 belong to ANOTHER argument block index than its first (rings of 3 and 2: six blocks, a pair that starts on the last), a second
 chain's offsets into the action ring, the two pair kernels no other test reaches (Harvest 25 x 38 with 5 agents, Harvest 16 x 38

@@ -1,4 +1,4 @@
-"""Step pairs: the split coherent chains advance their envs by two steps per launch (ssd_capi.hip, rollout_aql; the step-pair
+"""Step pairs: the split coherent chains advance their envs by two steps per launch (ssd_rollout_plan.hpp, Schedule, sent by ssd_rollout.hip, rollout_aql; the step-pair
 kernel, ssd_kernels.hip kModeStepPair).  Every case runs rollout calls against oracle/pyoracle.py -- every step's observations,
 rewards and dones as far as the ring still holds them, and the state after the call -- and asserts what ssd_rollout_path()
 reports.  Shapes are the smallest at which the form can go wrong: 9 envs at 4 per workgroup (two full workgroups and one with a

@@ -1,4 +1,4 @@
-"""Step runs: the split coherent chains advance their envs by up to FOUR steps per launch (ssd_capi.hip, rollout_aql; the step-pair
+"""Step runs: the split coherent chains advance their envs by up to FOUR steps per launch (ssd_rollout_plan.hpp, Schedule, sent by ssd_rollout.hip, rollout_aql; the step-pair
 kernels' pass loop with a pass count and their renderer role's rounds of two, ssd_kernels.hip kModeStepPair).  Every case runs
 rollout calls against oracle/pyoracle.py, bit for bit -- every step's observations, rewards and dones as far as the ring still holds
 them, and the state after the call -- and asserts what ssd_rollout_path() reports: aql, coherent, split, pairs and the longest run
