@@ -41,7 +41,7 @@ def main():
             logits, _, _ = evaluate_fragment(policy, batch, first, seq_len)
             logp = torch.log_softmax(logits, -1).gather(-1, batch["actions"].long().unsqueeze(-1)).squeeze(-1)
             rhos = torch.exp(logp - batch["logp"])
-            loss, stats = impala_loss_recurrent(policy, batch, seq_len=seq_len, obs_first=first, **hyper)
+            loss, stats = impala_loss_recurrent(policy, batch, seq_len=seq_len, obs_first=first, one_call=True, **hyper)
             optim.zero_grad()
             loss.backward()
             norms = clip_grad_by_set_norm(policy, 40.0)          # one global norm per agent's policy

@@ -1227,6 +1227,61 @@ int ssd_ws_policy_forward_seq(const float *weights, int32_t num_sets, int32_t ce
                               int32_t num_seqs, float *dist, float *value, float *logp, float *bootstrap_value,
                               float *state_out, int32_t device_id, uint32_t flags, void *stream);
 
+/* ======================================================================================================================
+ * SEQUENCE FORWARD -- ssd_policy_lstm_forward_seq, ssd_policy_moa_forward_seq: a sampled fragment of the recurrent or of the
+ * MOA policy under the CURRENT weights, without gradient, in one call: what V-trace needs of the target policy (logits, value
+ * and the bootstrap value) when the weights have moved since the rollout ran (csrc/ssd_policy_seq.hip; DESIGN.md section
+ * 23).  It replaces K + 1 chained calls of ssd_policy_lstm_forward / ssd_policy_moa_forward, each a trunk launch and a cell
+ * launch (two for the MOA policy) that read and write the carried state through memory.  Added after ABI 6 without a version
+ * bump: the calls are additive.
+ *
+ * Network, weight layout and cell rule: RECURRENT POLICY ROLLOUTS and MOA POLICY ROLLOUTS.  Of the MOA policy only the
+ * actions branch runs -- the conv, FC stack 0, the actions LSTM and its heads --, which is all that logits and value depend
+ * on: prev_actions is no argument, and rows 2 and 3 (h2, c2) of a state entry, the MOA cell and the counterfactual
+ * predictions are not touched.
+ *
+ * Rows: K = n_steps steps of E = num_envs envs and N = num_agents agents, in windows of T = seq_len steps, as RECURRENT PPO
+ * LOSS AND GRADIENTS.  Inputs: obs_first u8 [E, N, 15, 15, 3] or NULL, obs u8 [R, E, N, 15, 15, 3], state f32
+ * [ceil(K / T), E, N, 2, C] (the MOA call: [ceil(K / T), E, N, 4, C]), done u8 [K, E, N] or NULL.  Row k reads obs_first for
+ * k = 0 and obs[k - 1] otherwise, and the bootstrap row reads obs[K - 1] (R >= K); with obs_first NULL row k reads obs[k] and
+ * the bootstrap row obs[K] (R >= K + 1).  All of this is by address, as the loss calls read their rows.  Outputs, each may be
+ * NULL: logits f32 [K, E, N, A], value f32 [K, E, N], bootstrap_value f32 [E, N], state_out f32 [E, N, 2, C] (the cell's two
+ * rows in the state's order: (c, h) for the recurrent policy, (h1, c1) for the MOA policy).  A NULL output is not written.
+ *
+ * State rule: that of the loss calls.  Step k uses state[k / T] as stored when k % T == 0 (done is NOT looked at there),
+ * otherwise the state this call computed for step k - 1, zero where done[k - 1, e, n] != 0.  The bootstrap row runs one more
+ * step on the carried state with the start rule of done[K - 1], and never takes a state entry (not even when K % T == 0).
+ * state_out is the state after step K - 1; the bootstrap step changes nothing.
+ *
+ * Arithmetic: the per-step forwards', every sum in their order on the same device pieces.  logits, value, bootstrap_value and
+ * state_out equal, bit for bit, what ssd_policy_lstm_forward / ssd_policy_moa_forward give when they are chained step by step
+ * under the same rule.
+ *
+ * Scratch and launches.  features is caller scratch of feature_rows rows of 32 floats, at least one window's and the
+ * bootstrap's: (min(T, K) + 1) E N rows.  The call works in chunks of as many whole windows as the scratch holds, the
+ * bootstrap row with the last window.  A chunk is two launches: the trunk over the chunk's rows (ssd_policy_kernel up to fc2;
+ * FC stack 0 alone for the MOA policy) -- two launches where obs_first splits the rows, in the first chunk --, then one cell
+ * launch over (tile of 16 envs, agent, window): a workgroup of 4 C threads walks its window's steps with h in LDS and c in
+ * registers, and the last window's workgroup the bootstrap row after them.  The outputs do not depend on feature_rows.
+ * Everything runs on `stream`: no allocation, no synchronisation.
+ *
+ * SSD_E_INVALID before anything is launched (ssd_policy_last_error says why) for everything the per-step forwards refuse (a
+ * NULL weights, obs, state or features; misaligned weights; a cell_size other than 64, 128 or 256; num_agents outside 1 .. 64,
+ * for the MOA call 2 .. 16; num_sets other than 1 or num_agents; num_actions outside 1 .. 15; flags other than 0; a device
+ * that does not exist), for a misaligned float buffer, seq_len, n_steps or num_envs < 1, more than 2^31 - 17 rows with the
+ * bootstrap's, and a feature_rows below the minimum.
+ * ====================================================================================================================== */
+int ssd_policy_lstm_forward_seq(const float *weights, int32_t num_sets, int32_t num_actions, int32_t cell_size, int32_t seq_len,
+                                const uint8_t *obs_first, const uint8_t *obs, const float *state, const uint8_t *done,
+                                int32_t n_steps, int32_t num_envs, int32_t num_agents, float *features, int64_t feature_rows,
+                                float *logits, float *value, float *bootstrap_value, float *state_out, int32_t device_id,
+                                uint32_t flags, void *stream);
+int ssd_policy_moa_forward_seq(const float *weights, int32_t num_sets, int32_t num_actions, int32_t cell_size, int32_t seq_len,
+                               const uint8_t *obs_first, const uint8_t *obs, const float *state, const uint8_t *done,
+                               int32_t n_steps, int32_t num_envs, int32_t num_agents, float *features, int64_t feature_rows,
+                               float *logits, float *value, float *bootstrap_value, float *state_out, int32_t device_id,
+                               uint32_t flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 // csrc/ssd_policy.hpp -- the policy kernels' argument blocks, their launchers and the argument checks every policy entry point
 // shares (host-readable; the device pieces the kernels share are in ssd_policy_device.hpp).  Used by ssd_policy.hip (trunk kernel,
 // ssd_policy_forward), ssd_policy_lstm.hip, ssd_policy_moa.hip, ssd_ws_policy.hip, ssd_capi.hip (the rollouts, which interleave
-// the launches with the step kernel) and the three gradient files (check_policy_grad and the BPTT calls' window helpers).
+// the launches with the step kernel), ssd_policy_seq.hip (the sequence forwards) and the three gradient files (check_policy_grad and the BPTT calls' window helpers).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

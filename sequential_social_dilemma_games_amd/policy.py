@@ -724,9 +724,9 @@ def unpack_gradient(policy, grads, scale=None, only_set=None):
     return out
 
 
-def _state_tensors(policy, batch, K, E, N, seq_len, dev):
+def _state_tensors(policy, batch, K, E, N, seq_len, dev, need_prev=True):
     """The state ring [S, E, N, STATE_ROWS, C], done [K, E, N] (or None) and, for a ConvMOAPolicy, prev_actions [K, E, N] (else
-    None) of a recurrent fragment, checked."""
+    None) of a recurrent fragment, checked.  need_prev False: a ConvMOAPolicy's prev_actions may be missing (None then)."""
     C, R, S = policy.cell_size, policy.STATE_ROWS, -(-K // seq_len)
     state = batch.get("state")
     if state is None and seq_len >= K and batch.get("state_in") is not None:
@@ -744,7 +744,8 @@ def _state_tensors(policy, batch, K, E, N, seq_len, dev):
         _check_tensor(done, torch.uint8, (K, E, N), "done", dev)
     if isinstance(policy, ConvMOAPolicy):
         prev = batch.get("prev_actions")
-        _check_tensor(prev, torch.int32, (K, E, N), "prev_actions", dev)
+        if need_prev or prev is not None:
+            _check_tensor(prev, torch.int32, (K, E, N), "prev_actions", dev)
     return state, done, prev
 
 
@@ -1042,9 +1043,10 @@ def a3c_loss_moa(policy, batch, *, seq_len, moa_weight, vf_loss_coeff, entropy_c
 # ---- the IMPALA loss of the three policies: V-trace targets under the current weights, then the A3C loss's path
 # ---- (include/ssd.h, V-TRACE TARGETS) ----
 
-def _fragment_tensors(policy, batch, obs_first, seq_len):
+def _fragment_tensors(policy, batch, obs_first, seq_len, one_call=False):
     """What evaluate_fragment reads of the dict sample() returns, checked -> (t, (K, E, N), seq_len).  The observations must
-    reach one row further than a loss call's: the bootstrap reads obs[K - 1] (obs[K] without obs_first)."""
+    reach one row further than a loss call's: the bootstrap reads obs[K - 1] (obs[K] without obs_first).  one_call with CUDA
+    tensors: a ConvMOAPolicy's prev_actions is not read and may be missing."""
     if not isinstance(batch, dict):
         raise ValueError("batch must be the dict sample() returns")
     acts, obs = batch.get("actions"), batch.get("obs")
@@ -1078,7 +1080,8 @@ def _fragment_tensors(policy, batch, obs_first, seq_len):
     seq_len = _check_seq_len(seq_len)
     if isinstance(policy, ConvMOAPolicy) and N != policy.num_agents:
         raise ValueError("the policy is for %d agents, the batch has %d" % (policy.num_agents, N))
-    t["state"], t["done"], t["prev_actions"] = _state_tensors(policy, batch, K, E, N, seq_len, dev)
+    t["state"], t["done"], t["prev_actions"] = _state_tensors(policy, batch, K, E, N, seq_len, dev,
+                                                              need_prev=not (one_call and dev.type == "cuda"))
     return t, (K, E, N), seq_len
 
 
@@ -1127,6 +1130,39 @@ def _evaluate_device(policy, t, dims, T):
     return logits[:K], value[:K], value[K]
 
 
+def _seq_scratch_rows(policy, dims, T):
+    """The feature rows of the one-call evaluation's scratch: the whole fragment's, the bootstrap's included, when those take no
+    more memory than the policy's loss call needs for this batch anyway (ppo_scratch_shape: one window's rows and the partial
+    sums); otherwise as many whole windows as fit in that size, and never less than one window and the bootstrap row."""
+    K, E, N = dims
+    whole, least = (K + 1) * E * N, (min(T, K) + 1) * E * N
+    limit = int(policy.ppo_scratch_shape(K, E, N, T)[0]) // _capi.SSD_LSTM_X
+    if whole <= limit:
+        return whole
+    return max(least, ((limit // (E * N) - 1) // T * T + 1) * E * N)
+
+
+def _evaluate_device_seq(policy, t, dims, T):
+    """evaluate_fragment through ssd_policy_lstm_forward_seq / ssd_policy_moa_forward_seq on torch's current stream: one call,
+    a trunk launch and a cell launch per chunk of windows."""
+    K, E, N = dims
+    A, P, Cs, dev = policy.num_actions, policy.num_sets, policy.cell_size, t["actions"].device
+    weights = policy.packed()
+    logits = torch.empty((K, E, N, A), dtype=torch.float32, device=dev)
+    value = torch.empty((K, E, N), dtype=torch.float32, device=dev)
+    boot = torch.empty((E, N), dtype=torch.float32, device=dev)
+    rows = _seq_scratch_rows(policy, dims, T)
+    scratch = getattr(policy, "_eval_seq_scratch", None)          # kept between calls, as _eval_scratch is
+    if scratch is None or scratch.device != dev or scratch.numel() < rows * _capi.SSD_LSTM_X:
+        scratch = policy._eval_seq_scratch = torch.empty(rows * _capi.SSD_LSTM_X, dtype=torch.float32, device=dev)
+    ptr, index, stream = _device_handles(dev)
+    L = _capi.lib()
+    call = L.ssd_policy_moa_forward_seq if isinstance(policy, ConvMOAPolicy) else L.ssd_policy_lstm_forward_seq
+    _capi.policy_check(call(ptr(weights), P, A, Cs, T, ptr(t["obs_first"]), ptr(t["obs"]), ptr(t["state"]), ptr(t["done"]), K, E, N,
+                            ptr(scratch), rows, ptr(logits), ptr(value), ptr(boot), None, index, 0, stream))
+    return logits, value, boot
+
+
 def _evaluate_host(policy, t, dims, T):
     """evaluate_fragment in plain torch: the loss calls' forwards window by window, and one more step for the bootstrap."""
     K, E, N = dims
@@ -1143,7 +1179,7 @@ def _evaluate_host(policy, t, dims, T):
     return logits, value, boot
 
 
-def evaluate_fragment(policy, batch, obs_first=None, seq_len=None):
+def evaluate_fragment(policy, batch, obs_first=None, seq_len=None, one_call=False):
     """A sampled fragment under the policy's CURRENT weights -> (logits [K,E,N,A], value [K,E,N], bootstrap_value [E,N]),
     without gradient: what V-trace needs of the target policy (postprocessing.vtrace) when the weights have moved since
     sample() ran.  Row k reads obs_first for k = 0 and obs[k - 1] otherwise (the loss calls' shift, by address; obs_first None:
@@ -1159,18 +1195,26 @@ def evaluate_fragment(policy, batch, obs_first=None, seq_len=None):
     CUDA tensors go to the library's forward entry points on torch's current stream, no synchronisation: one or two launches
     of ssd_policy_forward for the whole fragment, K + 1 launches of ssd_policy_lstm_forward / ssd_policy_moa_forward (their
     feature scratch is kept on the policy).  With unchanged weights on a fresh sample(..., state_every=T) they give back
-    batch["value"] and batch["last_value"] to the bit.  CPU tensors run the modules' forwards under no_grad."""
+    batch["value"] and batch["last_value"] to the bit.  CPU tensors run the modules' forwards under no_grad.
+    one_call=True with CUDA tensors sends a ConvLSTMPolicy or a ConvMOAPolicy through ssd_policy_lstm_forward_seq /
+    ssd_policy_moa_forward_seq instead (include/ssd.h, SEQUENCE FORWARD): one library call, the trunk over
+    all rows and one cell launch that walks every window, the same bits as the K + 1 launches.  Of the MOA policy only the
+    actions branch runs, so "prev_actions" may be missing from the batch then.  Its feature scratch is kept on the policy too
+    and is never larger than the scratch of the loss call that follows.  For a ConvFCPolicy and for CPU tensors the keyword
+    has no effect."""
     if not isinstance(policy, (ConvFCPolicy, ConvLSTMPolicy, ConvMOAPolicy)):
         raise ValueError("evaluate_fragment is for a ConvFCPolicy, ConvLSTMPolicy or ConvMOAPolicy")
-    t, dims, T = _fragment_tensors(policy, batch, obs_first, seq_len)
+    t, dims, T = _fragment_tensors(policy, batch, obs_first, seq_len, bool(one_call))
     with torch.no_grad():
         if t["actions"].device.type == "cuda":
+            if one_call and not isinstance(policy, ConvFCPolicy):
+                return _evaluate_device_seq(policy, t, dims, T)
             return _evaluate_device(policy, t, dims, T)
         return _evaluate_host(policy, t, dims, T)
 
 
 def _impala_targets(policy, batch, obs_first, seq_len, gamma, clip_rho_threshold, clip_pg_rho_threshold, bonus_key=None,
-                    bonus_weight=1.0):
+                    bonus_weight=1.0, one_call=False):
     """Steps 1 to 3 of the IMPALA calls -> the batch with "advantages" = pg_advantages and "value_targets" = vs (data)."""
     from .postprocessing import vtrace
     if not isinstance(batch, dict):
@@ -1178,7 +1222,7 @@ def _impala_targets(policy, batch, obs_first, seq_len, gamma, clip_rho_threshold
     for key in ("logp", "rew") + ((bonus_key,) if bonus_key else ()):
         if not isinstance(batch.get(key), torch.Tensor):
             raise ValueError("%s is required" % key)
-    logits, value, boot = evaluate_fragment(policy, batch, obs_first, seq_len)
+    logits, value, boot = evaluate_fragment(policy, batch, obs_first, seq_len, one_call)
     acts, logp = batch["actions"], batch["logp"]
     if logp.dtype != torch.float32 or tuple(logp.shape) != tuple(acts.shape) or logp.device != acts.device:
         raise ValueError("logp must be a torch.float32 tensor of shape %s on %s" % (tuple(acts.shape), acts.device))
@@ -1222,34 +1266,36 @@ def impala_loss(policy, batch, *, gamma=0.99, vf_loss_coeff=0.5, entropy_coeff=0
 
 
 def impala_loss_recurrent(policy, batch, *, seq_len, gamma=0.99, vf_loss_coeff=0.5, entropy_coeff=0.01, clip_rho_threshold=1.0,
-                          clip_pg_rho_threshold=1.0, obs_first=None):
+                          clip_pg_rho_threshold=1.0, obs_first=None, one_call=False):
     """impala_loss for a ConvLSTMPolicy, with truncated BPTT over windows of seq_len steps as a3c_loss_recurrent -> (loss,
     stats).  The evaluation under the current weights follows the same state rule as the loss (evaluate_fragment): K + 1
-    forward launches on the device.  The batch's keys ("state", "done") and the minibatch slices are ppo_loss_recurrent's.
+    forward launches on the device, or with one_call=True the sequence forward's one call (evaluate_fragment: the same bits).
+    The batch's keys ("state", "done") and the minibatch slices are ppo_loss_recurrent's.
 
         batch = env.sample(policy, 128, state_every=16)
         loss, stats = impala_loss_recurrent(policy, batch, seq_len=16, gamma=0.99, vf_loss_coeff=0.5, entropy_coeff=0.01,
                                             clip_rho_threshold=1.0, clip_pg_rho_threshold=1.0, obs_first=first)"""
     if not isinstance(policy, ConvLSTMPolicy):
         raise ValueError("impala_loss_recurrent is for a ConvLSTMPolicy (impala_loss is the ConvFCPolicy's)")
-    batch = _impala_targets(policy, batch, obs_first, seq_len, gamma, clip_rho_threshold, clip_pg_rho_threshold)
+    batch = _impala_targets(policy, batch, obs_first, seq_len, gamma, clip_rho_threshold, clip_pg_rho_threshold, one_call=one_call)
     return a3c_loss_recurrent(policy, batch, seq_len=seq_len, vf_loss_coeff=vf_loss_coeff, entropy_coeff=entropy_coeff,
                               obs_first=obs_first)
 
 
 def impala_loss_moa(policy, batch, *, seq_len, moa_weight, influence_weight=1.0, gamma=0.99, vf_loss_coeff=0.5, entropy_coeff=0.01,
-                    clip_rho_threshold=1.0, clip_pg_rho_threshold=1.0, obs_first=None):
+                    clip_rho_threshold=1.0, clip_pg_rho_threshold=1.0, obs_first=None, one_call=False):
     """The causal-influence trainer's IMPALA loss for a ConvMOAPolicy: impala_loss_recurrent's terms + moa_weight * MOALoss as
     a3c_loss_moa -> (loss, stats), stats MOA_A3C_STATS.  The V-trace reward is rew + influence_weight * batch["influence"]
     (the reference's causal_postprocess_trajectory), formed in float64 inside the scan.  The batch's keys ("state", "done",
-    "prev_actions", and "influence") and the minibatch slices are ppo_loss_moa's.
+    "prev_actions", and "influence") and the minibatch slices are ppo_loss_moa's.  one_call: as impala_loss_recurrent (the
+    evaluation then runs the actions branch alone; the loss that follows reads prev_actions as before).
 
         batch = env.sample(policy, 128, state_every=16)
         loss, stats = impala_loss_moa(policy, batch, seq_len=16, moa_weight=10.0, influence_weight=1.0, obs_first=first)"""
     if not isinstance(policy, ConvMOAPolicy):
         raise ValueError("impala_loss_moa is for a ConvMOAPolicy (impala_loss and impala_loss_recurrent are the other policies')")
     batch = _impala_targets(policy, batch, obs_first, seq_len, gamma, clip_rho_threshold, clip_pg_rho_threshold, "influence",
-                            influence_weight)
+                            influence_weight, one_call=one_call)
     return a3c_loss_moa(policy, batch, seq_len=seq_len, moa_weight=moa_weight, vf_loss_coeff=vf_loss_coeff,
                         entropy_coeff=entropy_coeff, obs_first=obs_first)
 
