@@ -26,7 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch  # noqa: E402
 
-from sequential_social_dilemma_games_amd import (WatershedLSTMPolicy, WatershedVecEngine, _capi, clip_grad_by_set_norm,  # noqa: E402
+from sequential_social_dilemma_games_amd import (WatershedEpisodeStats, WatershedLSTMPolicy, WatershedVecEngine, _capi, clip_grad_by_set_norm,  # noqa: E402
                                                  impala_loss_watershed)
 
 
@@ -68,9 +68,13 @@ def main():
     policy = WatershedLSTMPolicy(_capi.SSD_WS_SEQ_COMM, cell_size=128, seed=0).cuda()
     optim = torch.optim.Adam(policy.parameters(), lr=1e-4)
 
+    episodes = WatershedEpisodeStats(_capi.SSD_WS_SEQ_COMM, E)              # what the launchers' callbacks log, folded by the stepping kernel
+    eng.attach_stats(episodes)                                               # ... before the reset that opens the first episodes
     before = eng.reset()[0].clone()
     batch = eng.sample(policy, steps)
-    print("%d envs x %d phases, reward sum %.1f" % (E, steps, float(batch["rew"].sum())))
+    s = episodes.summary()
+    print("%d envs x %d phases: %d episodes, episode_reward_mean %.1f, custom_metrics %s"
+          % (E, steps, s["episodes"], s["episode_reward_mean"], {k: round(v, 3) for k, v in s["custom_metrics"].items() if k.endswith("_mean")}))
     for agent_id in range(policy.num_sets):                                  # one loss per agent id, as the reference's policies
         seq = own_steps(batch, before, agent_id, seq_len)
         if seq is None:

@@ -423,6 +423,69 @@ int ssd_stats_drain(ssd_stats *st, int64_t *counts, int64_t *agent_sums, double 
 const char *ssd_stats_last_error(const ssd_stats *st);  /* NULL st: error of the last failed ssd_stats_create */
 
 /* ======================================================================================================================
+ * WATERSHED EPISODE STATISTICS -- RLlib's episode_reward_mean, policy_reward_mean and episode_len_mean and the three custom
+ * metrics of the reference's Watershed launchers (social_dilemmas/envs/watershedLogging.py: violations, Equality, Utility),
+ * folded INSIDE the Watershed stepping kernel while a handle is attached to the engine (csrc/ssd_ws_stats.hip, the stats
+ * instances of csrc/ssd_watershed.hip).  Added after ABI 6 without a version bump: the calls are
+ * additive.  Nothing is recorded per step; one drain per training iteration reads the numbers back.
+ *
+ * An episode of env e runs from a reset (ssd_ws_reset, or the in-kernel reset of SSD_AUTO_RESET) to the step whose done
+ * carries SSD_WS_DONE_ALL: 43 steps (Seq) / 131 (SeqComm).  Per finished episode, every float64 operation one IEEE operation
+ * in the stated order, no contraction:
+ *   len             the number of steps
+ *   reward          the float64 sum, from 0.0, in step order, of the values the rew output gets for that env
+ *   agent_reward[8] the same sum over the steps whose reward was delivered to agent i (Seq: 0..3).  The receiver is the agent
+ *                   whose observation the step returns; at a DONE_ALL step the variant's last agent (3 / 7), not the agent an
+ *                   auto-reset then writes into `agent`
+ *   total_rews[4]   running_rew as ssd_ws_info would report it at the DONE_ALL step (before an auto-reset)
+ *   Utility         2 * sum(total_rews), the sum sequential from 0
+ *   Equality        1 - num / Utility, num = sum over i (outer), j (inner) of |total_rews[i] - total_rews[j]|, added from 0
+ *   violations      (double)S / (double)C: S the sum over the episode's steps 4, 5, ... of popcount(viol after the step),
+ *                   C six times the number of those steps.  This is np.mean of the list on_episode_step builds UNDER THE
+ *                   ASSUMPTION (RLlib is not part of this project) that RLlib calls on_episode_step once after every
+ *                   env.step, the last included, and that last_info_for(a) is the latest info the env returned for a in this
+ *                   episode: agent-0's first info comes with step 4 in both variants, and from then on its latest viol is the
+ *                   env's current one.  In SeqComm the first eight counted steps hold the initial zeros, as in the reference.
+ * A finished episode stays closed until the env is reset: further steps of that env are not counted.  A never-reset env is
+ * ignored.  An episode is counted only from a reset made while the handle is attached.  ssd_ws_reset on an attached engine
+ * first discards the open episodes of the envs it resets (truncated, if they had a step).  Observations, rewards, dones and
+ * the engine state are bit-identical with and without a handle, and the results do not depend on how the steps are split
+ * into calls.
+ * ====================================================================================================================== */
+typedef struct ssd_ws_stats ssd_ws_stats;
+
+/* variant SSD_WS_SEQ / SSD_WS_SEQ_COMM, num_envs 1..2^26 (else SSD_E_INVALID); SSD_E_DEVICE without a usable HIP device.
+ * 413 bytes of device memory per env. */
+int ssd_ws_stats_create(int32_t variant, int32_t num_envs, int32_t device_id, ssd_ws_stats **out);
+/* SSD_E_INVALID while an engine still holds the handle. */
+int ssd_ws_stats_destroy(ssd_ws_stats *st);
+/* Attach `st` to the engine (NULL detaches): from now on ssd_ws_step, ssd_ws_rollout_actions and ssd_ws_rollout_policy fold
+ * into it and ssd_ws_reset opens its episodes.  SSD_E_INVALID (ssd_ws_last_error(env) says why) when the handle's variant,
+ * env count or device differ from the engine's.  Host state only: nothing is launched.  A handle serves one engine at a time;
+ * its open episodes are not touched (discard them when the envs were stepped in between). */
+int ssd_ws_stats_attach(ssd_ws_env *env, ssd_ws_stats *st);
+/* Discard the open episode of every env with env_mask[e] != 0 (u8 [E] device, NULL = all): it counts as truncated if it had a
+ * step, and the env is not counted again before its next reset. */
+int ssd_ws_stats_discard(ssd_ws_stats *st, const uint8_t *env_mask, void *stream);
+/* Copy the per-env accumulators since the last drain out (device pointers, any may be NULL) and clear them (unless
+ * SSD_STATS_KEEP).  Metrics in the order violations, Equality, Utility.
+ *   counts          i64 [E,3]  episodes, truncated, sum of lengths
+ *   reward_sum      f64 [E]    sum of `reward`, in episode order from 0.0 (as every float64 sum here)
+ *   agent_sums      f64 [E,8]  sums of agent_reward
+ *   metric_sums     f64 [E,3]  sums of the finite values
+ *   metric_counts   i64 [E,3]  how many values each sum holds
+ *   metric_min/max  f64 [E,3]  over the same values (+inf / -inf where there is none)
+ *   last_len        i64 [E]    the last episode that finished (0: none since the last drain) ...
+ *   last_reward     f64 [E]
+ *   last_agent      f64 [E,8]
+ *   last_total_rews f64 [E,4]
+ *   last_metrics    f64 [E,3]  ... non-finite values included */
+int ssd_ws_stats_drain(ssd_ws_stats *st, int64_t *counts, double *reward_sum, double *agent_sums, double *metric_sums,
+                       int64_t *metric_counts, double *metric_min, double *metric_max, int64_t *last_len, double *last_reward,
+                       double *last_agent, double *last_total_rews, double *last_metrics, uint32_t flags, void *stream);
+const char *ssd_ws_stats_last_error(const ssd_ws_stats *st);  /* NULL st: error of the last failed ssd_ws_stats_create */
+
+/* ======================================================================================================================
  * POLICY ROLLOUTS -- the conv-FC policy network of models/conv_to_fc_net.py:1-51 (Jaques et al. 2019) run on the device and
  * interleaved with the step kernel, so that a closed-loop rollout (observe, act, step: visuallizer_rllib.py:121-153) is
  * enqueued by one call (csrc/ssd_policy.hip).  Exact float32 throughout.

@@ -4,6 +4,7 @@
     from sequential_social_dilemma_games_amd import VecEngine                  # batched tensor API
     from sequential_social_dilemma_games_amd import WatershedSeqEnv, WatershedSeqCommEnv, WatershedVecEngine
     from sequential_social_dilemma_games_amd import EpisodeStats                # per-episode returns and social metrics
+    from sequential_social_dilemma_games_amd import WatershedEpisodeStats       # the same for Watershed, with the launchers' metrics
     from sequential_social_dilemma_games_amd import ConvFCPolicy                # the conv-FC policy net, run in the loop
     from sequential_social_dilemma_games_amd import ConvLSTMPolicy              # the same trunk under the baseline's LSTM
     from sequential_social_dilemma_games_amd import ConvMOAPolicy               # the causal-influence (MOA) policy
@@ -42,6 +43,9 @@ def __getattr__(name):
     if name == "EpisodeStats":
         from .episode_stats import EpisodeStats
         return EpisodeStats
+    if name == "WatershedEpisodeStats":
+        from .watershed_stats import WatershedEpisodeStats
+        return WatershedEpisodeStats
     if name in ("ConvFCPolicy", "ConvLSTMPolicy", "ConvMOAPolicy", "WatershedLSTMPolicy", "ppo_loss", "ppo_loss_recurrent",
                 "ppo_loss_moa", "ppo_loss_watershed", "ws_ppo_terms", "a3c_loss", "a3c_loss_recurrent", "a3c_loss_moa", "clip_grad_by_set_norm", "A3C_STATS",
                 "MOA_A3C_STATS", "evaluate_fragment", "impala_loss", "impala_loss_recurrent", "impala_loss_moa",

@@ -278,7 +278,9 @@ SYMBOLS = ("ssd_create", "ssd_destroy", "ssd_reset", "ssd_step", "ssd_step_rando
            "ssd_policy_ppo_grad", "ssd_policy_lstm_ppo_grad", "ssd_policy_moa_ppo_grad",
            "ssd_policy_ac_grad", "ssd_policy_lstm_ac_grad", "ssd_policy_moa_ac_grad", "ssd_vtrace", "ssd_vtrace_last_error",
            "ssd_ws_policy_ppo_grad", "ssd_ws_policy_ac_grad", "ssd_ws_policy_forward_seq",
-           "ssd_policy_lstm_forward_seq", "ssd_policy_moa_forward_seq")
+           "ssd_policy_lstm_forward_seq", "ssd_policy_moa_forward_seq",
+           "ssd_ws_stats_create", "ssd_ws_stats_destroy", "ssd_ws_stats_attach", "ssd_ws_stats_discard", "ssd_ws_stats_drain",
+           "ssd_ws_stats_last_error")
 # added after ABI 6 without a version bump (the calls are additive): a library built before them lacks them
 LSTM_SYMBOLS = ("ssd_policy_lstm_forward", "ssd_rollout_policy_lstm")
 MOA_SYMBOLS = ("ssd_policy_moa_forward", "ssd_rollout_policy_moa")
@@ -292,6 +294,8 @@ VTRACE_SYMBOLS = ("ssd_vtrace", "ssd_vtrace_last_error")
 WS_PPO_SYMBOLS = ("ssd_ws_policy_ppo_grad",)
 WS_A3C_SYMBOLS = ("ssd_ws_policy_ac_grad", "ssd_ws_policy_forward_seq")
 FORWARD_SEQ_SYMBOLS = ("ssd_policy_lstm_forward_seq", "ssd_policy_moa_forward_seq")
+WS_STATS_SYMBOLS = ("ssd_ws_stats_create", "ssd_ws_stats_destroy", "ssd_ws_stats_attach", "ssd_ws_stats_discard", "ssd_ws_stats_drain",
+                    "ssd_ws_stats_last_error")
 
 
 class SsdConfig(C.Structure):
@@ -404,9 +408,9 @@ def lib():
         L.ssd_policy_last_error.argtypes = []
         L.ssd_policy_last_error.restype = C.c_char_p
         L.ssd_rollout_policy.argtypes = [vp, vp, i32, vp, i32, i32] + [vp] * 7 + [i32, vp, u32, vp]
-        missing = [name for name in LSTM_SYMBOLS + MOA_SYMBOLS + WS_POLICY_SYMBOLS + ADVANTAGES_SYMBOLS + PPO_SYMBOLS + LSTM_PPO_SYMBOLS + MOA_PPO_SYMBOLS + A3C_SYMBOLS + VTRACE_SYMBOLS + WS_PPO_SYMBOLS + WS_A3C_SYMBOLS + FORWARD_SEQ_SYMBOLS if not hasattr(L, name)]
+        missing = [name for name in LSTM_SYMBOLS + MOA_SYMBOLS + WS_POLICY_SYMBOLS + ADVANTAGES_SYMBOLS + PPO_SYMBOLS + LSTM_PPO_SYMBOLS + MOA_PPO_SYMBOLS + A3C_SYMBOLS + VTRACE_SYMBOLS + WS_PPO_SYMBOLS + WS_A3C_SYMBOLS + FORWARD_SEQ_SYMBOLS + WS_STATS_SYMBOLS if not hasattr(L, name)]
         if missing:
-            raise SsdError("%s lacks %s (built before the recurrent, MOA or Watershed policy calls, the advantages call, the PPO or A3C gradient calls, the V-trace call, the Watershed PPO gradient call or the sequence forwards): rebuild it with `python -c 'import "
+            raise SsdError("%s lacks %s (built before the recurrent, MOA or Watershed policy calls, the advantages call, the PPO or A3C gradient calls, the V-trace call, the Watershed PPO gradient call, the sequence forwards or the Watershed episode statistics): rebuild it with `python -c 'import "
                            "__graft_entry__ as g; g.build()'`" % (LIB_PATH, ", ".join(missing)))
         L.ssd_policy_lstm_forward.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, u32, vp]
         L.ssd_rollout_policy_lstm.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, vp, i32, i32] + [vp] * 8 + [i32, vp, u32, vp]
@@ -438,6 +442,13 @@ def lib():
         L.ssd_ws_policy_forward_seq.argtypes = [vp, i32, i32, i32, i32, i32] + [vp] * 6 + [i32, i32] + [vp] * 5 + [i32, u32, vp]
         for name in FORWARD_SEQ_SYMBOLS:
             getattr(L, name).argtypes = [vp, i32, i32, i32, i32] + [vp] * 4 + [i32, i32, i32, vp, C.c_int64] + [vp] * 4 + [i32, u32, vp]
+        L.ssd_ws_stats_create.argtypes = [i32, i32, i32, C.POINTER(vp)]
+        L.ssd_ws_stats_destroy.argtypes = [vp]
+        L.ssd_ws_stats_attach.argtypes = [vp, vp]
+        L.ssd_ws_stats_discard.argtypes = [vp, vp, vp]
+        L.ssd_ws_stats_drain.argtypes = [vp] + [vp] * 12 + [u32, vp]
+        L.ssd_ws_stats_last_error.argtypes = [vp]
+        L.ssd_ws_stats_last_error.restype = C.c_char_p
         for name in SYMBOLS:
             getattr(L, name)
         if L.ssd_abi_version() != ABI_VERSION:
@@ -456,6 +467,12 @@ def stats_check(rc, handle=None):
     if rc != SSD_OK:
         msg = lib().ssd_stats_last_error(handle)
         raise SsdError("libssd_hip episode-statistics call failed (%d): %s" % (rc, msg.decode() if msg else "?"))
+
+
+def ws_stats_check(rc, handle=None):
+    if rc != SSD_OK:
+        msg = lib().ssd_ws_stats_last_error(handle)
+        raise SsdError("libssd_hip Watershed episode-statistics call failed (%d): %s" % (rc, msg.decode() if msg else "?"))
 
 
 def policy_check(rc):

@@ -17,6 +17,7 @@
 #include "../../include/ssd.h"
 #include "ssd_ws_policy.hpp"
 #include "ssd_ws_square.hpp"
+#include "ssd_ws_stats.hpp"
 
 namespace {
 
@@ -337,6 +338,62 @@ __global__ void __launch_bounds__(kBlock) ws_rollout_kernel(WsParams p, const fl
     if (status) atomicOr(p.d.status, status);
 }
 
+// ws_rollout_kernel with an attached statistics handle (ssd_ws_stats.hpp): the lane's open episode is
+// loaded from the handle, folded in registers step by step, finalised into the handle's accumulators where a step sets
+// SSD_WS_DONE_ALL, and stored back.  A kernel of its own, not a branch of the one above: the instances above are launched exactly
+// when no handle is attached and stay, instruction for instruction, what they were before the statistics existed.
+template <int V, int LO, int LR>
+__global__ void __launch_bounds__(kBlock) ws_rollout_stats_kernel(WsParams p, ssd::WsStatsDev sd, const float *actions, int action_ring,
+                                                                  int n_steps, int step0, float *obs, int8_t *agent, double *rew,
+                                                                  uint8_t *done, int ring, int auto_reset) {
+    const int e = blockIdx.x * kBlock + threadIdx.x;
+    if (e >= p.E) return;
+    const size_t E = (size_t)p.E;
+    Lane s;
+    load(p, e, s);
+    uint32_t status = 0;
+    if (s.phase == 0) {                                          // never reset: left alone, zero outputs, no statistics
+        status |= SSD_ST_NOT_RESET;
+        StepOut z = {};
+        for (int k = 0; k < n_steps; ++k) {
+            const size_t os = (size_t)((step0 + k) % ring) * E;
+            write_out(e, z, obs ? obs + os * SSD_WS_OBS_WIDTH : nullptr, agent ? agent + os : nullptr, rew ? rew + os : nullptr,
+                      done ? done + os : nullptr);
+        }
+    } else {
+        ssd::WsOpenEpisode<V == SSD_WS_SEQ ? 4 : 8> ep;
+        ep.load(sd, e);
+        float win[kAhead];                                       // as above
+#pragma unroll
+        for (int i = 0; i < kAhead; ++i) win[i] = i < n_steps ? actions[(size_t)((step0 + i) % action_ring) * E + e] : 0.0f;
+        for (int k = 0; k < n_steps; ++k) {
+            const float a = win[0];
+#pragma unroll
+            for (int i = 0; i + 1 < kAhead; ++i) win[i] = win[i + 1];
+            win[kAhead - 1] = k + kAhead < n_steps ? actions[(size_t)((step0 + k + kAhead) % action_ring) * E + e] : 0.0f;
+            StepOut o;
+            // the phase without its auto-reset, so that viol and running_rew are still the finished episode's
+            step_lane<V, LO, LR>(p, e, s, a, false, o, status);
+            if (ep.open) ep.step(o.rew, o.agent, s.viol);
+            if (o.done & SSD_WS_DONE_ALL) {
+                if (ep.open) ep.finish(sd, e, s.run);
+                ep.clear();
+                ep.open = auto_reset != 0;                       // closed until the env's next reset
+                if (auto_reset) {                                // what step_lane does itself when it is told to
+                    reset_lane(p, e, s);
+                    o.agent = observe<V, LO>(s, 0, o.obs);
+                }
+            }
+            const size_t os = (size_t)((step0 + k) % ring) * E;
+            write_out(e, o, obs ? obs + os * SSD_WS_OBS_WIDTH : nullptr, agent ? agent + os : nullptr, rew ? rew + os : nullptr,
+                      done ? done + os : nullptr);
+        }
+        store(p, e, s);
+        ep.store(sd, e);
+    }
+    if (status) atomicOr(p.d.status, status);
+}
+
 __global__ void __launch_bounds__(kBlock) ws_info_kernel(WsParams p, uint8_t *viol, uint8_t *true_end, double *running, double *temp,
                                                          int64_t *other) {
     const int e = blockIdx.x * kBlock + threadIdx.x;
@@ -368,6 +425,7 @@ std::string g_ws_create_error;
 struct ssd_ws_env {
     WsParams p;
     int device;
+    ssd_ws_stats *stats;                                         // attached episode statistics, or null
     void *block;                                                 // the one device allocation behind p.d
     std::string err;
 };
@@ -437,6 +495,7 @@ int ssd_ws_create(const ssd_ws_config *cfg, ssd_ws_env **out) {
     if (hipSetDevice(cfg->device_id) != hipSuccess) { g_ws_create_error = "hipSetDevice failed"; return SSD_E_DEVICE; }
     ssd_ws_env *env = new ssd_ws_env();
     env->device = cfg->device_id;
+    env->stats = nullptr;
     WsParams &p = env->p;
     const size_t E = (size_t)cfg->num_envs;
     p.E = cfg->num_envs; p.variant = cfg->variant; p.local_obs = cfg->local_obs != 0; p.local_rew = cfg->local_rew != 0;
@@ -472,6 +531,7 @@ int ssd_ws_destroy(ssd_ws_env *env) {
     (void)hipSetDevice(env->device);
     (void)hipDeviceSynchronize();
     (void)hipFree(env->block);
+    if (env->stats) env->stats->attached -= 1;
     delete env;
     return SSD_OK;
 }
@@ -482,6 +542,7 @@ int ssd_ws_reset(ssd_ws_env *env, const uint8_t *env_mask, float *obs, int8_t *a
     const WsParams &p = env->p;
     const hipStream_t st = (hipStream_t)stream;
     const int g = grid(env);
+    if (env->stats) WS_HIP(env, (hipError_t)ssd::ws_stats_discard(env->stats, env_mask, true, stream));   // truncated; a new episode opens
     if (p.variant == SSD_WS_SEQ) {
         if (p.local_obs) ws_reset_kernel<SSD_WS_SEQ, 1><<<g, kBlock, 0, st>>>(p, env_mask, obs, agent);
         else ws_reset_kernel<SSD_WS_SEQ, 0><<<g, kBlock, 0, st>>>(p, env_mask, obs, agent);
@@ -502,9 +563,14 @@ int ssd_ws_rollout_actions(ssd_ws_env *env, const float *actions, int32_t action
     WS_HIP(env, hipSetDevice(env->device));
     const WsParams &p = env->p;
     const int ar = (flags & SSD_AUTO_RESET) ? 1 : 0;
+    // the instances without the statistics are launched exactly when no handle is attached
 #define WS_ROLLOUT(V, LO, LR)                                                                                               \
-    ws_rollout_kernel<V, LO, LR><<<grid(env), kBlock, 0, (hipStream_t)stream>>>(p, actions, action_ring, n_steps, step0, obs, agent, \
-                                                                                 rew, done, ring, ar)
+    if (env->stats)                                                                                                         \
+        ws_rollout_stats_kernel<V, LO, LR><<<grid(env), kBlock, 0, (hipStream_t)stream>>>(p, env->stats->d, actions, action_ring, n_steps, \
+                                                                                           step0, obs, agent, rew, done, ring, ar);  \
+    else                                                                                                                    \
+        ws_rollout_kernel<V, LO, LR><<<grid(env), kBlock, 0, (hipStream_t)stream>>>(p, actions, action_ring, n_steps, step0, obs,    \
+                                                                                     agent, rew, done, ring, ar)
     switch ((p.variant == SSD_WS_SEQ_COMM ? 4 : 0) | (p.local_obs ? 2 : 0) | (p.local_rew ? 1 : 0)) {
         case 0: WS_ROLLOUT(SSD_WS_SEQ, 0, 0); break;
         case 1: WS_ROLLOUT(SSD_WS_SEQ, 0, 1); break;
@@ -517,6 +583,18 @@ int ssd_ws_rollout_actions(ssd_ws_env *env, const float *actions, int32_t action
     }
 #undef WS_ROLLOUT
     WS_HIP(env, hipGetLastError());
+    return SSD_OK;
+}
+
+int ssd_ws_stats_attach(ssd_ws_env *env, ssd_ws_stats *stats) {
+    if (!env) return SSD_E_INVALID;
+    if (stats && (stats->variant != env->p.variant || stats->d.E != env->p.E || stats->device != env->device)) {
+        env->err = "the statistics handle's variant, env count or device differ from the engine's";
+        return SSD_E_INVALID;
+    }
+    if (env->stats) env->stats->attached -= 1;
+    env->stats = stats;
+    if (stats) stats->attached += 1;
     return SSD_OK;
 }
 

@@ -58,6 +58,7 @@ class WatershedVecEngine(object):
         eng.rollout_actions(actions [R,E], n_steps, obs [ring,E,12], agent, rew, done)   n_steps phases in one launch
         eng.info()                                          viol, true_end, running_rew, temp, other_agent_actions
         eng.sample(policy, n_steps)                         a closed-loop rollout with a WatershedLSTMPolicy (policy.py) on the device
+        eng.attach_stats(stats)                             episode statistics folded by the stepping kernel (watershed_stats.py)
     """
 
     def __init__(self, variant=SEQ, num_envs=1, seed=0, local_obs=False, local_rew=False, env_index_base=0, device=0):
@@ -76,17 +77,33 @@ class WatershedVecEngine(object):
         self._dev = torch.device("cuda", self.device)
         self._last_obs = self._last_agent = None                 # the current observation and its agent, for sample()
         self._pol_scratch = self._pol_key = self._pol_state = None   # rollout_policy's action scratch; sample()'s policy state
+        self._stats = None                                       # the attached WatershedEpisodeStats (attach_stats)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
-            self._L.ssd_ws_destroy(self._h)
+            self._L.ssd_ws_destroy(self._h)                      # lets go of an attached statistics handle
             self._h = None
+            self._stats = None
 
     def __del__(self):
         try:
             self.close()
         except Exception:
             pass
+
+    def attach_stats(self, stats):
+        """Fold every later step() / rollout_actions() / rollout_policy() / sample() into `stats` (a WatershedEpisodeStats of this
+        engine's variant, env count and device; None detaches), inside the stepping kernel.  An episode is counted from a reset()
+        (or an auto-reset) made while the handle is attached: attach before the reset that starts the first one.  Whatever the
+        handle had open is discarded here (on torch's current stream), since the envs may have moved on meanwhile; reset(mask)
+        discards the open episodes of the envs it resets.  Observations, rewards, dones and the state do not change."""
+        from .watershed_stats import WatershedEpisodeStats
+        if stats is not None and not isinstance(stats, WatershedEpisodeStats):
+            raise ValueError("stats must be a WatershedEpisodeStats or None")
+        self._check(self._L.ssd_ws_stats_attach(self._h, None if stats is None else stats._h))
+        self._stats = stats                                      # keeps the handle alive while the engine holds it
+        if stats is not None:
+            stats.discard()
 
     def _outputs(self, lead=()):
         import torch
