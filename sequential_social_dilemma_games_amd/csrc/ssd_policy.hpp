@@ -159,6 +159,8 @@ hipError_t launch_window_features(PolicyArgs f, bool moa, const GradWindow &o, i
 PpoGradArgs window_trunk_args(const PolicyArgs &f, const GradWindow &o, int trunk_floats, int groups, int set_rows, int step_rows,
                               float *part_trunk, const float *dx, int accumulate);
 
+// p is not a multiple of n bytes, n a power of two (a null pointer is aligned)
+inline bool misaligned(const void *p, unsigned n = 4) { return (reinterpret_cast<uintptr_t>(p) & (n - 1u)) != 0; }
 // state_out may be state_in itself (in place) or a buffer that does not overlap its `bytes` bytes: null = fine
 const char *check_state_out(const float *state_in, const float *state_out, size_t bytes);
 // Makes device_id the calling thread's device unless it is already: hipSuccess, or hipSetDevice's error.

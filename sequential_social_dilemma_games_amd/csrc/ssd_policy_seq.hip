@@ -33,6 +33,7 @@ constexpr int kMaxWindows = 65535;      // windows of one launch: the grid's z
 static_assert(SSD_MOA_X == kX, "both policies' cells take 32 features");
 
 using ssd::f32x4;
+using ssd::misaligned;
 
 // The two nets: the cell rule, the rows of a ring entry (the cell's two are the first), and where the cell and the heads sit
 // in a weight set.
@@ -179,8 +180,6 @@ hipError_t launch_cell(const SeqArgs &a, int C, int windows, void *stream) {
     }
     return hipGetLastError();
 }
-
-bool misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
 
 // Both entry points: the checks, then the chunks.  A chunk is as many whole windows as the scratch holds (the bootstrap row with
 // the last): its rows' features in one trunk launch (two where obs_first splits them), then its windows in one cell launch.

@@ -16,7 +16,10 @@
 //   5. dist and value on the VALU (head: fmaf chains over the C cells of h');
 //   6. rollouts: one thread per env draws the action (policy_pick for the comm agents, the Gaussian rule on policy_key's draws
 //      for the action agents) and writes the clipped action where the env's step launch reads it.
-// load_h (step 1), lstm_gates, cell_update and head are ssd_policy_device.hpp's, shared with the other policy kernels.
+// load_h (step 1), lstm_gates, cell_update and head are ssd_policy_device.hpp's, shared with the other policy kernels; the
+// constants, the Gaussian's expressions, the comm-agent rule and the argument rules are ssd_ws_policy_device.hpp's, shared with
+// the sequence forward (ssd_ws_policy_seq.hip) and the losses (ssd_ws_policy_grad.hip).  Step 2 is that header's ws_dense0 and
+// ws_dense1 written out (see there).
 // The state may be updated in place: a workgroup reads only rows it owns, and the h rows are in LDS before any is written.
 #include <hip/hip_runtime.h>
 
@@ -24,18 +27,16 @@
 #include <stdint.h>
 
 #include "../../include/ssd.h"
-#include "ssd_policy_device.hpp"
 #include "ssd_ws_policy.hpp"
+#include "ssd_ws_policy_device.hpp"
 
 namespace {
 
-constexpr int kX = SSD_WSP_X;           // dense1's width: the x columns of the tile
-constexpr int kObs = SSD_WS_OBS_WIDTH;
-constexpr int kOut = SSD_WSP_OUT;
-constexpr int kM = 16;                  // envs per workgroup
-
+using namespace ssd::wsp;               // kX, kObs, kOut, kTile, Cell, WsGauss, ws_is_comm and ws_check_net
 using ssd::f32x4;
-using Cell = ssd::KerasCell;             // gates i, f, c~, o, no forget bias; a state is (h, c)
+using ssd::misaligned;
+
+constexpr int kM = kTile;               // envs per workgroup
 
 struct WspArgs {
     const float *w;                // num_sets weight sets of set_floats floats each
@@ -120,6 +121,8 @@ __global__ void __launch_bounds__(4 * C) ssd_ws_policy_kernel(WspArgs a) {
 
         // ---- 2. dense0 and dense1: thread (m, j) ----
         const int m2 = tid >> 4, j2 = tid & 15;
+        // (ws_dense0 and ws_dense1 written out: called, they give this kernel another register allocation, and the forward
+        // measured 4 to 6 % slower -- profiles/r27_ws_shared/)
         if (tid < kM * kX) {
             float s = 0.f;
 #pragma unroll
@@ -174,13 +177,12 @@ __global__ void __launch_bounds__(4 * C) ssd_ws_policy_kernel(WspArgs a) {
         float act = 0.f, lp = 0.f, clipped = 0.f;
         if (ag >= 0) {
             const uint32_t env = a.env_base + (uint32_t)b;
-            if (a.variant == SSD_WS_SEQ_COMM && ag < 4) {        // a comm agent: Categorical over dist[0:5]
+            if (ws_is_comm(a.variant, ag)) {                     // a comm agent: Categorical over dist[0:5]
                 act = (float)ssd::policy_pick(l, kOut, a.greedy, uint4{0u, s_t[tid], s_ep[tid], 0u}, a.seed_lo, a.seed_hi, env,
                                               (uint32_t)ag, &lp);
                 clipped = act;
             } else {                                             // an action agent: DiagGaussian(dist[0], dist[1])
-                const float mean = l[0], log_std = l[1];
-                const float sd = expf(log_std);
+                const WsGauss gs(l[0], l[1]);
                 float n = 0.f;
                 if (!a.greedy) {
                     const uint32_t pk = ssd::policy_key(a.seed_lo, a.seed_hi, env, s_ep[tid], s_t[tid]);
@@ -188,9 +190,8 @@ __global__ void __launch_bounds__(4 * C) ssd_ws_policy_kernel(WspArgs a) {
                     const float u1 = (float)((d1 >> 8) + 1u) * 0x1p-24f, u2 = (float)(d2 >> 8) * 0x1p-24f;
                     n = sqrtf(-2.f * logf(u1)) * cosf(6.2831855f * u2);
                 }
-                act = a.greedy ? mean : mean + sd * n;
-                const float z = (act - mean) / sd;
-                lp = ((-0.5f * (z * z)) - log_std) - 0.9189385f;
+                act = a.greedy ? gs.mean : gs.mean + gs.sd * n;
+                lp = gs.logp(gs.z(act));
                 clipped = fminf(fmaxf(act, 0.f), 1.f);
             }
         }
@@ -213,18 +214,6 @@ hipError_t launch(const WspArgs &a, void *stream) {
     return hipGetLastError();
 }
 
-// the argument rules both calls share; null = fine.  (One acting agent per env and 5 outputs: check_policy_net's rules for the
-// weights and the cell; the sets follow the variant.)
-const char *check_net(const float *weights, int32_t num_sets, int32_t cell_size, int32_t variant) {
-    if (!weights) return "weights are required";
-    if (const char *why = ssd::check_policy_net(ssd::kNetLstm, weights, 1, 1, kOut, cell_size)) return why;
-    if (variant != SSD_WS_SEQ && variant != SSD_WS_SEQ_COMM) return "unknown variant";
-    if (num_sets != (variant == SSD_WS_SEQ ? 4 : 8)) return "num_sets must be 4 (Seq) or 8 (SeqComm): one set per agent id";
-    return nullptr;
-}
-
-bool misaligned(const void *p, unsigned n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1u)) != 0; }
-
 }  // namespace
 
 extern "C" {
@@ -233,7 +222,7 @@ int ssd_ws_policy_forward(const float *weights, int32_t num_sets, int32_t cell_s
                           const int8_t *agent, const float *state_in, const uint8_t *starts, int32_t batch, float *state_out,
                           float *dist, float *value, int32_t device_id, uint32_t flags, void *stream) {
     using ssd::policy_fail;
-    if (const char *why = check_net(weights, num_sets, cell_size, variant)) return policy_fail(why);
+    if (const char *why = ws_check_net(weights, num_sets, cell_size, variant)) return policy_fail(why);
     if (!obs || !agent || !state_in) return policy_fail("obs, agent and state_in are required");
     if (misaligned(obs, 4) || misaligned(state_in, 4) || misaligned(state_out, 4) || misaligned(dist, 4) || misaligned(value, 4))
         return policy_fail("float buffers must be 4-byte aligned");
@@ -255,7 +244,7 @@ int ssd_ws_rollout_policy(ssd_ws_env *env, const float *weights, int32_t num_set
     if (!env) return SSD_E_INVALID;
     ssd::WsPolicyView v;
     ssd::ws_policy_view(env, &v);
-    if (const char *why = check_net(weights, num_sets, cell_size, v.variant)) return ssd::ws_fail_invalid(env, why);
+    if (const char *why = ws_check_net(weights, num_sets, cell_size, v.variant)) return ssd::ws_fail_invalid(env, why);
     if (!obs_in || !agent_in || !state || !scratch || !obs || !agent || !actions)
         return ssd::ws_fail_invalid(env, "obs_in, agent_in, state, scratch, obs, agent and actions are required");
     if (n_steps < 1 || step0 < 0 || ring < 1) return ssd::ws_fail_invalid(env, "n_steps >= 1, step0 >= 0 and ring >= 1 are required");

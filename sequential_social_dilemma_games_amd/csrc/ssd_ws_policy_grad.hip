@@ -9,7 +9,8 @@
 // The kernels are this file's own (the shared BPTT kernels of ssd_bptt_device.hpp are built around 32 trunk features a row and
 // an integer action; this net has 16 and two kinds of head), put together from the inline pieces the headers define once:
 // lstm_gates, head, KerasCell, ppo_row (ssd_policy_device.hpp), cell_state, cell_backward, bptt_column_sum and the transposer
-// (ssd_bptt_device.hpp).  No header's code changes, so every other kernel keeps its instruction text.
+// (ssd_bptt_device.hpp), the dense chains, WsGauss and the argument rules (ssd_ws_policy_device.hpp, shared with the rollout
+// kernel and the sequence forward).
 //
 // The fragment is walked window by window (seq_len steps, the last one possibly shorter) by a host loop that only enqueues.
 // Per window, on the caller's scratch:
@@ -33,25 +34,19 @@
 
 #include "../../include/ssd.h"
 #include "ssd_bptt_device.hpp"
+#include "ssd_ws_policy_device.hpp"
 
 namespace {
 
-constexpr int kX = SSD_WSP_X;           // dense1's width: the x columns of the [x, h] tile
-constexpr int kObs = SSD_WS_OBS_WIDTH;
-constexpr int kOut = SSD_WSP_OUT;
-constexpr int kTile = SSD_WSPPO_TILE;   // sequences of a sequence-kernel tile, rows of a trunk-kernel tile
+using namespace ssd::wsp;               // kX, kObs, kOut, kTile, kTrunk, kHd, Cell, the dense chains, WsGauss and the argument rules
+using ssd::f32x4;
+using ssd::misaligned;
+using ssd::PpoHyper;
+
 constexpr int kChunk = SSD_WSPPO_CHUNK; // rows of a split-K chunk
 constexpr int kStatFloats = SSD_PPO_STAT_FLOATS;
-constexpr int kTrunk = SSD_WSP_LSTM_W;  // floats of a partial trunk set: the packed layout below lstm_w
-constexpr int kHd = 8;                  // pitch of a row's head outputs: dist 0..4, the value at 5, two zeros
 
-static_assert(kTile == 16 && kChunk == 64 && kX == 16 && kOut + 1 <= kHd, "the tiles of the kernels below");
-static_assert(SSD_WSP_D0_B == SSD_WSP_D0_W + kObs * kX && SSD_WSP_D1_W >= SSD_WSP_D0_B + kX && SSD_WSP_D1_B == SSD_WSP_D1_W + kX * kX &&
-              kTrunk >= SSD_WSP_D1_B + kX, "weight layout of include/ssd.h");
-
-using ssd::f32x4;
-using ssd::PpoHyper;
-using Cell = ssd::KerasCell;             // gates i, f, c~, o, no forget bias; a state is (h, c)
+static_assert(kChunk == 64, "the chunk of the split-K kernel below");
 
 // One window of the call's one weight set.  Rows of the window's arrays: step t of sequence q is row t Q + q.
 struct WsGradArgs {
@@ -84,11 +79,9 @@ struct WsGradArgs {
 // clipped value loss, the derivatives at the kinks and the statistics are ppo_row's lines; d[2..4] = 0 exactly.
 __device__ __forceinline__ void ws_gauss_row(const float *l, float *d, float act, float adv, float vt, float vfp, float lpo,
                                              const float *bl, const PpoHyper &a, double (&st)[5]) {
-    const float mean = l[0], log_std = l[1], value = l[kOut];
-    const float sd = expf(log_std);
-    const float z = (act - mean) / sd;
-    const float logp = ((-0.5f * (z * z)) - log_std) - 0.9189385f;
-    const float ent = log_std + 1.4189385f;
+    const WsGauss gs(l[0], l[1]);
+    const float mean = gs.mean, log_std = gs.log_std, sd = gs.sd, value = l[kOut];
+    const float z = gs.z(act), logp = gs.logp(z), ent = gs.entropy();
     float kl = 0.f, dkl_mean = 0.f, dkl_ls = 0.f;
     if (bl) {
         const float dm = bl[0] - mean, iv = 1.f / expf(2.f * log_std);
@@ -121,11 +114,9 @@ __device__ __forceinline__ void ws_gauss_row(const float *l, float *d, float act
 // policy, vf, entropy in 0..3 (st[4] is left alone).  No kinks; d[2..4] = 0 exactly.
 __device__ __forceinline__ void ws_gauss_ac_row(const float *l, float *d, float act, float adv, float vt, const PpoHyper &a,
                                                 double (&st)[5]) {
-    const float mean = l[0], log_std = l[1], value = l[kOut];
-    const float sd = expf(log_std);
-    const float z = (act - mean) / sd;
-    const float logp = ((-0.5f * (z * z)) - log_std) - 0.9189385f;
-    const float ent = log_std + 1.4189385f;
+    const WsGauss gs(l[0], l[1]);
+    const float sd = gs.sd, value = l[kOut];
+    const float z = gs.z(act), logp = gs.logp(z), ent = gs.entropy();
     const float pi = -(logp * adv);
     const float d1 = value - vt;
     const float vf = 0.5f * (d1 * d1);
@@ -189,20 +180,14 @@ __global__ void __launch_bounds__(4 * C) ssd_ws_seq_kernel(WsGradArgs a) {
                 if (t == 0) s_in[m * kPitch + kX + k] = live(m) ? a.ring[((size_t)(s0 + m) * 2 + Cell::kRowH) * C + k] : 0.f;
                 else if (s_start[m]) s_in[m * kPitch + kX + k] = 0.f;
             }
-            if (tid < kTile * kX) {                                  // dense0
-                float s = 0.f;
-#pragma unroll
-                for (int k = 0; k < kObs; ++k) s = fmaf(s_obs[m2 * kObs + k], s_wd[SSD_WSP_D0_W + k * kX + j2], s);
-                const float v = fmaxf(s + s_wd[SSD_WSP_D0_B + j2], 0.f);
+            if (tid < kTile * kX) {
+                const float v = ws_dense0(s_obs, s_wd, m2, j2);
                 s_d0[tid] = v;
                 if (live(m2)) a.d0[row(t, m2) * kX + j2] = v;
             }
             __syncthreads();
-            if (tid < kTile * kX) {                                  // dense1
-                float s = 0.f;
-#pragma unroll
-                for (int k = 0; k < kX; ++k) s = fmaf(s_d0[m2 * kX + k], s_wd[SSD_WSP_D1_W + k * kX + j2], s);
-                const float v = fmaxf(s + s_wd[SSD_WSP_D1_B + j2], 0.f);
+            if (tid < kTile * kX) {
+                const float v = ws_dense1(s_d0, s_wd, m2, j2);
                 s_in[m2 * kPitch + j2] = v;
                 if (live(m2)) a.x[row(t, m2) * kX + j2] = v;
             }
@@ -553,8 +538,6 @@ hipError_t launch_window(int loss, const WsGradArgs &a, hipStream_t stream) {
     return hipGetLastError();
 }
 
-bool misaligned(const void *p, unsigned n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1u)) != 0; }
-
 // Both entry points.  loss: ssd::kLossPpo or ssd::kLossAc; the A3C call passes null for logp_old, vf_preds and behaviour_dist
 // and 0 for the hyper-parameters it does not have.
 int ws_grad(int loss, const float *weights, int32_t num_sets, int32_t cell_size, int32_t variant, int32_t agent_id, int32_t seq_len,
@@ -564,14 +547,8 @@ int ws_grad(int loss, const float *weights, int32_t num_sets, int32_t cell_size,
             float *scratch, float *grads, double *stats, int32_t device_id, uint32_t flags, void *stream_) {
     using ssd::policy_fail;
     const bool ac = loss == ssd::kLossAc;
-    if (!weights) return policy_fail("weights are required");
-    if (variant != SSD_WS_SEQ && variant != SSD_WS_SEQ_COMM) return policy_fail("unknown variant");
-    if (num_sets != (variant == SSD_WS_SEQ ? 4 : 8)) return policy_fail("num_sets must be 4 (Seq) or 8 (SeqComm): one set per agent id");
-    if (agent_id < 0 || agent_id >= num_sets) return policy_fail("agent_id is no id of the variant");
-    if (cell_size != 64 && cell_size != 128 && cell_size != 256) return policy_fail("cell_size must be 64, 128 or 256");
-    if (seq_len < 1) return policy_fail("seq_len must be >= 1");
-    if (n_steps < 1 || num_seqs < 1) return policy_fail("n_steps and num_seqs must be >= 1");
-    if ((int64_t)n_steps * num_seqs > (int64_t)INT32_MAX - 16) return policy_fail("at most 2^31 - 17 rows");
+    if (const char *why = ws_check_seq_call(weights, num_sets, cell_size, variant, agent_id, seq_len, n_steps, num_seqs, 0))
+        return policy_fail(why);
     if (ac) {
         if (!obs || !state || !actions || !advantages || !value_targets)
             return policy_fail("obs, state, actions, advantages and value_targets are required");
@@ -604,7 +581,7 @@ int ws_grad(int loss, const float *weights, int32_t num_sets, int32_t cell_size,
     a.G = SSD_WSPPO_GROUPS(Q);
     a.S = SSD_WSPPO_SPLITS((int64_t)win_rows);
     a.TG = SSD_WSPPO_TRUNK_GROUPS((int64_t)win_rows);
-    a.comm = variant == SSD_WS_SEQ_COMM && agent_id < 4;
+    a.comm = ws_is_comm(variant, agent_id);
     a.h = PpoHyper{(float)clip_param, (float)vf_clip_param, (float)vf_loss_coeff, (float)entropy_coeff, (float)kl_coeff};
     float *at = scratch;
     float *wT = at; at += (size_t)(kX + C) * 4 * C;

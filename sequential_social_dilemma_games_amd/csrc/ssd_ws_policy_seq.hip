@@ -10,29 +10,22 @@
 // C <= 128 with the lane's share of lstm_w held in registers across the steps), h stays in LDS and c in registers across all
 // steps of the call; at m % T == 0 the recorded state[m / T] is loaded in their place.
 //
-// The arithmetic is the rollout kernel's, piece by piece (the dense chains, lstm_gates, Cell::update, head), so dist, value and
-// the state equal what ssd_ws_policy_forward gives when it is chained step by step under the same rule, bit for bit.
+// The arithmetic is the rollout kernel's, piece by piece (ws_dense0, ws_dense1 and WsGauss of ssd_ws_policy_device.hpp; lstm_gates,
+// Cell::update and head of ssd_policy_device.hpp), so dist, value and the state equal what ssd_ws_policy_forward gives when it
+// is chained step by step under the same rule, bit for bit.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
 #include <stdint.h>
 
 #include "../../include/ssd.h"
-#include "ssd_policy_device.hpp"
+#include "ssd_ws_policy_device.hpp"
 
 namespace {
 
-constexpr int kX = SSD_WSP_X;           // dense1's width: the x columns of the [x, h] tile
-constexpr int kObs = SSD_WS_OBS_WIDTH;
-constexpr int kOut = SSD_WSP_OUT;
-constexpr int kTile = SSD_WSPPO_TILE;   // sequences of a tile
-constexpr int kTrunk = SSD_WSP_LSTM_W;  // floats of dense0 and dense1 in the packed layout
-constexpr int kHd = 8;                  // pitch of a row's head outputs: dist 0..4, the value at 5
-
-static_assert(kTile == 16 && kX == 16 && kOut + 1 <= kHd, "the tile of the kernel below");
-
+using namespace ssd::wsp;               // kX, kObs, kOut, kTile, kTrunk, kHd, Cell, the dense chains, WsGauss and the argument rules
 using ssd::f32x4;
-using Cell = ssd::KerasCell;             // gates i, f, c~, o, no forget bias; a state is (h, c)
+using ssd::misaligned;
 
 struct WsSeqArgs {
     const float *w;                // the agent id's weight set
@@ -128,19 +121,9 @@ __global__ void __launch_bounds__(4 * C) ssd_ws_fwd_seq_kernel(WsSeqArgs a) {
                 if (s_start[mm]) s_in[mm * kPitch + kX + k] = 0.f;
                 else if (ring) s_in[mm * kPitch + kX + k] = st[((size_t)(s0 + mm) * 2 + Cell::kRowH) * C + k];
             }
-            if (tid < kTile * kX) {                                  // dense0
-                float s = 0.f;
-#pragma unroll
-                for (int k = 0; k < kObs; ++k) s = fmaf(s_obs[m2 * kObs + k], s_wd[SSD_WSP_D0_W + k * kX + j2], s);
-                s_d0[tid] = fmaxf(s + s_wd[SSD_WSP_D0_B + j2], 0.f);
-            }
+            if (tid < kTile * kX) s_d0[tid] = ws_dense0(s_obs, s_wd, m2, j2);
             __syncthreads();
-            if (tid < kTile * kX) {                                  // dense1
-                float s = 0.f;
-#pragma unroll
-                for (int k = 0; k < kX; ++k) s = fmaf(s_d0[m2 * kX + k], s_wd[SSD_WSP_D1_W + k * kX + j2], s);
-                s_in[m2 * kPitch + j2] = fmaxf(s + s_wd[SSD_WSP_D1_B + j2], 0.f);
-            }
+            if (tid < kTile * kX) s_in[m2 * kPitch + j2] = ws_dense1(s_d0, s_wd, m2, j2);
             __syncthreads();
             f32x4 acc[4][1];
             if constexpr (kHeld) gates_held<C, kK, kPitch>(s_in, wreg, tid, acc);
@@ -202,10 +185,8 @@ __global__ void __launch_bounds__(4 * C) ssd_ws_fwd_seq_kernel(WsSeqArgs a) {
                         for (int k = 0; k < kOut; ++k) s += expf(l[k] - mx);
                         lp = l[k_act] - (mx + logf(s));
                     } else {
-                        const float mean = l[0], log_std = l[1];
-                        const float sd = expf(log_std);
-                        const float z = (act - mean) / sd;
-                        lp = ((-0.5f * (z * z)) - log_std) - 0.9189385f;
+                        const WsGauss gs(l[0], l[1]);
+                        lp = gs.logp(gs.z(act));
                     }
                     a.logp[row] = lp;
                 }
@@ -215,8 +196,6 @@ __global__ void __launch_bounds__(4 * C) ssd_ws_fwd_seq_kernel(WsSeqArgs a) {
     }
 }
 
-bool misaligned(const void *p, unsigned n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1u)) != 0; }
-
 }  // namespace
 
 extern "C" int ssd_ws_policy_forward_seq(const float *weights, int32_t num_sets, int32_t cell_size, int32_t variant, int32_t agent_id,
@@ -225,14 +204,8 @@ extern "C" int ssd_ws_policy_forward_seq(const float *weights, int32_t num_sets,
                                          int32_t num_seqs, float *dist, float *value, float *logp, float *bootstrap_value,
                                          float *state_out, int32_t device_id, uint32_t flags, void *stream) {
     using ssd::policy_fail;
-    if (!weights) return policy_fail("weights are required");
-    if (variant != SSD_WS_SEQ && variant != SSD_WS_SEQ_COMM) return policy_fail("unknown variant");
-    if (num_sets != (variant == SSD_WS_SEQ ? 4 : 8)) return policy_fail("num_sets must be 4 (Seq) or 8 (SeqComm): one set per agent id");
-    if (agent_id < 0 || agent_id >= num_sets) return policy_fail("agent_id is no id of the variant");
-    if (cell_size != 64 && cell_size != 128 && cell_size != 256) return policy_fail("cell_size must be 64, 128 or 256");
-    if (seq_len < 1) return policy_fail("seq_len must be >= 1");
-    if (n_steps < 1 || num_seqs < 1) return policy_fail("n_steps and num_seqs must be >= 1");
-    if (((int64_t)n_steps + 1) * num_seqs > (int64_t)INT32_MAX - 16) return policy_fail("at most 2^31 - 17 rows, the bootstrap's included");
+    if (const char *why = ws_check_seq_call(weights, num_sets, cell_size, variant, agent_id, seq_len, n_steps, num_seqs, 1))
+        return policy_fail(why);
     if (!obs || !state) return policy_fail("obs and state are required");
     if (logp && !actions) return policy_fail("logp needs actions");
     if (bootstrap_value && !obs_next) return policy_fail("bootstrap_value needs obs_next");
@@ -245,7 +218,7 @@ extern "C" int ssd_ws_policy_forward_seq(const float *weights, int32_t num_sets,
     WsSeqArgs a{};
     a.w = weights + (size_t)agent_id * SSD_WSP_SET_FLOATS(cell_size);
     a.C = cell_size; a.Q = num_seqs; a.G = SSD_WSPPO_GROUPS(num_seqs); a.M = n_steps; a.T = seq_len;
-    a.comm = variant == SSD_WS_SEQ_COMM && agent_id < 4;
+    a.comm = ws_is_comm(variant, agent_id);
     a.obs = obs; a.state = state; a.starts = starts; a.actions = actions;
     a.obs_next = bootstrap_value ? obs_next : nullptr;               // without its output the bootstrap step is not walked
     a.start_next = start_next;

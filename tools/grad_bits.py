@@ -1,12 +1,14 @@
-"""Do two builds of the library -- or two versions of the Python layer on one library -- give the same bits in the ten loss
-calls?  For the four BPTT calls (ppo_loss_recurrent, a3c_loss_recurrent, ppo_loss_moa, a3c_loss_moa), fixed inputs from the tests' makers (tests/ppo_lstm_ref.py, tests/ppo_moa_ref.py)
+"""Do two builds of the library -- or two versions of the Python layer on one library -- give the same bits in the eleven loss
+calls and the Watershed sequence forward?  For the four BPTT calls (ppo_loss_recurrent, a3c_loss_recurrent, ppo_loss_moa, a3c_loss_moa), fixed inputs from the tests' makers (tests/ppo_lstm_ref.py, tests/ppo_moa_ref.py)
 at the smallest shapes that reach every shared device piece of csrc/ssd_bptt_device.hpp: (K, T) = (5, 3) (a ragged last window
 and the accumulate path), E = 17 (two 16-sequence tiles, the second with one live row), N = P = 5, A = 8, done per env, obs_first
 and behaviour logits given, at C = 64, 128 and 256; at C = 64 also P = 1 (stride 1), E = 33 (a second 64-row chunk) and, for the
 MOA policy, N = P = 11 (string order differs from index order, and the prediction tile is partial).  ppo_loss and a3c_loss:
 tests/ppo_ref.py's and tests/a3c_ref.py's makers at (K, E, N) = (3, 17, 5) with P = 1 and P = 5, obs_first and behaviour logits
-given.  ppo_loss_watershed: tests/ws_ppo_ref.py's makers at M = 5, T = 3, Q = 17, C = 64 for SEQ_COMM, a comm id and an action
-id, starts and dist given.  The three IMPALA calls: tests/impala_ref.py's make_batch at the shapes of tests/test_impala_loss_cpu.py
+given.  ppo_loss_watershed, a3c_loss_watershed and evaluate_sequences (dist, value, logp, bootstrap value): tests/ws_ppo_ref.py's
+makers at M = 5, T = 3, Q = 17 (one full tile and one live row) at C = 64, 128 and 256, and Q = 33 at C = 64 (a window of 99
+rows: a second, ragged 64-row chunk), for SEQ_COMM, a comm id and an action id, starts per sequence and dist given.  The three
+IMPALA calls: tests/impala_ref.py's make_batch at the shapes of tests/test_impala_loss_cpu.py
 (K = 5, E = 3, N = P = 2, T = 2).  Loss, statistics and every parameter's gradient of every call go to an .npz; run once per
 library (or per tree) in a fresh process, then compare the uint32 views.  --cpu: the same cases on CPU tensors, the plain-torch
 paths, which need no GPU.
@@ -30,7 +32,8 @@ MOA_CASES = LSTM_CASES + [(64, 17, 11, 11)]
 A = 8
 A3C = dict(vf_loss_coeff=0.5, entropy_coeff=0.01)
 FC_SHAPE = (3, 17, 5)                                               # (K, E, N) of ppo_loss and a3c_loss, with P = 1 and P = N
-WS_SHAPE = dict(M=5, Q=17, T=3)                                     # ppo_loss_watershed, C = 64
+WS_M, WS_T = 5, 3                                                   # the Watershed calls: a ragged last window, the accumulate path
+WS_CASES = [(64, 17), (128, 17), (256, 17), (64, 33)]               # (C, Q): a second tile with one live row; 99 rows, a second chunk
 WS_AGENTS = (1, 5)                                                  # a comm id and an action id of SEQ_COMM
 IMPALA_SHAPE = dict(A=8, N=2, P=2, K=5, E=3, T=2)
 
@@ -87,13 +90,22 @@ def main(path, cpu=False):
         pol, t, first = pol.to(dev), {k: v.to(dev) for k, v in t.items()}, first.to(dev)
         record(out, "fc/P%d/a3c" % P, pol, *ssd.a3c_loss(pol, t, obs_first=first, **A3C))
         print("fc/P%d" % P)
-    M, Q, Tw = WS_SHAPE["M"], WS_SHAPE["Q"], WS_SHAPE["T"]
-    for agent in WS_AGENTS:
-        pol = ws_ppo_ref.make_policy(_capi.SSD_WS_SEQ_COMM, 64, seed=20 + agent)
-        t = ws_ppo_ref.make_inputs(pol, agent, M, Q, Tw, seed=120 + agent, starts_mode="per_seq")
-        pol, t = pol.to(dev), {k: v.to(dev) for k, v in t.items()}
-        record(out, "ws/agent%d/ppo" % agent, pol, *ssd.ppo_loss_watershed(pol, agent, t, seq_len=Tw, **ppo_ref.HYPER))
-        print("ws/agent%d" % agent)
+    M, Tw = WS_M, WS_T
+    for C, Q in WS_CASES:
+        for agent in WS_AGENTS:
+            pol = ws_ppo_ref.make_policy(_capi.SSD_WS_SEQ_COMM, C, seed=20 + agent + C + Q)
+            t = ws_ppo_ref.make_inputs(pol, agent, M, Q, Tw, seed=120 + agent + C + Q, starts_mode="per_seq")
+            g = torch.Generator().manual_seed(220 + agent + C + Q)
+            t["obs_next"] = t["obs"][torch.randint(0, M, (1,), generator=g).item()].flip(0).contiguous()
+            t["start_next"] = (torch.rand((Q,), generator=g) < 0.3).to(torch.uint8)
+            pol, t = pol.to(dev), {k: v.to(dev) for k, v in t.items()}
+            tag = "ws/C%d_Q%d_agent%d" % (C, Q, agent)
+            record(out, tag + "/ppo", pol, *ssd.ppo_loss_watershed(pol, agent, t, seq_len=Tw, **ppo_ref.HYPER))
+            record(out, tag + "/a3c", pol, *ssd.a3c_loss_watershed(pol, agent, t, seq_len=Tw, **A3C))
+            names = ("dist", "value", "logp", "bootstrap_value")
+            for name, x in zip(names, ssd.evaluate_sequences(pol, agent, t, Tw)):
+                out[tag + "/eval/" + name] = x.detach().cpu().numpy()
+            print(tag)
     s = IMPALA_SHAPE
     for kind in ("fc", "lstm", "moa"):
         pol, t, first = impala_ref.make_batch(kind, s["A"], s["N"], s["P"], s["K"], s["E"], s["T"], seed=40)
