@@ -84,10 +84,12 @@ __device__ __forceinline__ void ws_gauss_row(const float *l, float *d, float act
     const float z = gs.z(act), logp = gs.logp(z), ent = gs.entropy();
     float kl = 0.f, dkl_mean = 0.f, dkl_ls = 0.f;
     if (bl) {
-        const float dm = bl[0] - mean, iv = 1.f / expf(2.f * log_std);
-        const float q = (expf(2.f * bl[1]) + dm * dm) * iv;      // (var_old + (mean_old - mean)^2) / var
+        // divisions, as the header writes them, not products with 1 / var: x * (1 / x) is not always 1 in float32, and a row
+        // whose behaviour dist is the current one must give q = 1, kl = 0 and no KL gradient exactly
+        const float dm = bl[0] - mean, var = expf(2.f * log_std);
+        const float q = (expf(2.f * bl[1]) + dm * dm) / var;     // (var_old + (mean_old - mean)^2) / var
         kl = ((log_std - bl[1]) + 0.5f * q) - 0.5f;
-        dkl_mean = -(dm * iv);
+        dkl_mean = -(dm / var);
         dkl_ls = 1.f - q;
     }
     const float ratio = expf(logp - lpo);

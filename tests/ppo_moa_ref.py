@@ -317,15 +317,27 @@ def counting_inputs(A, C, K, E, N, T, seed):
     return t, first
 
 
-def clipped_rows(policy, t, first, T):
-    """ppo_ref.clipped_rows on the MOA policy's forward: every row clipped and dead."""
+def clipped_rows(policy, t, first, T, live=False, seed=None):
+    """ppo_ref.clipped_rows on the MOA policy's forward: every row clipped (adv = +1 at ratio 1.5) and dead (vf_pred = value + 2,
+    value_targets = value + 0.2).  With a seed, both signs of the advantage: a seeded mask keeps that for half the rows and
+    gives the other half adv = -1 at ratio 0.5 (s1 = -0.5 > s2 = -0.7: the clipped operand is the minimum again), and the side
+    vf_pred lies on is random too (value - 2 s, value_targets = value - 0.2 s).  live: value_targets = value + 3, or with a
+    seed value - 3 s: clipped and live, vf1 = 9 > vf2 = 4, d vf / d value = 2 (value - vt)."""
     import numpy as np
     with torch.no_grad():
         logits, value, _ = forward(copy.deepcopy(policy).double(), shifted_obs(t["obs"], first, t["actions"].shape[0]),
                                    t["prev_actions"], t["state"], t.get("done"), T)
         logp = torch.log_softmax(logits, -1).gather(-1, t["actions"].long().unsqueeze(-1)).squeeze(-1)
-    return {"advantages": torch.ones(t["actions"].shape), "logp_old": (logp - float(np.log(1.5))).float().contiguous(),
-            "vf_pred": (value + 2.0).float().contiguous(), "value_targets": (value + 0.2).float().contiguous()}
+    rows = t["actions"].shape
+    if seed is None:
+        return {"advantages": torch.ones(rows), "logp_old": (logp - float(np.log(1.5))).float().contiguous(),
+                "vf_pred": (value + 2.0).float().contiguous(), "value_targets": (value + (3.0 if live else 0.2)).float().contiguous()}
+    g = torch.Generator().manual_seed(7000 + seed)
+    pos = torch.rand(rows, generator=g) < 0.5
+    s = torch.where(torch.rand(rows, generator=g) < 0.5, -1.0, 1.0).double()
+    shift = torch.where(pos, float(np.log(1.5)), float(np.log(0.5))).double()
+    return {"advantages": torch.where(pos, 1.0, -1.0).float().contiguous(), "logp_old": (logp - shift).float().contiguous(),
+            "vf_pred": (value - 2.0 * s).float().contiguous(), "value_targets": (value - (3.0 if live else 0.2) * s).float().contiguous()}
 
 
 def split_case(shape, C, splits, chunk):

@@ -273,3 +273,41 @@ def saturate(policy, t_builder, floor=-80.0):
         with torch.no_grad():
             policy.logits_w.mul_(2.0)
     raise AssertionError("the logits did not saturate")
+
+
+# ---- rows that are exactly on policy: the first PPO epoch of every training run ----
+
+TIGHT, LOOSE = dict(clip_param=0.0, vf_clip_param=0.0), dict(clip_param=1e6, vf_clip_param=1e6)
+
+
+def on_policy_checks(call, stat_names, what):
+    """What a PPO call must give on a fresh sample() fragment with the weights that sampled, logp_old = the rollout's logp,
+    vf_pred = its value and the behaviour logits the library's forward of the same rows, when its forward is the rollout's bit
+    for bit.  call(clip_param, vf_clip_param, kl=True, ones=False) -> (loss, {stat: tensor}, {param: grad}): the loss call
+    with the test's other hyper-parameters; kl=False: kl_coeff = 0 and no behaviour logits; ones: advantages = 1.
+     - the clip range (0, 0) -- lo = hi = 1 and a value clip of 0: a ratio or a value one ulp off is clipped -- gives the uint32
+       words of the range (1e6, 1e6) in the loss, every statistic and every gradient, and is non-zero where that one is;
+     - with advantages = 1, policy_loss is -1.0 and kl is 0.0 exactly (blp - lp is 0 term by term);
+     - the gradients with the KL term equal those without it (by value: x + 0.2 * 0 may turn a -0.0 into +0.0).
+    Prints every figure before it asserts; returns the (0, 0) call's outputs."""
+    tight, loose = call(**TIGHT), call(**LOOSE)
+    print(what, "stats (0, 0)", {k: tight[1][k].tolist() for k in stat_names})
+    diff = {"loss": int((as_numpy_u32(tight[0]) != as_numpy_u32(loose[0])).sum())}
+    diff.update({k: int((as_numpy_u32(tight[1][k]) != as_numpy_u32(loose[1][k])).sum()) for k in stat_names})
+    for name in loose[2]:
+        diff[name] = int((as_numpy_u32(tight[2][name]) != as_numpy_u32(loose[2][name])).sum())
+        print("%s %-14s max |g| %.3e words that differ between the clip ranges %d" % (what, name, float(loose[2][name].abs().max()), diff[name]))
+    ones = call(ones=True, **TIGHT)
+    print(what, "adv = 1: policy_loss", [repr(x) for x in ones[1]["policy_loss"].reshape(-1).tolist()],
+          "kl", [repr(x) for x in ones[1]["kl"].reshape(-1).tolist()])
+    bare = call(kl=False, **TIGHT)
+    moved = {name: max_err(tight[2][name], bare[2][name]) for name in bare[2]}
+    print(what, "the KL term moves", moved)
+    assert not any(diff.values()), diff
+    for name in loose[2]:
+        assert (float(tight[2][name].abs().max()) > 0.0) == (float(loose[2][name].abs().max()) > 0.0), name
+    assert all(float(x.abs().max()) > 0.0 for x in loose[2].values())
+    assert bool((ones[1]["policy_loss"] == -1.0).all()) and bool((ones[1]["kl"] == 0.0).all())
+    for name in bare[2]:
+        assert torch.equal(tight[2][name], bare[2][name]), name
+    return tight

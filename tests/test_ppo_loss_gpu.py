@@ -1,15 +1,16 @@
 """ppo_loss on the MI355X (csrc/ssd_policy_grad.hip, ssd_policy_ppo_grad): the kernel's gradients and statistics against the
 float64 restatement (ppo_ref.py) with torch's own float32 autograd on the same device as the yardstick, bit-equal repeats, a
-caller's stream, and one optimiser step end to end from sample()."""
+caller's stream, rows exactly on policy (the clip range does not show, policy_loss = -1 and kl = 0 exactly), and one optimiser
+step end to end from sample()."""
 import copy
 
 import numpy as np
 import pytest
 import torch
 
-from ppo_ref import HYPER, MARGIN, as_numpy_u32, autograd_loss, branch_report, make_inputs, make_policy, max_err
+from ppo_ref import HYPER, LOOSE, MARGIN, as_numpy_u32, autograd_loss, branch_report, make_inputs, make_policy, max_err, on_policy_checks
 from sequential_social_dilemma_games_amd import constants as K
-from sequential_social_dilemma_games_amd import ppo_loss
+from sequential_social_dilemma_games_amd import evaluate_fragment, ppo_loss
 from sequential_social_dilemma_games_amd.policy import PPO_STATS
 from sequential_social_dilemma_games_amd.vector_env import SSDVectorEnv
 
@@ -147,6 +148,43 @@ def test_packed_gradient_padding_and_scaling():
     assert torch.equal(a, b)
     for name in ga:
         assert torch.equal(ga[name], gb[name]), name
+
+
+def test_on_policy_rows_exactly():
+    """test_sample_loss_step_sample's fragment before any step: the weights that sampled, logp_old = the rollout's logp, vf_pred
+    = its value, and the behaviour logits from the library's forward of the same rows (sample() records no logits; that call
+    gives the rollout's to the bit).  The loss call's forward is exact float32 as that forward, so the kernel's ratio is 1 and
+    its value - vf_pred is 0 exactly: ppo_ref.on_policy_checks -- the clip ranges (0, 0) and (1e6, 1e6) give the same bits,
+    policy_loss = -1 and kl = 0 exactly under advantages = 1, the KL term moves no gradient -- and the (0, 0) gradient against
+    the float64 reference of the unclipped loss."""
+    E, N, steps = 64, 5, 8
+    h = dict(vf_loss_coeff=1e-2, entropy_coeff=1e-3, kl_coeff=0.2)
+    env = SSDVectorEnv(K.GAME_HARVEST, E, N, horizon=1000, seed=5)
+    pol = make_policy(env.engine.num_actions, N, seed=31).to(DEV)
+    first = env.reset().clone()
+    batch = env.sample(pol, steps, gamma=0.99, lambda_=0.95)
+    logits, value, _ = evaluate_fragment(pol, batch, obs_first=first)
+    assert torch.equal(value, batch["value"])                  # the library's forward gives back the rollout's values ...
+    lp = torch.log_softmax(logits, -1).gather(-1, batch["actions"].long().unsqueeze(-1)).squeeze(-1)
+    assert float((torch.exp(lp - batch["logp"]) - 1).abs().max()) < 1e-4      # ... and its logits the rollout's logp
+
+    def call(clip_param, vf_clip_param, kl=True, ones=False):
+        b = dict(batch, advantages=torch.ones_like(batch["value"])) if ones else dict(batch)
+        if kl:
+            b["logits"] = logits.contiguous()
+        out = _run(pol, b, first, dict(h, clip_param=clip_param, vf_clip_param=vf_clip_param, kl_coeff=h["kl_coeff"] if kl else 0.0))
+        torch.cuda.synchronize()
+        return out
+    loss, stats, g = on_policy_checks(call, PPO_STATS, "conv-FC")
+    t = {"obs": batch["obs"], "actions": batch["actions"], "logp_old": batch["logp"], "advantages": batch["advantages"],
+         "value_targets": batch["value_targets"], "vf_pred": batch["value"], "behaviour_logits": logits.contiguous()}
+    cpu_t = {k: v.cpu() for k, v in t.items()}
+    hl = dict(h, **LOOSE)
+    loss64, stats64, g64 = autograd_loss(copy.deepcopy(pol).cpu(), cpu_t, hl, first.cpu())
+    loss32, stats32, g32 = autograd_loss(pol, cpu_t, hl, first.cpu(), dtype=torch.float32, device=DEV)
+    _check_against_reference(g, g32, g64, "on-policy grad")
+    _check_against_reference(stats, stats32, stats64, "on-policy stat")
+    _check_against_reference({"loss": loss}, {"loss": loss32}, {"loss": loss64}, "on-policy loss")
 
 
 def test_sample_loss_step_sample():

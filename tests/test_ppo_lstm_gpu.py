@@ -4,7 +4,8 @@ yardstick, the persistent tile loop, the split-K kernel's
 second chunks (windows of more than 32 chunks of one set's rows: the second pass over the accumulators, a ragged last chunk that
 is a second chunk, splits that get no chunk of the second window, rows >= 2048; spotlight inputs make a single row count), exact
 row accounting, exact zeros where no gradient may flow, bit-equal repeats, set
-isolation, the kink rules, and one optimiser step end to end from sample()."""
+isolation, the kink rules, rows exactly on policy (the clip range does not show, policy_loss = -1 and kl = 0 exactly), and one
+optimiser step end to end from sample()."""
 import copy
 import ctypes as C
 
@@ -14,10 +15,10 @@ import torch
 
 from ppo_lstm_ref import (HYPER, MARGIN, as_numpy_u32, autograd_loss, branch_report, clipped_rows, counting_inputs, forward, make_inputs,
                           make_policy, max_err, set_fragment, set_policy, shifted_obs, split_case, zero_policy)
-from ppo_ref import COUNTING_HYPER
+from ppo_ref import COUNTING_HYPER, LOOSE, on_policy_checks
 from sequential_social_dilemma_games_amd import _capi
 from sequential_social_dilemma_games_amd import constants as K
-from sequential_social_dilemma_games_amd import ppo_loss_recurrent
+from sequential_social_dilemma_games_amd import evaluate_fragment, ppo_loss_recurrent
 from sequential_social_dilemma_games_amd.policy import PPO_STATS
 from sequential_social_dilemma_games_amd.vector_env import SSDVectorEnv
 
@@ -322,6 +323,44 @@ def test_packed_gradient_padding_and_scaling():
     a = _run(pol, dict(mb, state=t["state"][1:]), t["obs"][1], HYPER, T)
     b = _run(pol, dict(mb, state=t["state"][1:].clone(), obs=t["obs"][1:4].clone()), None, HYPER, T)
     _equal_bits(a, b)
+
+
+def test_on_policy_rows_exactly():
+    """test_sample_loss_step_sample's fragment before any step: the weights that sampled, logp_old = the rollout's logp, vf_pred
+    = its value, and the behaviour logits from the library's sequence forward of the same rows (sample() records no logits;
+    that call gives the rollout's to the bit).  The header builds the loss call's forward from the device pieces of the
+    rollout, so the kernel's ratio is 1 and its value - vf_pred is 0 exactly: ppo_ref.on_policy_checks -- the clip ranges
+    (0, 0) and (1e6, 1e6) give the same bits, policy_loss = -1 and kl = 0 exactly under advantages = 1, the KL term moves no
+    gradient -- and the (0, 0) gradient against the float64 reference of the unclipped loss."""
+    E, N, steps, T = 64, 5, 12, 4
+    h = dict(vf_loss_coeff=1e-2, entropy_coeff=1e-3, kl_coeff=0.2)
+    env = SSDVectorEnv(K.GAME_HARVEST, E, N, horizon=7, seed=5)
+    pol = make_policy(env.engine.num_actions, N, 64, seed=31, recur=2.0).to(DEV)
+    first = env.reset().clone()
+    batch = env.sample(pol, steps, state_every=T, gamma=0.99, lambda_=0.95)
+    logits, value, _ = evaluate_fragment(pol, batch, obs_first=first, seq_len=T, one_call=True)
+    assert torch.equal(value, batch["value"])                  # the sequence forward gives back the rollout's values ...
+    lp = torch.log_softmax(logits, -1).gather(-1, batch["actions"].long().unsqueeze(-1)).squeeze(-1)
+    assert float((torch.exp(lp - batch["logp"]) - 1).abs().max()) < 1e-4      # ... and its logits the rollout's logp
+
+    def call(clip_param, vf_clip_param, kl=True, ones=False):
+        b = dict(batch, advantages=torch.ones_like(batch["value"])) if ones else dict(batch)
+        if kl:
+            b["logits"] = logits.contiguous()
+        out = _run(pol, b, first, dict(h, clip_param=clip_param, vf_clip_param=vf_clip_param, kl_coeff=h["kl_coeff"] if kl else 0.0), T)
+        torch.cuda.synchronize()
+        return out
+    loss, stats, g = on_policy_checks(call, PPO_STATS, "recurrent")
+    t = {"obs": batch["obs"], "actions": batch["actions"], "logp_old": batch["logp"], "advantages": batch["advantages"],
+         "value_targets": batch["value_targets"], "vf_pred": batch["value"], "behaviour_logits": logits.contiguous(),
+         "state": batch["state"], "done": batch["done"]}
+    cpu_t = {k: v.cpu() for k, v in t.items()}
+    hl = dict(h, **LOOSE)
+    loss64, stats64, g64 = autograd_loss(copy.deepcopy(pol).cpu(), cpu_t, hl, first.cpu(), T)
+    loss32, stats32, g32 = autograd_loss(pol, cpu_t, hl, first.cpu(), T, dtype=torch.float32, device=DEV)
+    _check_against_reference(g, g32, g64, "on-policy grad")
+    _check_against_reference(stats, stats32, stats64, "on-policy stat")
+    _check_against_reference({"loss": loss}, {"loss": loss32}, {"loss": loss64}, "on-policy loss")
 
 
 def test_sample_loss_step_sample():

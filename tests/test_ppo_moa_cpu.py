@@ -103,6 +103,28 @@ def test_clipped_and_dead_rows_leave_the_moa_branch_alone():
         assert float(g[name].abs().max()) > 0.0 and max_err(g[name], gm[name]) < 1e-12, name
 
 
+@pytest.mark.parametrize("live", [False, True])
+def test_clipped_rows_on_both_signs_on_the_reference(live):
+    """clipped_rows with a seed, on the float64 reference and the fragment of the GPU tests: every row clipped on both signs of
+    the advantage, dead or clipped and live, 0.1 and more from every boundary; with moa_weight = entropy_coeff = kl_coeff = 0
+    the dead case's gradient is exactly zero, the live case's is exactly zero in the logits layer and the MOA branch and
+    reaches every other tensor."""
+    T = 3
+    h = dict(HYPER, entropy_coeff=0.0, kl_coeff=0.0)
+    pol = make_policy(8, 5, 5, 64, seed=80)
+    t, first = make_inputs(pol, 7, 17, 5, T, seed=81, behaviour=False, done_mode="per_env")
+    t = dict(t, **clipped_rows(pol, t, first, T, live=live, seed=82))
+    rep = branch_report(pol, t, h, first, T)
+    assert rep["open_pos"] == 0.0 and rep["open_neg"] == 0.0 and rep["clipped_pos"] > 0.3 and rep["clipped_neg"] > 0.3, rep
+    assert rep["margin"] > 0.1 and rep["conv_margin"] >= CONV_MARGIN and rep["vf_clipped_live" if live else "vf_dead"] == 1.0, rep
+    _, stats, g = autograd_loss(pol, t, h, first, T, moa_weight=0.0)
+    pos = (t["advantages"] > 0).double().reshape(-1, 5).mean(0)
+    assert max_err(stats["policy_loss"], -(1.3 * pos) + 0.7 * (1.0 - pos)) < 1e-6
+    for name in g:
+        zero = not live or name in MOA_BRANCH + ("logits_w", "logits_b")
+        assert (float(g[name].abs().max()) == 0.0) == zero, name
+
+
 def test_conv_gradient_is_the_sum_of_the_branches():
     pol = make_policy(8, 5, 5, 64, seed=9)
     t, first = make_inputs(pol, 7, 3, 5, 3, seed=10, done_mode="mid")

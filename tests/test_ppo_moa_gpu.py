@@ -3,7 +3,8 @@ against the float64 restatement (ppo_moa_ref.py) with torch's own float32 autogr
 persistent tile loop (in the row accounting, and an accuracy case with the float64 restatement on the device), the split-K kernels' second chunks (windows of
 more than 32 chunks of one set's rows: the second pass over the accumulators, a ragged last chunk that is a second chunk, splits
 that get no chunk of the second window, rows >= 2048), exact row accounting, exact zeros where no gradient may flow, bit-equal repeats, set isolation,
-moa_weight = 0, and one optimiser step end to end from sample()."""
+moa_weight = 0, the kink rules on rows clipped on both signs of the advantage (dead and live), rows exactly on policy (the
+clip range does not show, policy_loss = -1 and kl = 0 exactly), and one optimiser step end to end from sample()."""
 import copy
 import ctypes as C
 
@@ -11,12 +12,12 @@ import numpy as np
 import pytest
 import torch
 
-from ppo_moa_ref import (ACTIONS_BRANCH, CONV_MARGIN, HYPER, MARGIN, MOA_BRANCH, MOA_WEIGHT, as_numpy_u32, autograd_loss, branch_report, counting_inputs,
-                         forward, make_inputs, make_policy, max_err, shifted_obs, split_case, zero_policy)
-from ppo_ref import COUNTING_HYPER
+from ppo_moa_ref import (ACTIONS_BRANCH, CONV_MARGIN, HYPER, MARGIN, MOA_BRANCH, MOA_WEIGHT, as_numpy_u32, autograd_loss, branch_report, clipped_rows,
+                         counting_inputs, forward, make_inputs, make_policy, max_err, shifted_obs, split_case, zero_policy)
+from ppo_ref import COUNTING_HYPER, LOOSE, on_policy_checks
 from sequential_social_dilemma_games_amd import _capi
 from sequential_social_dilemma_games_amd import constants as K
-from sequential_social_dilemma_games_amd import ppo_loss_moa
+from sequential_social_dilemma_games_amd import evaluate_fragment, ppo_loss_moa
 from sequential_social_dilemma_games_amd.policy import MOA_PPO_STATS
 from sequential_social_dilemma_games_amd.vector_env import SSDVectorEnv
 
@@ -366,6 +367,101 @@ def test_moa_weight_zero():
     for k in MOA_PPO_STATS[1:]:
         assert np.array_equal(as_numpy_u32(s0[k]), as_numpy_u32(s1[k])), k
     assert float((s1["total_loss"] - s0["total_loss"] - MOA_WEIGHT * s1["moa_loss"]).abs().max()) < 1e-12
+
+
+KINK_HYPER = dict(HYPER, entropy_coeff=0.0, kl_coeff=0.0)
+
+
+def _clipped_fragment(live):
+    """The file's smallest standard fragment (K = 7, T = 3, 17 envs, N = P = 5, A = 8, C = 64, done per env) with every row
+    clipped on both signs of the advantage (ppo_moa_ref.clipped_rows with a seed) -> (policy, t, obs_first, branch report),
+    the conditions on the float64 reference asserted."""
+    T = 3
+    pol = make_policy(8, 5, 5, 64, seed=80)
+    t, first = make_inputs(pol, 7, 17, 5, T, seed=81, behaviour=False, done_mode="per_env")
+    t = dict(t, **clipped_rows(pol, t, first, T, live=live, seed=82))
+    rep = branch_report(pol, t, KINK_HYPER, first, T)
+    print("clipped, live" if live else "clipped, dead", rep)
+    assert rep["open_pos"] == 0.0 and rep["open_neg"] == 0.0 and abs(rep["clipped_pos"] + rep["clipped_neg"] - 1.0) <= 1e-12, rep
+    assert rep["clipped_pos"] > 0.3 and rep["clipped_neg"] > 0.3 and rep["margin"] > 0.1 and rep["conv_margin"] >= CONV_MARGIN, rep
+    assert (rep["vf_clipped_live"] == 1.0 and rep["vf_dead"] == 0.0) if live else (rep["vf_dead"] == 1.0), rep
+    return pol, t, first, rep
+
+
+def test_clipped_and_dead_rows_give_exactly_zero():
+    """The kink rules on ssd_policy_moa_ppo_grad: every row clipped with the clipped operand the minimum (adv = +1 at ratio 1.5,
+    adv = -1 at ratio 0.5) and dead; with moa_weight = entropy_coeff = kl_coeff = 0 every gradient tensor is exactly zero, and a
+    set's policy_loss is -(1.3 * its share of adv > 0) + 0.7 * its share of adv < 0 (the tolerance of the recurrent test)."""
+    pol, t, first, _ = _clipped_fragment(live=False)
+    loss, stats, g = _run(pol.to(DEV), _to_dev(t), first.to(DEV), KINK_HYPER, 3, moa_weight=0.0)
+    torch.cuda.synchronize()
+    pos = (t["advantages"] > 0).double().reshape(-1, 5).mean(0)
+    want = -(1.3 * pos) + 0.7 * (1.0 - pos)
+    print("policy_loss", stats["policy_loss"].tolist(), "want", want.tolist(), "vf_loss", stats["vf_loss"].tolist())
+    for name in g:
+        assert float(g[name].abs().max()) == 0.0, name
+    assert float((stats["policy_loss"].cpu() - want).abs().max()) < 1e-4 and float((stats["vf_loss"] - 0.64).abs().max()) < 1e-3
+    assert all(bool(torch.isfinite(stats[k]).all()) for k in MOA_PPO_STATS) and bool(torch.isfinite(loss))
+
+
+def test_clipped_and_live_rows_pull_through_the_value_alone():
+    """The same rows with the value branch clipped and live: d vf / d value = 2 (value - vt), nothing through the ratio.  The
+    logits layer is exactly zero in the kernel and in the float64 reference, the MOA branch is exactly zero (moa_weight = 0), and
+    the value head, the actions LSTM, stack 0 and the conv are non-zero and within the project's bound of float64."""
+    T = 3
+    pol, t, first, _ = _clipped_fragment(live=True)
+    loss64, stats64, g64 = autograd_loss(pol, t, KINK_HYPER, first, T, moa_weight=0.0)
+    loss32, stats32, g32 = autograd_loss(pol, t, KINK_HYPER, first, T, moa_weight=0.0, dtype=torch.float32, device=DEV)
+    loss, stats, g = _run(copy.deepcopy(pol).to(DEV), _to_dev(t), first.to(DEV), KINK_HYPER, T, moa_weight=0.0)
+    torch.cuda.synchronize()
+    for name in ("logits_w", "logits_b") + MOA_BRANCH:
+        assert float(g[name].abs().max()) == 0.0 and float(g64[name].abs().max()) == 0.0, name
+    rest = [name for name in g if name not in ("logits_w", "logits_b") + MOA_BRANCH]
+    assert set(rest) == set(ACTIONS_BRANCH + ("conv_w", "conv_b")) - {"logits_w", "logits_b"}
+    for name in rest:
+        assert float(g[name].abs().max()) > 0.0 and float(g64[name].abs().max()) > 0.0, name
+    assert all(bool(torch.isfinite(x).all()) for x in list(g.values()) + list(stats.values()) + [loss])
+    _check_against_reference(g, g32, g64, "live grad")
+    _check_against_reference(stats, stats32, stats64, "live stat")
+    _check_against_reference({"loss": loss}, {"loss": loss32}, {"loss": loss64}, "live loss")
+
+
+def test_on_policy_rows_exactly():
+    """test_sample_loss_step_sample's fragment before any step: the weights that sampled, logp_old = the rollout's logp, vf_pred
+    = its value, and the behaviour logits from the library's sequence forward of the same rows (sample() records no logits;
+    that call gives the rollout's to the bit).  The header builds the loss call's forward from the device pieces of the
+    rollout, so the kernel's ratio is 1 and its value - vf_pred is 0 exactly: ppo_ref.on_policy_checks -- the clip ranges
+    (0, 0) and (1e6, 1e6) give the same bits, policy_loss = -1 and kl = 0 exactly under advantages = 1, the KL term moves no
+    gradient -- and the (0, 0) gradient against the float64 reference of the unclipped loss."""
+    E, N, steps, T = 64, 5, 12, 4
+    h = dict(vf_loss_coeff=1e-2, entropy_coeff=1e-3, kl_coeff=0.2)
+    env = SSDVectorEnv(K.GAME_HARVEST, E, N, horizon=7, seed=5)
+    pol = make_policy(env.engine.num_actions, N, N, 64, seed=31, recur=2.0).to(DEV)
+    first = env.reset().clone()
+    batch = env.sample(pol, steps, state_every=T, gamma=0.99, lambda_=0.95, influence_weight=1.0)
+    logits, value, _ = evaluate_fragment(pol, batch, obs_first=first, seq_len=T, one_call=True)
+    assert torch.equal(value, batch["value"])                  # the sequence forward gives back the rollout's values ...
+    lp = torch.log_softmax(logits, -1).gather(-1, batch["actions"].long().unsqueeze(-1)).squeeze(-1)
+    assert float((torch.exp(lp - batch["logp"]) - 1).abs().max()) < 1e-4      # ... and its logits the rollout's logp
+
+    def call(clip_param, vf_clip_param, kl=True, ones=False):
+        b = dict(batch, advantages=torch.ones_like(batch["value"])) if ones else dict(batch)
+        if kl:
+            b["logits"] = logits.contiguous()
+        out = _run(pol, b, first, dict(h, clip_param=clip_param, vf_clip_param=vf_clip_param, kl_coeff=h["kl_coeff"] if kl else 0.0), T)
+        torch.cuda.synchronize()
+        return out
+    loss, stats, g = on_policy_checks(call, MOA_PPO_STATS, "moa")
+    t = {"obs": batch["obs"], "actions": batch["actions"], "logp_old": batch["logp"], "advantages": batch["advantages"],
+         "value_targets": batch["value_targets"], "vf_pred": batch["value"], "behaviour_logits": logits.contiguous(),
+         "state": batch["state"], "done": batch["done"], "prev_actions": batch["prev_actions"]}
+    cpu_t = {k: v.cpu() for k, v in t.items()}
+    hl = dict(h, **LOOSE)
+    loss64, stats64, g64 = autograd_loss(copy.deepcopy(pol).cpu(), cpu_t, hl, first.cpu(), T)
+    loss32, stats32, g32 = autograd_loss(pol, cpu_t, hl, first.cpu(), T, dtype=torch.float32, device=DEV)
+    _check_against_reference(g, g32, g64, "on-policy grad")
+    _check_against_reference(stats, stats32, stats64, "on-policy stat")
+    _check_against_reference({"loss": loss}, {"loss": loss32}, {"loss": loss64}, "on-policy loss")
 
 
 def test_sample_loss_step_sample():
