@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """A few PPO iterations on Watershed SeqComm with the baselines' LSTM-FC policy, sampler and learner both on the device: sample a
-lock-step batch (WatershedVecEngine.sample), gather each agent id's own steps, form advantages with compute_advantages, then one
+lock-step batch (WatershedVecEngine.sample), gather each agent id's own steps, form advantages with compute_advantages and
+standardise them over the id's [M, E] rows (standardize_advantages, one weight set: an agent id is one RLlib policy), then one
 ppo_loss_watershed call per agent id -- the loss with truncated backpropagation through time, its statistics and the gradient of
-that id's weight set from one library call -- and one Adam step.  An example of how the pieces fit, not a trainer.
+that id's weight set from one library call -- and one Adam step; vf_explained_var is printed per id.  An example of how the pieces fit, not a trainer.
 
 The gather (own_steps): Watershed is turn-based, one agent acts per phase.  Agent i's own steps are the steps k with
 actor[k] == i; envs reset together stay in lock step, so that is the same k in every env (it raises if not).  The observation
@@ -25,7 +26,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from sequential_social_dilemma_games_amd import (WatershedEpisodeStats, WatershedLSTMPolicy, WatershedVecEngine, _capi,  # noqa: E402
-                                                 compute_advantages, ppo_loss_watershed)
+                                                 compute_advantages, explained_variance, ppo_loss_watershed,
+                                                 standardize_advantages)
 
 
 def own_steps(batch, obs_before, agent_id, seq_len, gamma=0.99, lambda_=0.95):
@@ -54,6 +56,7 @@ def own_steps(batch, obs_before, agent_id, seq_len, gamma=0.99, lambda_=0.95):
     value = batch["value"][idx].contiguous()
     adv, vt = compute_advantages(torch.zeros((M, E), dtype=torch.int32, device=dev), value, last_value=batch["value"][ks[M]].contiguous(),
                                  done=done, gamma=gamma, lambda_=lambda_, bonus=rew, bonus_weight=1.0)
+    standardize_advantages(adv, num_sets=1, out=adv)                        # once per batch, before the epochs, as RLlib's PPO
     return {"obs": prev[idx].contiguous(), "actions": batch["actions"][idx].contiguous(), "logp": batch["logp"][idx].contiguous(),
             "value": value, "dist": batch["dist"][idx].contiguous(), "advantages": adv, "value_targets": vt, "starts": starts,
             "state": batch["state_in"][idx[::seq_len]].contiguous()}
@@ -90,9 +93,9 @@ def main():
                 continue
             loss, stats = ppo_loss_watershed(policy, agent_id, seq, seq_len=seq_len, **hyper)
             loss.backward()                                                  # fills row agent_id of every parameter's .grad
-            print("  agent %d: %d own steps, total %.5f, policy %.5f, vf %.4f, entropy %.4f" %
+            print("  agent %d: %d own steps, total %.5f, policy %.5f, vf %.4f, entropy %.4f, vf_explained_var %.3f" %
                   (agent_id, seq["actions"].shape[0], float(stats["total_loss"]), float(stats["policy_loss"]), float(stats["vf_loss"]),
-                   float(stats["entropy"])))
+                   float(stats["entropy"]), float(explained_variance(seq["value_targets"], seq["value"])[0])))
         optim.step()                                                         # the next call packs the updated parameters
         before = batch["obs"][steps - 1].clone()                             # the next batch's first step acts on this one's last observation
 

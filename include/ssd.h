@@ -1116,6 +1116,65 @@ int ssd_vtrace(const int32_t *rew, const float *bonus, double bonus_weight, cons
 const char *ssd_vtrace_last_error(void);   /* the calling thread's last ssd_vtrace error */
 
 /* ======================================================================================================================
+ * BATCH MOMENTS -- the step RLlib 0.7.6's PPO trainer takes between compute_advantages and its SGD epochs, and one of the
+ * statistics it reports (csrc/ssd_moments.hip).  Its optimizers are built with
+ * standardize_fields=["advantages"]: each policy's train batch has its advantages replaced by
+ * (value - value.mean()) / max(1e-4, value.std()) -- ssd_standardize; vf_explained_var is
+ * max(-1, 1 - var(targets - prediction) / var(targets)) -- ssd_explained_variance.  RLlib is not installed beside this
+ * library: both rules are stated from memory of its source.  Added after ABI 6 without a version bump: the calls are additive.
+ *
+ * Lanes and rows are those of ssd_advantages: x is f32 [ring, lanes], row k of a call is slot (step0 + k) % ring for
+ * k < n_steps, rows outside the call are neither read nor written.  The weight set of lane l is l % num_sets (num_sets is 1,
+ * or any value that divides lanes: the lanes of [E, N] rings with one set per agent).  Per set p the call holds
+ * n = n_steps * (lanes / num_sets) elements; element j of the set, j = k * (lanes / num_sets) + l / num_sets, is the call's
+ * flat element (k * lanes + l) = j * num_sets + p.
+ *
+ * THE SUMMATION ORDER IS THE CONTRACT.  It is a function of (n_steps, lanes, num_sets) and the three constants below alone --
+ * not of the grid, the device or the number of compute units.  Every operation is one IEEE float64 operation, round to
+ * nearest even, in the order written here; there is no fused multiply-add and no atomic.  SUM(f), for a quantity f(j) of a set:
+ *   chunk c = 0 .. SSD_MOM_CHUNKS - 1 holds the elements j in [c * SSD_MOM_CHUNK, (c + 1) * SSD_MOM_CHUNK), j < n
+ *   thread t = 0 .. SSD_MOM_BLOCK - 1 of chunk c:   a[t] = 0.0;  for u = 0 .. SSD_MOM_ITEMS - 1, in this order, with
+ *       j = c * SSD_MOM_CHUNK + u * SSD_MOM_BLOCK + t:   if j < n:  a[t] = a[t] + f(j)
+ *   the workgroup's tree:   for off = SSD_MOM_BLOCK / 2, SSD_MOM_BLOCK / 4, ..., 1:   a[t] = a[t] + a[t + off] for every t < off
+ *       (all t of one off at once, from the values before that off);   partial[c] = a[0]
+ *   across chunks:   s = 0.0;  for c = 0 .. SSD_MOM_CHUNKS - 1:  s = s + partial[c];   SUM(f) = s
+ * With nd = (double)n, per set, for a quantity x(j) converted to float64:
+ *   mean = SUM(x) / nd
+ *   var  = SUM(d * d) / nd  with  d = x(j) - mean   (subtract, multiply, then the add of SUM: a true second pass over the
+ *          data, never E[x^2] - mean^2)
+ *   std  = sqrt(var)        (the correctly rounded square root)
+ *
+ * ssd_standardize:  denom = std if std > min_std, else min_std;  out = (float)((x(j) - mean) / denom), one subtraction and one
+ * correctly rounded division in float64, one rounding to float32.  A set of one element, or of equal elements, has std = 0
+ * and out exactly 0.  out may be x itself (in place); it must not overlap x otherwise.  moments, when not NULL, is
+ * f64 [num_sets][2] = (mean, std) per set.  RLlib's min_std is 1e-4.
+ *
+ * ssd_explained_variance:  with y(j) and diff(j) = (double)y - (double)pred (formed in float64), both variances by the rule
+ * above;  r = 1.0 - var(diff) / var(y);  out[p] = (float)(-1.0 if r < -1.0, else r);  out is f32 [num_sets].  var(y) = 0
+ * follows IEEE arithmetic: var(diff) > 0 gives -inf and so -1; both 0 give 0 / 0, and out[p] is a NaN (of no particular sign
+ * or payload); a set of one element is such a set.
+ *
+ * scratch is SSD_MOM_SCRATCH_DOUBLES(n_steps, lanes, num_sets) float64 of device memory, aligned to 8 bytes, the call's own
+ * until it has finished (the chunk partials; contents on entry do not matter).  Inputs are assumed finite.  Device pointers on
+ * device_id.  Three launches on `stream` (the sums; the squared deviations; the result), each of which adds up the earlier
+ * ones' partials again in the order above; no allocation, no synchronisation, no launch that waits for another workgroup.
+ * SSD_E_INVALID before any device call (ssd_moments_last_error says why) for lanes < 1, ring < 1, n_steps < 1 or > ring,
+ * step0 < 0, num_sets < 1 or not a divisor of lanes or > 65535, a missing x, y, pred, out or scratch pointer, a pointer
+ * not aligned to its element, a min_std that is not finite or <= 0; SSD_E_DEVICE without a usable HIP device.
+ * ====================================================================================================================== */
+#define SSD_MOM_BLOCK 256                                     /* threads of a workgroup */
+#define SSD_MOM_ITEMS 16                                      /* elements a thread adds, one after the other */
+#define SSD_MOM_CHUNK (SSD_MOM_BLOCK * SSD_MOM_ITEMS)         /* elements of one set a workgroup takes per pass */
+#define SSD_MOM_CHUNKS(n_steps, lanes, num_sets) \
+    (((int64_t)(n_steps) * ((lanes) / (num_sets)) + SSD_MOM_CHUNK - 1) / SSD_MOM_CHUNK)
+#define SSD_MOM_SCRATCH_DOUBLES(n_steps, lanes, num_sets) (4 * (int64_t)(num_sets) * SSD_MOM_CHUNKS(n_steps, lanes, num_sets))
+int ssd_standardize(const float *x, int32_t lanes, int32_t ring, int32_t step0, int32_t n_steps, int32_t num_sets, double min_std,
+                    double *scratch, double *moments, float *out, int32_t device_id, void *stream);
+int ssd_explained_variance(const float *y, const float *pred, int32_t lanes, int32_t ring, int32_t step0, int32_t n_steps,
+                           int32_t num_sets, double *scratch, float *out, int32_t device_id, void *stream);
+const char *ssd_moments_last_error(void);   /* the calling thread's last ssd_standardize / ssd_explained_variance error */
+
+/* ======================================================================================================================
  * WATERSHED PPO LOSS AND GRADIENTS -- the learner's half of the loop for the Watershed baselines' policy (LSTMFCNet, WATERSHED
  * POLICY ROLLOUTS above), whose launchers default to PPO (run_scripts/train_watershed_baseline.py,
  * train_watershed_comm_baseline.py): RLlib 0.7.6's PPO loss on sequences the caller has gathered, with truncated

@@ -10,6 +10,7 @@
     from sequential_social_dilemma_games_amd import ConvMOAPolicy               # the causal-influence (MOA) policy
     from sequential_social_dilemma_games_amd import WatershedLSTMPolicy         # the Watershed baselines' LSTM-FC policy
     from sequential_social_dilemma_games_amd import compute_advantages          # GAE / discounted returns of a rollout batch
+    from sequential_social_dilemma_games_amd import standardize_advantages, explained_variance, update_kl_coeff   # PPO's batch moments
     from sequential_social_dilemma_games_amd import ppo_loss                    # the PPO loss and its gradients, on the device
     from sequential_social_dilemma_games_amd import ppo_loss_recurrent          # the same for the recurrent policy, with BPTT
     from sequential_social_dilemma_games_amd import ppo_loss_moa                # PPO + MOA loss for the MOA policy, with BPTT
@@ -52,7 +53,7 @@ def __getattr__(name):
                 "ws_a3c_terms", "a3c_loss_watershed", "evaluate_sequences", "impala_loss_watershed"):
         from . import policy
         return getattr(policy, name)
-    if name in ("compute_advantages", "vtrace"):
+    if name in ("compute_advantages", "vtrace", "standardize_advantages", "explained_variance", "update_kl_coeff"):
         from . import postprocessing
         return getattr(postprocessing, name)
     if name == "MapEnv":

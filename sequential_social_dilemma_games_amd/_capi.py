@@ -264,6 +264,19 @@ def SSD_WSPPO_SCRATCH_FLOATS(M, Q, C, T):
             + SSD_WSPPO_GROUPS(Q) * (8 * C + 8 + SSD_PPO_STAT_FLOATS) + SSD_WSPPO_SPLITS(rows) * ((16 + C) * 4 * C + 4 * C))
 
 
+# the batch moments' summation order and scratch (include/ssd.h, SSD_MOM_*)
+SSD_MOM_BLOCK, SSD_MOM_ITEMS = 256, 16
+SSD_MOM_CHUNK = SSD_MOM_BLOCK * SSD_MOM_ITEMS
+
+
+def SSD_MOM_CHUNKS(n_steps, lanes, num_sets):
+    return (int(n_steps) * (int(lanes) // int(num_sets)) + SSD_MOM_CHUNK - 1) // SSD_MOM_CHUNK
+
+
+def SSD_MOM_SCRATCH_DOUBLES(n_steps, lanes, num_sets):
+    return 4 * int(num_sets) * SSD_MOM_CHUNKS(n_steps, lanes, num_sets)
+
+
 # every symbol include/ssd.h declares
 SYMBOLS = ("ssd_create", "ssd_destroy", "ssd_reset", "ssd_step", "ssd_step_random", "ssd_rollout_random", "ssd_rollout_actions", "ssd_rollout_path", "ssd_set_rollout_chains",
            "ssd_profiler_attached", "ssd_observe",
@@ -280,7 +293,7 @@ SYMBOLS = ("ssd_create", "ssd_destroy", "ssd_reset", "ssd_step", "ssd_step_rando
            "ssd_ws_policy_ppo_grad", "ssd_ws_policy_ac_grad", "ssd_ws_policy_forward_seq",
            "ssd_policy_lstm_forward_seq", "ssd_policy_moa_forward_seq",
            "ssd_ws_stats_create", "ssd_ws_stats_destroy", "ssd_ws_stats_attach", "ssd_ws_stats_discard", "ssd_ws_stats_drain",
-           "ssd_ws_stats_last_error")
+           "ssd_ws_stats_last_error", "ssd_standardize", "ssd_explained_variance", "ssd_moments_last_error")
 # added after ABI 6 without a version bump (the calls are additive): a library built before them lacks them
 LSTM_SYMBOLS = ("ssd_policy_lstm_forward", "ssd_rollout_policy_lstm")
 MOA_SYMBOLS = ("ssd_policy_moa_forward", "ssd_rollout_policy_moa")
@@ -296,6 +309,7 @@ WS_A3C_SYMBOLS = ("ssd_ws_policy_ac_grad", "ssd_ws_policy_forward_seq")
 FORWARD_SEQ_SYMBOLS = ("ssd_policy_lstm_forward_seq", "ssd_policy_moa_forward_seq")
 WS_STATS_SYMBOLS = ("ssd_ws_stats_create", "ssd_ws_stats_destroy", "ssd_ws_stats_attach", "ssd_ws_stats_discard", "ssd_ws_stats_drain",
                     "ssd_ws_stats_last_error")
+MOMENTS_SYMBOLS = ("ssd_standardize", "ssd_explained_variance", "ssd_moments_last_error")
 
 
 class SsdConfig(C.Structure):
@@ -408,9 +422,9 @@ def lib():
         L.ssd_policy_last_error.argtypes = []
         L.ssd_policy_last_error.restype = C.c_char_p
         L.ssd_rollout_policy.argtypes = [vp, vp, i32, vp, i32, i32] + [vp] * 7 + [i32, vp, u32, vp]
-        missing = [name for name in LSTM_SYMBOLS + MOA_SYMBOLS + WS_POLICY_SYMBOLS + ADVANTAGES_SYMBOLS + PPO_SYMBOLS + LSTM_PPO_SYMBOLS + MOA_PPO_SYMBOLS + A3C_SYMBOLS + VTRACE_SYMBOLS + WS_PPO_SYMBOLS + WS_A3C_SYMBOLS + FORWARD_SEQ_SYMBOLS + WS_STATS_SYMBOLS if not hasattr(L, name)]
+        missing = [name for name in LSTM_SYMBOLS + MOA_SYMBOLS + WS_POLICY_SYMBOLS + ADVANTAGES_SYMBOLS + PPO_SYMBOLS + LSTM_PPO_SYMBOLS + MOA_PPO_SYMBOLS + A3C_SYMBOLS + VTRACE_SYMBOLS + WS_PPO_SYMBOLS + WS_A3C_SYMBOLS + FORWARD_SEQ_SYMBOLS + WS_STATS_SYMBOLS + MOMENTS_SYMBOLS if not hasattr(L, name)]
         if missing:
-            raise SsdError("%s lacks %s (built before the recurrent, MOA or Watershed policy calls, the advantages call, the PPO or A3C gradient calls, the V-trace call, the Watershed PPO gradient call, the sequence forwards or the Watershed episode statistics): rebuild it with `python -c 'import "
+            raise SsdError("%s lacks %s (built before the recurrent, MOA or Watershed policy calls, the advantages call, the PPO or A3C gradient calls, the V-trace call, the Watershed PPO gradient call, the sequence forwards, the Watershed episode statistics or the batch moments): rebuild it with `python -c 'import "
                            "__graft_entry__ as g; g.build()'`" % (LIB_PATH, ", ".join(missing)))
         L.ssd_policy_lstm_forward.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, u32, vp]
         L.ssd_rollout_policy_lstm.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, vp, i32, i32] + [vp] * 8 + [i32, vp, u32, vp]
@@ -449,6 +463,10 @@ def lib():
         L.ssd_ws_stats_drain.argtypes = [vp] + [vp] * 12 + [u32, vp]
         L.ssd_ws_stats_last_error.argtypes = [vp]
         L.ssd_ws_stats_last_error.restype = C.c_char_p
+        L.ssd_standardize.argtypes = [vp, i32, i32, i32, i32, i32, C.c_double, vp, vp, vp, i32, vp]
+        L.ssd_explained_variance.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp]
+        L.ssd_moments_last_error.argtypes = []
+        L.ssd_moments_last_error.restype = C.c_char_p
         for name in SYMBOLS:
             getattr(L, name)
         if L.ssd_abi_version() != ABI_VERSION:
@@ -491,6 +509,12 @@ def vtrace_check(rc):
     if rc != SSD_OK:
         msg = lib().ssd_vtrace_last_error()
         raise SsdError("libssd_hip V-trace call failed (%d): %s" % (rc, msg.decode() if msg else "?"))
+
+
+def moments_check(rc):
+    if rc != SSD_OK:
+        msg = lib().ssd_moments_last_error()
+        raise SsdError("libssd_hip batch-moments call failed (%d): %s" % (rc, msg.decode() if msg else "?"))
 
 
 def check(rc, handle=None):

@@ -15,6 +15,15 @@ conventions.
 
     logits, value, boot = evaluate_fragment(policy, batch, first, seq_len)            # under the learner's current weights
     vs, pg = vtrace(batch["rew"], value, rhos, boot, batch["done"], gamma=0.99)       # rhos = exp(logp_target - batch["logp"])
+
+standardize_advantages() and explained_variance() are the per-weight-set moments RLlib's PPO trainer takes of a train batch
+(csrc/ssd_moments.hip, include/ssd.h BATCH MOMENTS): the advantages standardised before the SGD epochs,
+and vf_explained_var, as two-pass float64 moments in a fixed summation order.  update_kl_coeff() is the trainer's rule for
+its KL coefficient, on the host.
+
+    adv = standardize_advantages(batch["advantages"], num_sets=policy.num_sets)       # or sample(..., standardize=True)
+    ev = explained_variance(batch["value_targets"], batch["value"], num_sets=policy.num_sets)
+    kl_coeff = update_kl_coeff(kl_coeff, float(stats["kl"].mean()), kl_target=0.01)
 """
 import ctypes as C
 import math
@@ -241,3 +250,174 @@ def vtrace(rew, value, rhos, bootstrap_value=None, done=None, gamma=0.99, clip_r
                                               ptr(bootstrap_value), L, R, step0, n_steps, gamma, clip_rho, clip_pg, 0,
                                               ptr(vs), ptr(pg), index, stream))
     return vs, pg
+
+
+# ---- batch moments (csrc/ssd_moments.hip, include/ssd.h BATCH MOMENTS) ----
+
+def _ordered_sum(f):
+    """SUM(f) of include/ssd.h, BATCH MOMENTS, for the float64 values f [n] of one set: the threads' sequential sums (all
+    chunks and threads at once, the items one after the other), the workgroup's tree by halving, the chunks in their order.
+    The places past n hold +0.0, which changes no sum: an accumulator that starts at +0.0 is never -0.0."""
+    B, I, W = _capi.SSD_MOM_BLOCK, _capi.SSD_MOM_ITEMS, _capi.SSD_MOM_CHUNK
+    n = f.shape[0]
+    chunks = (n + W - 1) // W
+    padded = np.zeros(chunks * W, np.float64)
+    padded[:n] = f
+    padded = padded.reshape(chunks, I, B)
+    a = np.zeros((chunks, B), np.float64)
+    for u in range(I):
+        a = a + padded[:, u, :]
+    off = B // 2
+    while off >= 1:
+        a = a[:, :off] + a[:, off:2 * off]
+        off //= 2
+    s = np.float64(0.0)
+    for c in range(chunks):
+        s = s + a[c, 0]
+    return s
+
+
+def _mean_var(f):
+    """(mean, var) of the float64 values f [n] by the two passes of the contract."""
+    nd = np.float64(f.shape[0])
+    mean = _ordered_sum(f) / nd
+    d = f - mean
+    return mean, _ordered_sum(d * d) / nd
+
+
+def _moments_args(torch, x, num_sets, step0, n_steps, name):
+    if not isinstance(x, torch.Tensor) or x.dim() < 1:
+        raise ValueError("%s must be a float32 tensor of shape [R, ...]" % name)
+    shape, dev = tuple(x.shape), x.device
+    R = shape[0]
+    L = int(np.prod(shape[1:], dtype=np.int64))
+    if R < 1 or L < 1:
+        raise ValueError("%s holds no step" % name)
+    if L >= 2 ** 31 or R >= 2 ** 31:
+        raise ValueError("%s is too large: fewer than 2^31 rows and trajectories" % name)
+    _check(torch, x, torch.float32, shape, dev, name)
+    num_sets = int(num_sets)
+    if num_sets < 1 or L % num_sets or num_sets > 65535:
+        raise ValueError("num_sets (%d) must be 1..65535 and divide the %d trajectories of a row: trajectory l belongs to set "
+                         "l %% num_sets" % (num_sets, L))
+    step0 = int(step0)
+    n_steps = R if n_steps is None else int(n_steps)
+    if n_steps < 1 or n_steps > R:
+        raise ValueError("n_steps (%d) must be 1..%d, the ring length: a call reads each slot once" % (n_steps, R))
+    if step0 < 0 or step0 >= 2 ** 31:
+        raise ValueError("step0 must be 0..2^31 - 1")
+    return shape, dev, R, L, num_sets, step0, n_steps
+
+
+_moments_scratch = {}
+
+
+def _scratch(torch, dev, doubles):
+    """The calls' float64 scratch: one torch allocation per device and size, kept.  Calls that share it are ordered by the
+    stream they run on; use one stream per device for these calls."""
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    key = (index, doubles)
+    buf = _moments_scratch.get(key)
+    if buf is None:
+        buf = _moments_scratch[key] = torch.empty(doubles, dtype=torch.float64, device=dev)
+    return index, buf
+
+
+def standardize_advantages(adv, num_sets=1, min_std=1e-4, step0=0, n_steps=None, out=None, return_moments=False):
+    """-> adv standardised per weight set, a float32 tensor of adv's shape: (adv - mean) / max(min_std, std) with the set's
+    mean and population std, what RLlib 0.7.6's PPO optimizers do to each policy's train batch before the SGD epochs
+    (standardize_fields=["advantages"], min_std 1e-4; stated from memory of its source).  include/ssd.h, BATCH MOMENTS states
+    every operation: two-pass float64 moments in a fixed summation order, one rounding to float32, so that two runs of one
+    seed give the same bits on any device.
+
+    adv float32 [R, ...] contiguous (any trailing shape, as compute_advantages takes: [K,E,N] from sample(), [M,E], [R,L]).
+    The weight set of trailing index l is l % num_sets, as the loss calls have it: num_sets is 1 or policy.num_sets, and
+    divides the trailing size.  Row k of the call is ring slot (step0 + k) % R, k < n_steps (default R); rows outside the call
+    are not written (zero in a tensor this function allocates).  out: the tensor to write into; it may be adv itself.
+    return_moments: -> (out, moments) with moments float64 [num_sets, 2] = (mean, std) per set, on adv's device.
+    CUDA tensors go to the kernels (three launches on torch's current stream, no synchronisation, no temporary of the
+    batch's size); CPU tensors run a NumPy restatement of the same contract, bit for bit.
+    """
+    import torch
+    shape, dev, R, L, num_sets, step0, n_steps = _moments_args(torch, adv, num_sets, step0, n_steps, "adv")
+    min_std = float(min_std)
+    if not (math.isfinite(min_std) and min_std > 0.0):
+        raise ValueError("min_std must be finite and > 0")
+    if out is None:
+        out = (torch.empty if n_steps == R else torch.zeros)(shape, dtype=torch.float32, device=dev)
+    else:
+        _check(torch, out, torch.float32, shape, dev, "out")
+    moments = torch.empty((num_sets, 2), dtype=torch.float64, device=dev) if return_moments else None
+    if dev.type == "cpu":
+        rows = [(step0 + k) % R for k in range(n_steps)]
+        x = adv.numpy().reshape(R, L)[rows].reshape(-1, num_sets)
+        res = np.empty_like(x)
+        for p in range(num_sets):
+            xs = x[:, p].astype(np.float64)
+            mean, var = _mean_var(xs)
+            sd = np.sqrt(var)
+            denom = sd if sd > min_std else np.float64(min_std)
+            res[:, p] = ((xs - mean) / denom).astype(np.float32)
+            if moments is not None:
+                moments[p, 0], moments[p, 1] = float(mean), float(sd)
+        out.numpy().reshape(R, L)[rows] = res.reshape(n_steps, L)
+        return (out, moments) if return_moments else out
+    if dev.type != "cuda":
+        raise ValueError("the tensors must be on the CPU or on a GPU, not on %s" % (dev,))
+    index, scratch = _scratch(torch, dev, _capi.SSD_MOM_SCRATCH_DOUBLES(n_steps, L, num_sets))
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _capi.moments_check(_capi.lib().ssd_standardize(
+        C.c_void_p(adv.data_ptr()), L, R, step0, n_steps, num_sets, min_std, C.c_void_p(scratch.data_ptr()),
+        None if moments is None else C.c_void_p(moments.data_ptr()), C.c_void_p(out.data_ptr()), index, stream))
+    return (out, moments) if return_moments else out
+
+
+def explained_variance(targets, pred, num_sets=1, step0=0, n_steps=None):
+    """-> float32 [num_sets] on the tensors' device: max(-1, 1 - var(targets - pred) / var(targets)) per weight set, RLlib's
+    vf_explained_var (rllib/utils/explained_variance.py, stated from memory) of value_targets and the value predictions.
+
+    targets and pred float32 [R, ...] of one shape, contiguous, on one device; num_sets, step0 and n_steps as
+    standardize_advantages takes them.  The difference is formed in float64 and both population variances are the two-pass
+    float64 moments of include/ssd.h, BATCH MOMENTS, in its fixed order.  var(targets) == 0 follows IEEE arithmetic: -1 when the
+    residual's variance is > 0, NaN when both are 0.  CUDA tensors go to the kernels (three launches on torch's current
+    stream, no synchronisation); CPU tensors run the NumPy restatement, bit for bit.
+    """
+    import torch
+    shape, dev, R, L, num_sets, step0, n_steps = _moments_args(torch, targets, num_sets, step0, n_steps, "targets")
+    _check(torch, pred, torch.float32, shape, dev, "pred")
+    out = torch.empty(num_sets, dtype=torch.float32, device=dev)
+    if dev.type == "cpu":
+        rows = [(step0 + k) % R for k in range(n_steps)]
+        y = targets.numpy().reshape(R, L)[rows].reshape(-1, num_sets)
+        q = pred.numpy().reshape(R, L)[rows].reshape(-1, num_sets)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            for p in range(num_sets):
+                ys = y[:, p].astype(np.float64)
+                var_y = _mean_var(ys)[1]
+                var_d = _mean_var(ys - q[:, p].astype(np.float64))[1]
+                r = np.float64(1.0) - var_d / var_y
+                out[p] = float(np.float32(-1.0 if r < -1.0 else r))
+        return out
+    if dev.type != "cuda":
+        raise ValueError("the tensors must be on the CPU or on a GPU, not on %s" % (dev,))
+    index, scratch = _scratch(torch, dev, _capi.SSD_MOM_SCRATCH_DOUBLES(n_steps, L, num_sets))
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _capi.moments_check(_capi.lib().ssd_explained_variance(
+        C.c_void_p(targets.data_ptr()), C.c_void_p(pred.data_ptr()), L, R, step0, n_steps, num_sets,
+        C.c_void_p(scratch.data_ptr()), C.c_void_p(out.data_ptr()), index, stream))
+    return out
+
+
+def update_kl_coeff(kl_coeff, sampled_kl, kl_target):
+    """-> the next KL coefficient(s): RLlib 0.7.6's KLCoeffMixin.update_kl (stated from memory), elementwise over scalars or
+    arrays that broadcast: kl_coeff * 1.5 where sampled_kl > 2 * kl_target, kl_coeff * 0.5 where sampled_kl < 0.5 * kl_target,
+    kl_coeff otherwise (a sampled_kl exactly on a threshold changes nothing).  Pure NumPy on the host: sampled_kl is the "kl"
+    statistic the PPO loss calls return (one value per weight set).  The loss calls take ONE scalar kl_coeff for all weight
+    sets; a coefficient per weight set inside the loss kernels is out of scope here, so a caller with several sets either
+    adapts one coefficient from the mean kl, or runs one loss call per coefficient.  Scalars in, a Python float out; arrays
+    in, a float64 array out."""
+    k = np.asarray(kl_coeff, np.float64)
+    s = np.asarray(sampled_kl, np.float64)
+    t = np.asarray(kl_target, np.float64)
+    nxt = np.where(s > 2.0 * t, k * 1.5, np.where(s < 0.5 * t, k * 0.5, k))
+    return float(nxt) if nxt.ndim == 0 else nxt

@@ -152,7 +152,7 @@ class SSDVectorEnv(object):
         return self._wrap(obs, self._act_buf, done if self.horizon > 0 else None), rew, done
 
     def sample(self, policy, n_steps, greedy=False, state_every=None, influence_weight=1.0, gamma=None, lambda_=1.0, use_gae=True,
-               use_critic=True):
+               use_critic=True, standardize=False):
         """n_steps closed-loop steps of a ConvFCPolicy or a ConvLSTMPolicy on the device in one call (VecEngine.rollout_policy): returns a dict of
         device tensors obs u8 [K,E,N,15,15,3], actions i32, logp f32, value f32, rew i32, done u8 (all [K,E,N], step k in row
         k) and last_value f32 [E,N] (the value of the final observation).  Episodes end at the horizon as in step(): a finished
@@ -169,7 +169,10 @@ class SSDVectorEnv(object):
         influence.
         With a gamma the dict gains "advantages" and "value_targets" f32 [K,E,N]: postprocessing.compute_advantages of rew,
         value, done and last_value (for a ConvMOAPolicy of rew + influence_weight * influence, formed in float64), enqueued
-        behind the rollout on the same stream."""
+        behind the rollout on the same stream.  With standardize=True (it needs a gamma) "advantages" is standardised per weight
+        set of the policy, postprocessing.standardize_advantages with num_sets = policy.num_sets, in place behind the
+        advantages' launch: what RLlib's PPO optimizers do to a train batch before the SGD epochs.  "value_targets" is
+        untouched."""
         import torch
         if self.float32_obs:
             raise ValueError("sample() records uint8 observations: construct with float32_obs=False")
@@ -180,6 +183,8 @@ class SSDVectorEnv(object):
             raise ValueError("n_steps must be >= 1")
         eng = self.engine
         eng._policy_weights(policy)                  # (every check before anything is enqueued)
+        if standardize and gamma is None:
+            raise ValueError("standardize=True standardises the advantages: give a gamma")
         if gamma is not None:
             import math
             gamma, lambda_ = float(gamma), float(lambda_)
@@ -238,6 +243,9 @@ class SSDVectorEnv(object):
             out["advantages"], out["value_targets"] = compute_advantages(
                 out["rew"], out["value"], out["last_value"], out["done"], gamma=gamma, lambda_=lambda_, use_gae=use_gae,
                 use_critic=use_critic, **bonus)
+            if standardize:
+                from .postprocessing import standardize_advantages
+                standardize_advantages(out["advantages"], num_sets=policy.num_sets, out=out["advantages"])
         return out
 
     @staticmethod
