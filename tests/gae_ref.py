@@ -64,14 +64,15 @@ def rewards(rng, shape):
                       p=[.25, .3, .1, .1, .08, .05, .04, .04, .02, .02]).astype(np.int32)
 
 
-def make_rings(seed, R, trailing, done_mode, with_bonus=False, with_last=True):
-    """Random rings: rew as the games pay it, value and bonus normal float32, done nowhere / everywhere / at rate 0.02."""
+def make_rings(seed, R, trailing, done_mode, with_bonus=False, with_last=True, done_rate=0.02):
+    """Random rings: rew as the games pay it, value and bonus normal float32, done nowhere / everywhere / at done_rate / on no
+    row yet ("last": build() sets the call's last row)."""
     rng = np.random.default_rng(seed)
     shape = (R,) + tuple(trailing)
     c = {"rew": rewards(rng, shape), "value": (rng.standard_normal(shape) * 3).astype(np.float32),
          "last_value": np.asarray(rng.standard_normal(tuple(trailing)) * 3, dtype=np.float32) if with_last else None,
-         "done": {"none": None, "all": np.ones(shape, np.uint8),
-                  "some": (rng.random(shape) < 0.02).astype(np.uint8)}[done_mode],
+         "done": {"none": None, "all": np.ones(shape, np.uint8), "last": np.zeros(shape, np.uint8),
+                  "some": (rng.random(shape) < done_rate).astype(np.uint8)}[done_mode],
          "bonus": np.abs(rng.standard_normal(shape)).astype(np.float32) * np.float32(0.05) if with_bonus else None}
     return c
 
@@ -110,6 +111,79 @@ def matrix():
             out.append(("wrap-R%d-K%d-s%d-%s" % (R, K, step0, mode),
                         dict(seed=100 + n, R=R, trailing=(67,), done_mode="some", with_bonus=True),
                         dict(gamma=0.99, lambda_=0.95, bonus_weight=0.25, step0=step0, n_steps=K, **MODES[mode])))
+            n += 1
+    return out
+
+
+# The kernel requests LOAD_BLOCK steps at a time through two register buffers that swap roles (csrc/ssd_gae.hip, kLoad).
+LOAD_BLOCK = 16
+# no full block, then one, two (the odd buffer's exit) and three full blocks: each alone, one short and one over
+BLOCK_STEPS = (15, 16, 17, 31, 32, 33, 47, 48, 49)
+# spare lanes, a whole last wave (64, 128), a second and a third wave
+BLOCK_LANES = (1, 63, 64, 65, 128, 130)
+BLOCK_DONES = ("all", "last", "some")
+# The seeds of the "some" cases in the order block_matrix() makes them, found on the CPU: for the i-th of them the first of
+# 700 + 10 i, 701 + 10 i, ... whose rings have what some_conditions() asks for; test_advantages_cpu.py asserts that each does.
+# The rate is 0.3 for one lane (it needs two done rows of its own in as few as 17 steps) and 0.06 otherwise (a lane of 49
+# steps stays without a done row with probability 0.05).
+SOME_SEEDS = (700, 710, 720, 730, 740, 751, 760, 770, 780, 790, 801, 810, 820, 830, 840, 850, 860, 870)
+
+
+def some_rate(L):
+    return 0.3 if L == 1 else 0.06
+
+
+def some_conditions(done, K):
+    """What a "some" case of K steps (rows 0 .. K - 1 of done [K, L]) must hold: a done row inside a full block (the kernel
+    walks down from row K - 1, so the full blocks are rows K % LOAD_BLOCK ... K - 1; the call's last row cuts by itself and does
+    not count), one among the K % LOAD_BLOCK rows left at the fragment's start where there are any, and a lane without any when
+    there is more than one lane.  -> the three as booleans, True where a condition does not apply."""
+    done = np.asarray(done).reshape(K, -1) != 0
+    left = K % LOAD_BLOCK
+    return (K < LOAD_BLOCK or bool(done[left:K - 1].any()), left == 0 or bool(done[:left].any()),
+            done.shape[1] == 1 or bool((~done.any(axis=0)).any()))
+
+
+def build(rings, call):
+    """The rings of a block_matrix() case; done mode "last" sets the whole last row of the call and no other."""
+    c = make_rings(**rings)
+    if rings["done_mode"] == "last":
+        R = rings["R"]
+        c["done"][(call.get("step0", 0) + call.get("n_steps", R) - 1) % R] = 1
+    return c
+
+
+def block_matrix(some_seeds=None):
+    """(id, rings kwargs, call kwargs) for build(): at every K of BLOCK_STEPS each of the twelve kernel instances (mode x bonus
+    given / absent x done given / absent) once, with the lane counts, gamma, lambda and the absent last_value rotating so that
+    every lane count meets every mode; where done is given, "all", the call's last row only and "some" rotate; then three
+    rings that wrap per mode in the instance without bonus and done.  some_seeds: SOME_SEEDS, or a function of (case index
+    among the "some" cases, rings kwargs without a seed) for the search that found them."""
+    seeds = SOME_SEEDS if some_seeds is None else some_seeds
+    out, n, some = [], 0, 0
+    for ki, K in enumerate(BLOCK_STEPS):
+        for mi, mode in enumerate(MODES):
+            for bi, bonus in enumerate((False, True)):
+                for di, given in enumerate((False, True)):
+                    L = BLOCK_LANES[(ki + 2 * bi + di + mi) % 6]
+                    g, lam = GAMMAS[(n + n // 4) % 4], LAMBDAS[(2 * ki + 2 * mi + bi) % 3]
+                    dm = BLOCK_DONES[(ki + 2 * mi + bi) % 3] if given else "none"
+                    last = n % 5 != 0
+                    rings = dict(R=K, trailing=(L,), done_mode=dm, with_bonus=bonus, with_last=last)
+                    if dm == "some":
+                        rings["done_rate"] = some_rate(L)
+                        rings["seed"] = seeds(some, rings) if callable(seeds) else seeds[some]
+                        some += 1
+                    else:
+                        rings["seed"] = 500 + n
+                    out.append(("K%d-L%d-%s-%s-g%s-l%s%s%s" % (K, L, mode, dm, g, lam, "-bonus" if bonus else "", "" if last else "-nolast"),
+                                rings, dict(gamma=g, lambda_=lam, bonus_weight=0.25, **MODES[mode])))
+                    n += 1
+    for mode in MODES:
+        for (R, K, step0), L in zip(((40, 33, 30), (17, 16, 9), (48, 48, 47)), (65, 64, 130)):
+            out.append(("wrap-R%d-K%d-s%d-L%d-%s" % (R, K, step0, L, mode),
+                        dict(seed=500 + n, R=R, trailing=(L,), done_mode="none", with_bonus=False),
+                        dict(gamma=0.99, lambda_=0.95, step0=step0, n_steps=K, **MODES[mode])))
             n += 1
     return out
 

@@ -1,4 +1,4 @@
-"""The tests' own statement of the batch moments (include/ssd.h, BATCH MOMENTS), in two parts.
+"""The tests' own statement of the batch moments (include/ssd.h, BATCH MOMENTS), in three parts.
 
 1. The restatement: the header's summation order followed line by line in NumPy -- a thread's items one after the other, the
    workgroup's tree by halving, the chunk partials in their order -- with the header's own constants, read from the header.
@@ -18,6 +18,8 @@ The bound.  u = 2^-53.  A float64 sum of n terms, in any order, errs by at most 
          by e_m and carries two roundings (subtract, divide):
          |d o| <= e_o = (e_m + 2 u (|x - mu| + e_m)) / (den - e_s) + |x - mu| * e_s / (den * (den - e_s))
          and the one rounding to float32 adds 2^-24 * (|o| + e_o) + 2^-150 (half an ulp, or half the smallest subnormal).
+3. The inputs at the stage boundaries of the across-chunk sum (255 to 513 chunks per set) and that sum in four orders the
+   contract does not allow, which the inputs are chosen to tell from the right one.
 Both the restatement and the independent check are float64 evaluations of the same two passes in some order, so each is
 within e of the exact value and they are within 2 e of each other; the float32 rounding is counted once.
 """
@@ -184,3 +186,75 @@ def out_bound(v, min_std=1e-4):
 def noise(seed, shape, scale=1.0, offset=0.0):
     r = np.random.RandomState(seed)
     return (offset + scale * r.standard_normal(shape)).astype(np.float32)
+
+
+# ---- 3. the stage boundaries of the across-chunk sum, and orders it must not take ----
+# The device stages BLOCK chunk partials at a time (csrc/ssd_moments.hip, combine()): a short stage and a full one are two
+# branches, and LDS is handed from stage to stage.  (num_sets, per-set count, seed of noise()): the fewest chunks at which
+# each path exists -- the longest short stage, exactly one full stage (its last chunk holds one element), a full stage and a
+# stage of one partial, two full stages and a short one; then 257 chunks per set for three sets (blockIdx.y > 0, an odd
+# stride between the sets' partials, every third float read).  Random data alone need not tell a wrong order from the right
+# one, and `out`, a float32, does not at all (a 256-wide regrouping of 513 chunks changed none of 2.1 M elements), so the seeds
+# are chosen on the CPU, the first of 1, 2, ... under which every order of WRONG_ORDERS that can differ at that count changes
+# the bits of both the mean and the std of every set: all five at 513 chunks (seeds 2, 4 and 6 of 1 .. 8 do), the reversed one
+# and the two 64-wide ones at 255 to 257 chunks, where sub-totals of 256 are the contract's own order (the pairwise sum is left
+# to the 513-chunk case).  test_moments_cpu.py asserts it for every case.
+STAGE_CASES = [(1, (BLOCK - 1) * W, 5), (1, (BLOCK - 1) * W + 1, 2), (1, BLOCK * W + 1, 2), (1, 2 * BLOCK * W + 7, 2),
+               (3, BLOCK * W + 1, 7)]
+STAGE_IDS = ["P%d-%dchunks" % (P, -(-n // W)) for P, n, _ in STAGE_CASES]
+_stage = {}
+
+
+def stage_input(P, n, seed):
+    """x [n, P], pred, and their restatement (out, moments, explained variance): computed once, shared, read-only."""
+    if (P, n, seed) not in _stage:
+        x = noise(seed, (n, P), scale=2.0, offset=0.25)
+        pred = (x * np.float32(0.5) + noise(seed + 1000, (n, P), scale=0.3)).astype(np.float32)     # (never x's own draw)
+        _stage[P, n, seed] = (x, pred) + standardize_ref(x, num_sets=P) + (explained_variance_ref(x, pred, num_sets=P),)
+        for a in _stage[P, n, seed]:
+            a.setflags(write=False)
+    return _stage[P, n, seed]
+
+
+def _in_order(partial):
+    s = np.float64(0.0)
+    for v in partial:
+        s = s + v
+    return s
+
+
+def _subtotals(width):
+    """Sub-totals of `width` partials, each from +0.0 in chunk order, then the sub-totals in their order from +0.0."""
+    return lambda partial: _in_order([_in_order(partial[i:i + width]) for i in range(0, len(partial), width)])
+
+
+# name -> the chunk partials of one set added up in an order that is not the contract's
+def _waves_then_pairs(partial):
+    """Per stage of BLOCK partials: four sub-totals of 64, added among themselves as (w0 + w1) + (w2 + w3), then onto the sum."""
+    s = np.float64(0.0)
+    for i in range(0, len(partial), BLOCK):
+        w = [_in_order(partial[j:j + 64]) for j in range(i, i + BLOCK, 64)]
+        s = s + ((w[0] + w[1]) + (w[2] + w[3]))
+    return s
+
+
+WRONG_ORDERS = {"reversed": lambda partial: _in_order(partial[::-1]),
+                "subtotals_of_64": _subtotals(64),               # every wave adding its own share of a stage
+                "waves_then_pairs": _waves_then_pairs,           # ... with the four shares added among themselves first
+                "subtotals_of_256": _subtotals(BLOCK),           # every stage from +0.0
+                "pairwise": lambda partial: np.asarray(partial, np.float64).sum()}
+
+
+def wrong_moments(v, orders):
+    """For one set's float64 values v: {order: (mean, std)} with the mean from S1's chunk partials added in that wrong order,
+    and the std from the RIGHT mean with only S2's chunk partials added in it; and the contract's (mean, std) under None."""
+    v = np.asarray(v, np.float64)
+    nd = np.float64(v.shape[0])
+    s1, p1 = ordered_sum(v)
+    mean = s1 / nd
+    d = v - mean
+    s2, p2 = ordered_sum(d * d)
+    res = {None: (mean, np.sqrt(s2 / nd))}
+    for o in orders:
+        res[o] = WRONG_ORDERS[o](p1) / nd, np.sqrt(WRONG_ORDERS[o](p2) / nd)
+    return res

@@ -16,6 +16,7 @@ from sequential_social_dilemma_games_amd.postprocessing import compute_advantage
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = gae_ref.matrix()
+BLOCK_CASES = gae_ref.block_matrix()
 
 
 def _tensors(c):
@@ -54,6 +55,57 @@ def test_the_matrix_covers_what_it_should():
                     assert (g, lam, mode["use_gae"], mode["use_critic"], bonus) in pairs
     assert any(not c[1].get("with_last", True) for c in CASES)
     assert any(c[2].get("n_steps", c[1]["R"]) < c[1]["R"] and c[2]["step0"] % c[1]["R"] + c[2]["n_steps"] > c[1]["R"] for c in CASES)
+
+
+@pytest.mark.parametrize("name,rings,call", BLOCK_CASES, ids=[c[0] for c in BLOCK_CASES])
+def test_host_path_equals_the_restatement_on_the_block_matrix(name, rings, call):
+    c = gae_ref.build(rings, call)
+    adv, vt = _run(c, **call)
+    want_a, want_t = advantages_ref(c["rew"], c["value"], c["last_value"], c["done"], bonus=c["bonus"], **call)
+    assert same_bits(adv, want_a), np.argwhere(gae_ref.bits(adv) != gae_ref.bits(want_a))[:5]
+    assert same_bits(vt, want_t), np.argwhere(gae_ref.bits(vt) != gae_ref.bits(want_t))[:5]
+
+
+def test_the_block_matrix_reaches_every_instance_at_every_step_count():
+    """The kernel has twelve instances (mode x bonus given / absent x done given / absent), and its two-buffer loop another
+    path for no, one, two and three full blocks of 16 steps with and without rows left over: every instance meets every step
+    count; every lane count -- spare lanes, whole last waves, a second and a third wave -- meets every mode and every step count;
+    the three done patterns meet every mode; and each "some" case has what it is there for."""
+    assert gae_ref.LOAD_BLOCK == int(re.search(r"#define SSD_GAE_LOAD_BLOCK (\d+)", open(os.path.join(
+        REPO, "sequential_social_dilemma_games_amd", "csrc", "ssd_gae.hip")).read()).group(1))
+    seen, some, wraps = set(), 0, set()
+    for _, rings, call in BLOCK_CASES:
+        c = gae_ref.build(rings, call)
+        R, (L,) = rings["R"], rings["trailing"]
+        K = call.get("n_steps", R)
+        mode = (call["use_gae"], call["use_critic"])
+        if "step0" in call:
+            assert call["step0"] % R + K > R and c["bonus"] is None and c["done"] is None     # the rows wrap
+            wraps.add((mode, R, K, call["step0"]))
+            continue
+        seen.add((K, L, mode, c["bonus"] is not None, c["done"] is not None, rings["done_mode"], call["gamma"], call["lambda_"],
+                  c["last_value"] is not None))
+        if rings["done_mode"] == "all":
+            assert c["done"].all()
+        if rings["done_mode"] == "last":
+            assert c["done"][K - 1].all() and not c["done"][:K - 1].any()
+        if rings["done_mode"] == "some":
+            assert gae_ref.some_conditions(c["done"], K) == (True, True, True), (rings, gae_ref.some_conditions(c["done"], K))
+            some += 1
+    modes = {(m["use_gae"], m["use_critic"]) for m in gae_ref.MODES.values()}
+    instances = {(m, b, d) for m in modes for b in (False, True) for d in (False, True)}
+    for K in gae_ref.BLOCK_STEPS:
+        assert {(s[2], s[3], s[4]) for s in seen if s[0] == K} == instances, K
+        assert {s[1] for s in seen if s[0] == K} == set(gae_ref.BLOCK_LANES), K
+    for m in modes:
+        mine = [s for s in seen if s[2] == m]
+        assert {s[1] for s in mine} == set(gae_ref.BLOCK_LANES)
+        assert {s[5] for s in mine} == {"none", "all", "last", "some"}
+        assert {s[6] for s in mine} == set(gae_ref.GAMMAS) and {s[7] for s in mine} == set(gae_ref.LAMBDAS)
+        assert {s[8] for s in mine} == {False, True}                   # last_value given and absent
+        assert {w[1:] for w in wraps if w[0] == m} == {(40, 33, 30), (17, 16, 9), (48, 48, 47)}
+    assert some == len(gae_ref.SOME_SEEDS) == 18
+    assert {s[1] for s in seen if s[5] == "some"} >= {1, 64, 65, 128}  # one lane, whole last waves and a wave with spare lanes
 
 
 def test_three_steps_by_hand():

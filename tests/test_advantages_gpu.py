@@ -1,6 +1,7 @@
 """Advantages and value targets on the device (csrc/ssd_gae.hip): the kernel against the tests'
-restatement (gae_ref.py) bit for bit -- the synthetic matrix of the CPU suite, the full-size shapes, out= and a stream of the
-caller's -- and SSDVectorEnv.sample(..., gamma=...) end to end for the three Harvest / Cleanup policies."""
+restatement (gae_ref.py) bit for bit -- the synthetic matrix of the CPU suite, every kernel instance at every count of full
+blocks of 16 steps (gae_ref.block_matrix()), the full-size shapes, out= and a stream of the caller's -- and
+SSDVectorEnv.sample(..., gamma=...) end to end for the three Harvest / Cleanup policies."""
 import numpy as np
 import pytest
 import torch
@@ -15,6 +16,7 @@ from sequential_social_dilemma_games_amd.vector_env import SSDVectorEnv
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
 CASES = gae_ref.matrix()
+BLOCK_CASES = gae_ref.block_matrix()
 
 
 def _dev(c):
@@ -34,6 +36,13 @@ def _check(c, call, **extra):
 @pytest.mark.parametrize("name,rings,call", CASES, ids=[c[0] for c in CASES])
 def test_kernel_equals_the_restatement(name, rings, call):
     _check(make_rings(**rings), call)
+
+
+@pytest.mark.parametrize("name,rings,call", BLOCK_CASES, ids=[c[0] for c in BLOCK_CASES])
+def test_blocks_buffers_and_waves(name, rings, call):
+    """Every kernel instance at no, one, two and three full blocks of 16 steps, each alone, one step short and one over; whole
+    and partial last waves; test_advantages_cpu.py asserts what the cases cover."""
+    _check(gae_ref.build(rings, call), call)
 
 
 @pytest.mark.parametrize("mode", sorted(gae_ref.MODES))

@@ -1,6 +1,7 @@
 """Batch moments without a device (include/ssd.h, BATCH MOMENTS): the tests' restatement of the header's
 summation order against an independent float64 check within the bound moments_ref derives, the package's host path against
-the restatement bit for bit, every refusal by its words, update_kl_coeff at its thresholds, and the ABI block."""
+the restatement bit for bit (at 255 to 513 chunks per set too, with inputs that tell five wrong orders of the across-chunk
+sum from the right one), every refusal by its words, update_kl_coeff at its thresholds, and the ABI block."""
 import ctypes as C
 import os
 import re
@@ -76,6 +77,39 @@ def test_host_path_equals_the_restatement(name, P, x):
     pred = (x * np.float32(0.75) + M.noise(9, x.shape, scale=0.1)).astype(np.float32)
     ev = explained_variance(torch.from_numpy(x), torch.from_numpy(pred), num_sets=P)
     assert same_bits_or_nan(ev.numpy(), M.explained_variance_ref(x, pred, num_sets=P))
+
+
+@pytest.mark.parametrize("P,n,seed", M.STAGE_CASES, ids=M.STAGE_IDS)
+def test_host_path_equals_the_restatement_at_the_stage_boundaries(P, n, seed):
+    """255, 256, 257 and 513 chunks per set: the twin of the device test of that name."""
+    x, pred, want, want_m, want_ev = M.stage_input(P, n, seed)
+    assert -(-n // W) in (M.BLOCK - 1, M.BLOCK, M.BLOCK + 1, 2 * M.BLOCK + 1) and x.shape == (n, P)
+    x, pred = torch.tensor(x), torch.tensor(pred)                # (copies: the shared inputs are read-only)
+    out, moments = standardize_advantages(x, num_sets=P, return_moments=True)
+    assert same_bits(moments.numpy(), want_m), (moments.numpy(), want_m)
+    assert same_bits(out.numpy(), want)
+    ev = explained_variance(x, pred, num_sets=P)
+    assert same_bits(ev.numpy(), want_ev) and np.isfinite(want_ev).all()
+
+
+@pytest.mark.parametrize("P,n,seed", M.STAGE_CASES, ids=M.STAGE_IDS)
+def test_the_stage_inputs_tell_a_wrong_order_from_the_right_one(P, n, seed):
+    """`moments` is what pins the across-chunk order on the device, so for every set of every input each wrong order that can
+    differ at its chunk count changes the bits of the mean, and -- from the right mean, with S2 alone added in that order -- of
+    the std: all five at 513 chunks; below, the reversed one and the two ways of letting each wave add its 64 partials (the
+    four sub-totals one after the other onto the sum, or among themselves first).  Sub-totals of 256 are the contract's own
+    order up to 257 chunks, which is asserted too."""
+    x, _, _, want_m, _ = M.stage_input(P, n, seed)
+    chunks = -(-n // W)
+    orders = list(M.WRONG_ORDERS) if chunks > 2 * M.BLOCK else ["reversed", "subtotals_of_64", "waves_then_pairs"]
+    for p in range(P):
+        got = M.wrong_moments(x[:, p].astype(np.float64), orders + ["subtotals_of_256"])
+        assert same_bits(np.array(got[None]), want_m[p])
+        for o in orders:
+            assert M.bits(got[o][0]) != M.bits(want_m[p, 0]), (p, o, "mean")
+            assert M.bits(got[o][1]) != M.bits(want_m[p, 1]), (p, o, "std")
+        if chunks <= M.BLOCK + 1:
+            assert same_bits(np.array(got["subtotals_of_256"]), want_m[p])
 
 
 def test_host_path_ring_rows_in_place_and_shapes():

@@ -1,8 +1,9 @@
 """Batch moments on the device (csrc/ssd_moments.hip; include/ssd.h, BATCH MOMENTS): ssd_standardize and
 ssd_explained_variance against the tests' restatement of the header's summation order (moments_ref.py) bit for bit -- out,
-moments and the explained variance -- at the per-set counts around W, the elements a workgroup takes per pass; the ring rows,
-in place, the second pass, the edges of the explained variance; and SSDVectorEnv.sample(..., standardize=True) and one PPO
-loss on standardised advantages end to end."""
+moments and the explained variance -- at the per-set counts around W, the elements a workgroup takes per pass, and at 255 to
+513 chunks per set, where the kernels add the partials in stages of 256; the ring rows, in place, the second pass, the edges
+of the explained variance; and SSDVectorEnv.sample(..., standardize=True) and one PPO loss on standardised advantages end to
+end."""
 import copy
 
 import numpy as np
@@ -97,6 +98,101 @@ def test_in_place_equals_out_of_place_over_several_workgroups():
     assert apart.data_ptr() != t.data_ptr() and torch.equal(t, _dev(x))        # the input is left alone
     standardize_advantages(t, num_sets=5, out=t)
     assert same_bits(t.cpu().numpy(), apart.cpu().numpy())
+
+
+# ------------------------------------------------------------------------- past 256 chunks: the stages of combine()
+# The kernels add the chunk partials of a set 256 at a time from LDS: a full stage and a short one are two branches, and LDS is
+# reused from stage to stage and from quantity to quantity.  The counts above reach four chunks.  `moments` is float64 and
+# pins the order; `out`, a float32, hides a wrong one (moments_ref.STAGE_CASES has how the inputs were chosen).
+BIG = M.STAGE_CASES[3]                                            # one set of 513 chunks: two full stages and a short one
+THREE = M.STAGE_CASES[4]                                          # three sets of 257 chunks: a full stage and one partial
+
+
+@pytest.mark.parametrize("P,n,seed", M.STAGE_CASES, ids=M.STAGE_IDS)
+def test_device_equals_the_restatement_at_the_stage_boundaries(P, n, seed):
+    x, pred, want, want_m, want_ev = M.stage_input(P, n, seed)
+    a, b = _dev(x), _dev(pred)
+    out, moments = standardize_advantages(a, num_sets=P, return_moments=True)
+    ev = explained_variance(a, b, num_sets=P)
+    out2, moments2 = standardize_advantages(a, num_sets=P, return_moments=True)
+    ev2 = explained_variance(a, b, num_sets=P)
+    out, moments, ev = out.cpu().numpy(), moments.cpu().numpy(), ev.cpu().numpy()
+    assert same_bits(moments, want_m), (moments, want_m)
+    assert same_bits(out, want), np.argwhere(M.bits(out) != M.bits(want))[:5]
+    assert same_bits(ev, want_ev), (ev, want_ev)
+    for u, v in ((out, out2), (moments, moments2), (ev, ev2)):    # a second call gives the same bits
+        assert same_bits(u, v.cpu().numpy())
+
+
+def test_the_wrap_inside_a_late_chunk():
+    """[260, 4099], step0 = 130, n_steps = 257: 258 chunks, and split = 130 x 4099 = 130 W + 130 x 3 falls in chunk 130 at
+    offset 390 = 1 x 256 + 134 -- item 1 of thread 134, whose sixteen elements so come from both ends of the ring."""
+    R, L, step0, K = 260, 4099, 130, 257
+    assert -(-(K * L) // W) == 258 and divmod((R - step0) * L, W) == (130, 256 + 134)
+    x, pred = M.noise(31, (R, L), scale=2.0, offset=0.25), M.noise(32, (R, L))
+    want, want_m = M.standardize_ref(x, step0=step0, n_steps=K)
+    inside = M.call_rows(R, step0, K)
+    outside = sorted(set(range(R)) - set(inside))
+    assert outside == [127, 128, 129]
+    fill = torch.full((R, L), 9.0, device=DEV)
+    out, moments = standardize_advantages(_dev(x), step0=step0, n_steps=K, out=fill, return_moments=True)
+    got = out.cpu().numpy()
+    assert out is fill and same_bits(moments.cpu().numpy(), want_m)
+    assert same_bits(got[inside], want[inside]) and np.all(got[outside] == 9.0)
+    t = _dev(x)
+    assert standardize_advantages(t, step0=step0, n_steps=K, out=t) is t
+    assert same_bits(t.cpu().numpy(), want)                      # (want holds x in the rows outside the call)
+    past, past_m = standardize_advantages(_dev(x), step0=step0 + R * 3, n_steps=K, return_moments=True)   # step0 past the ring: mod
+    past = past.cpu().numpy()
+    assert same_bits(past[inside], want[inside]) and not past[outside].any() and same_bits(past_m.cpu().numpy(), want_m)
+    ev = explained_variance(_dev(x), _dev(pred), step0=step0, n_steps=K).cpu().numpy()
+    assert same_bits(ev, M.explained_variance_ref(x, pred, step0=step0, n_steps=K))
+
+
+def test_the_scratch_on_entry_does_not_matter():
+    """The 513-chunk call once; NaN in every scratch tensor the package holds; a one-chunk call, which has another scratch size;
+    then the big call and the big explained variance give their bits again."""
+    from sequential_social_dilemma_games_amd import postprocessing
+    P, n, seed = BIG
+    x, pred, want, want_m, want_ev = M.stage_input(P, n, seed)
+    a, b = _dev(x), _dev(pred)
+    standardize_advantages(a, num_sets=P)
+    explained_variance(a, b, num_sets=P)
+    torch.cuda.synchronize()
+    assert len(postprocessing._moments_scratch) >= 1
+    for buf in postprocessing._moments_scratch.values():
+        buf.fill_(float("nan"))
+    small = _input(W, 1)
+    got = standardize_advantages(_dev(small[0]), num_sets=1)
+    assert same_bits(got.cpu().numpy(), small[2])
+    assert len({buf.numel() for buf in postprocessing._moments_scratch.values()}) >= 2
+    out, moments = standardize_advantages(a, num_sets=P, return_moments=True)
+    ev = explained_variance(a, b, num_sets=P)
+    assert same_bits(moments.cpu().numpy(), want_m) and same_bits(out.cpu().numpy(), want) and same_bits(ev.cpu().numpy(), want_ev)
+
+
+def test_in_place_equals_out_of_place_at_513_chunks():
+    P, n, seed = BIG
+    x, _, want, _, _ = M.stage_input(P, n, seed)
+    t = _dev(x)
+    apart = standardize_advantages(t, num_sets=P)
+    assert apart.data_ptr() != t.data_ptr() and torch.equal(t, _dev(x))        # the input is left alone
+    standardize_advantages(t, num_sets=P, out=t)
+    assert same_bits(t.cpu().numpy(), apart.cpu().numpy()) and same_bits(t.cpu().numpy(), want)
+
+
+def test_one_constant_set_among_three_at_257_chunks():
+    """A float32 constant adds up exactly through every stage, so a stray or a missing partial of that set shows as a mean
+    that is not the constant, a std or an `out` that is not 0; the other two sets are the restatement's as they were."""
+    P, n, seed = THREE
+    x0, _, want0, want_m0, _ = M.stage_input(P, n, seed)
+    x = x0.copy()
+    x[:, 1] = np.float32(3.7)
+    out, moments = standardize_advantages(_dev(x), num_sets=P, return_moments=True)
+    out, moments = out.cpu().numpy(), moments.cpu().numpy()
+    assert same_bits(out[:, 1], np.zeros(n, np.float32))
+    assert same_bits(moments[1], np.array([np.float64(np.float32(3.7)), 0.0]))
+    assert same_bits(out[:, [0, 2]], want0[:, [0, 2]]) and same_bits(moments[[0, 2]], want_m0[[0, 2]])
 
 
 def test_the_second_pass_at_a_large_offset():

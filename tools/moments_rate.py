@@ -1,6 +1,8 @@
 """What the batch moments cost: ssd_standardize and ssd_explained_variance (three launches each) against
 the torch expressions a user writes without them, alternated in one process, with the bytes each must move as a fraction of the
-practical HBM rate, and SSDVectorEnv.sample of 128 steps with and without standardize.  Device events around work that ends in
+practical HBM rate, and SSDVectorEnv.sample of 128 steps with and without standardize.  Before a shape is timed the device's
+out, moments and explained variance are compared with the package's CPU path bit for bit, on the whole shape, and the tool stops
+with a message if they differ.  Device events around work that ends in
 a synchronise; per leg the median over the rounds and the rounds' range; one JSON line per figure, the library's sha first.
 
     python tools/moments_rate.py [--rounds 7] [--reps 100] [--skip-sample]
@@ -59,11 +61,32 @@ def torch_explained_variance(y, pred, P):
     return (1 - d.var(0, unbiased=False) / y.var(0, unbiased=False)).clamp_min(-1)
 
 
+def same_bits(a, b):
+    """Two tensors of one dtype hold the same bits (a NaN equals itself, +0.0 does not equal -0.0)."""
+    a, b = a.cpu().contiguous(), b.cpu().contiguous()
+    as_int = torch.int32 if a.dtype == torch.float32 else torch.int64
+    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.view(as_int), b.view(as_int))
+
+
+def verify(x, pred, P):
+    """What is timed below is what the contract says: the device's out, moments and explained variance against the package's
+    CPU path (the NumPy restatement of the summation order, which the suite pins), bit for bit, on the whole shape."""
+    out, moments = standardize_advantages(x, num_sets=P, return_moments=True)
+    ev = explained_variance(x, pred, num_sets=P)
+    host_out, host_moments = standardize_advantages(x.cpu(), num_sets=P, return_moments=True)
+    host_ev = explained_variance(x.cpu(), pred.cpu(), num_sets=P)
+    for name, got, want in (("out", out, host_out), ("moments", moments, host_moments), ("explained variance", ev, host_ev)):
+        if not same_bits(got, want):
+            sys.exit("moments_rate: at shape %s with %d set(s) the device's %s differs from the package's CPU path: nothing timed"
+                     % (list(x.shape), P, name))
+
+
 def kernel_rate(shape, P, rounds, reps):
     g = torch.Generator(device=DEV)
     g.manual_seed(0)
     x = torch.randn(shape, device=DEV, generator=g) * 3.0 + 0.5
     pred = x * 0.7 + 0.3 * torch.randn(shape, device=DEV, generator=g)
+    verify(x, pred, P)
     out = torch.empty_like(x)
     res = alternated({"ssd_standardize": lambda: standardize_advantages(x, num_sets=P, out=out),
                       "torch_standardize": lambda: torch_standardize(x, P),
@@ -73,7 +96,8 @@ def kernel_rate(shape, P, rounds, reps):
     moved = {"ssd_standardize": 3 * 4 * floats,                  # two reads and one write of the tensor
              "ssd_explained_variance": 4 * 4 * floats}           # two reads of both tensors
     diff = float((out - torch_standardize(x, P)).abs().max())
-    line = {"shape": list(shape), "num_sets": P, "floats": floats, "max_abs_diff_to_torch": diff}
+    line = {"shape": list(shape), "num_sets": P, "floats": floats, "equals_cpu_path_bit_for_bit": True,   # (verify() above)
+            "max_abs_diff_to_torch": diff}
     for name, r in res.items():
         line[name] = r
         if name in moved:
