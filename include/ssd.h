@@ -177,7 +177,9 @@ int ssd_rollout_actions(ssd_env *env, const int32_t *actions, const uint8_t *ord
  *   SSD_PATH_COHERENT  ... with the kernel variant that needs no cache write-back between a chain's launches
  *   SSD_PATH_SPLIT     ... and every step's observations rendered by extra workgroups of the next launch
  *   SSD_PATH_PAIRS     ... and the chains' launches took more than one step each: runs of four wherever four steps remained before
- *                      the call's end and the next reset, else of two where two remained (bits 20..22 say how long the longest was)
+ *                      the call's end and the next reset, else of two where two remained; in calls of 256 steps or more, where the
+ *                      form's kernel has a long instantiation (Harvest 16 x 38 with 5 agents), runs of eight wherever eight remained
+ *                      (bits 20..23 say how long the longest was)
  *   SSD_PATH_FUSED     the call ran as the fused rollout kernel
  *   SSD_PATH_SYNC      ... with host-side waits instead of waiting kernels (a profiling tool is attached, or SSD_AQL_SYNC=1)
  *   SSD_PATH_FORKED    ... behind a fork from `stream`, which had work pending when the call came
@@ -185,7 +187,7 @@ int ssd_rollout_actions(ssd_env *env, const int32_t *actions, const uint8_t *ord
  *   bits 8..11         number of chains        bits 12..14  dispatch queues the device's pool has settled on
  *   bits 16..17        how the library found the HSA agent of the handle's HIP device: 1 PCI address, 2 UUID, 3 ordinal (cross-
  *                      checked by architecture and compute-unit count); 0: not at all -- no dispatch path of its own on this device
- *   bits 20..22        the longest run of steps one launch of the call took: 1, 2 or 4 (SSD_PATH_RUN_SHIFT; 0: the call did not go
+ *   bits 20..23        the longest run of steps one launch of the call took: 1, 2, 4 or 8 (SSD_PATH_RUN_SHIFT; 0: the call did not go
  *                      through the library's own queues)
  * So that a caller (a test, a benchmark) can tell a silent fallback from the path it meant to measure. */
 enum { SSD_PATH_AQL = 1, SSD_PATH_COHERENT = 2, SSD_PATH_SPLIT = 4, SSD_PATH_FUSED = 8, SSD_PATH_SYNC = 16, SSD_PATH_QUEUE_DROPPED = 32,
@@ -223,8 +225,8 @@ int ssd_rollout_path(const ssd_env *env);
  *   SSD_ROLLOUT_CHAINS=n chains of the rollout calls when ssd_set_rollout_chains is 0
  *   SSD_ENVS_PER_BLOCK=n envs (waves) per workgroup, 1..16
  * Nothing here changes results.  The knobs that CAN (fence scopes, alternating geometries, forced forks) -- and SSD_AQL_PAIRS=0,
- * which keeps the split chains at one step per launch, and SSD_AQL_RUN=1..4, which caps the steps one launch takes (same results;
- * for A/B runs and tests) -- exist only in the
+ * which keeps the split chains at one step per launch, and SSD_AQL_RUN=1..4, which caps the steps one launch takes (4: long
+ * calls in runs of four, as calls below 256 steps; 8: no cap; same results; for A/B runs and tests) -- exist only in the
  * test-hook build, libssd_hip_testhooks.so (make testhooks), which the product never loads. */
 int ssd_set_rollout_chains(ssd_env *env, int32_t chains);
 

@@ -16,7 +16,7 @@ SSD_HOST_PTRS, SSD_NO_ROTATE, SSD_OBS_F32, SSD_ROLLOUT_FUSED, SSD_AUTO_RESET, SS
 SSD_POLICY_GREEDY = 256
 SSD_PATH_AQL, SSD_PATH_COHERENT, SSD_PATH_SPLIT, SSD_PATH_FUSED, SSD_PATH_SYNC, SSD_PATH_QUEUE_DROPPED, SSD_PATH_FORKED = 1, 2, 4, 8, 16, 32, 64
 SSD_PATH_PAIRS = 128
-SSD_PATH_RUN_SHIFT = 20            # bits 20..22: the longest run of steps one launch of the call took
+SSD_PATH_RUN_SHIFT = 20            # bits 20..23: the longest run of steps one launch of the call took
 SSD_ST_BAD_ACTION, SSD_ST_NO_SPAWN, SSD_ST_MOVE_LOOKUP, SSD_ST_WAIT_TIMEOUT = 1, 2, 4, 8
 ABI_VERSION = 6
 SSD_WS_SEQ, SSD_WS_SEQ_COMM = 0, 1

@@ -31,8 +31,10 @@ enum Mode : int32_t {
     kModeStep = 0, kModeReset = 1, kModeObserve = 2,
     kModeRollout = 3,      // n_steps random-action steps in ONE launch
     kModeStepAuto = 4,     // a step that also resets, in the same launch, the envs that reach the horizon (SSD_AUTO_RESET)
-    kModeStepPair = 5      // split rollouts: the env waves take a RUN of 1 .. kMaxRun consecutive steps per launch, the env resident in LDS
+    kModeStepPair = 5,     // split rollouts: the env waves take a RUN of 1 .. kMaxRun consecutive steps per launch, the env resident in LDS
                            // and registers between them (the map-specific coherent kernels only; ssd_rollout_plan.hpp, Schedule)
+    kModeStepLong = 6      // the same with runs of up to kLongRun steps and a LongParams block: the launches of long calls that take or
+                           // render a run of kLongRun (a kernel of its own: the step-pair kernels stay what they are)
 };
 
 // PRNG streams (sequential_social_dilemma_games_amd/prng.py)
@@ -137,6 +139,17 @@ struct PairParams {
     uint8_t *obs_b0[kMaxRun - 1];
 };
 
+// A long launch's block (kModeStepLong): PairParams' layout with room for a run of kLongRun -- 8 pass records, and the renderers' 7 mid
+// inputs laid out from the end of the run they render: slot kLongRun - 1 is its last step (Params::beam_list_in / snap_in / obs_b),
+// slot t < kLongRun - 1 the step kLongRun - 1 - t before it.  n_pass and n_render are 0, 1, 2, 4 or 8, one of them 8.
+constexpr int kLongRun = 8;
+struct LongParams {
+    PassRec pass[kLongRun];
+    int32_t n_pass, n_render;
+    MidIn mid_in[kLongRun - 1];
+    uint8_t *obs_b0[kLongRun - 1];
+};
+
 // The kernarg segment of ssd_env_kernel: its nine leading arguments (repeated Params fields, 56 bytes: preloaded into SGPRs
 // by the command processor) followed by the parameter block.  Natural C layout == the code object's argument offsets.
 struct KernArgs {
@@ -149,6 +162,9 @@ static_assert(sizeof(KernArgs) == 56 + sizeof(Params), "kernarg layout");
 // ... and of ssd_env_pair_kernel: the same, then the pair's block
 struct PairKernArgs { KernArgs k; PairParams q; };
 static_assert(sizeof(PairKernArgs) == sizeof(KernArgs) + sizeof(PairParams), "kernarg layout");
+// ... and of its long instantiations (kModeStepLong)
+struct LongKernArgs { KernArgs k; LongParams q; };
+static_assert(sizeof(LongKernArgs) == sizeof(KernArgs) + sizeof(LongParams), "kernarg layout");
 
 // One launch, fully resolved: instantiation (host stub of the __global__), geometry, dynamic LDS bytes, kernel arguments.
 struct Launch {
@@ -156,6 +172,7 @@ struct Launch {
     uint32_t grid_x = 0, block_x = 0, lds = 0;
     KernArgs args;
     PairParams pair{};             // (kModeStepPair: lies right behind `args`, together the kernel's PairKernArgs)
+    // (kModeStepLong: the caller lays the launch's LongParams behind a copy of `args` itself)
     size_t args_bytes() const { return args.p.mode == kModeStepPair ? sizeof(PairKernArgs) : sizeof(KernArgs); }
 };
 static_assert(offsetof(Launch, pair) == offsetof(Launch, args) + sizeof(KernArgs), "Launch::args + Launch::pair == PairKernArgs");
@@ -170,6 +187,7 @@ size_t lds_bytes(const Params &p, int envs_per_block, bool f32);
 int envs_per_block(const Params &p, bool f32);
 int fast_profile(const Params &p, int game);    // which map-specific step kernel a launch gets (0: the general ones)
 int pair_profile(const Params &p, int game);    // the longest run of steps a coherent step launch of this form has a kernel for (1: single steps only)
+int long_profile(const Params &p, int game);    // kLongRun where that form also has a kernel for runs of kLongRun steps (kModeStepLong), else 0
 bool select(const Params &p, int game, Launch *out, const PairParams *pair = nullptr);   // resolve a launch without issuing it (kModeStepPair: with its block)
 void launch(const Launch &L, void *stream);            // hipLaunchKernel of a resolved launch
 void launch(const Params &p, int game, void *stream);

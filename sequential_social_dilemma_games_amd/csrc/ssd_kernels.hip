@@ -376,7 +376,7 @@ template <int GAME, int MODE, bool F32, int NA, bool STD, int FAST, bool COH = f
 // loads of the env's state go out without first waiting ~0.3 us for a scalar load of the kernel arguments.
 // The step-pair kernels (kModeStepPair) are held to eight waves per SIMD: a step's two launches fill the device's wave slots exactly
 // (DESIGN.md section 5).  (0, 0 = no attribute: the other kernels are compiled as ever.)
-__global__ __launch_bounds__(64 * kMaxEnvsPerBlock) __attribute__((amdgpu_waves_per_eu(MODE == kModeStepPair ? 8 : 0, MODE == kModeStepPair ? 8 : 0)))
+__global__ __launch_bounds__(64 * kMaxEnvsPerBlock) __attribute__((amdgpu_waves_per_eu((MODE == kModeStepPair || MODE == kModeStepLong) ? 8 : 0, (MODE == kModeStepPair || MODE == kModeStepLong) ? 8 : 0)))
 void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const a_world,
                                                                         const int a_E, const int a_e_begin, const int a_epb, const int a_n_apple,
                                                                         const uint32_t *const a_apple_cells, const uint32_t *const a_lut,
@@ -385,12 +385,15 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
     // dispatch (ssd_capi.hip, aql_set) writes a PairKernArgs -- so that the other kernels keep their signature, argument offsets and code.
     // Nothing of it is copied here: a pass of the env role fetches its own record (PassRec) a phase ahead of its first use, the
     // renderer role its five inputs inside its branch -- scalar loads of what the role under way needs, and of nothing else.
+    // (a long instantiation, kModeStepLong: the same block with room for a run of kLongRun -- LongParams; QP names whichever it is)
+    constexpr bool lng = MODE == kModeStepLong;
+    using QP = std::conditional_t<lng, LongParams, PairParams>;
     typedef const __attribute__((address_space(4))) uint64_t karg_u64;
     [[maybe_unused]] karg_u64 *const qargs = (karg_u64 *)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(KernArgs));
     // (one pointer of the block, by its byte offset in PairParams)
     [[maybe_unused]] auto qptr = [&](size_t at, auto *like) { return reinterpret_cast<decltype(like)>(qargs[at / 8]); };
     [[maybe_unused]] auto load_rec = [&](int k) {
-        const size_t at = offsetof(PairParams, pass) + (size_t)k * sizeof(PassRec);
+        const size_t at = offsetof(QP, pass) + (size_t)k * sizeof(PassRec);
         PassRec r;
         r.world = qptr(at + offsetof(PassRec, world), r.world); r.agents = qptr(at + offsetof(PassRec, agents), r.agents);
         r.beam_list = qptr(at + offsetof(PassRec, beam_list), r.beam_list); r.snap = qptr(at + offsetof(PassRec, snap), r.snap);
@@ -428,7 +431,7 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
     constexpr bool auto_mode = MODE == kModeStepAuto;
     // Two steps per launch (split rollouts, the map-specific coherent kernels): the step pass twice, the env resident in LDS and
     // registers in between as in a rollout launch, every step's state handed to the renderer workgroups of the next launch.
-    constexpr bool pair = MODE == kModeStepPair;
+    constexpr bool pair = MODE == kModeStepPair || lng;
     constexpr bool stepping = MODE == kModeStep || auto_mode || pair;   // the launch takes actions
     uint32_t *s_lut = reinterpret_cast<uint32_t *>(smem + (size_t)wv * (512 + 256 + (F32 ? 2048 : 0) + (size_t)A0 + (size_t)A1 +
                                                                             (roll ? 4 : 3) * (size_t)S));
@@ -534,7 +537,7 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
     //      the first use; the wave's LDS region holds two layers with aprons, so the steps are filled and rendered in rounds of two:
     //      slots 0 and 1, then slots 2 and 3.  With a ring of one slot all steps store the same bytes from the same lanes with the
     //      same policy, in program order: the last step's stay. ----
-    if constexpr (pair && COH && STD && NA > 0 && NA % 5 == 0 && !F32 && FAST != 0) {
+    if constexpr (pair && !lng && COH && STD && NA > 0 && NA % 5 == 0 && !F32 && FAST != 0) {
         if ((p.snap_mode & 2) && blk >= p.blocks_a) {
             const int eb = a_e_begin + (blk - p.blocks_a) * a_epb + wv;
             if (eb < a_E) {
@@ -655,6 +658,128 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
             return;
         }
     }
+    // ---- and in the long instantiations (kModeStepLong): the launch before took a run of n_render = 1, 2, 4 or kLongRun steps.  A wave
+    //      does not hold eight steps' state in registers (7 registers a step): it runs the four-step body above once per HALF of the
+    //      block's eight slots -- slots 0 .. 3 (a run of eight alone), then slots 4 .. 7 -- loading, filling and rendering a half's
+    //      steps before it loads the next half's, strictly in step order.  A half's last slot is its fourth: slot 3 is a mid set like
+    //      the others, slot 7 the state this launch steps from.  The aprons are written once; with a ring of one slot the last step's
+    //      bytes stay, as above. ----
+    if constexpr (lng && COH && STD && NA > 0 && NA % 5 == 0 && !F32 && FAST != 0) {
+        if ((p.snap_mode & 2) && blk >= p.blocks_a) {
+            const int eb = a_e_begin + (blk - p.blocks_a) * a_epb + wv;
+            if (eb < a_E) {
+                typedef __attribute__((address_space(3))) const uint8_t lds_u8;
+                constexpr int kGridLoads = (fm.S + 1023) / 1024;
+                constexpr bool kTwoLists = GAME == 1 && NA > 5;
+                constexpr int kHalf = kLongRun / 2;
+                static_assert(kHalf == 4, "a half is the step-pair kernels' two rounds of two layers");
+                const int n_render = (int)(uint32_t)(qargs[offsetof(LongParams, n_pass) / 8] >> 32);
+                struct MidPtr { const uint8_t *world; const uint32_t *agents; const uint32_t *list; const uint8_t *snap; uint8_t *obs; };
+                auto mid_ptr = [&](int t) {                              // (t: wave-uniform, 0 .. kLongRun - 2)
+                    const size_t at = offsetof(LongParams, mid_in) + (size_t)t * sizeof(MidIn);
+                    MidPtr m;
+                    m.world = qptr(at + offsetof(MidIn, world), m.world); m.agents = qptr(at + offsetof(MidIn, agents), m.agents);
+                    m.list = qptr(at + offsetof(MidIn, beam_list), m.list); m.snap = qptr(at + offsetof(MidIn, snap), m.snap);
+                    m.obs = qptr(offsetof(LongParams, obs_b0) + (size_t)t * sizeof(uint8_t *), m.obs);
+                    return m;
+                };
+                struct StepIn { u32x4_t g[kGridLoads]; uint32_t areg, entry, entry2; };
+                auto fetch = [&](const uint8_t *world, const uint32_t *agents, const uint32_t *list) {
+                    StepIn s;
+                    const rsrc_t grid_r = make_rsrc(world + (size_t)eb * S, (uint32_t)S);
+#pragma unroll
+                    for (int j = 0; j < kGridLoads; ++j) s.g[j] = load16_sc1(grid_r, (uint32_t)(lane * 16 + j * 1024));
+                    s.areg = 0; s.entry2 = 0;
+                    if (lane < N) s.areg = __hip_atomic_load(agents + (size_t)eb * N + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    s.entry = __hip_atomic_load(list + (size_t)eb * 64 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    return s;
+                };
+                auto fetch_rare = [&](StepIn &s, const uint32_t *list, const uint8_t *snap) {
+                    const uint32_t flags = rfl(s.areg) >> 20;
+                    if (kTwoLists && (flags & 4u)) s.entry2 = __hip_atomic_load(list + ((size_t)p.E_total + eb) * 64 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (flags & 2u) {
+                        const rsrc_t snap_r = make_rsrc(snap + (size_t)eb * S, (uint32_t)S);
+#pragma unroll
+                        for (int j = 0; j < kGridLoads; ++j) s.g[j] = load16_sc1(snap_r, (uint32_t)(lane * 16 + j * 1024));
+                    }
+                };
+                const uint32_t lut_a = a_lut[lane], lut_b = a_lut[lane + 64];
+                const uint4 vt0 = reinterpret_cast<const uint4 *>(p.view_tab)[2 * lane], vt1 = reinterpret_cast<const uint4 *>(p.view_tab)[2 * lane + 1];
+                static_assert(fm.S >= fm.A0 + fm.A1, "the renderer's second layer fits the beam and occupancy layers");
+                uint8_t *const s_world2 = s_world + S + A1 + A0;
+                {   // the aprons of both layers, once for all halves and rounds (a single step uses the first layer alone)
+                    const uint4 z = make_uint4(0x30303030u, 0x30303030u, 0x30303030u, 0x30303030u);
+                    const int n0 = A0 >> 4, n1 = A1 >> 4;
+                    for (int i = lane; i < n0 + n1; i += 64) {
+                        const int at = i < n0 ? i * 16 - A0 : S + (i - n0) * 16;
+                        *reinterpret_cast<uint4 *>(s_world + at) = z;
+                        if (n_render > 1) *reinterpret_cast<uint4 *>(s_world2 + at) = z;
+                    }
+                }
+                s_lut[lane] = lut_a; s_lut[lane + 64] = lut_b;
+                auto fill = [&](const StepIn &s, uint8_t *layer) {
+                    const uint32_t flags = rfl(s.areg) >> 20;
+#pragma unroll
+                    for (int j = 0; j < kGridLoads; ++j) {
+                        if (lane * 16 + j * 1024 < S) *reinterpret_cast<uint4 *>(layer + lane * 16 + j * 1024) = make_uint4(s.g[j].x, s.g[j].y, s.g[j].z, s.g[j].w);
+                    }
+                    wave_sync();
+                    if (!(flags & 2u)) {
+                        if (lane < N && (s.areg & (1u << 19))) layer[s.areg & 0xFFFFu] = agent_glyph((uint32_t)lane);
+                        wave_sync();
+                        if (flags & 1u) {
+                            if (s.entry) layer[s.entry & 0xFFFFu] = (uint8_t)(s.entry >> 16);
+                            wave_sync();
+                            if constexpr (kTwoLists) {
+                                if (s.entry2) layer[s.entry2 & 0xFFFFu] = (uint8_t)(s.entry2 >> 16);
+                                wave_sync();
+                            }
+                        }
+                    }
+                };
+                auto views = [&](const uint32_t areg, const uint8_t *layer, uint8_t *obs_to) {
+                    const uint32_t cellb = areg & 0xFFFFu, orientb = (areg >> 16) & 3u;
+                    const uint32_t kq = (0x8Du >> (2u * orientb)) & 3u;
+                    const uint32_t s0 = (uint32_t)((int)cellb - 7 * (WP + 1) + (kq >= 2 ? 14 * (WP + 1) : 0));
+                    render_views_std<NA, true>(lane, WP, kq, s0, (uint32_t)(uintptr_t)(lds_u8 *)layer, s_lut, obs_to + (size_t)eb * N * SSD_OBS_STRIDE, p.obs_wt,
+                                               vt0, vt1);
+                };
+                // (one body for both halves, not unrolled: four steps' registers at a time)
+#pragma nounroll
+                for (int h = n_render > kHalf ? 0 : 1; h < 2; ++h) {
+                    const int t0 = kHalf * h;
+                    // slot t0 + t of the block is in use (wave-uniform); a half's last slot always is
+                    auto used = [&](int t) { return t0 + t >= kLongRun - n_render; };
+                    MidPtr last = MidPtr{a_world, a_agents, p.beam_list_in, p.snap_in, p.obs_b};
+                    if (h == 0) last = mid_ptr(kHalf - 1);
+                    StepIn sm[kHalf - 1];
+                    MidPtr mp[kHalf - 1];
+                    StepIn sb = fetch(last.world, last.agents, last.list);
+#pragma unroll
+                    for (int t = kHalf - 2; t >= 0; --t) {
+                        sm[t] = sb; mp[t] = MidPtr{};
+                        if (used(t)) { mp[t] = mid_ptr(t0 + t); sm[t] = fetch(mp[t].world, mp[t].agents, mp[t].list); }
+                    }
+                    fetch_rare(sb, last.list, last.snap);
+#pragma unroll
+                    for (int t = kHalf - 2; t >= 0; --t)
+                        if (used(t)) fetch_rare(sm[t], mp[t].list, mp[t].snap);
+                    if (used(1)) {                                       // the half's first round: its slots 0 and 1
+                        fill(sm[1], s_world);
+                        if (used(0)) { fill(sm[0], s_world2); views(sm[0].areg, s_world2, mp[0].obs); }
+                        views(sm[1].areg, s_world, mp[1].obs);
+                        wave_sync();                                     // (the round's LDS reads are issued ahead of the next round's writes)
+                    }
+                    fill(sb, s_world);
+                    if (used(2)) { fill(sm[2], s_world2); views(sm[2].areg, s_world2, mp[2].obs); }
+                    views(sb.areg, s_world, last.obs);
+                    wave_sync();                                         // (... and ahead of the next half's)
+                }
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+            return;
+        }
+    }
     const int e = a_e_begin + blk * a_epb + wv;             // (a_epb = blockDim.x / 64, without the implicit-argument load)
     constexpr int mode = pair ? (int)kModeStep : MODE;       // compile-time: step / reset / observe (a pair's passes are steps)
     bool active = e < a_E;                                   // wave-uniform
@@ -696,7 +821,7 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
         // kMaxRun - 1 counts higher -- lane l holds the entries of (count in the header + kPreUp - l), a pass reads lane (count in the
         // header + kPreUp - its own count).
         constexpr bool kPre = GAME == 1 && (MODE == kModeStep || pair) && COH && FAST != 0;
-        constexpr int kPreUp = pair ? kMaxRun - 1 : 0;
+        constexpr int kPreUp = lng ? kLongRun - 1 : pair ? kMaxRun - 1 : 0;
         uint4 hdr;
         // (a step-pair launch: where the pass under way leaves its state and outputs -- the record of the launch's first pass comes
         // with the prologue's other argument fetches, the second pass's at the top of that pass)
@@ -706,7 +831,7 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
             const uint32_t hv = cload(reinterpret_cast<const uint32_t *>(a_hdr + e) + (lane & 3));
             if constexpr (pair) {
                 rec = load_rec(0);
-                n_pass = (int)(uint32_t)qargs[offsetof(PairParams, n_pass) / 8];
+                n_pass = (int)(uint32_t)qargs[offsetof(QP, n_pass) / 8];
                 asm volatile("" ::"s"(rec.world), "s"(rec.agents), "s"(rec.beam_list), "s"(rec.snap), "s"(rec.rew), "s"(rec.done), "s"(n_pass));
             }
             // (these kernel arguments are fetched while the header is on its way)
@@ -725,7 +850,7 @@ void ssd_env_kernel(uint4 *const a_hdr, uint32_t *const a_agents, uint8_t *const
         int act_next = -1;                                     // (the actions of the pass or step after the one under way, where fetched ahead)
         // (a step-pair launch: pass k's slot of the caller's action ring, out of its record)
         [[maybe_unused]] auto next_actions = [&](int k) {
-            return qptr(offsetof(PairParams, pass) + (size_t)k * sizeof(PassRec) + offsetof(PassRec, actions), (const uint32_t *)nullptr);
+            return qptr(offsetof(QP, pass) + (size_t)k * sizeof(PassRec) + offsetof(PassRec, actions), (const uint32_t *)nullptr);
         };
         uint32_t ord_in = 0xFFu;
         // (the env's offset in every [E][N] array -- agents, actions, rewards, dones -- computed ONCE and kept in a scalar register: left
@@ -2075,6 +2200,12 @@ static const void *select_step(const Params &p) {
             if (p.coherent) return kernel_fn<GAME, kModeStepPair, false, NA, STD, FAST, true>();
         }
         return nullptr;
+    } else if (p.mode == kModeStepLong) {
+        // (runs of kLongRun: the forms long_profile() below names -- Harvest 16 x 38 with 5 agents)
+        if constexpr (GAME == 0 && FAST == 1 && NA == 5 && !F32 && STD) {
+            if (p.coherent) return kernel_fn<GAME, kModeStepLong, false, NA, STD, FAST, true>();
+        }
+        return nullptr;
     } else {
         if constexpr (!F32 && FAST != 0) {           // (the kernels rollouts of the known maps use)
             if (p.coherent) return kernel_fn<GAME, kModeStep, false, NA, STD, FAST, true>();
@@ -2108,9 +2239,16 @@ int pair_profile(const Params &p, int game) {
     return p.N == 5 ? run_max<1, 5, 1>() : run_max<1, 10, 1>();
 }
 
+// Where the form also has a long kernel (kModeStepLong, runs of kLongRun steps): kLongRun, else 0.  A long kernel is built only where
+// it compiles to eight waves per SIMD without scratch memory, without a spilled vector register and within 80 scalar registers
+// (profiles/r28_long_runs/spills.txt): Harvest 16 x 38 with 5 agents.
+int long_profile(const Params &p, int game) {
+    return (game == 0 && p.N == 5 && !p.obs_f32 && fast_profile(p, game) == 1 && pair_profile(p, game) == kMaxRun) ? kLongRun : 0;
+}
+
 template <int GAME, bool F32>
 static const void *select_game(const Params &p) {
-    if (p.mode == kModeStep || p.mode == kModeRollout || p.mode == kModeStepAuto || p.mode == kModeStepPair) {
+    if (p.mode == kModeStep || p.mode == kModeRollout || p.mode == kModeStepAuto || p.mode == kModeStepPair || p.mode == kModeStepLong) {
         // specialised step kernels for the reference's configurations (view 7, beam 5; 5 or 10 agents), and
         // among those the FAST ones for the game's shipped map called in the plain way
         const bool std_view = p.view_len == 7 && p.beam_len == 5;
@@ -2176,7 +2314,7 @@ bool select(const Params &p_in, int game, Launch *out, const PairParams *pair) {
 }
 
 void launch(const Launch &L, void *stream) {
-    if (L.args.p.mode == kModeStepPair) return;             // (its PairKernArgs only travel in the library's own packets)
+    if (L.args.p.mode == kModeStepPair || L.args.p.mode == kModeStepLong) return;   // (their blocks only travel in the library's own packets)
     KernArgs &k = const_cast<KernArgs &>(L.args);
     void *args[] = {&k.hdr, &k.agents, &k.world, &k.E, &k.e_begin, &k.epb, &k.n_apple, &k.apple_cells, &k.lut, &k.p};
     (void)hipLaunchKernel(L.fn, dim3(L.grid_x), dim3(L.block_x), args, L.lds, static_cast<hipStream_t>(stream));

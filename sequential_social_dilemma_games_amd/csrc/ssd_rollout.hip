@@ -74,19 +74,30 @@ struct AqlState : plan::SplitBuffers {          // (the buffers of split rollout
     struct Set {
         bool valid = false;
         Key key;
-        uint8_t *dev = nullptr;                     // [chains][slots][n_dense] blocks of kBlock bytes
+        uint8_t *dev = nullptr;                     // [chains][slots][n_dense] blocks of kBlock bytes; a long set: then [chains][slots][n_long] of kLongBlock
         size_t cap = 0;
-        Geo geo[8][plan::kKinds];                   // per chain and kind
+        Geo geo[8][plan::kAllKinds];                // per chain and kind
         plan::KindTable kinds;                      // the kinds the key's calls can use, and their blocks' places in one (chain, slot)
+        plan::LongKindTable long_kinds;             // ... and the long kinds' (a long set's; else none)
+        size_t long_at = 0;                         // where the long blocks begin
+        // the argument block of a packet: chain c, block index `block`, kind
+        uint8_t *block_of(int c, size_t block, int kind) const {
+            if (plan::is_long_kind(kind))
+                return dev + long_at + (((size_t)c * key.slots + block) * long_kinds.n_dense + long_kinds.dense[kind - plan::kKinds]) * kLongBlock;
+            return dev + (((size_t)c * key.slots + block) * kinds.n_dense + kinds.dense[kind]) * kBlock;
+        }
         uint64_t last_use[8] = {};                  // index of the last join packet after a use, per chain (+1)
         uint64_t stamp = 0;
     };
     static constexpr int kSets = 4;
     static constexpr size_t kBlock = 896;           // >= sizeof(ssd::PairKernArgs), a multiple of 64
+    static constexpr size_t kLongBlock = 1216;      // >= sizeof(ssd::LongKernArgs), a multiple of 64
+    bool long_tried = false;                        // the long mid sets were asked for once (SplitBuffers::long_*: all there, or none)
     Set sets[kSets];
     uint64_t clock = 0;
 };
 static_assert(AqlState::kBlock >= sizeof(ssd::PairKernArgs), "an argument block holds the largest kernarg segment");
+static_assert(AqlState::kLongBlock >= sizeof(ssd::LongKernArgs) && AqlState::kLongBlock % 64 == 0, "a long block holds a long launch's kernarg segment");
 
 void RolloutDelete::operator()(ChainWorker *w) const { delete w; }
 void RolloutDelete::operator()(AqlState *a) const { delete a; }
@@ -265,6 +276,9 @@ void aql_teardown(ssd_env *env) {
     for (int k = 0; k < plan::kMids; ++k)
         for (int i = 0; i < 2; ++i)
             for (void *m : {(void *)A.mid_world[k][i], (void *)A.mid_snap[k][i], (void *)A.mid_agents[k][i], (void *)A.mid_list[k][i]}) if (m) (void)hipFree(m);
+    for (int k = 0; k < plan::kLongMids - plan::kMids; ++k)
+        for (int i = 0; i < 2; ++i)
+            for (void *m : {(void *)A.long_world[k][i], (void *)A.long_snap[k][i], (void *)A.long_agents[k][i], (void *)A.long_list[k][i]}) if (m) (void)hipFree(m);
     env->aql.reset();
 }
 
@@ -362,6 +376,31 @@ static bool aql_split_buffers(ssd_env *env) {
     return true;
 }
 
+// The mid sets of a long call's runs of eight beyond those of runs of four (four more per orientation), with the handle's first long
+// argument set: all thirty-two buffers or none.  false: the handle's long calls keep runs of four.
+static bool aql_long_buffers(ssd_env *env) {
+    AqlState &A = *env->aql;
+    constexpr int kSets = plan::kLongMids - plan::kMids;
+    if (A.long_tried) return A.long_world[0][0] != nullptr;
+    A.long_tried = true;
+    const size_t grid = (size_t)env->E * env->S, agents = (size_t)env->E * (env->N ? env->N : 1) * 4, lists = (size_t)env->E * 128 * 4;
+    const size_t mids[8] = {grid, grid, grid, grid, agents, agents, lists, lists};
+    void *buf[8 * kSets] = {};
+    for (int i = 0; i < 8 * kSets; ++i)
+        if (hipMalloc(&buf[i], mids[i % 8]) != hipSuccess) {
+            (void)hipGetLastError();
+            for (int j = 0; j < i; ++j) (void)hipFree(buf[j]);
+            return false;
+        }
+    for (int k = 0; k < kSets; ++k)
+        for (int i = 0; i < 2; ++i) {
+            void **b = buf + 8 * k;
+            A.long_world[k][i] = static_cast<uint8_t *>(b[i]); A.long_snap[k][i] = static_cast<uint8_t *>(b[2 + i]);
+            A.long_agents[k][i] = static_cast<uint32_t *>(b[4 + i]); A.long_list[k][i] = static_cast<uint32_t *>(b[6 + i]);
+        }
+    return true;
+}
+
 // The kernel-argument set for this call's parameters: found among the cached ones, or built, uploaded (synchronously) and cached.
 // Argument block `i` of a chain serves the steps whose index is i modulo key.slots = lcm(output ring, action ring): its output slot
 // is i % ring, its action slot i % action_ring.
@@ -374,9 +413,12 @@ static AqlState::Set *aql_set(ssd_env *env, const AqlState::Key &key, int chains
     AqlState::Set &st = *victim;
     if (st.valid) for (int c = 0; c < 8 && c < A.nq; ++c) aql_wait_consumed(A.q[c], st.last_use[c]);   // nobody reads the old blocks any more
     st.valid = false;
+    st.key = key;                                   // (block_of() goes by the key's slots)
     st.kinds = plan::kind_table(key.split, key.pairs);
+    st.long_kinds = plan::long_kind_table(key.long_cap);
     const int n_dense = st.kinds.n_dense;
-    const size_t need = (size_t)chains * key.slots * n_dense * AqlState::kBlock;
+    st.long_at = (size_t)chains * key.slots * n_dense * AqlState::kBlock;
+    const size_t need = st.long_at + (size_t)chains * key.slots * st.long_kinds.n_dense * AqlState::kLongBlock;
     if (need > st.cap) {
         if (st.dev) (void)hipFree(st.dev);
         st.dev = nullptr; st.cap = 0;
@@ -402,6 +444,24 @@ static AqlState::Set *aql_set(ssd_env *env, const AqlState::Key &key, int chains
                     g.grid_x = L.grid_x; g.block_x = L.block_x; g.lds = L.lds;
                 }
                 std::memcpy(host.data() + (((size_t)c * key.slots + i) * n_dense + st.kinds.dense[kind]) * AqlState::kBlock, &L.args, L.args_bytes());
+            }
+        // (a long set: the long kinds' blocks behind the others -- the launch's KernArgs, then its LongParams)
+        for (int i = 0; i < key.slots; ++i)
+            for (int kind = plan::kKinds; kind < plan::kAllKinds; ++kind) {
+                if (st.long_kinds.dense[kind - plan::kKinds] < 0) continue;
+                Params p;
+                ssd::LongParams q;
+                plan::fill_long_block(cur.p, cur, key, A, kind, i, p, q);
+                ssd::Launch L;
+                if (!ssd::select(p, env->game, &L)) return nullptr;
+                AqlState::Geo &g = st.geo[c][kind];
+                if (i == 0) {
+                    if (!ssd::aql::lookup(env->device, L.fn, &g.k) || g.k.kernarg_size > AqlState::kLongBlock || g.k.kernarg_size < sizeof(ssd::KernArgs)) return nullptr;
+                    g.grid_x = L.grid_x; g.block_x = L.block_x; g.lds = L.lds;
+                }
+                uint8_t *at = host.data() + (st.block_of(c, (size_t)i, kind) - st.dev);
+                std::memcpy(at, &L.args, sizeof(ssd::KernArgs));
+                std::memcpy(at + sizeof(ssd::KernArgs), &q, sizeof q);
             }
     }
     if (hipMemcpy(st.dev, host.data(), need, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
@@ -522,15 +582,18 @@ static int rollout_aql(ssd_env *env, int chains, const ChainJob *jobs, hipStream
     static const int env_alternate = SSD_HOOK("SSD_AQL_ALTERNATE", 0);
     static const int env_split = SSD_KNOB("SSD_AQL_SPLIT", 1);
     static const int env_pairs = SSD_HOOK("SSD_AQL_PAIRS", 1);
-    static const int env_run = SSD_HOOK("SSD_AQL_RUN", ssd::kMaxRun);
+    static const int env_run = SSD_HOOK("SSD_AQL_RUN", ssd::kLongRun);
     plan::FormIn in;
     in.per_launch = (env->E + chains - 1) / chains; in.chains = chains;
     in.f32 = key.f32 != 0; in.order = key.order != nullptr; in.obs = j0.obs != nullptr; in.n_steps = j0.n_steps;
     in.fast_profile = ssd::fast_profile(env->p, env->game); in.pair_profile = ssd::pair_profile(env->p, env->game);
     in.aql_coherent = env_coh; in.aql_split = env_split; in.aql_alternate = env_alternate; in.aql_pairs = env_pairs; in.aql_run = env_run;
-    const plan::Form form = plan::choose_form(in);
+    in.long_profile = ssd::long_profile(env->p, env->game);
+    plan::Form form = plan::choose_form(in);
+    // (a long set names four more mid sets per orientation; a handle that cannot have them keeps runs of four, and says nothing)
+    if (form.key_long && !aql_long_buffers(env)) form.key_long = form.long_cap = 0;
     const bool coherent = form.coherent != 0, split = form.split;
-    key.coherent = form.coherent; key.split = form.key_split; key.pairs = form.pairs;
+    key.coherent = form.coherent; key.split = form.key_split; key.pairs = form.pairs; key.long_cap = form.key_long;
     // (a split set holds its launches for both orientations of the state pair; any other set names the buffer that is current now)
     key.world = key.split ? nullptr : env->p.world;
     // SET
@@ -558,21 +621,19 @@ static int rollout_aql(ssd_env *env, int chains, const ChainJob *jobs, hipStream
     const int kAcq = env_acq >= 0 ? env_acq : (coherent ? 0 : 1), kRel = env_rel >= 0 ? env_rel : (coherent ? 0 : 1);
     const bool obs_wb = !key.f32 && plan::ring_past_cache(j0.obs, j0.ring, obs_bytes(env, false));   // (chain_cursor's obs_nt)
     const int o = plan::start_orientation(key.split, A.world_buf[1] && env->p.world == A.world_buf[1]);
-    plan::Schedule sched(j0.n_steps, j0.step0, j0.reset_every, j0.ring, key.slots, split, form.run_cap, coherent, obs_wb, kAcq, kRel, o);
+    plan::Schedule sched(j0.n_steps, j0.step0, j0.reset_every, j0.ring, key.slots, split, form.run_cap, coherent, obs_wb, kAcq, kRel, o, form.long_cap);
     plan::Group g;
     while (sched.next(g))
         for (int c = 0; c < chains; ++c) {
             for (int j = 0; j < g.n_packets; ++j) {
                 const plan::Packet &pk = g.packet[j];
                 const AqlState::Geo &geo = st->geo[c][pk.kind];
-                ssd::aql::dispatch(A.q[c], geo.k, geo.grid_x, geo.block_x, geo.lds,
-                                   st->dev + (((size_t)c * key.slots + pk.block) * st->kinds.n_dense + st->kinds.dense[pk.kind]) * AqlState::kBlock,
-                                   /*barrier=*/true, pk.acquire, pk.release);
+                ssd::aql::dispatch(A.q[c], geo.k, geo.grid_x, geo.block_x, geo.lds, st->block_of(c, pk.block, pk.kind), /*barrier=*/true, pk.acquire, pk.release);
             }
             if (g.ring) ssd::aql::ring(A.q[c]);
         }
     if (sched.longest() > 1) env->last_path |= SSD_PATH_PAIRS;
-    env->last_path = (env->last_path & ~(7 << SSD_PATH_RUN_SHIFT)) | (sched.longest() << SSD_PATH_RUN_SHIFT);
+    env->last_path = (env->last_path & ~(15 << SSD_PATH_RUN_SHIFT)) | (sched.longest() << SSD_PATH_RUN_SHIFT);
     if (split) {                                          // the current state now sits in buffer orientation()
         env->p.world = A.world_buf[sched.orientation()]; env->p.agents = A.agents_buf[sched.orientation()];
     }
@@ -639,7 +700,7 @@ static int rollout(ssd_env *env, const int32_t *actions, const uint8_t *order, i
             const int rc = rollout_aql(env, chains, jobs, s);
             env->last_path |= ssd::aql::pool_report(env->device);
             if (rc <= 0) return rc;
-            env->last_path &= ~(SSD_PATH_AQL | SSD_PATH_COHERENT | SSD_PATH_SPLIT | SSD_PATH_PAIRS | SSD_PATH_SYNC | SSD_PATH_FORKED | (7 << SSD_PATH_RUN_SHIFT));
+            env->last_path &= ~(SSD_PATH_AQL | SSD_PATH_COHERENT | SSD_PATH_SPLIT | SSD_PATH_PAIRS | SSD_PATH_SYNC | SSD_PATH_FORKED | (15 << SSD_PATH_RUN_SHIFT));
             // (this call created a queue that failed its probe: an automatic chain count is chosen again for the pool that is left)
             if (!automatic || ssd::aql::pool_size(env->device) >= pool_before) break;
             chains = by_size();

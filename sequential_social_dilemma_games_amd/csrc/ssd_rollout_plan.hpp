@@ -55,6 +55,35 @@ inline KindTable kind_table(int split, int pairs) {
     return t;
 }
 
+// Long launches (long calls alone -- choose_form; the long kernels, ssd::kModeStepLong): the launches that take or render a run of
+// kLongRun = 8 steps.  A family of kinds of its own, numbered behind kKinds, with a dense table of its own: (n, rendered) with n or
+// rendered equal to kLongRun and the other one of 0, 1, 2, 4, kLongRun.  Per orientation: the five (kLongRun, rendered) in that
+// order of `rendered`, then the four (n, kLongRun) with n below kLongRun.  Only a key whose set is long (Key::long_cap) holds blocks
+// for them; every other launch of a long call is of the kinds above, as in a call that is not long.
+constexpr int kLongLens = 5;
+constexpr int kLongLen[kLongLens] = {0, 1, 2, 4, kLongRun};
+constexpr int kLongPerO = 2 * kLongLens - 1, kLongKinds = 2 * kLongPerO, kAllKinds = kKinds + kLongKinds;
+constexpr int long_len_index(int n) { return n == 0 ? 0 : n == 1 ? 1 : n == 2 ? 2 : n == 4 ? 3 : n == kLongRun ? 4 : -1; }
+constexpr bool is_long_kind(int kind) { return kind >= kKinds; }
+// (n, rendered) is a long launch
+constexpr bool long_counts(int n, int rendered) {
+    return (n == kLongRun && long_len_index(rendered) >= 0) || (rendered == kLongRun && long_len_index(n) >= 0);
+}
+constexpr int long_kind(int o, int n, int rendered) {
+    return kKinds + o * kLongPerO + (n == kLongRun ? long_len_index(rendered) : kLongLens + long_len_index(n));
+}
+constexpr int long_kind_o(int kind) { return (kind - kKinds) / kLongPerO; }
+constexpr int long_kind_n(int kind) { return (kind - kKinds) % kLongPerO < kLongLens ? kLongRun : kLongLen[(kind - kKinds) % kLongPerO - kLongLens]; }
+constexpr int long_kind_rendered(int kind) { return (kind - kKinds) % kLongPerO < kLongLens ? kLongLen[(kind - kKinds) % kLongPerO] : kLongRun; }
+// their places among the long blocks of one chain and slot: dense[kind - kKinds] (-1: none)
+struct LongKindTable { int8_t dense[kLongKinds]; int n_dense; };
+inline LongKindTable long_kind_table(int long_cap) {
+    LongKindTable t;
+    t.n_dense = 0;
+    for (int k = 0; k < kLongKinds; ++k) t.dense[k] = long_cap == kLongRun ? (int8_t)t.n_dense++ : (int8_t)-1;
+    return t;
+}
+
 // What an argument set is cached by: everything the caller passed that its blocks name.
 struct Key {
     const void *obs = nullptr, *rew = nullptr, *done = nullptr;
@@ -63,8 +92,9 @@ struct Key {
     int32_t slots = 0;                                       // argument blocks per chain and kind: lcm(ring, action_ring)
     const void *stamps = nullptr; uint32_t dbg_skip = 0;     // (diagnostic builds: part of the kernel arguments too)
     const void *world = nullptr;                             // sets that are not split: the state buffer their blocks name
+    int32_t long_cap = 0;                                    // kLongRun: the set also holds the long launches' blocks (Form::key_long)
     bool operator==(const Key &o) const {
-        return stamps == o.stamps && dbg_skip == o.dbg_skip && world == o.world && obs == o.obs && rew == o.rew && done == o.done && ring == o.ring && f32 == o.f32 && num_actions == o.num_actions &&
+        return long_cap == o.long_cap && stamps == o.stamps && dbg_skip == o.dbg_skip && world == o.world && obs == o.obs && rew == o.rew && done == o.done && ring == o.ring && f32 == o.f32 && num_actions == o.num_actions &&
                chains == o.chains && horizon == o.horizon && coherent == o.coherent && split == o.split && pairs == o.pairs && actions == o.actions && order == o.order &&
                action_ring == o.action_ring && slots == o.slots;
     }
@@ -76,7 +106,7 @@ inline int32_t block_slots(int32_t ring, int32_t action_ring, int chains) {
     long long a = ring, b = ar;
     while (b) { const long long t = a % b; a = b; b = t; }
     const long long l = (long long)ring / a * ar;
-    if (l * chains > 2048) return 0;                            // (up to 36 x 896 B per chain and block index)
+    if (l * chains > 2048) return 0;                            // (up to 36 x 896 B per chain and block index, a long set's 18 x 1216 B more)
     return (int32_t)l;
 }
 
@@ -87,6 +117,7 @@ struct FormIn {
     int n_steps;
     int fast_profile, pair_profile;          // ssd::fast_profile(), ssd::pair_profile() of the handle
     int aql_coherent, aql_split, aql_alternate, aql_pairs, aql_run;   // SSD_AQL_COHERENT, _SPLIT, _ALTERNATE, _PAIRS, _RUN
+    int long_profile;                        // ssd::long_profile() of the handle: kLongRun where its kernel has a long form, else 0
 };
 struct Form {
     int coherent;                            // key.coherent: 0 plain kernels, 1 coherent, 2 coherent with alternating geometries
@@ -94,7 +125,15 @@ struct Form {
     bool split;                              // this call is split
     int pairs;                               // key.pairs: the longest run the set has blocks for (0: none)
     int run_cap;                             // the longest run of this call (0: single steps)
+    int long_cap;                            // kLongRun: this call is LONG -- runs of kLongRun wherever that many steps remain, run_cap elsewhere (0: not)
+    int key_long;                            // key.long_cap: kLongRun where the argument set also holds the long launches (the form CAN be long)
 };
+// A call is long from this many steps on.  (Above 45, the longest call the suite pins to runs of four.  Measured, EXPERIMENTS.md
+// round 28: a long call's closing renderer-only launch delivers eight steps per wave instead of four, some 10 us more per call --
+// behind calls of its own length a 64-step call gains nothing, a 128-step call 0.06 us per step, calls of 600 and 1000 steps 0.15;
+// and a process's FIRST long call runs a kernel no launch has run before, 20 us: at 64 steps a loss of 0.3 us per step.  From 256
+// steps on a call gains even there.)
+constexpr int kLongCallSteps = 256;
 inline Form choose_form(const FormIn &in) {
     Form f;
     // Coherent chains: with a map-specific uint8 kernel (and its write-through observation stores: up to 16 384 envs per launch)
@@ -134,6 +173,15 @@ inline Form choose_form(const FormIn &in) {
     if (in.aql_run >= 1 && in.aql_run < cap) cap = in.aql_run;
     f.pairs = cap >= 2 ? cap : 0;
     f.run_cap = f.split ? f.pairs : 0;
+    // Long calls: a split call of kLongCallSteps steps or more whose kernel has a long form takes runs of kLongRun = 8 -- half the
+    // dependent launches again, the fixed cost of a launch (2.4 us) spread over eight steps.  The call's length decides once, for
+    // the whole call; every shorter call plans exactly as above.  Only beside runs of four (a capped run has no long form), and not
+    // under SSD_AQL_RUN = 1 .. 7 (test-hook build: SSD_AQL_RUN=4 gives a long call the plan of a call that is not).
+    // The argument set holds the long launches wherever the form can be long, whatever this call's length (as a split set holds the
+    // launches of calls too short to be split): a handle's first long call then finds its blocks and its mid sets in place, and
+    // pays for neither in the middle of a loop of calls.
+    f.key_long = (f.key_split && f.pairs == kMaxRun && in.long_profile >= kLongRun && (in.aql_run < 1 || in.aql_run >= kLongRun)) ? kLongRun : 0;
+    f.long_cap = (f.key_long && f.split && in.n_steps >= kLongCallSteps) ? kLongRun : 0;
     return f;
 }
 
@@ -159,7 +207,7 @@ inline void cursor_actions(const ChainRings &c, Params &p, size_t step_index) {
 }
 
 // The buffers of split rollouts, once per handle.
-constexpr int kMids = kMaxRun - 1;
+constexpr int kMids = kMaxRun - 1, kLongMids = kLongRun - 1;
 struct SplitBuffers {
     uint8_t *world_buf[2] = {};                     // the pair of state buffers ([0]: the handle's original ones)
     uint32_t *agents_buf[2] = {};
@@ -169,7 +217,59 @@ struct SplitBuffers {
     // launch's renderers alone)
     uint8_t *mid_world[kMids][2] = {}, *mid_snap[kMids][2] = {};
     uint32_t *mid_agents[kMids][2] = {}, *mid_list[kMids][2] = {};
+    // long calls: the mid sets of passes kMids .. kLongRun - 2 of a run of kLongRun, [k - kMids][o] (allocated with the handle's first
+    // long argument set, all or none)
+    uint8_t *long_world[kLongMids - kMids][2] = {}, *long_snap[kLongMids - kMids][2] = {};
+    uint32_t *long_agents[kLongMids - kMids][2] = {}, *long_list[kLongMids - kMids][2] = {};
+    // mid set [k][o], k = 0 .. kLongRun - 2, wherever it lives
+    struct MidSet { uint8_t *world; uint32_t *agents; uint32_t *list; uint8_t *snap; };
+    MidSet mid_set(int k, int o) const {
+        if (k < kMids) return MidSet{mid_world[k][o], mid_agents[k][o], mid_list[k][o], mid_snap[k][o]};
+        return MidSet{long_world[k - kMids][o], long_agents[k - kMids][o], long_list[k - kMids][o], long_snap[k - kMids][o]};
+    }
 };
+
+// The step-run part of a block, for the step-pair kernels' PairParams (kMax = kMaxRun) and the long kernels' LongParams (kMax =
+// kLongRun) alike: Q's arrays hold kMax pass records and kMax - 1 mid inputs.
+// Block i serves steps i .. i + n - 1 (output slots r .. r + n - 1, action slots likewise).  The env waves read buffer o, leave pass
+// k of their first n - 1 in mid set [k][o] and their last in buffer 1 - o with its marks in list o, as a single step's.  The
+// renderer workgroups deliver the `rd` steps of the launch before (orientation 1 - o): its last step -- or a single step -- from
+// buffer o and list 1 - o, the steps before it from mid sets [.][1 - o]; into the rd slots before r (renderer workgroups only: the
+// run is this block's own, slots r .. r + rd - 1).
+template <int kMax, class Q>
+inline void fill_run(const ChainRings &cur, const Key &key, const SplitBuffers &A, int o, int n, int rd, int i, int r, int mode, Params &p, Q &q) {
+    auto ring_slot = [&](int d) { return ((r + d) % key.ring + key.ring) % key.ring; };
+    auto slot_obs = [&](int sl) { return cur.obs ? cur.obs + (size_t)sl * cur.ob : nullptr; };
+    p.mode = mode;
+    p.obs = nullptr;
+    p.snap_mode = (n == 0 ? 4 : 1) | (rd > 0 ? 2 : 0);
+    p.world_out = A.world_buf[1 - o]; p.agents_out = A.agents_buf[1 - o];
+    p.beam_list = A.beam_list[o]; p.snap = A.snap_grid[o];
+    p.beam_list_in = A.beam_list[1 - o]; p.snap_in = A.snap_grid[1 - o];
+    // (the env waves' records, one per pass of the launch: every pass but the last into its mid set of orientation
+    // o, the launch's last step as a single step's -- each with the ring and action slots of its own step)
+    q.n_pass = n; q.n_render = rd;
+    for (int k = 0; k < n; ++k) {
+        const int rk = ring_slot(k);
+        PassRec &rec = q.pass[k];
+        const SplitBuffers::MidSet m = k + 1 < n ? A.mid_set(k, o) : SplitBuffers::MidSet{p.world_out, p.agents_out, p.beam_list, p.snap};
+        rec = PassRec{m.world, m.agents, m.list, m.snap, nullptr, nullptr, nullptr};
+        rec.rew = cur.rew ? cur.rew + (size_t)rk * cur.en : nullptr;
+        rec.done = cur.done ? cur.done + (size_t)rk * cur.en : nullptr;
+        rec.actions = cur.actions ? cur.actions + ((size_t)(i + k) % (size_t)cur.action_ring) * cur.en : nullptr;
+    }
+    // (the renderers' inputs, laid out from the run's end: slot kMax - 1 is its last step -- p.beam_list_in, p.snap_in,
+    // p.obs_b -- and slot t the step kMax - 1 - t before it, which is step j = t - (kMax - rd) of the run)
+    const int first = n == 0 ? 0 : -rd;      // (ring slot of the run's first step, relative to r)
+    for (int t = kMax - rd; t < kMax - 1; ++t) {
+        if (t < 0) continue;
+        const int j = t - (kMax - rd);
+        const SplitBuffers::MidSet m = A.mid_set(j, 1 - o);
+        q.mid_in[t] = MidIn{m.world, m.agents, m.list, m.snap};
+        q.obs_b0[t] = slot_obs(ring_slot(first + j));
+    }
+    p.obs_b = slot_obs(ring_slot(first + rd - 1));
+}
 
 // The kernel parameters of argument block (kind, i) of a chain: `base` is the chain's Params (its env range, the call's constant
 // fields), block i serves the steps whose index is i modulo key.slots -- output slot i % key.ring, action slot i % action_ring.
@@ -194,44 +294,7 @@ inline void fill_block(const Params &base, const ChainRings &cur, const Key &key
     cursor_actions(cur, p, (size_t)i);
     p.rew = cur.rew ? cur.rew + (size_t)r * cur.en : nullptr; p.done = cur.done ? cur.done + (size_t)r * cur.en : nullptr;
     if (pair_kind) {
-        // Block i serves steps i .. i + n - 1 (output slots r .. r + n - 1, action slots likewise).  The env waves read
-        // buffer o, leave pass k of their first n - 1 in mid set [k][o] and their last in buffer 1 - o with its marks in
-        // list o, as a single step's.  The renderer workgroups deliver the `rd` steps of the launch before (orientation
-        // 1 - o): its last step -- or a single step -- from buffer o and list 1 - o, the steps before it from mid sets
-        // [.][1 - o]; into the rd slots before r (renderer workgroups only: the run is this block's own, slots r ..
-        // r + rd - 1).
-        constexpr int kMax = kMaxRun;
-        const int n = (kb - kRun) / (kMax + 1), rd = (kb - kRun) % (kMax + 1);
-        auto ring_slot = [&](int d) { return ((r + d) % key.ring + key.ring) % key.ring; };
-        auto slot_obs = [&](int sl) { return cur.obs ? cur.obs + (size_t)sl * cur.ob : nullptr; };
-        p.mode = kModeStepPair;
-        p.obs = nullptr;
-        p.snap_mode = (n == 0 ? 4 : 1) | (rd > 0 ? 2 : 0);
-        p.world_out = A.world_buf[1 - o]; p.agents_out = A.agents_buf[1 - o];
-        p.beam_list = A.beam_list[o]; p.snap = A.snap_grid[o];
-        p.beam_list_in = A.beam_list[1 - o]; p.snap_in = A.snap_grid[1 - o];
-        // (the env waves' records, one per pass of the launch: every pass but the last into its mid set of orientation
-        // o, the launch's last step as a single step's -- each with the ring and action slots of its own step)
-        q.n_pass = n; q.n_render = rd;
-        for (int k = 0; k < n; ++k) {
-            const int rk = ring_slot(k);
-            PassRec &rec = q.pass[k];
-            if (k + 1 < n) rec = PassRec{A.mid_world[k][o], A.mid_agents[k][o], A.mid_list[k][o], A.mid_snap[k][o], nullptr, nullptr, nullptr};
-            else rec = PassRec{p.world_out, p.agents_out, p.beam_list, p.snap, nullptr, nullptr, nullptr};
-            rec.rew = cur.rew ? cur.rew + (size_t)rk * cur.en : nullptr;
-            rec.done = cur.done ? cur.done + (size_t)rk * cur.en : nullptr;
-            rec.actions = cur.actions ? cur.actions + ((size_t)(i + k) % (size_t)cur.action_ring) * cur.en : nullptr;
-        }
-        // (the renderers' inputs, laid out from the run's end: slot kMax - 1 is its last step -- p.beam_list_in, p.snap_in,
-        // p.obs_b -- and slot t the step kMax - 1 - t before it, which is step j = t - (kMax - rd) of the run)
-        const int first = n == 0 ? 0 : -rd;      // (ring slot of the run's first step, relative to r)
-        for (int t = kMax - rd; t < kMax - 1; ++t) {
-            if (t < 0) continue;
-            const int j = t - (kMax - rd);
-            q.mid_in[t] = MidIn{A.mid_world[j][1 - o], A.mid_agents[j][1 - o], A.mid_list[j][1 - o], A.mid_snap[j][1 - o]};
-            q.obs_b0[t] = slot_obs(ring_slot(first + j));
-        }
-        p.obs_b = slot_obs(ring_slot(first + rd - 1));
+        fill_run<kMaxRun>(cur, key, A, o, (kb - kRun) / (kMaxRun + 1), (kb - kRun) % (kMaxRun + 1), i, r, kModeStepPair, p, q);
     } else if (kb >= kA) {
         // env waves: read buffer o, write buffer 1 - o, leave their beam marks in list o.  Renderer workgroups of
         // a kAB launch: the step before produced buffer o (a launch of orientation 1 - o: its marks are in list
@@ -248,6 +311,19 @@ inline void fill_block(const Params &base, const ChainRings &cur, const Key &key
             p.obs_b = kb == kB ? obs_r : obs_prev;
         }
     }
+}
+
+// The same for a long kind (is_long_kind; a long set): the step launch's Params with ssd::kModeStepLong, and the launch's LongParams.
+inline void fill_long_block(const Params &base, const ChainRings &cur, const Key &key, const SplitBuffers &A, int kind, int i, Params &p, LongParams &q) {
+    const int r = i % key.ring, o = long_kind_o(kind);
+    p = base;
+    q = LongParams{};
+    p.world = A.world_buf[o]; p.agents = A.agents_buf[o];
+    p.coherent = key.coherent ? ((key.coherent == 2 && o == 1) ? 2u : 1u) : 0u;
+    p.rotate = 1;
+    cursor_actions(cur, p, (size_t)i);
+    p.rew = cur.rew ? cur.rew + (size_t)r * cur.en : nullptr; p.done = cur.done ? cur.done + (size_t)r * cur.en : nullptr;
+    fill_run<kLongRun>(cur, key, A, o, long_kind_n(kind), long_kind_rendered(kind), i, r, kModeStepLong, p, q);
 }
 
 // The orientation a call starts from: which buffer of the pair holds the current state (always 0 until the first split rollout of
@@ -273,10 +349,13 @@ class Schedule {
 public:
     // split: the call is split (launches alternate between the state buffers, from orientation o); run_cap: its longest run (0: single
     // steps; split calls only); coherent: coherent chains (the doorbell rule); obs_wb: the output ring is written with write-back
-    // stores (ring_past_cache, uint8); acq / rel: the fence scopes of the chain's own packets.
-    Schedule(int n_steps, int step0, int reset_every, int ring, int slots, bool split, int run_cap, bool coherent, bool obs_wb, int acq, int rel, int o)
+    // stores (ring_past_cache, uint8); acq / rel: the fence scopes of the chain's own packets; long_cap: kLongRun in a long call
+    // (Form::long_cap: a launch takes kLongRun steps wherever that many remain before the call's end and the next reset, else
+    // what run_cap gives; launches that take or render such a run are of the long kinds), else 0.
+    Schedule(int n_steps, int step0, int reset_every, int ring, int slots, bool split, int run_cap, bool coherent, bool obs_wb, int acq, int rel, int o,
+             int long_cap = 0)
         : n_steps_(n_steps), step0_(step0), reset_every_(reset_every), ring_(ring), slots_(slots), split_(split), run_cap_(split ? run_cap : 0),
-          coherent_(coherent), obs_wb_(obs_wb), kAcq(acq), kRel(rel), o_(o) {}
+          long_cap_((split && run_cap == kMaxRun && long_cap == kLongRun) ? kLongRun : 0), coherent_(coherent), obs_wb_(obs_wb), kAcq(acq), kRel(rel), o_(o) {}
     __attribute__((always_inline)) bool next(Group &g) {       // (into the enqueue loop: its state then lives in registers)
         const int k = k_;
         if (k >= n_steps_) return false;
@@ -286,13 +365,13 @@ public:
         // (a run never spans a reset or the call's end: the steps left before either go as shorter runs and single launches)
         int avail = n_steps_ - k;
         if (reset_every_ > 0) { const int to_reset = reset_every_ - (step0_ + k) % reset_every_; if (to_reset < avail) avail = to_reset; }
-        const int n = (run_cap_ > 2 && avail >= run_cap_) ? run_cap_ : (run_cap_ >= 2 && avail >= 2) ? 2 : 1;
+        const int n = (long_cap_ > 0 && avail >= long_cap_) ? long_cap_ : (run_cap_ > 2 && avail >= run_cap_) ? run_cap_ : (run_cap_ >= 2 && avail >= 2) ? 2 : 1;
         const bool last = k + n >= n_steps_;
         const int acq = k == 0 ? 1 : kAcq;                                 // (the call's first launch of the chain)
         Packet *pk = g.packet;
         if (reset) {
             // (a reset works in place: the launch before it must have been rendered from that buffer first)
-            if (split_ && pending_) *pk++ = Packet{i_prev_, o_ * KO + render_only(pending_), kAcq, kRel};
+            if (split_ && pending_) *pk++ = Packet{i_prev_, render_kind(o_, pending_), kAcq, kRel};
             *pk++ = Packet{i, o_ * KO + (split_ ? kRn : kR), acq, kRel};
         }
         const int rendered = reset ? 0 : pending_;
@@ -305,8 +384,10 @@ public:
         bool round = false;
         for (int j = 0; j < n; ++j) round = round || (step0_ + k + j) % ring_ == 0;
         const int rel = (obs_wb_ && round) ? 1 : kRel;
-        *pk++ = Packet{i, o_ * KO + base, reset ? kAcq : acq, rel};
-        if (split_ && last) *pk++ = Packet{i, (1 - o_) * KO + render_only(n), kAcq, kRel};   // (renders the buffer this launch wrote)
+        // (a launch that takes or renders a run of kLongRun: its long kind)
+        const int kind = (n == kLongRun || rendered == kLongRun) ? long_kind(o_, n, rendered) : o_ * KO + base;
+        *pk++ = Packet{i, kind, reset ? kAcq : acq, rel};
+        if (split_ && last) *pk++ = Packet{i, render_kind(1 - o_, n), kAcq, kRel};   // (renders the buffer this launch wrote)
         g.n_packets = (int)(pk - g.packet);
         g.step = k; g.steps = n; g.reset = reset;
         // (the doorbell -- an uncached write across the bus, 0.3 - 0.5 us -- after the first two launches, so that the device starts
@@ -328,10 +409,12 @@ public:
     int longest() const { return longest_; }     // the longest run one launch took
     // (the renderer workgroups that deliver a run of `rendered` steps, alone: a single step's are kB)
     static constexpr int render_only(int rendered) { return rendered == 1 ? (int)kB : run_kind(0, rendered); }
+    // (... of orientation o, with the orientation in the kind: a run of kLongRun takes the long kind)
+    static constexpr int render_kind(int o, int rendered) { return rendered == kLongRun ? long_kind(o, 0, rendered) : o * kKindsPerO + render_only(rendered); }
 
 private:
     int n_steps_, step0_, reset_every_, ring_, slots_;
-    bool split_; int run_cap_; bool coherent_, obs_wb_;
+    bool split_; int run_cap_, long_cap_; bool coherent_, obs_wb_;
     int kAcq, kRel;
     int o_;                      // orientation: which buffer of the pair holds the current state
     int k_ = 0;

@@ -278,7 +278,8 @@ class VecEngine(object):
         Same steps, bit for bit, as n_steps calls of step_random(), without the host as the bottleneck -- not the same launches:
         the library's split chains render a step's observations in the next launch, and on Harvest's shipped and enlarged maps and
         Cleanup's shipped one a launch advances its envs by a run of steps -- four wherever four remain before the call's end and the
-        next reset, else two where two remain (Cleanup with 10 agents: two at the most); rollout_path()["pairs"] and ["run"] say so.
+        next reset, else two where two remain (Cleanup with 10 agents: two at the most; Harvest's shipped map with 5 agents in calls of
+        256 steps or more: eight wherever eight remain); rollout_path()["pairs"] and ["run"] say so.
         fused=True: ONE kernel launch for the whole call (SSD_ROLLOUT_FUSED) -- every env stays in LDS / registers across
         its steps; same results, uint8 observations only.  fused="auto": the library picks (SSD_ROLLOUT_AUTO: the fused kernel
         for uint8 observations and two steps or more, the chains otherwise; rollout_path() says which form ran).
@@ -571,14 +572,14 @@ class VecEngine(object):
         """How the last rollout call was dispatched (ssd_rollout_path): {"aql", "coherent", "split", "pairs", "fused", "sync", "forked",
         "queue_dropped": bool, "chains": n, "pool": dispatch queues the device's pool settled on, "agent_match": how the HSA agent
         of the handle's HIP device was found ("pci" / "uuid" / "ordinal" / "none"), "run": the longest run of steps one launch of
-        the call took (1, 2 or 4; 0: the call did not go through the library's own queues)} -- lets a benchmark or a test
+        the call took (1, 2, 4 or 8; 0: the call did not go through the library's own queues)} -- lets a benchmark or a test
         tell a silent fallback from the path it meant to measure."""
         m = self._L.ssd_rollout_path(self._h)
         return {"aql": bool(m & _capi.SSD_PATH_AQL), "coherent": bool(m & _capi.SSD_PATH_COHERENT), "split": bool(m & _capi.SSD_PATH_SPLIT),
                 "pairs": bool(m & _capi.SSD_PATH_PAIRS),
                 "fused": bool(m & _capi.SSD_PATH_FUSED), "sync": bool(m & _capi.SSD_PATH_SYNC), "forked": bool(m & _capi.SSD_PATH_FORKED),
                 "queue_dropped": bool(m & _capi.SSD_PATH_QUEUE_DROPPED), "chains": (m >> 8) & 15, "pool": (m >> 12) & 7,
-                "agent_match": ("none", "pci", "uuid", "ordinal")[(m >> 16) & 3], "run": (m >> _capi.SSD_PATH_RUN_SHIFT) & 7}
+                "agent_match": ("none", "pci", "uuid", "ordinal")[(m >> 16) & 3], "run": (m >> _capi.SSD_PATH_RUN_SHIFT) & 15}
 
     def observe(self, rotate=True, obs=None):
         torch, dev = self._torch()
