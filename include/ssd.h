@@ -407,7 +407,9 @@ int ssd_stats_destroy(ssd_stats *st);
  * a scratch buffer of about n_steps * E * N bytes, grown (with a device synchronisation) when a fold needs more. */
 int ssd_stats_fold(ssd_stats *st, const int32_t *rew, const uint8_t *done, int32_t ring, int32_t step0, int32_t n_steps,
                    int32_t reset_every, uint32_t flags, void *stream);
-/* Steps per time chunk of the fold (0 = automatic, 64).  Changes speed only, never a result. */
+/* Steps per time chunk of the fold (0 = automatic, 64; any value up to INT32_MAX).  Changes speed only, never a result: a
+ * fold clamps it to 1 .. n_steps, so a chunk above n_steps acts as n_steps (one chunk).  A fold whose chunks are too many
+ * for one launch (about 2^26 waves of 64 / num_agents envs each) returns SSD_E_INVALID and says so. */
 int ssd_stats_set_chunk(ssd_stats *st, int32_t steps);
 /* Discard the open episode of every env with env_mask[e] != 0 (u8 [E] device, NULL = all) that has t > 0; it counts as
  * truncated. */

@@ -14,6 +14,7 @@
 // between the first and the last end of a chunk that holds more than one (episodes shorter than a chunk), and opens the tail.
 // Every float operation -- the metrics and their sums -- happens in pass 2 in the order a sequential loop over the steps
 // would do it, so the results do not depend on L.  There are no atomics; integers stay integers until a metric is formed.
+// L, the number of chunks, both grids and the scratch carve come from ssd_stats_plan.hpp (no HIP, 64-bit, tested on the host).
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -21,12 +22,13 @@
 #include <string>
 
 #include "../../include/ssd.h"
+#include "ssd_stats_plan.hpp"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kWave = 64;
-constexpr int kAutoChunk = 64;                                   // steps per chunk when the caller has not set one
+namespace plan = ssd::stats_plan;                                // L, C, the grids and the scratch: decided there, in 64 bits
+using plan::kBlock;
+using plan::kWave;
 constexpr int kBatch = 8;                                        // pass 1: steps whose loads are issued together
 
 struct Seg {                                                     // sums of one agent over a run of steps
@@ -90,39 +92,39 @@ __device__ __forceinline__ bool ends_at(const uint8_t *done, size_t slot_off, in
 // ---------------------------------------------------------------- pass 1: chunk partials
 __global__ void __launch_bounds__(kBlock) stats_chunk_kernel(const int32_t *__restrict__ rew, const uint8_t *__restrict__ done,
                                                              int32_t ring, int32_t step0, int32_t n_steps, int32_t reset_every,
-                                                             int32_t E, int32_t N, int32_t L, int32_t waves_per_row, Part head,
-                                                             Part tail, int4 *__restrict__ meta) {
+                                                             int32_t E, int32_t N, int32_t L, int32_t C, int32_t waves_per_row,
+                                                             Part head, Part tail, int4 *__restrict__ meta) {
     const int wave = (int)((blockIdx.x * (unsigned)kBlock + threadIdx.x) / kWave);
     const int c = wave / waves_per_row;
     const Lanes l = lanes_of(wave - c * waves_per_row, threadIdx.x % kWave, E, N);
-    const int k0 = c * L;
-    if (!l.ok || k0 >= n_steps) return;
-    const int k1 = min(n_steps, k0 + L);
+    if (!l.ok || !plan::wave_has_chunk(c, C)) return;            // (the spare waves of the last block: no product of c to wrap)
+    // k0 < k1 <= n_steps fit an int; the batch loop runs up to 7 past k1, and n_steps may be INT32_MAX: 64 bits
+    const int64_t k0 = plan::chunk_begin(c, L), k1 = plan::chunk_end(k0, L, n_steps);
     const size_t EN = (size_t)E * N, lane_off = (size_t)l.e * N + l.i;
     int slot = (int)(((int64_t)step0 + k0) % ring);
     Seg cur = {0, 0, 0, 0, 0}, hd = cur;
     int64_t t = 0;
     int nb = 0, first = -1, last = -1;
-    for (int kb = k0; kb < k1; kb += kBatch) {
+    for (int64_t kb = k0; kb < k1; kb += kBatch) {
         // the batch's loads first (they do not depend on the sums), then the steps in order
         int32_t r[kBatch];
         bool end[kBatch];
 #pragma unroll
         for (int u = 0; u < kBatch; ++u) {
-            const int k = kb + u;
+            const int64_t k = kb + u;
             const size_t off = (size_t)slot * EN;
             r[u] = k < k1 ? rew[off + lane_off] : 0;
-            end[u] = k < k1 && ends_at(done, off, l.e, N, (int64_t)step0 + k + 1, reset_every);
+            end[u] = k < k1 && ends_at(done, off, l.e, N, plan::global_step1(step0, k), reset_every);
             if (++slot == ring) slot = 0;
         }
 #pragma unroll
         for (int u = 0; u < kBatch; ++u) {
-            const int k = kb + u;
+            const int64_t k = kb + u;
             if (k >= k1) break;
             seg_add(cur, r[u], ++t);
             if (end[u]) {
-                if (nb == 0) { hd = cur; first = k; }
-                last = k;
+                if (nb == 0) { hd = cur; first = (int)k; }
+                last = (int)k;
                 ++nb;
                 cur = Seg{0, 0, 0, 0, 0};
                 t = 0;
@@ -199,7 +201,7 @@ __device__ __forceinline__ void add_shifted(Seg &o, const Part &p, size_t idx, i
 __global__ void __launch_bounds__(kBlock) stats_combine_kernel(StatsDev d, const int32_t *__restrict__ rew,
                                                                const uint8_t *__restrict__ done, int32_t ring, int32_t step0,
                                                                int32_t n_steps, int32_t reset_every, int32_t E, int32_t N, int32_t L,
-                                                               Part head, Part tail, const int4 *__restrict__ meta) {
+                                                               int32_t C, Part head, Part tail, const int4 *__restrict__ meta) {
     const int wave = (int)((blockIdx.x * (unsigned)kBlock + threadIdx.x) / kWave);
     const Lanes l = lanes_of(wave, threadIdx.x % kWave, E, N);
     if (!l.ok) return;
@@ -219,10 +221,9 @@ __global__ void __launch_bounds__(kBlock) stats_combine_kernel(StatsDev d, const
         t = 0;
         o = Seg{0, 0, 0, 0, 0};
     }
-    const int C = (n_steps + L - 1) / L;
     for (int c = 0; c < C; ++c) {
         const int4 mt = meta[(size_t)c * E + e];
-        const int k0 = c * L, k1 = min(n_steps, k0 + L);
+        const int k0 = (int)plan::chunk_begin(c, L), k1 = (int)plan::chunk_end(k0, L, n_steps);   // k0 < k1 <= n_steps
         const size_t pi = (size_t)c * EN + li;
         add_shifted(o, head, pi, t);
         if (mt.x == 0) { t += k1 - k0; continue; }
@@ -234,7 +235,7 @@ __global__ void __launch_bounds__(kBlock) stats_combine_kernel(StatsDev d, const
             for (int k = mt.y + 1; k <= mt.z; ++k) {
                 const size_t off = (size_t)slot * EN;
                 seg_add(o, rew[off + li], ++t);
-                if (ends_at(done, off, e, N, (int64_t)step0 + k + 1, reset_every)) {
+                if (ends_at(done, off, e, N, plan::global_step1(step0, k), reset_every)) {
                     close_episode(a, o, t, l, N);
                     o = Seg{0, 0, 0, 0, 0};
                     t = 0;
@@ -328,13 +329,6 @@ int stats_fail(ssd_stats *st, const char *what, hipError_t e) {
         if (e_ != hipSuccess) return stats_fail((st), #call, e_);          \
     } while (0)
 
-int waves_per_row(const ssd_stats *st) {                          // waves that hold every (env, agent) lane once
-    const int per = kWave / st->N;
-    return (st->E + per - 1) / per;
-}
-
-size_t part_bytes(size_t lanes) { return lanes * (3 * 8 + 2 * 4); }
-
 Part carve_part(char *&c, size_t lanes) {
     Part p;
     p.R = (int64_t *)c; c += lanes * 8;
@@ -418,11 +412,10 @@ int ssd_stats_fold(ssd_stats *st, const int32_t *rew, const uint8_t *done, int32
     if (n_steps == 0) return SSD_OK;
     ST_HIP(st, hipSetDevice(st->device));
     const hipStream_t s = (hipStream_t)stream;
-    const int L = st->chunk > 0 ? st->chunk : kAutoChunk;
-    const int C = (n_steps + L - 1) / L;
-    const int rows = waves_per_row(st);
-    const size_t lanes = (size_t)st->E * st->N;
-    const size_t need = (size_t)C * (2 * part_bytes(lanes) + (size_t)st->E * sizeof(int4));
+    plan::Plan p;
+    if (!plan::plan_fold(st->E, st->N, n_steps, st->chunk, p)) { st->err = p.why; return SSD_E_INVALID; }
+    static_assert(sizeof(int4) == plan::kMetaBytes, "the plan's meta record");
+    const size_t need = p.scratch_bytes;
     if (need > st->scratch_bytes) {
         // the partials of the previous fold may still be read on another stream: wait before the buffer goes
         ST_HIP(st, hipDeviceSynchronize());
@@ -431,14 +424,13 @@ int ssd_stats_fold(ssd_stats *st, const int32_t *rew, const uint8_t *done, int32
         st->scratch_bytes = need;
     }
     char *c = static_cast<char *>(st->scratch);
-    int4 *meta = (int4 *)c; c += (size_t)C * st->E * sizeof(int4);
-    const Part head = carve_part(c, (size_t)C * lanes), tail = carve_part(c, (size_t)C * lanes);
-    const int waves1 = C * rows;
-    stats_chunk_kernel<<<(waves1 * kWave + kBlock - 1) / kBlock, kBlock, 0, s>>>(rew, done, ring, step0, n_steps, reset_every, st->E,
-                                                                               st->N, L, rows, head, tail, meta);
+    int4 *meta = (int4 *)c; c += p.meta_bytes;
+    const Part head = carve_part(c, p.part_lanes), tail = carve_part(c, p.part_lanes);
+    stats_chunk_kernel<<<p.grid1, kBlock, 0, s>>>(rew, done, ring, step0, n_steps, reset_every, st->E, st->N, p.L, p.C, p.rows, head,
+                                                  tail, meta);
     ST_HIP(st, hipGetLastError());
-    stats_combine_kernel<<<(rows * kWave + kBlock - 1) / kBlock, kBlock, 0, s>>>(st->d, rew, done, ring, step0, n_steps, reset_every,
-                                                                               st->E, st->N, L, head, tail, meta);
+    stats_combine_kernel<<<p.grid2, kBlock, 0, s>>>(st->d, rew, done, ring, step0, n_steps, reset_every, st->E, st->N, p.L, p.C, head,
+                                                    tail, meta);
     ST_HIP(st, hipGetLastError());
     return SSD_OK;
 }
