@@ -475,49 +475,32 @@ def lib():
     return _lib
 
 
-def ws_check(rc, handle=None):
-    if rc != SSD_OK:
-        msg = lib().ssd_ws_last_error(handle)
-        raise SsdError("libssd_hip Watershed call failed (%d): %s" % (rc, msg.decode() if msg else "?"))
+def _fail(symbol, what, rc, *handle):
+    msg = getattr(lib(), symbol)(*handle)
+    raise SsdError("libssd_hip %s failed (%d): %s" % (what, rc, msg.decode() if msg else "?"))
 
 
-def stats_check(rc, handle=None):
-    if rc != SSD_OK:
-        msg = lib().ssd_stats_last_error(handle)
-        raise SsdError("libssd_hip episode-statistics call failed (%d): %s" % (rc, msg.decode() if msg else "?"))
+def _checker(symbol, what):
+    """-> check(rc) of a family without a handle: raises SsdError with the calling thread's last error text unless rc is SSD_OK."""
+    def check(rc):
+        if rc != SSD_OK:
+            _fail(symbol, what, rc)
+    return check
 
 
-def ws_stats_check(rc, handle=None):
-    if rc != SSD_OK:
-        msg = lib().ssd_ws_stats_last_error(handle)
-        raise SsdError("libssd_hip Watershed episode-statistics call failed (%d): %s" % (rc, msg.decode() if msg else "?"))
+def _handle_checker(symbol, what):
+    """-> check(rc, handle=None) of a family whose last-error call takes the handle."""
+    def check(rc, handle=None):
+        if rc != SSD_OK:
+            _fail(symbol, what, rc, handle)
+    return check
 
 
-def policy_check(rc):
-    if rc != SSD_OK:
-        msg = lib().ssd_policy_last_error()
-        raise SsdError("libssd_hip policy call failed (%d): %s" % (rc, msg.decode() if msg else "?"))
-
-
-def advantages_check(rc):
-    if rc != SSD_OK:
-        msg = lib().ssd_advantages_last_error()
-        raise SsdError("libssd_hip advantages call failed (%d): %s" % (rc, msg.decode() if msg else "?"))
-
-
-def vtrace_check(rc):
-    if rc != SSD_OK:
-        msg = lib().ssd_vtrace_last_error()
-        raise SsdError("libssd_hip V-trace call failed (%d): %s" % (rc, msg.decode() if msg else "?"))
-
-
-def moments_check(rc):
-    if rc != SSD_OK:
-        msg = lib().ssd_moments_last_error()
-        raise SsdError("libssd_hip batch-moments call failed (%d): %s" % (rc, msg.decode() if msg else "?"))
-
-
-def check(rc, handle=None):
-    if rc != SSD_OK:
-        msg = lib().ssd_last_error(handle)
-        raise SsdError("libssd_hip call failed (%d): %s" % (rc, msg.decode() if msg else "?"))
+check = _handle_checker("ssd_last_error", "call")
+ws_check = _handle_checker("ssd_ws_last_error", "Watershed call")
+stats_check = _handle_checker("ssd_stats_last_error", "episode-statistics call")
+ws_stats_check = _handle_checker("ssd_ws_stats_last_error", "Watershed episode-statistics call")
+policy_check = _checker("ssd_policy_last_error", "policy call")
+advantages_check = _checker("ssd_advantages_last_error", "advantages call")
+vtrace_check = _checker("ssd_vtrace_last_error", "V-trace call")
+moments_check = _checker("ssd_moments_last_error", "batch-moments call")

@@ -16,9 +16,9 @@
 
 #include <math.h>
 #include <stdint.h>
-#include <string>
 
 #include "../../include/ssd.h"
+#include "ssd_batch.hpp"
 
 #ifndef SSD_GAE_LOAD_BLOCK
 #define SSD_GAE_LOAD_BLOCK 16                                    // DESIGN.md section 15 has the lengths tried
@@ -150,20 +150,15 @@ __global__ void __launch_bounds__(kBlock) gae_kernel(GaeArgs a) {
     }
 }
 
-thread_local std::string g_adv_error;
+thread_local ssd::BatchError g_adv_error;
 
-int fail(const char *msg) {
-    g_adv_error = msg;
-    return SSD_E_INVALID;
-}
+int fail(const char *msg) { return g_adv_error.invalid(msg); }
 
 template <int kMode>
 void launch(const GaeArgs &a, dim3 grid, hipStream_t s) {
-    const bool bonus = a.bonus != nullptr, done = a.done != nullptr;
-    if (bonus && done) hipLaunchKernelGGL((gae_kernel<kMode, true, true>), grid, dim3(kBlock), 0, s, a);
-    else if (bonus) hipLaunchKernelGGL((gae_kernel<kMode, true, false>), grid, dim3(kBlock), 0, s, a);
-    else if (done) hipLaunchKernelGGL((gae_kernel<kMode, false, true>), grid, dim3(kBlock), 0, s, a);
-    else hipLaunchKernelGGL((gae_kernel<kMode, false, false>), grid, dim3(kBlock), 0, s, a);
+    ssd::with_bonus_done(a.bonus != nullptr, a.done != nullptr, [&](auto kBonus, auto kDone) {
+        hipLaunchKernelGGL((gae_kernel<kMode, decltype(kBonus)::value, decltype(kDone)::value>), grid, dim3(kBlock), 0, s, a);
+    });
 }
 
 }  // namespace
@@ -175,11 +170,7 @@ const char *ssd_advantages_last_error(void) { return g_adv_error.c_str(); }
 int ssd_advantages(const int32_t *rew, const float *bonus, double bonus_weight, const float *value, const uint8_t *done,
                    const float *last_value, int32_t lanes, int32_t ring, int32_t step0, int32_t n_steps, double gamma,
                    double lambda, uint32_t flags, float *advantages, float *value_targets, int32_t device_id, void *stream) {
-    if (lanes < 1) return fail("lanes must be >= 1");
-    if (ring < 1) return fail("ring must be >= 1");
-    if (n_steps < 1) return fail("n_steps must be >= 1");
-    if (n_steps > ring) return fail("n_steps > ring: a call reads each step's slot once");
-    if (step0 < 0) return fail("step0 must be >= 0");
+    if (const char *msg = ssd::check_ring(lanes, ring, step0, n_steps)) return fail(msg);
     if ((flags & ~(uint32_t)(SSD_ADV_GAE | SSD_ADV_CRITIC)) != 0) return fail("unsupported flag");
     const bool gae = (flags & SSD_ADV_GAE) != 0, critic = (flags & SSD_ADV_CRITIC) != 0;
     if (gae && !critic) return fail("generalised advantage estimation needs the critic: set both flags");
@@ -188,16 +179,7 @@ int ssd_advantages(const int32_t *rew, const float *bonus, double bonus_weight, 
     if (critic && !value) return fail("value is required when the critic is used");
     if (!isfinite(gamma) || !isfinite(lambda)) return fail("gamma and lambda must be finite");
     if (bonus && !isfinite(bonus_weight)) return fail("bonus_weight must be finite");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
-        g_adv_error = "no HIP device available: this call has no CPU path";
-        return SSD_E_DEVICE;
-    }
-    if (device_id < 0 || device_id >= count) return fail("device_id out of range");
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != device_id) {
-        if (hipSetDevice(device_id) != hipSuccess) { g_adv_error = "hipSetDevice failed"; return SSD_E_DEVICE; }
-    }
+    if (const int rc = ssd::use_device(g_adv_error, device_id)) return rc;
     GaeArgs a{};
     a.rew = rew; a.bonus = bonus; a.value = value; a.last_value = last_value; a.done = done;
     a.adv = advantages; a.vt = value_targets;
@@ -208,9 +190,7 @@ int ssd_advantages(const int32_t *rew, const float *bonus, double bonus_weight, 
     if (gae) launch<kGae>(a, grid, s);
     else if (critic) launch<kReturnsCritic>(a, grid, s);
     else launch<kReturns>(a, grid, s);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_adv_error = std::string("advantages launch: ") + hipGetErrorString(e); return SSD_E_DEVICE; }
-    return SSD_OK;
+    return g_adv_error.launched("advantages");
 }
 
 }  // extern "C"

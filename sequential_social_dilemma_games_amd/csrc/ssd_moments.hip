@@ -19,9 +19,9 @@
 
 #include <math.h>
 #include <stdint.h>
-#include <string>
 
 #include "../../include/ssd.h"
+#include "ssd_batch.hpp"
 
 namespace {
 
@@ -176,37 +176,21 @@ __global__ void __launch_bounds__(kBlock) explained_variance_pass(MomArgs a) {
     if (threadIdx.x == 0) a.out[p] = (float)(r < -1.0 ? -1.0 : r);   // (a NaN stays one)
 }
 
-thread_local std::string g_mom_error;
+thread_local ssd::BatchError g_mom_error;
 
-int fail(const char *msg) {
-    g_mom_error = msg;
-    return SSD_E_INVALID;
-}
+int fail(const char *msg) { return g_mom_error.invalid(msg); }
 
 // the checks both calls share, then the device; fills what the passes share of `a`
 int prepare(int32_t lanes, int32_t ring, int32_t step0, int32_t n_steps, int32_t num_sets, const void *scratch, int32_t device_id,
             MomArgs &a) {
-    if (lanes < 1) return fail("lanes must be >= 1");
-    if (ring < 1) return fail("ring must be >= 1");
-    if (n_steps < 1) return fail("n_steps must be >= 1");
-    if (n_steps > ring) return fail("n_steps > ring: a call reads each step's slot once");
-    if (step0 < 0) return fail("step0 must be >= 0");
+    if (const char *msg = ssd::check_ring(lanes, ring, step0, n_steps)) return fail(msg);
     if (num_sets < 1) return fail("num_sets must be >= 1");
     if (lanes % num_sets != 0) return fail("num_sets must divide lanes: lane l belongs to set l % num_sets");
     if (!scratch) return fail("scratch is required");
     if ((uintptr_t)scratch % sizeof(double) != 0) return fail("scratch must be aligned to 8 bytes");
     const int64_t chunks = SSD_MOM_CHUNKS(n_steps, lanes, num_sets);
     if (chunks > 0x7fffffff || num_sets > 65535) return fail("too many chunks or sets for one grid");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
-        g_mom_error = "no HIP device available: this call has no CPU path";
-        return SSD_E_DEVICE;
-    }
-    if (device_id < 0 || device_id >= count) return fail("device_id out of range");
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != device_id) {
-        if (hipSetDevice(device_id) != hipSuccess) { g_mom_error = "hipSetDevice failed"; return SSD_E_DEVICE; }
-    }
+    if (const int rc = ssd::use_device(g_mom_error, device_id)) return rc;
     const int64_t s0 = step0 % ring;
     a.n = (int64_t)n_steps * (lanes / num_sets);
     a.base = s0 * lanes;
@@ -214,12 +198,6 @@ int prepare(int32_t lanes, int32_t ring, int32_t step0, int32_t n_steps, int32_t
     a.P = num_sets;
     a.chunks = (int32_t)chunks;
     a.scratch = (double *)scratch;
-    return SSD_OK;
-}
-
-int launched(const char *what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_mom_error = std::string(what) + " launch: " + hipGetErrorString(e); return SSD_E_DEVICE; }
     return SSD_OK;
 }
 
@@ -246,7 +224,7 @@ int ssd_standardize(const float *x, int32_t lanes, int32_t ring, int32_t step0, 
     hipLaunchKernelGGL((moments_pass<1, false>), grid, dim3(kBlock), 0, s, a);
     hipLaunchKernelGGL((moments_pass<1, true>), grid, dim3(kBlock), 0, s, a);
     hipLaunchKernelGGL(standardize_pass, grid, dim3(kBlock), 0, s, a);
-    return launched("standardize");
+    return g_mom_error.launched("standardize");
 }
 
 int ssd_explained_variance(const float *y, const float *pred, int32_t lanes, int32_t ring, int32_t step0, int32_t n_steps,
@@ -263,7 +241,7 @@ int ssd_explained_variance(const float *y, const float *pred, int32_t lanes, int
     hipLaunchKernelGGL((moments_pass<2, false>), grid, dim3(kBlock), 0, s, a);
     hipLaunchKernelGGL((moments_pass<2, true>), grid, dim3(kBlock), 0, s, a);
     hipLaunchKernelGGL(explained_variance_pass, dim3((unsigned)a.P), dim3(kBlock), 0, s, a);
-    return launched("explained variance");
+    return g_mom_error.launched("explained variance");
 }
 
 }  // extern "C"

@@ -14,9 +14,9 @@
 
 #include <math.h>
 #include <stdint.h>
-#include <string>
 
 #include "../../include/ssd.h"
+#include "ssd_batch.hpp"
 
 #ifndef SSD_VTRACE_LOAD_BLOCK
 #define SSD_VTRACE_LOAD_BLOCK 16                                 // DESIGN.md section 20 has the lengths tried
@@ -134,12 +134,9 @@ __global__ void __launch_bounds__(kBlock) vtrace_kernel(VtArgs a) {
     }
 }
 
-thread_local std::string g_vt_error;
+thread_local ssd::BatchError g_vt_error;
 
-int fail(const char *msg) {
-    g_vt_error = msg;
-    return SSD_E_INVALID;
-}
+int fail(const char *msg) { return g_vt_error.invalid(msg); }
 
 }  // namespace
 
@@ -151,11 +148,7 @@ int ssd_vtrace(const int32_t *rew, const float *bonus, double bonus_weight, cons
                const uint8_t *done, const float *bootstrap_value, int32_t lanes, int32_t ring, int32_t step0, int32_t n_steps,
                double gamma, double clip_rho_threshold, double clip_pg_rho_threshold, uint32_t flags, float *vs,
                float *pg_advantages, int32_t device_id, void *stream) {
-    if (lanes < 1) return fail("lanes must be >= 1");
-    if (ring < 1) return fail("ring must be >= 1");
-    if (n_steps < 1) return fail("n_steps must be >= 1");
-    if (n_steps > ring) return fail("n_steps > ring: a call reads each step's slot once");
-    if (step0 < 0) return fail("step0 must be >= 0");
+    if (const char *msg = ssd::check_ring(lanes, ring, step0, n_steps)) return fail(msg);
     if (flags != 0) return fail("unsupported flag");
     if (!rew) return fail("rew is required");
     if (!value) return fail("value is required: the target policy's values");
@@ -165,16 +158,7 @@ int ssd_vtrace(const int32_t *rew, const float *bonus, double bonus_weight, cons
     if (!(clip_rho_threshold > 0.0) || !(clip_pg_rho_threshold > 0.0))
         return fail("clip_rho_threshold and clip_pg_rho_threshold must be > 0 (+inf: no clip)");
     if (bonus && !isfinite(bonus_weight)) return fail("bonus_weight must be finite");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
-        g_vt_error = "no HIP device available: this call has no CPU path";
-        return SSD_E_DEVICE;
-    }
-    if (device_id < 0 || device_id >= count) return fail("device_id out of range");
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != device_id) {
-        if (hipSetDevice(device_id) != hipSuccess) { g_vt_error = "hipSetDevice failed"; return SSD_E_DEVICE; }
-    }
+    if (const int rc = ssd::use_device(g_vt_error, device_id)) return rc;
     VtArgs a{};
     a.rew = rew; a.bonus = bonus; a.value = value; a.rhos = rhos; a.bootstrap = bootstrap_value; a.done = done;
     a.vs = vs; a.pg = pg_advantages;
@@ -182,13 +166,10 @@ int ssd_vtrace(const int32_t *rew, const float *bonus, double bonus_weight, cons
     a.L = lanes; a.ring = ring; a.step0 = step0; a.K = n_steps;
     const dim3 grid((unsigned)(((int64_t)lanes + kBlock - 1) / kBlock));
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    if (bonus && done) hipLaunchKernelGGL((vtrace_kernel<true, true>), grid, dim3(kBlock), 0, s, a);
-    else if (bonus) hipLaunchKernelGGL((vtrace_kernel<true, false>), grid, dim3(kBlock), 0, s, a);
-    else if (done) hipLaunchKernelGGL((vtrace_kernel<false, true>), grid, dim3(kBlock), 0, s, a);
-    else hipLaunchKernelGGL((vtrace_kernel<false, false>), grid, dim3(kBlock), 0, s, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_vt_error = std::string("vtrace launch: ") + hipGetErrorString(e); return SSD_E_DEVICE; }
-    return SSD_OK;
+    ssd::with_bonus_done(bonus != nullptr, done != nullptr, [&](auto kBonus, auto kDone) {
+        hipLaunchKernelGGL((vtrace_kernel<decltype(kBonus)::value, decltype(kDone)::value>), grid, dim3(kBlock), 0, s, a);
+    });
+    return g_vt_error.launched("vtrace");
 }
 
 }  // extern "C"

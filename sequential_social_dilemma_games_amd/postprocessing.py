@@ -39,6 +39,82 @@ def _check(torch, t, dtype, shape, device, name):
         raise ValueError("%s must be a contiguous %s tensor of shape %s on %s" % (name, dtype, tuple(shape), device))
 
 
+# ---- what the four calls on the [R, ...] rings share: each rule once ----
+
+def _leading(torch, t, dtype, name):
+    """The tensor that gives a call its shape -> shape, device, R (ring rows), L (trajectories of a row)."""
+    what = {torch.int32: "an int32", torch.float32: "a float32"}[dtype]
+    if not isinstance(t, torch.Tensor) or t.dim() < 1:
+        raise ValueError("%s must be %s tensor of shape [R, ...]" % (name, what))
+    shape, dev = tuple(t.shape), t.device
+    R = shape[0]
+    L = int(np.prod(shape[1:], dtype=np.int64))
+    if R < 1 or L < 1:
+        raise ValueError("%s holds no step" % name)
+    if L >= 2 ** 31 or R >= 2 ** 31:
+        raise ValueError("%s is too large: fewer than 2^31 rows and trajectories" % name)
+    _check(torch, t, dtype, shape, dev, name)
+    return shape, dev, R, L
+
+
+def _ring_rows(R, step0, n_steps):
+    """-> step0, n_steps as ints: row k of the call is ring slot (step0 + k) % R, k < n_steps (default R)."""
+    step0 = int(step0)
+    n_steps = R if n_steps is None else int(n_steps)
+    if n_steps < 1 or n_steps > R:
+        raise ValueError("n_steps (%d) must be 1..%d, the ring length: a call reads each slot once" % (n_steps, R))
+    if step0 < 0 or step0 >= 2 ** 31:
+        raise ValueError("step0 must be 0..2^31 - 1")
+    return step0, n_steps
+
+
+def _slots(R, step0, n_steps):
+    return [(step0 + k) % R for k in range(n_steps)]
+
+
+def _episode_inputs(torch, shape, dev, bootstrap, bootstrap_name, done, bonus, bonus_weight):
+    """The optional inputs compute_advantages and vtrace take alike -> bonus_weight as a float."""
+    if bootstrap is not None:
+        _check(torch, bootstrap, torch.float32, shape[1:], dev, bootstrap_name)
+    if done is not None:
+        _check(torch, done, torch.uint8, shape, dev, "done")
+    if bonus is not None:
+        _check(torch, bonus, torch.float32, shape, dev, "bonus")
+    bonus_weight = float(bonus_weight)
+    if bonus is not None and not math.isfinite(bonus_weight):
+        raise ValueError("bonus_weight must be finite")
+    return bonus_weight
+
+
+def _out_pair(torch, out, shape, dev, whole_ring, names):
+    """The two float32 results: allocated (zero where the call writes only some of the rows), or the caller's pair."""
+    if out is None:
+        make = torch.empty if whole_ring else torch.zeros
+        return make(shape, dtype=torch.float32, device=dev), make(shape, dtype=torch.float32, device=dev)
+    if not isinstance(out, (tuple, list)) or len(out) != 2:
+        raise ValueError("out must be a pair (%s, %s)" % names)
+    first, second = out
+    _check(torch, first, torch.float32, shape, dev, "out[0]")
+    _check(torch, second, torch.float32, shape, dev, "out[1]")
+    if first.data_ptr() == second.data_ptr():
+        raise ValueError("out[0] and out[1] must be two tensors")
+    return first, second
+
+
+def _kernel_target(torch, dev):
+    """-> None where the NumPy path runs (CPU tensors), else (device index, torch's current stream) for the kernels."""
+    if dev.type == "cpu":
+        return None
+    if dev.type != "cuda":
+        raise ValueError("the tensors must be on the CPU or on a GPU, not on %s" % (dev,))
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    return index, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _ptr(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
 def _host(rew, value, last_value, done, bonus, bonus_weight, gamma, lambda_, use_gae, use_critic, step0, n_steps, adv, vt):
     """The contract on the host: the lanes at once, the steps one after the other, every operation a float64 array operation."""
     R = rew.shape[0]
@@ -90,61 +166,27 @@ def compute_advantages(rew, value, last_value=None, done=None, gamma=0.99, lambd
     be None otherwise, and value_targets is 0).  out: (advantages, value_targets) tensors to write into.
     """
     import torch
-    if not isinstance(rew, torch.Tensor) or rew.dim() < 1:
-        raise ValueError("rew must be an int32 tensor of shape [R, ...]")
-    shape, dev = tuple(rew.shape), rew.device
-    R = shape[0]
-    L = int(np.prod(shape[1:], dtype=np.int64))
-    if R < 1 or L < 1:
-        raise ValueError("rew holds no step")
-    if L >= 2 ** 31 or R >= 2 ** 31:
-        raise ValueError("rew is too large: fewer than 2^31 rows and trajectories")
-    _check(torch, rew, torch.int32, shape, dev, "rew")
+    shape, dev, R, L = _leading(torch, rew, torch.int32, "rew")
     use_gae, use_critic = bool(use_gae), bool(use_critic)
     if use_gae and not use_critic:
         raise ValueError("use_gae needs use_critic: generalised advantage estimation uses the value function")
     if value is not None or use_critic:
         _check(torch, value, torch.float32, shape, dev, "value")
-    if last_value is not None:
-        _check(torch, last_value, torch.float32, shape[1:], dev, "last_value")
-    if done is not None:
-        _check(torch, done, torch.uint8, shape, dev, "done")
-    if bonus is not None:
-        _check(torch, bonus, torch.float32, shape, dev, "bonus")
-    gamma, lambda_, bonus_weight = float(gamma), float(lambda_), float(bonus_weight)
+    bonus_weight = _episode_inputs(torch, shape, dev, last_value, "last_value", done, bonus, bonus_weight)
+    gamma, lambda_ = float(gamma), float(lambda_)
     if not (math.isfinite(gamma) and math.isfinite(lambda_)):
         raise ValueError("gamma and lambda_ must be finite")
-    if bonus is not None and not math.isfinite(bonus_weight):
-        raise ValueError("bonus_weight must be finite")
-    step0 = int(step0)
-    n_steps = R if n_steps is None else int(n_steps)
-    if n_steps < 1 or n_steps > R:
-        raise ValueError("n_steps (%d) must be 1..%d, the ring length: a call reads each slot once" % (n_steps, R))
-    if step0 < 0 or step0 >= 2 ** 31:
-        raise ValueError("step0 must be 0..2^31 - 1")
-    if out is None:
-        make = torch.empty if n_steps == R else torch.zeros
-        adv, vt = make(shape, dtype=torch.float32, device=dev), make(shape, dtype=torch.float32, device=dev)
-    else:
-        if not isinstance(out, (tuple, list)) or len(out) != 2:
-            raise ValueError("out must be a pair (advantages, value_targets)")
-        adv, vt = out
-        _check(torch, adv, torch.float32, shape, dev, "out[0]")
-        _check(torch, vt, torch.float32, shape, dev, "out[1]")
-        if adv.data_ptr() == vt.data_ptr():
-            raise ValueError("out[0] and out[1] must be two tensors")
-    if dev.type == "cpu":
+    step0, n_steps = _ring_rows(R, step0, n_steps)
+    adv, vt = _out_pair(torch, out, shape, dev, n_steps == R, ("advantages", "value_targets"))
+    target = _kernel_target(torch, dev)
+    if target is None:
         _host(rew, value, last_value, done, bonus, bonus_weight, gamma, lambda_, use_gae, use_critic, step0, n_steps, adv, vt)
         return adv, vt
-    if dev.type != "cuda":
-        raise ValueError("the tensors must be on the CPU or on a GPU, not on %s" % (dev,))
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
+    index, stream = target
     flags = (_capi.SSD_ADV_GAE if use_gae else 0) | (_capi.SSD_ADV_CRITIC if use_critic else 0)
-    index = dev.index if dev.index is not None else torch.cuda.current_device()
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _capi.advantages_check(_capi.lib().ssd_advantages(ptr(rew), ptr(bonus), bonus_weight, ptr(value) if use_critic else None,
-                                                      ptr(done), ptr(last_value), L, R, step0, n_steps, gamma, lambda_, flags,
-                                                      ptr(adv), ptr(vt), index, stream))
+    _capi.advantages_check(_capi.lib().ssd_advantages(_ptr(rew), _ptr(bonus), bonus_weight, _ptr(value) if use_critic else None,
+                                                      _ptr(done), _ptr(last_value), L, R, step0, n_steps, gamma, lambda_, flags,
+                                                      _ptr(adv), _ptr(vt), index, stream))
     return adv, vt
 
 
@@ -195,60 +237,26 @@ def vtrace(rew, value, rhos, bootstrap_value=None, done=None, gamma=0.99, clip_r
     of the same contract, bit for bit.
     """
     import torch
-    if not isinstance(rew, torch.Tensor) or rew.dim() < 1:
-        raise ValueError("rew must be an int32 tensor of shape [R, ...]")
-    shape, dev = tuple(rew.shape), rew.device
-    R = shape[0]
-    L = int(np.prod(shape[1:], dtype=np.int64))
-    if R < 1 or L < 1:
-        raise ValueError("rew holds no step")
-    if L >= 2 ** 31 or R >= 2 ** 31:
-        raise ValueError("rew is too large: fewer than 2^31 rows and trajectories")
-    _check(torch, rew, torch.int32, shape, dev, "rew")
+    shape, dev, R, L = _leading(torch, rew, torch.int32, "rew")
     _check(torch, value, torch.float32, shape, dev, "value")
     _check(torch, rhos, torch.float32, shape, dev, "rhos")
-    if bootstrap_value is not None:
-        _check(torch, bootstrap_value, torch.float32, shape[1:], dev, "bootstrap_value")
-    if done is not None:
-        _check(torch, done, torch.uint8, shape, dev, "done")
-    if bonus is not None:
-        _check(torch, bonus, torch.float32, shape, dev, "bonus")
-    gamma, bonus_weight = float(gamma), float(bonus_weight)
+    bonus_weight = _episode_inputs(torch, shape, dev, bootstrap_value, "bootstrap_value", done, bonus, bonus_weight)
+    gamma = float(gamma)
     clip_rho, clip_pg = float(clip_rho_threshold), float(clip_pg_rho_threshold)
     if not math.isfinite(gamma):
         raise ValueError("gamma must be finite")
     if not (clip_rho > 0.0 and clip_pg > 0.0):
         raise ValueError("clip_rho_threshold and clip_pg_rho_threshold must be > 0 (inf: no clip)")
-    if bonus is not None and not math.isfinite(bonus_weight):
-        raise ValueError("bonus_weight must be finite")
-    step0 = int(step0)
-    n_steps = R if n_steps is None else int(n_steps)
-    if n_steps < 1 or n_steps > R:
-        raise ValueError("n_steps (%d) must be 1..%d, the ring length: a call reads each slot once" % (n_steps, R))
-    if step0 < 0 or step0 >= 2 ** 31:
-        raise ValueError("step0 must be 0..2^31 - 1")
-    if out is None:
-        make = torch.empty if n_steps == R else torch.zeros
-        vs, pg = make(shape, dtype=torch.float32, device=dev), make(shape, dtype=torch.float32, device=dev)
-    else:
-        if not isinstance(out, (tuple, list)) or len(out) != 2:
-            raise ValueError("out must be a pair (vs, pg_advantages)")
-        vs, pg = out
-        _check(torch, vs, torch.float32, shape, dev, "out[0]")
-        _check(torch, pg, torch.float32, shape, dev, "out[1]")
-        if vs.data_ptr() == pg.data_ptr():
-            raise ValueError("out[0] and out[1] must be two tensors")
-    if dev.type == "cpu":
+    step0, n_steps = _ring_rows(R, step0, n_steps)
+    vs, pg = _out_pair(torch, out, shape, dev, n_steps == R, ("vs", "pg_advantages"))
+    target = _kernel_target(torch, dev)
+    if target is None:
         _host_vtrace(rew, value, rhos, bootstrap_value, done, bonus, bonus_weight, gamma, clip_rho, clip_pg, step0, n_steps, vs, pg)
         return vs, pg
-    if dev.type != "cuda":
-        raise ValueError("the tensors must be on the CPU or on a GPU, not on %s" % (dev,))
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
-    index = dev.index if dev.index is not None else torch.cuda.current_device()
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _capi.vtrace_check(_capi.lib().ssd_vtrace(ptr(rew), ptr(bonus), bonus_weight, ptr(value), ptr(rhos), ptr(done),
-                                              ptr(bootstrap_value), L, R, step0, n_steps, gamma, clip_rho, clip_pg, 0,
-                                              ptr(vs), ptr(pg), index, stream))
+    index, stream = target
+    _capi.vtrace_check(_capi.lib().ssd_vtrace(_ptr(rew), _ptr(bonus), bonus_weight, _ptr(value), _ptr(rhos), _ptr(done),
+                                              _ptr(bootstrap_value), L, R, step0, n_steps, gamma, clip_rho, clip_pg, 0,
+                                              _ptr(vs), _ptr(pg), index, stream))
     return vs, pg
 
 
@@ -286,41 +294,25 @@ def _mean_var(f):
 
 
 def _moments_args(torch, x, num_sets, step0, n_steps, name):
-    if not isinstance(x, torch.Tensor) or x.dim() < 1:
-        raise ValueError("%s must be a float32 tensor of shape [R, ...]" % name)
-    shape, dev = tuple(x.shape), x.device
-    R = shape[0]
-    L = int(np.prod(shape[1:], dtype=np.int64))
-    if R < 1 or L < 1:
-        raise ValueError("%s holds no step" % name)
-    if L >= 2 ** 31 or R >= 2 ** 31:
-        raise ValueError("%s is too large: fewer than 2^31 rows and trajectories" % name)
-    _check(torch, x, torch.float32, shape, dev, name)
+    shape, dev, R, L = _leading(torch, x, torch.float32, name)
     num_sets = int(num_sets)
     if num_sets < 1 or L % num_sets or num_sets > 65535:
         raise ValueError("num_sets (%d) must be 1..65535 and divide the %d trajectories of a row: trajectory l belongs to set "
                          "l %% num_sets" % (num_sets, L))
-    step0 = int(step0)
-    n_steps = R if n_steps is None else int(n_steps)
-    if n_steps < 1 or n_steps > R:
-        raise ValueError("n_steps (%d) must be 1..%d, the ring length: a call reads each slot once" % (n_steps, R))
-    if step0 < 0 or step0 >= 2 ** 31:
-        raise ValueError("step0 must be 0..2^31 - 1")
-    return shape, dev, R, L, num_sets, step0, n_steps
+    return (shape, dev, R, L, num_sets) + _ring_rows(R, step0, n_steps)
 
 
 _moments_scratch = {}
 
 
-def _scratch(torch, dev, doubles):
+def _scratch(torch, dev, index, doubles):
     """The calls' float64 scratch: one torch allocation per device and size, kept.  Calls that share it are ordered by the
     stream they run on; use one stream per device for these calls."""
-    index = dev.index if dev.index is not None else torch.cuda.current_device()
     key = (index, doubles)
     buf = _moments_scratch.get(key)
     if buf is None:
         buf = _moments_scratch[key] = torch.empty(doubles, dtype=torch.float64, device=dev)
-    return index, buf
+    return buf
 
 
 def standardize_advantages(adv, num_sets=1, min_std=1e-4, step0=0, n_steps=None, out=None, return_moments=False):
@@ -348,8 +340,9 @@ def standardize_advantages(adv, num_sets=1, min_std=1e-4, step0=0, n_steps=None,
     else:
         _check(torch, out, torch.float32, shape, dev, "out")
     moments = torch.empty((num_sets, 2), dtype=torch.float64, device=dev) if return_moments else None
-    if dev.type == "cpu":
-        rows = [(step0 + k) % R for k in range(n_steps)]
+    target = _kernel_target(torch, dev)
+    if target is None:
+        rows = _slots(R, step0, n_steps)
         x = adv.numpy().reshape(R, L)[rows].reshape(-1, num_sets)
         res = np.empty_like(x)
         for p in range(num_sets):
@@ -362,13 +355,10 @@ def standardize_advantages(adv, num_sets=1, min_std=1e-4, step0=0, n_steps=None,
                 moments[p, 0], moments[p, 1] = float(mean), float(sd)
         out.numpy().reshape(R, L)[rows] = res.reshape(n_steps, L)
         return (out, moments) if return_moments else out
-    if dev.type != "cuda":
-        raise ValueError("the tensors must be on the CPU or on a GPU, not on %s" % (dev,))
-    index, scratch = _scratch(torch, dev, _capi.SSD_MOM_SCRATCH_DOUBLES(n_steps, L, num_sets))
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    index, stream = target
+    scratch = _scratch(torch, dev, index, _capi.SSD_MOM_SCRATCH_DOUBLES(n_steps, L, num_sets))
     _capi.moments_check(_capi.lib().ssd_standardize(
-        C.c_void_p(adv.data_ptr()), L, R, step0, n_steps, num_sets, min_std, C.c_void_p(scratch.data_ptr()),
-        None if moments is None else C.c_void_p(moments.data_ptr()), C.c_void_p(out.data_ptr()), index, stream))
+        _ptr(adv), L, R, step0, n_steps, num_sets, min_std, _ptr(scratch), _ptr(moments), _ptr(out), index, stream))
     return (out, moments) if return_moments else out
 
 
@@ -386,8 +376,9 @@ def explained_variance(targets, pred, num_sets=1, step0=0, n_steps=None):
     shape, dev, R, L, num_sets, step0, n_steps = _moments_args(torch, targets, num_sets, step0, n_steps, "targets")
     _check(torch, pred, torch.float32, shape, dev, "pred")
     out = torch.empty(num_sets, dtype=torch.float32, device=dev)
-    if dev.type == "cpu":
-        rows = [(step0 + k) % R for k in range(n_steps)]
+    target = _kernel_target(torch, dev)
+    if target is None:
+        rows = _slots(R, step0, n_steps)
         y = targets.numpy().reshape(R, L)[rows].reshape(-1, num_sets)
         q = pred.numpy().reshape(R, L)[rows].reshape(-1, num_sets)
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -398,13 +389,10 @@ def explained_variance(targets, pred, num_sets=1, step0=0, n_steps=None):
                 r = np.float64(1.0) - var_d / var_y
                 out[p] = float(np.float32(-1.0 if r < -1.0 else r))
         return out
-    if dev.type != "cuda":
-        raise ValueError("the tensors must be on the CPU or on a GPU, not on %s" % (dev,))
-    index, scratch = _scratch(torch, dev, _capi.SSD_MOM_SCRATCH_DOUBLES(n_steps, L, num_sets))
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    index, stream = target
+    scratch = _scratch(torch, dev, index, _capi.SSD_MOM_SCRATCH_DOUBLES(n_steps, L, num_sets))
     _capi.moments_check(_capi.lib().ssd_explained_variance(
-        C.c_void_p(targets.data_ptr()), C.c_void_p(pred.data_ptr()), L, R, step0, n_steps, num_sets,
-        C.c_void_p(scratch.data_ptr()), C.c_void_p(out.data_ptr()), index, stream))
+        _ptr(targets), _ptr(pred), L, R, step0, n_steps, num_sets, _ptr(scratch), _ptr(out), index, stream))
     return out
 
 
